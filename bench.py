@@ -21,7 +21,15 @@ rank.  A plain `python bench.py --gpus N` with N > 1 and no WORLD_SIZE is the PA
 N fresh child interpreters of this file (one rank per GPU, rendezvous on 127.0.0.1 at a free port), waits for them and exits
 non-zero if any of them failed; it never exec()s and never initialises HIP itself.
 
-Reported next to the metric:
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, dtype, config, host_ms).
+`--dump-outputs DIR` also writes what the last timed step returned to its caller (the augmented planes A and B of get_output()
+and the augmented latents of get_latent_output()) as DIR/<name>.npy, float32; inputs are seeded, so two builds given the same
+arguments can be compared output for output.
+
+With `--full`, reported next to the metric as well (each leg can still be left out with its --no-* flag):
+  * witness -- the last timed batch against the reference's fixture of the workload (tests/golden/fullsize_{B,F}.npz);
+  * gpu_busy -- the SMI's GFX activity sampled in-process during the timed region;
+  * multi_gpu -- with N ranks, every rank's own time per step, its shard's loop and the collective (HIP events);
   * roofline -- HIP-event brackets around every launch of ONE extra batch run right after the timed region (the timed
     region replays a captured step as a hipGraph and cannot be bracketed per launch; the extra batch launches the same
     kernels eagerly), per kernel class, against gfx950 peaks;
@@ -57,6 +65,7 @@ CONTRACTION = {
 }
 # launch-profiler classes (include/latentaug_hip.h, la_prof_end_classes)
 LAUNCH_MODES = {1: 'captured step replayed (hipGraph)', 0: 'eager', -1: 'eager (step capture refused by the runtime)'}
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: payload of all .npy files together (headers on top stay well below 64 MB)
 from latentaugment_amd.kernel_classes import CLASSES, CLASS_KERNELS      # noqa: E402  (shared with scripts/pmc_classes.py)
 
 
@@ -89,9 +98,15 @@ def parse():
     p.add_argument('--overlap-mode', type=int, default=2, choices=[0, 1, 2],
                    help='2 (default): discriminator and perceptual branch as parallel branches of the captured step; 1: the perceptual branch replayed as '
                         'its own graph on a side stream (measured equal); 0 = --no-overlap')
-    p.add_argument('--no-cpu-baseline', action='store_true')
-    p.add_argument('--no-busy-sample', action='store_true', help='do not sample torch.cuda.utilization() during the timed region')
-    p.add_argument('--no-roofline', action='store_true', help='skip the HIP-event leg (used under rocprofv3)')
+    p.add_argument('--full', action='store_true',
+                   help='everything beyond the headline figure: the correctness witness, the GPU-activity sample, the per-rank figures of an '
+                        'N-rank run, the roofline leg and the CPU baseline (off by default: a plain run times the steps and prints the line)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed step returned (A, B, w_aug) as DIR/<name>.npy, float32, '
+                        f'at most {DUMP_BUDGET_BYTES >> 20} MiB in all (a fixed, seeded sample of larger outputs)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    p.add_argument('--no-busy-sample', action='store_true', help='with --full: do not sample torch.cuda.utilization() during the timed region')
+    p.add_argument('--no-roofline', action='store_true', help='with --full: skip the HIP-event leg (used under rocprofv3)')
     p.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                    help="'gloo' + --force-device rehearses the multi-rank path on a 1-GPU box (collective staged through host)")
     p.add_argument('--force-device', type=int, default=-1, help='rehearsal only: every rank uses this device index')
@@ -101,7 +116,10 @@ def parse():
     p.add_argument('--force-dist', action='store_true',
                    help='rehearsal only: with ONE rank under a launcher, still create the process group and take the sharded path '
                         '(broadcast, shard, all_gather, barrier, max-reduce) -- the RCCL calls of the N-rank run on a 1-GPU box')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    return args
 
 
 def apply_preset(args):
@@ -216,6 +234,26 @@ def witness(args, w_aug, out, lo, hi):
             'reference_f32_rms_vs_f64': ref_rms, 'reference_f32_max_vs_f64': ref_max, 'img_rms_vs_f64': irms,
             'reference_f32_img_rms_vs_f64': iref_rms, 'bound': f'rms <= {WITNESS_SLACK} x reference float32 rms, max <= {2 * WITNESS_SLACK} x reference max',
             'w_checksum': float(w.sum())}
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as dirname/<name>.npy in float32.  When they exceed `budget` bytes together, each is replaced by the
+    same fraction of its entries: a fixed sample of flat indices (numpy default_rng(0), sorted), so two runs of the same arguments
+    write the same positions.  Returns {name: (shape of the output, entries written)}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = budget / total if total > budget else 1.0
+    info = {}
+    for name, a in arrays.items():
+        shape = a.shape
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=int(a.size * frac), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        info[name] = (shape, int(a.size))
+    return info
 
 
 def bracketed_batch(lib, _lib, one_step):
@@ -478,12 +516,12 @@ def main():
         except Exception as e:      # (no SMI library on the box: the line says so)
             busy.append(repr(e))
     busy_thread = None
-    if rank == 0 and not args.no_busy_sample:
+    if rank == 0 and args.full and not args.no_busy_sample:
         busy_thread = threading.Thread(target=busy_sampler, daemon=True)
         busy_thread.start()
     barrier()
     host_s[0] = 0.0
-    aug.latent_aug.shard_timers = [] if use_dist else None      # (sharded forward: HIP events around this rank's loop and the gather)
+    aug.latent_aug.shard_timers = [] if use_dist and args.full else None      # (sharded forward: HIP events around this rank's loop and the gather)
     t0 = time.time()
     for _ in range(args.steps):
         out = one_step()
@@ -504,7 +542,7 @@ def main():
     assert out['A'].shape == (gb, 1, args.res, args.res)
     lanes_used, launch_mode = aug.latent_aug.lanes_active, LAUNCH_MODES[aug.latent_aug.graph_state]      # (of the timed region: the roofline leg below also runs other modes)
     multi = None
-    if use_dist:
+    if use_dist and args.full:
         # what a scaling curve below the ideal is made of (rank 0 prints it): every rank's own time for the K steps, the time of its
         # shard's loop and of the one collective per step (device times between HIP events), the host part of the plugin protocol
         tm = aug.latent_aug.shard_timers or []
@@ -522,12 +560,17 @@ def main():
                  'host_ms': {'max': float(allr[:, 3].max()), 'min': float(allr[:, 3].min())},
                  'note': 'per_rank_ms: a rank\'s own wall time per step before the closing barrier; loop_ms / gather_ms: device time of its '
                          'shard\'s optimisation loop and of the single all_gather per step (HIP events); host_ms: set_input + get_output'}
+    if use_dist:
+        cdev = dev if args.dist_backend == 'nccl' else 'cpu'
         t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # what the last timed step handed its caller, before anything below runs other batches (the gathered batch: rank 0 writes it)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'A': out['A'].numpy(), 'B': out['B'].numpy(), 'w_aug': aug.get_latent_output()['w']})
     # correctness witness of the timed region's last batch (before the roofline legs run other schedules)
     lo_w, hi_w = (rank * args.batch, (rank + 1) * args.batch) if use_dist else (0, gb)
-    wit = witness(args, aug.w_AB_aug, out, lo_w, hi_w)
+    wit = witness(args, aug.w_AB_aug, out, lo_w, hi_w) if args.full else None
     if wit is not None and use_dist:
         cdev = dev if args.dist_backend == 'nccl' else 'cpu'
         t = torch.tensor([0.0 if wit['ok'] else 1.0, wit['w_rms_vs_f64_own_shard'], wit['w_max_vs_f64']], device=cdev, dtype=torch.float64)
@@ -535,7 +578,7 @@ def main():
         wit['all_ranks'] = {'ok': bool(t[0].item() == 0.0), 'worst_own_shard_w_rms_vs_f64': float(t[1].item()), 'worst_w_max_vs_f64': float(t[2].item())}
         wit['ok'] = wit['all_ranks']['ok']
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roof = roofline_leg(lib, _lib, args, one_step, 1e3 * elapsed / args.steps)      # (every rank runs it: forward() is collective)
         barrier()
     images = args.steps * gb
@@ -568,13 +611,13 @@ def main():
         if wit is not None:
             multi['witness'] = wit.get('all_ranks')
         line['multi_gpu'] = multi
-    else:
+    elif not use_dist:
         line['host_ms'] = 1e3 * host_s[0] / args.steps
     if args.dev_build:
         line['library'] = 'development build (liblatentaug_hip_dev.so): not a product measurement'
     if roof is not None:
         line['roofline'] = roof
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.preset == 'B' and args.w_disc == 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.preset == 'B' and args.w_disc == 0:
         line['cpu_baseline'] = cpu_baseline(sd, meta, args)
     sys.stdout.flush()
     if rank == 0:

@@ -299,6 +299,28 @@ def test_bench_witness_accepts_the_reference_and_rejects_a_wrong_batch():
     assert bench.witness(args, torch.zeros([4, 14, 512]), {}, 0, 4) is None
 
 
+def test_bench_dump_outputs_float32_and_seeded_sample_over_budget(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float32, whole while the arrays fit the budget; above it, the same fraction
+    of each array's entries at fixed positions, so that two runs write the same sample."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = np.arange(4000, dtype=np.float64).reshape(40, 100)
+    small = np.linspace(-1, 1, 1000).astype(np.float32)
+    info = bench.dump_outputs(str(tmp_path / 'whole'), {'big': big, 'small': small})
+    assert info == {'big': ((40, 100), 4000), 'small': ((1000,), 1000)}
+    got = np.load(tmp_path / 'whole' / 'big.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, big.astype(np.float32))
+    budget = 2000 * 4
+    info = bench.dump_outputs(str(tmp_path / 'a'), {'big': big, 'small': small}, budget=budget)
+    bench.dump_outputs(str(tmp_path / 'b'), {'big': big, 'small': small}, budget=budget)
+    a_big, a_small = np.load(tmp_path / 'a' / 'big.npy'), np.load(tmp_path / 'a' / 'small.npy')
+    assert a_big.dtype == a_small.dtype == np.float32 and (a_big.nbytes + a_small.nbytes) <= budget
+    assert info['big'] == ((40, 100), a_big.size) and a_big.size == 1600 and a_small.size == 400
+    assert np.all(np.diff(a_big) > 0) and np.isin(a_big, big).all()      # sorted positions of the flat array, values kept as they are
+    assert np.array_equal(a_big, np.load(tmp_path / 'b' / 'big.npy')) and np.array_equal(a_small, np.load(tmp_path / 'b' / 'small.npy'))
+
+
 def test_kernel_class_map_is_the_profilers():
     """One class map (latentaugment_amd/kernel_classes.py) for bench.py's brackets and the rocprofv3 post-processing: its order is the
     C enum's (csrc/la_common.h), every class is described, and the kernels of the contraction classes land where the library brackets them."""
