@@ -74,6 +74,43 @@ int la_upfirdn2d_f32(const float* x, const float* f_host, float* y, int N, int C
                      int upy, int downx, int downy, int padx0, int padx1, int pady0, int pady1, int flip, float gain,
                      la_stream_t stream);
 
+/* filtered_lrelu.  Replaces filtered_lrelu_plugin.filtered_lrelu(x,fu,fd,b,si,up,down,px0,px1,py0,py1,sx,sy,gain,slope,clamp,
+ * flip_filters,writeSigns) (filtered_lrelu.cpp:16-18; the nine steps of filtered_lrelu.py:59-108): per (n, c) plane
+ *   y = down-FIR fd + decimate by `down` ( clamp( lrelu( gain * up-FIR fu with gain up^2 ( pad ( zero-insert up ( x + b[c] ))))))
+ * x [N][C][H][W] -> y [N][C][OH][OW], OW = la_filtered_lrelu_out_size(W, up, down, px0, px1, fu_w, fd_w) (same for OH).
+ *   fu [fu_h][fu_w], fd [fd_h][fd_w]: taps in DEVICE memory (so the call needs no host copy and can be captured in a graph).  fu_h == 0
+ *     (fd_h == 0) passes a 1-D filter of fu_w taps, applied along both axes (the plugin's fuShape.y == 0).  NULL = the 1 x 1 identity
+ *     (its sizes are then ignored).  At most 64 taps per axis.
+ *   b [C] (device) or NULL; clamp = +INFINITY disables the clamp; flip = 1: correlation, 0: convolution.
+ *   Up, down, taps in the envelope of the fused kernel (up, down in {1, 2, 4}, <= 8 * up taps of fu and <= 8 * down taps of fd per
+ *   axis) run as one launch that keeps the up-sampled intermediate on chip; any other valid call runs on a direct (slow) kernel.
+ * Signs.  The intermediate after the up-FIR ("mid", active extent ah x aw = ((OH - 1) * down + fd rows) x ((OW - 1) * down + fd_w))
+ * can be recorded in a sign buffer of 2 bits per sample: bit 0 = negative (gain * value < 0), bit 1 = clamped (|lrelu| > clamp).
+ * Layout: per plane `rows` rows of `row_bytes` bytes (la_filtered_lrelu_sign_shape; the buffer is N * C * rows * row_bytes bytes);
+ * sample t of a row sits in bits 2 * (t % 4) .. 2 * (t % 4) + 1 of byte t / 4.  The layout is the same for the forward call and for
+ * the backward call below (and every higher order), so one buffer serves them all.
+ *   write_signs = 1: the samples of the active extent are written to `so` (si must be NULL, sx = sy = 0); the bytes past it are not.
+ *   si != NULL: read mode -- the activation stage multiplies mid sample (ty, tx) by the stored derivative of sample (ty + sy, tx + sx):
+ *     gain, gain * slope, or 0 where it was clamped (and gain outside the buffer), instead of evaluating lrelu and the clamp.
+ * Backward (filtered_lrelu.py:239-268): dx = the same call on dy in read mode with fu <-> fd, up <-> down, padding
+ *   [fu_w - 1 + fd_w - 1 - px0, W * up - OW * down + px0 - (up - 1), (same for y)], gain * up^2 / down^2, flip negated, no clamp,
+ *   sx - (fu_w - 1) + px0, sy - (fu rows - 1) + py0.  That call is linear in dy, so the same recipe gives every higher order.
+ * Arguments are checked on the host before any launch (the TORCH_CHECKs of filtered_lrelu.cpp:21-79; LA_ERR_ARG + la_last_error). */
+int la_filtered_lrelu_f32(const float* x, const float* fu, const float* fd, const float* b, const unsigned char* si, unsigned char* so,
+                          float* y, int N, int C, int H, int W, int fu_h, int fu_w, int fd_h, int fd_w, int up, int down, int px0, int px1,
+                          int py0, int py1, int sx, int sy, float gain, float slope, float clamp, int flip, int write_signs,
+                          la_stream_t stream);
+/* filtered_lrelu_act_ of the plugin (filtered_lrelu.cpp:213): x [N][C][H][W] IN PLACE = clamp(lrelu(gain * x)), or gain * x times the
+ * derivative read from si at (h + sy, w + sx) (read mode).  Sign buffer: per plane H rows of 4 * ceil(W / 16) bytes, same bit layout. */
+int la_filtered_lrelu_act_f32(float* x, const unsigned char* si, unsigned char* so, int N, int C, int H, int W, int sx, int sy, float gain,
+                              float slope, float clamp, int write_signs, la_stream_t stream);
+/* pure host queries: output size per axis, (in * up + pad0 + pad1 - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) // down (floor; the
+ * formula of filtered_lrelu.py:141-142), and the sign buffer of a call: *rows rows per plane of *row_bytes bytes (LA_ERR_ARG if the
+ * call is invalid).  fu_h / fd_h == 0: 1-D filters. */
+int la_filtered_lrelu_out_size(int in_size, int up, int down, int pad0, int pad1, int fu_taps, int fd_taps);
+int la_filtered_lrelu_sign_shape(int H, int W, int fu_h, int fu_w, int fd_h, int fd_w, int up, int down, int px0, int px1, int py0, int py1,
+                                 int* rows, int* row_bytes);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Modulated 3x3 convolution of a SynthesisLayer (the SG2 `modulated_conv2d` + `bias_act` pair that the reference
  * reaches through G.synthesis, util_latent_aug.py:227; resampling algebra conv2d_resample.py:82-134).

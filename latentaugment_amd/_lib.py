@@ -46,6 +46,10 @@ SIGNATURES = {
     'la_bias_sum_f32': (_I, [_P, _P, _L, _L, _I, _P]),
     'la_upfirdn2d_out_size': (_I, [_I] * 6),
     'la_upfirdn2d_f32': (_I, [_P, _P, _P] + [_I] * 15 + [_F, _P]),
+    'la_filtered_lrelu_f32': (_I, [_P] * 7 + [_I] * 16 + [_F, _F, _F, _I, _I, _P]),
+    'la_filtered_lrelu_act_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P]),
+    'la_filtered_lrelu_out_size': (_I, [_I] * 7),
+    'la_filtered_lrelu_sign_shape': (_I, [_I] * 12 + [_P, _P]),
     'la_pack_conv_weights_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'la_modconv3x3_fwd_f32': (_I, [_P, _L, _P, _P, _I, _P, _I, _P, _I, _P, _L, _F, _P, _I, _F, _F, _F, _P, _P, _Z, _I, _I, _I, _I, _P]),
     'la_modconv3x3_up2_fwd_f32': (_I, [_P, _L, _P, _P, _I, _P, _I, _P, _I, _P, _L, _F, _P, _I, _F, _F, _F, _P, _P, _P, _P, _Z, _I,

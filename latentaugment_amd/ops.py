@@ -3,9 +3,13 @@
 Same names, argument meaning and error behaviour as the reference's Python wrappers:
   bias_act(x, b, dim, act, alpha, gain, clamp)                      bias_act.py:52-86
   setup_filter / upfirdn2d / filter2d / upsample2d / downsample2d   upfirdn2d.py:70-387
+  filtered_lrelu(x, fu, fd, b, up, down, padding, gain, slope, clamp, flip_filter)   filtered_lrelu.py:59-108
 Each op is a torch.autograd.Function whose forward AND backward are HIP launches (bias_act: every activation of the reference's
-table with first- and second-order gradients; upfirdn2d: first order, which is all the latent-optimisation path uses).  torch only owns the device memory and the stream.
+table with first- and second-order gradients; upfirdn2d: first order, which is all the latent-optimisation path uses; filtered_lrelu: one
+fused launch whose backward is the same kernel reading the sign mask its forward wrote, so gradients of every order).  torch only owns the
+device memory and the stream.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -245,6 +249,97 @@ def downsample2d(x, f, down=2, padding=0, flip_filter=False, gain=1, impl='hip')
     fh, fw = _fshape(f)
     p = [px0 + (fw - dnx + 1) // 2, px1 + (fw - dnx) // 2, py0 + (fh - dny + 1) // 2, py1 + (fh - dny) // 2]
     return upfirdn2d(x, f, down=down, padding=p, flip_filter=flip_filter, gain=gain)
+
+
+def _flr_filter(f, dev, name):
+    """(device taps or None, rows (0 = 1-D), taps per row) of an fu / fd argument; None is the 1 x 1 identity."""
+    if f is None:
+        return None, 1, 1
+    assert isinstance(f, torch.Tensor) and 1 <= f.ndim <= 2
+    if f.dtype != torch.float32:
+        raise _lib.LatentAugHipError(f'filtered_lrelu: {name} must be float32, got {f.dtype}')
+    f = f.to(dev).contiguous()
+    return f, (f.shape[0] if f.ndim == 2 else 0), f.shape[-1]
+
+
+def _flr_sign_shape(h, w, fu_h, fu_w, fd_h, fd_w, up, down, px0, px1, py0, py1):
+    lib = _lib.load()
+    rows, row_bytes = C.c_int(0), C.c_int(0)
+    _lib.check(lib.la_filtered_lrelu_sign_shape(h, w, fu_h, fu_w, fd_h, fd_w, up, down, px0, px1, py0, py1, C.byref(rows), C.byref(row_bytes)),
+               'filtered_lrelu_sign_shape')
+    return rows.value, row_bytes.value
+
+
+class _FilteredLRelu(torch.autograd.Function):
+    """One launch of la_filtered_lrelu_f32.  The backward is the same Function in sign-read mode (filtered_lrelu.py:239-268); it is linear
+    in dy, so its own backward is that recipe again and every order of gradient is a launch of the same kernel."""
+
+    @staticmethod
+    def forward(ctx, x, b, fu, fd, si, cfg):
+        up, down, px0, px1, py0, py1, gain, slope, clamp, flip, sx, sy = cfg
+        (fut, fu_h, fu_w), (fdt, fd_h, fd_w) = fu, fd
+        lib = _lib.load()
+        n, c, h, w = x.shape
+        fuy, fdy = fu_h or fu_w, fd_h or fd_w
+        ow = lib.la_filtered_lrelu_out_size(w, up, down, px0, px1, fu_w, fd_w)
+        oh = lib.la_filtered_lrelu_out_size(h, up, down, py0, py1, fuy, fdy)
+        if ow < 1 or oh < 1:
+            raise _lib.LatentAugHipError(f'filtered_lrelu: output must be at least 1x1 (got {oh}x{ow})')
+        y = torch.empty([n, c, oh, ow], device=x.device, dtype=torch.float32)
+        so = None
+        write = si is None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])      # (filtered_lrelu.py:206)
+        if write:
+            rows, row_bytes = _flr_sign_shape(h, w, fu_h, fu_w, fd_h, fd_w, up, down, px0, px1, py0, py1)
+            so = torch.empty([n * c * rows * row_bytes], device=x.device, dtype=torch.uint8)
+        _lib.check(lib.la_filtered_lrelu_f32(_lib.ptr(x), _lib.ptr(fut), _lib.ptr(fdt), _lib.ptr(b), _lib.ptr(si), _lib.ptr(so), _lib.ptr(y),
+                                             n, c, h, w, fu_h, fu_w, fd_h, fd_w, up, down, px0, px1, py0, py1, sx, sy, gain, slope, clamp,
+                                             int(flip), int(write), _lib.stream_ptr()), 'filtered_lrelu')
+        ctx.fu, ctx.fd, ctx.signs = fu, fd, (si if si is not None else so)
+        ctx.meta = (cfg, tuple(x.shape), (oh, ow))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (up, down, px0, px1, py0, py1, gain, slope, clamp, flip, sx, sy), (n, c, h, w), (oh, ow) = ctx.meta
+        fu, fd = ctx.fu, ctx.fd
+        fu_w, fuy, fd_w, fdy = fu[2], fu[1] or fu[2], fd[2], fd[1] or fd[2]
+        dx = db = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            pp = [fu_w - 1 + fd_w - 1 - px0, w * up - ow * down + px0 - (up - 1), fuy - 1 + fdy - 1 - py0, h * up - oh * down + py0 - (up - 1)]
+            cfg = (down, up, *pp, gain * up ** 2 / down ** 2, slope, math.inf, not flip, sx - (fu_w - 1) + px0, sy - (fuy - 1) + py0)
+            dx = _FilteredLRelu.apply(dy.contiguous(), None, fd, fu, ctx.signs, cfg)
+        if ctx.needs_input_grad[1]:
+            db = _BiasSum.apply(dx, h * w, c)
+        return dx, db, None, None, None, None
+
+
+def filtered_lrelu(x, fu=None, fd=None, b=None, up=1, down=1, padding=0, gain=np.sqrt(2), slope=0.2, clamp=None, flip_filter=False, impl='hip'):
+    """Filtered leaky ReLU (reference: filtered_lrelu.py:59-108): bias, zero-insert up, pad / crop, FIR fu with gain up**2, gain, leaky
+    ReLU, clamp, FIR fd, keep every down-th sample -- one fused HIP launch per call.  fu / fd: float32 [taps] (separable), [h, w] or
+    None (identity); they are used from device memory.  Gradients with respect to x and b of every order (sign-read launches of the same
+    kernel); none with respect to the filters, as in the reference."""
+    assert isinstance(x, torch.Tensor)
+    _lib.require_gpu(x)
+    if x.dtype != torch.float32:
+        raise _lib.LatentAugHipError(f'filtered_lrelu: x must be float32 (got {x.dtype}); there is no other-precision kernel')
+    assert x.ndim == 4
+    if b is not None:
+        assert isinstance(b, torch.Tensor) and b.dtype == x.dtype
+        assert b.shape == (x.shape[1],), b.shape
+        _lib.require_gpu(b)
+    assert isinstance(up, (int, np.integer)) and up >= 1
+    assert isinstance(down, (int, np.integer)) and down >= 1
+    if isinstance(padding, (int, np.integer)):
+        padding = [padding, padding]
+    assert isinstance(padding, (list, tuple)) and all(isinstance(v, (int, np.integer)) for v in padding)
+    px0, px1, py0, py1 = _parse_padding(padding)
+    assert gain == float(gain) and gain > 0
+    assert slope == float(slope) and slope >= 0
+    assert clamp is None or (clamp == float(clamp) and clamp >= 0)
+    fu_ = _flr_filter(fu, x.device, 'fu')
+    fd_ = _flr_filter(fd, x.device, 'fd')
+    cfg = (int(up), int(down), px0, px1, py0, py1, float(gain), float(slope), math.inf if clamp is None else float(clamp), bool(flip_filter), 0, 0)
+    return _FilteredLRelu.apply(x.contiguous(), None if b is None else b.contiguous(), fu_, fd_, None, cfg)
 
 
 def l2_loss_vectorized(X, Y, compute_mean=True):
