@@ -52,12 +52,10 @@ const char* la_dev_env(const char* name);      // getenv
 static inline int la_dev_knob(int) { return 0; }
 static inline const char* la_dev_env(const char*) { return nullptr; }
 #endif
-#define LA_KNOB_HALO_MF 0     // halo contraction form: 0 = default, 8 = round-2 form, else the MF bits of la_conv_bf16_halo_kernel
 #define LA_KNOB_HALO_MING 1   // dev: grids of fewer points than this go to split-K instead of the halo kernel (0 = 1157: up to 34x34)
-#define LA_KNOB_FLAT_MF 2     // flat / split-K contraction form: 0 = default (16x16x32 MFMA), 8 = 32x32x16
 #define LA_KNOB_KSPLIT 3       // dev: force this many K slices on the split-K launches (0 = the cost model's choice)
-#define LA_KNOB_HALO_STAMP 5   // dev: 1 = the MF 5 halo kernel records per-wave segment clocks (la_dev_dbg_read)
-#define LA_KNOB_HALO_LDSPAD 6  // dev: extra KB of LDS per workgroup of the MF 5 halo kernel (occupancy experiments)
+#define LA_KNOB_HALO_STAMP 5   // dev: 1 = the MF 21 halo kernel records per-wave segment clocks (la_dev_dbg_read)
+#define LA_KNOB_HALO_LDSPAD 6  // dev: extra KB of LDS per workgroup of the MF 21 halo kernel (occupancy experiments)
 #define LA_NKNOB 16
 int la_prof_open(int cls, double flops, double bytes, hipStream_t stream);     // -> slot or -1
 void la_prof_close(int slot, hipStream_t stream);

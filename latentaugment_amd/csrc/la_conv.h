@@ -129,7 +129,7 @@ struct LaConvArgs {
     // gradient there is exactly zero.  (Flat kernel: rows of the pre-split operand's grid.)
     int in_row_lo, in_row_hi;
 #ifdef LA_DEV
-    int dbg_stamp;                 // development build: per-wave segment clocks of the MF 5 halo kernel (la_conv_bf16.hip, LA_STAMP)
+    int dbg_stamp;                 // development build: per-wave segment clocks of the MF 21 halo kernel (la_conv_bf16.hip, LA_STAMP)
 #endif
     int nphase;
     struct Phase {

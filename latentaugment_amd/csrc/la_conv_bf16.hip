@@ -38,9 +38,6 @@ __device__ __forceinline__ f32x16 la_mma(bf16x8 a, bf16x8 b, f32x16 c) {
 }
 
 #define KCB 32                 // channels per chunk
-#ifndef LA_MF3_DW
-#define LA_MF3_DW 5
-#endif
 
 // ------------------------------------------------------------------------------------------------------------
 // weight packing: W[o][i][t] (fp32) -> out[term][t][cc][m/32][k/16][lane][8] with (m,k) = (o,i) forward or (i,o) backward.
@@ -482,30 +479,20 @@ int la_conv_prepare_input(LaConvArgs& a, hipStream_t stream) {
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #define BPITCH 64
-// WV = waves per SIMD the kernel is compiled for (3: fp16 x2 pieces form only): as in the halo kernel below, ONE set of B fragments
-// (K-step 1 re-loaded in place under the MFMAs of K-step 0; the next step's K-step 0 after the barrier) and one set of weight
-// fragments re-loaded right after its MFMAs have issued.
-// MF = 1 (three-wave fp16 x2 form, 128-row tiles): the step on v_mfma_f32_16x16x32_f16, as in the halo kernel (2 x 8 tiles of 16 x 16
-// per wave, the pixel fragments read twice per step, LDS slots swizzled by 2 * ((pixel >> 2) & 1), accumulators brought into the
-// 32x32 layout through LDS before the shared epilogue).
-template <int MT, bool SPLIT, int FMT, int WV, int MFX = 0>
+// WV = waves per SIMD the kernel is compiled for.  MF = form of the step:
+//   0: v_mfma_f32_32x32x16 on two waves per SIMD, two sets of B fragments (K-step 1 read under the MFMAs of K-step 0), the weights of
+//      the next step loaded a full step ahead -- every format, 128- and 64-row tiles.
+//   1: the fp16 x2 split-K launches on 128-row tiles, three waves per SIMD: the step on v_mfma_f32_16x16x32_f16, as in the halo kernel
+//      (2 x 8 tiles of 16 x 16 per wave, every pixel fragment read once per step, LDS slots swizzled by 2 * ((pixel >> 2) & 1),
+//      accumulators brought into the 32x32 layout through LDS before the shared epilogue).
+//   2: MF 1 on THREE pixel buffers, for the direct launches.  The barrier at the end of step s then publishes the buffer of step s + 2,
+//      so the buffer of step s + 1 is already complete while step s computes: its first fragments are read under the last MFMAs of
+//      step s, and no LDS read latency is left exposed behind the barrier (two buffers: every step began with eight fragment reads
+//      nothing could cover).
+template <int MT, bool SPLIT, int FMT, int WV, int MF = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void la_conv_bf16_kernel(LaConvArgs a_in) {
-    // MFX bits 4 / 5 (development build only, WRONG results, timing only): the pixel records / the weight fragments are fetched for the
-    // first tap of a chunk only and re-used for its other taps -- what ANY scheme that removes the per-tap re-read (a linear halo in
-    // LDS, parity planes) could gain at most
-    constexpr int MF = MFX & 15;
-    constexpr bool ABL_PIX = (MFX & 16) != 0, ABL_WGT = (MFX & 32) != 0;
-    constexpr bool ABL_BAR = (MFX & 64) != 0, ABL_LDSW = (MFX & 128) != 0;      // (same status) no barrier per step / no LDS write per step
-    static_assert(MF == 0 || ((WV == 3 || ((MF == 3 || MF == 4) && WV <= 2)) && FMT == FMT_F16X2 && MT == 128), "the 16x16x32 form exists for the fp16 x2 kernel on 128-row tiles");
-    // MF = 3 (round 5, split-K launches, two waves per SIMD): MF = 1 with the operand loads FOUR steps ahead instead of one.  A K slice of
-    // the small grids is 9-72 (chunk, tap) steps of 48 MFMAs (0.3 us) walked by one or two workgroups per CU: with the weights of step
-    // s + 1 requested during step s (MF 1) every step waited a memory round trip (1.2 us per step at 4^2 .. 16^2, whose weights come from
-    // beyond L2, each byte once) -- nothing else is resident to cover it.  Here the weight fragments of steps s .. s + 3 and the pixel
-    // pieces of steps s + 1 .. s + 3 are in registers / in flight (rings of four, loop unrolled by four so that the slots are static;
-    // 128 more registers, hence two waves per SIMD), in ONE issue order in the prologue and in the loop so that every wait is a count.
-    // MF = 2: MF = 1 on THREE pixel buffers.  The barrier at the end of step s then publishes the buffer of step s + 2, so the buffer of
-    // step s + 1 is already complete while step s computes: its first fragments are read under the last MFMAs of step s, and no LDS
-    // read latency is left exposed behind the barrier (two buffers: every step began with eight fragment reads nothing could cover).
+    static_assert(MF == 0 ? WV == 2 : (MF <= 2 && WV == 3 && FMT == FMT_F16X2 && MT == 128),
+                  "the 16x16x32 forms exist for the three-wave fp16 x2 kernel on 128-row tiles, the 32x32x16 form for two waves");
     // merged output phases: blockIdx.z = phase * B + sample; the phase's grid, output offset and taps replace the launch-wide ones
     LaConvArgs a = a_in;
     int bz = blockIdx.z;
@@ -649,8 +636,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
     // ---- B gather of one step: 16 channels of this thread's pixel = 64 / 128 contiguous bytes
     unsigned ex[16], ey[NTERM == 3 ? 16 : 1];
     bool ok_r = false;
-    auto load_b = [&](int cc, int t, unsigned kill = 0u) {      // kill = OOB (uniform): the pieces read as zeros whatever the tap (MF 3's padding steps)
-        if constexpr (ABL_PIX) { if (t != 0) return; }
+    auto load_b = [&](int cc, int t) {
         if constexpr (PIECES) {
             const int dy = (int)((dypack >> (4 * t)) & 15u) - 8, dx = (int)((dxpack >> (4 * t)) & 15u) - 8;
             const unsigned delta = (unsigned)((dy * a.Win + dx) * (KCB * EB));      // (scalar)
@@ -658,7 +644,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int bad = __builtin_amdgcn_sbfe((int)pinv[k], (unsigned)t, 1u);      // -1: the tap is outside the image for this piece
-                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (plin[k] + delta) | ((unsigned)bad & OOB) | kill, so, 0);
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (plin[k] + delta) | ((unsigned)bad & OOB), so, 0);
                 ex[4 * k] = v.x; ex[4 * k + 1] = v.y; ex[4 * k + 2] = v.z; ex[4 * k + 3] = v.w;
             }
             return;
@@ -788,7 +774,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         mblk16 = mblk16 < (Mp >> 5) ? mblk16 : (Mp >> 5) - 1;
         const unsigned a16_off = (unsigned)mblk16 * 2048u + (unsigned)(kq * 32 + c16) * 16u;
         auto load_a16 = [&](int cc, int t, int mi, f16x8 (&dst)[2]) {
-            if constexpr (ABL_WGT) { if (t != 0) return; }
             const unsigned tw = (unsigned)((wpack >> (4 * t)) & 15u);
             const unsigned so = (tw * nck + cc) * slab_bytes;
 #pragma unroll
@@ -801,69 +786,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
             for (int q = 0; q < 2; ++q) dst[q] = *reinterpret_cast<const f16x8*>(buf + q * BPLANE + n * 16 * BPITCH + rb16);
         };
         f16x8 a16[2][2], b16[4][2];
-        const int c0 = c1, t0 = t1;      // (prologue in the loop's issue order: see the 32x32x16 form below)
-      if constexpr (MF == 3 || MF == 4) {
-        constexpr int DW = MF == 4 ? 9 : 3;            // weight ring depth = unroll factor (9-tap slices: no padding step).  MF 4 (one wave per SIMD,
-                                                       // launches of at most one workgroup per CU): a whole 9-step slice's weights are requested up front
-        f16x8 wr[DW][2][2];                            // weight fragments [slot][16-row half][term]
-        // The loop walks the steps three at a time in straight-line code (static ring slots, one entry and one exit: the waits stay counts
-        // and the accumulators keep one home); a slice whose step count is not a multiple of three is padded with steps whose pixel
-        // pieces read as zeros (out-of-range buffer offsets) under re-loaded weights: they add exact zeros.
-        // Issue order, prologue and loop alike:  P(0) | W(0) W(1) | [P(0) -> LDS] P(1) W(2) | iteration s: [P(s+1) -> LDS] P(s+2) W(s+3)
-        // -- the wait for P(s+1) covers the weights up to step s+1 and leaves W(s+2) in flight: two steps for a weight fragment to arrive
-        // where MF 1 gives it half a step.
-        int cw = ck_beg, tw = 0;
-        auto load_w = [&](int d) {                     // (d: a constant after unrolling)
-            load_a16(cw, tw, 0, wr[d][0]);
-            __builtin_amdgcn_sched_barrier(0);
-            load_a16(cw, tw, 1, wr[d][1]); adv(cw, tw);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        load_b(c0, t0);
-        adv(c1, t1);                                   // (c1, t1) = step 1
-        int c2 = c1, t2 = t1;
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int d = 0; d < DW - 1; ++d) load_w(d);
-        write_b(smem);                                 // step 0 -> buffer 0
-        __builtin_amdgcn_sched_barrier(0);
-        load_b(c1, t1, nstep > 1 ? 0u : OOB);          // step 1
-        __builtin_amdgcn_sched_barrier(0);
-        load_w(DW - 1);
-        __syncthreads();
-        adv(c2, t2);                                   // (c2, t2) = step 2
-        auto body = [&](int D, int s) {                // (D: a constant after unrolling)
-            const unsigned char* cur = smem + (s & 1) * BBUF;
-            unsigned char* nxt = smem + ((s + 1) & 1) * BBUF;
-#pragma unroll
-            for (int n = 0; n < 4; ++n) read_b16(cur, n, b16[n]);
-            write_b(nxt);                              // step s+1 (requested during step s-1)
-            load_b(c2, t2, s + 2 < nstep ? 0u : OOB); adv(c2, t2);      // step s+2 (zeros past the slice's last step)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-                for (int n = 0; n < 8; ++n) {
-                    f16x8 (&bs)[2] = b16[n & 3];
-                    acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[D][mi][1], bs[0], acc16[mi][n], 0, 0, 0);   // lh
-                    acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[D][mi][0], bs[1], acc16[mi][n], 0, 0, 0);   // hl
-                    acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[D][mi][0], bs[0], acc16[mi][n], 0, 0, 0);   // hh
-                    if (n < 4) read_b16(cur, n + 4, bs);
-                    else if (mi == 0) read_b16(cur, n - 4, bs);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                load_a16(cw, tw, mi, wr[D][mi]);       // this half's weights of step s+3
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            adv(cw, tw);
-            __syncthreads();
-        };
-#pragma unroll 1
-        for (int s = 0; s < nstep; s += DW) {
-#pragma unroll
-            for (int d = 0; d < DW; ++d) body(d, s + d);
-        }
-      } else if constexpr (MF == 2) {
+        // Prologue in the loop's own issue order -- [pieces of the step furthest ahead | weights of rows 0-15 | weights of rows 16-31] are
+        // the youngest loads when an iteration starts, on the first entry as on the back edge -- so that the counted waits of the loop hold
+        // for both and never fall back to vmcnt(0): with the weights requested first, every step began by waiting for the weight
+        // fragments issued just before its barrier.
+        const int c0 = c1, t0 = t1;
+      if constexpr (MF == 2) {
         load_b(c0, t0);
         adv(c1, t1);                                   // (c1, t1) = step 1
         int c2 = c1, t2 = t1;
@@ -889,7 +817,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
             const int ib1 = ib == 2 ? 0 : ib + 1, ib2 = ib1 == 2 ? 0 : ib1 + 1;
             const unsigned char* cur = smem + ib * BBUF;
             const unsigned char* nx1 = smem + ib1 * BBUF;
-            if constexpr (!ABL_LDSW) write_b(smem + ib2 * BBUF);                // step s+2 (loaded during step s-1)
+            write_b(smem + ib2 * BBUF);                // step s+2 (loaded during step s-1)
             load_b(c2, t2);                            // step s+3
             __builtin_amdgcn_sched_barrier(0);
             const bool more = s + 1 < nstep;
@@ -918,7 +846,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
             adv(c1, t1);           // weights run one step ahead, pieces three
             adv(c2, t2);
             ib = ib1;
-            if constexpr (!ABL_BAR) __syncthreads();
+            __syncthreads();
         }
       } else {
         load_b(c0, t0);
@@ -991,69 +919,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         __syncthreads();
       }
     } else
-    if constexpr (WV == 3) {
-      if (nstep > 0) {
-        static_assert(WV != 3 || (FMT == FMT_F16X2 ), "the three-wave form exists for the fp16 pieces loader only");
-        int c1 = ck_beg, t1 = 0;
-        auto adv = [&](int& c, int& t) {
-            if (t + 1 < ntaps) ++t;
-            else if (c + 1 < ck_end) { ++c; t = 0; }
-        };
-        bf16x8 acur[2][NTERM][TM], bf[NTERM][NJ];
-        // Prologue in the loop's own issue order -- [pieces of the step after next | weights K-step 0 | weights K-step 1] are the
-        // youngest loads when an iteration starts, on the first entry as on the back edge -- so that the counted waits of the loop
-        // (pieces: all but the 4 weight loads; weights: per K-step) hold for both and never fall back to vmcnt(0): with the weights
-        // requested first, every step began by waiting for the weight fragments issued just before its barrier.
-        const int c0 = c1, t0 = t1;
-        load_b(c0, t0);
-        adv(c1, t1);                                   // (c1, t1) = step 1
-        int c2 = c1, t2 = t1;
-        write_b(smem);
-        __builtin_amdgcn_sched_barrier(0);
-        load_b(c1, t1);
-        __builtin_amdgcn_sched_barrier(0);
-        load_a(c0, t0, 0, acur[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        load_a(c0, t0, 1, acur[1]);
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        adv(c2, t2);                                   // (c2, t2) = step 2
-#pragma unroll 1
-        for (int s = 0; s < nstep; ++s) {
-            const unsigned char* cur = smem + (s & 1) * BBUF;
-            unsigned char* nxt = smem + ((s + 1) & 1) * BBUF;
-            read_b(cur, 0, bf);
-            write_b(nxt);                              // step s+1 (loaded during step s-1)
-            load_b(c2, t2);                            // step s+2
-            __builtin_amdgcn_sched_barrier(0);
-            // K-step 0, every sub-tile re-loaded with its K-step 1 fragments right after its MFMAs
-            {
-                const int o1 = rbase + ((((2 + lh) ^ rsw) & 3) << 4);
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    acc[0][j] = la_mma<true>(acur[0][1][0], bf[0][j], acc[0][j]);
-                    acc[0][j] = la_mma<true>(acur[0][0][0], bf[1][j], acc[0][j]);
-                    acc[0][j] = la_mma<true>(acur[0][0][0], bf[0][j], acc[0][j]);
-#pragma unroll
-                    for (int q = 0; q < NTERM; ++q) bf[q][j] = *reinterpret_cast<const bf16x8*>(cur + q * BPLANE + j * 32 * BPITCH + o1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            load_a(c1, t1, 0, acur[0]);                // weights of step s+1, K-step 0
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                acc[0][j] = la_mma<true>(acur[1][1][0], bf[0][j], acc[0][j]);
-                acc[0][j] = la_mma<true>(acur[1][0][0], bf[1][j], acc[0][j]);
-                acc[0][j] = la_mma<true>(acur[1][0][0], bf[0][j], acc[0][j]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            load_a(c1, t1, 1, acur[1]);
-            c1 = c2; t1 = t2;
-            adv(c2, t2);
-            __syncthreads();
-        }
-      }
-    } else
     if (nstep > 0) {
         // (chunk, tap) of steps s, s+1, s+2; past the end they stay on the last valid step (harmless re-loads)
         int c1 = ck_beg, t1 = 0;
@@ -1063,7 +928,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         };
         bf16x8 acur[2][NTERM][TM], anxt[2][NTERM][TM], bf0[NTERM][NJ], bf1[NTERM][NJ];
         // (prologue in the loop's issue order -- pixel loads of the step after next, then the weight loads -- so that the loop's
-        //  waits are exact counts on both of its entries: see the three-wave form above)
+        //  waits are exact counts on both of its entries: see the 16x16x32 forms above)
         const int c0 = c1, t0 = t1;
         load_b(c0, t0);
         adv(c1, t1);                                   // (c1, t1) = step 1
@@ -1143,16 +1008,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
 // after its own three MFMAs, and ONE instance of the chunk loop (the last chunk issues dummy loads): the merge of two instances
 // cost a second set of 64 accumulator registers and 64 moves per chunk.  Measured per 154.6-GFLOP launch (WV 3 against 2):
 // 128->128 @256^2 fwd -9.5 %, bwd -7 %; 256->256 @128^2 fwd -8 %, bwd -8 %; 512->512 @64^2 +-0 (two rounds of workgroups only) --
-// la_conv_bf16_dispatch uses WV 3 for every 128-row fp16 launch.
-// MF = 1 (three-wave fp16 x2 form on 128-row tiles only): the same wave tile (32 rows x 128 pixels) on v_mfma_f32_16x16x32_f16 -- 2 x 8
-// tiles of 16 x 16, one MFMA per (tile, term pair) over the whole 32-channel chunk.  A 16x16x32 fragment feeds half the FLOPs of a
-// 32x32x16 one, so with the same 32 fragment registers per operand every pixel fragment is read from LDS twice per tap (once per
-// 16-row half); the weight fragments of a half die at the middle of the tap and are re-loaded then, as the K-step fragments are in the
-// 32x32x16 form.  Same weight pack (a 16-row fragment is four 256-byte pieces of the 32-row block), LDS slots swizzled by
-// 2 * ((pixel >> 2) & 1) (conflict-free for this lane map at every tap shift).  The accumulators are brought into the 32x32 layout
-// through LDS before the shared epilogue.
+// la_conv_bf16_dispatch uses WV 3 for every 128-row launch of the two-term formats.
+// MF bits: 4 = pixel-stationary halo loader (PSL, below); 1 = v_mfma_f32_16x16x32_f16; 16 = every pixel fragment read once per tap.
+// The forms: MF 0 for the bf16 formats; for fp16 x2, MF 21 on 128-row tiles of launches with more than one chunk and MF 4 (the loader
+// on the 32x32x16 form) for the others.  MF 21: the same wave tile (32 rows x 128 pixels) on v_mfma_f32_16x16x32_f16 -- 2 x 8 tiles of
+// 16 x 16, one MFMA per (tile, term pair) over the whole 32-channel chunk; the tap is walked in quarters (tap loop below).  Same weight
+// pack (a 16-row fragment is four 256-byte pieces of the 32-row block), LDS slots swizzled by 2 * ((column >> 2) & 1) (conflict-free
+// for this lane map at every tap shift).  The accumulators are brought into the 32x32 layout through LDS before the shared epilogue.
 #ifdef LA_DEV
-// Development build, dev knob LA_KNOB_HALO_STAMP = 1: every wave of the MF 5 halo kernel accumulates s_memtime differences per segment
+// Development build, dev knob LA_KNOB_HALO_STAMP = 1: every wave of the MF 21 halo kernel accumulates s_memtime differences per segment
 // (prologue issue / prologue wait + first stage / tap loops / chunk barriers / accumulator hand-over / epilogue) in scalar registers and
 // leaves them in la_dbg_buf[wave][16] (la_dev_dbg_read); segments 6-8 are stamped inside the epilogue (la_conv_device.h, LA_ESTAMP).  scripts/halo_wave_timeline.py
 __device__ unsigned long long la_dbg_buf[1 << 18];
@@ -1175,13 +1039,10 @@ extern "C" int la_dev_dbg_read(unsigned long long* dst, long n) {
 template <int MT, int FMT, int WV, int MF = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void la_conv_bf16_halo_kernel(LaConvArgs a) {
     constexpr bool SB = WV == 3;
-    static_assert(MF == 0 || FMT == FMT_F16X2, "the MF forms exist for the fp16 x2 format");
-    static_assert((MF & 1) == 0 || (WV == 3 && MT == 128), "the 16x16x32 form exists for the three-wave kernel on 128-row tiles");
-    // MF bits: 1 = 16x16x32 MFMA; 2 = dev ablation (the loader skips the modulation and the fp16 split arithmetic: WRONG results, timing
-    // only); 4 = pixel-stationary halo loader (below)
-    constexpr bool M16 = (MF & 1) != 0, ABL = (MF & 2) != 0, PSL = (MF & 4) != 0;
-    constexpr bool FR1 = (MF & 16) != 0;        // 16x16x32 form with every pixel fragment read once per tap (tap loop below)
-    static_assert(!FR1 || (M16 && PSL), "the fragment-once order exists for MF 5");
+    constexpr bool M16 = (MF & 1) != 0, PSL = (MF & 4) != 0;
+    static_assert(MF == 0 ? FMT != FMT_F16X2 : (MF == 4 || MF == 21) && FMT == FMT_F16X2, "MF 0 for the bf16 formats, MF 4 / 21 for fp16 x2");
+    static_assert(!M16 || (MF == 21 && WV == 3 && MT == 128), "the 16x16x32 form (M16) is MF 21: pixel-stationary loader, every pixel "
+                                                              "fragment read once per tap, three waves, 128-row tiles");
     constexpr int NTERM = FMT == FMT_BF16X3 ? 3 : 2;
     constexpr bool F16 = FMT == FMT_F16X2;
     constexpr int WM_ = MT / 32;                   // wave grid WM_ x WN_ over the MT x 128 tile: every wave owns 32 rows
@@ -1268,8 +1129,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         xpack |= (unsigned)(1 + a.tap_dx[t]) << (2 * t);
     }
 
-    // ---- halo slices.  Every load is unconditional (clamped address; out-of-image pixels are zeroed on the way to LDS,
-    // channels past C meet zero weights), so the compiler can count them: no wait in the tap loop is a vmcnt(0).
+    // ---- halo slices (the loader of MF 0, i.e. of the bf16 formats).  Every load is unconditional (clamped address; out-of-image
+    // pixels are zeroed on the way to LDS, channels past C meet zero weights), so the compiler can count them: no wait in the tap
+    // loop is a vmcnt(0).
     struct Slice { float x[4]; int wr, c0; bool ok; };
     auto slice_load = [&](int cc, int t, Slice& sl, bool live = true) {      // !live (uniform): one dword of traffic per wave, nothing written
         const int lt = (tid + 64 * t) & 255;                      // the idle lanes rotate over the waves
@@ -1282,7 +1144,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         sl.ok = iy >= vy0 && iy < vy1 && ix >= 0 && ix < a.Win;
         const int iyc = iy < 0 ? 0 : (iy >= a.Hin ? a.Hin - 1 : iy), ixc = ix < 0 ? 0 : (ix >= a.Win ? a.Win - 1 : ix);
         const unsigned off = (unsigned)(iyc * a.Win + ixc) * EB;
-        const int swz = M16 ? ((hp >> 2) & 1) << 1 : (hp >> 2);
+        const int swz = hp >> 2;
         sl.wr = valid ? hp * HPITCH + ((((c4 >> 1) ^ swz) & 3) << 4) + (c4 & 1) * 8 : -1;
         sl.c0 = cc * KCB + c4 * 4;
         const bool fast = cc * KCB + KCB <= a.C;                  // uniform: only a ragged last chunk clamps channels
@@ -1303,37 +1165,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         if (sl.wr >= 0) {
             // (2-wide vector types so that the packed v_cvt_pk_* / v_pk_* instructions are selected)
             typedef float f32x2 __attribute__((ext_vector_type(2)));
-            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
             typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
             const float4 f = *reinterpret_cast<const float4*>(scl + sl.c0);
             // (scalar fp32 arithmetic, only the conversions are packed: no v_pk_*_f32, Makefile)
             float p[4] = {sl.x[0] * f.x, sl.x[1] * f.y, sl.x[2] * f.z, sl.x[3] * f.w};
-            if constexpr (ABL) {
-                const uint2 w = make_uint2(__builtin_bit_cast(unsigned, sl.x[0]), __builtin_bit_cast(unsigned, sl.x[2]));
-                *reinterpret_cast<uint2*>(buf + sl.wr) = w;
-                *reinterpret_cast<uint2*>(buf + HPLANE + sl.wr) = w;
-                return;
-            }
 #pragma unroll
             for (int q = 0; q < NTERM; ++q) {
-                uint2 w;
-                if constexpr (F16) {
-                    const f16x2 h0 = __builtin_convertvector(f32x2{p[0], p[1]}, f16x2), h1 = __builtin_convertvector(f32x2{p[2], p[3]}, f16x2);
-                    w = make_uint2(__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1));
-                    if (q + 1 < NTERM) { p[0] -= (float)h0[0]; p[1] -= (float)h0[1]; p[2] -= (float)h1[0]; p[3] -= (float)h1[1]; }
-                } else {
-                    const bf16x2_t h0 = __builtin_convertvector(f32x2{p[0], p[1]}, bf16x2_t), h1 = __builtin_convertvector(f32x2{p[2], p[3]}, bf16x2_t);
-                    w = make_uint2(__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1));
-                    if (q + 1 < NTERM) { p[0] -= (float)h0[0]; p[1] -= (float)h0[1]; p[2] -= (float)h1[0]; p[3] -= (float)h1[1]; }
-                }
+                const bf16x2_t h0 = __builtin_convertvector(f32x2{p[0], p[1]}, bf16x2_t), h1 = __builtin_convertvector(f32x2{p[2], p[3]}, bf16x2_t);
+                const uint2 w = make_uint2(__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1));
+                if (q + 1 < NTERM) { p[0] -= (float)h0[0]; p[1] -= (float)h0[1]; p[2] -= (float)h1[0]; p[3] -= (float)h1[1]; }
                 *reinterpret_cast<uint2*>(buf + q * HPLANE + sl.wr) = sl.ok ? w : make_uint2(0u, 0u);
             }
         }
     };
 
-    // ---- pixel-stationary form of the halo loader (PSL).  The slices above give every thread a different (channel group, halo pixel)
-    // unit in every tap and recompute its image position, clamps and LDS slot from scratch: ~45 integer instructions per tap and
-    // thread (five of them quarter-rate 32-bit multiplies) beside the MFMAs.  Here thread hp < 204 owns halo pixel hp for the whole
+    // ---- pixel-stationary form of the halo loader (PSL: the fp16 x2 forms).  The slices above give every thread a different (channel
+    // group, halo pixel) unit in every tap and recompute its image position, clamps and LDS slot from scratch: ~45 integer instructions
+    // per tap and thread (five of them quarter-rate 32-bit multiplies) beside the MFMAs.  Here thread hp < 204 owns halo pixel hp for the whole
     // kernel -- image offset, validity and LDS row are computed ONCE -- and tap t (0..7) stages channel group t of the next chunk
     // for it (tap 8 repeats the loads of tap 0 and drops them, so that every wait in the tap loop stays a counted vmcnt): the channel is
     // wave-uniform, i.e. scalar arithmetic, and what is left per tap are the four loads, the split and one XOR for the LDS slot.
@@ -1374,12 +1222,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
             typedef float f32x2 __attribute__((ext_vector_type(2)));
             typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
             unsigned char* dst = buf + ps_row + ((((t >> 1) ^ ps_swz) & 3) << 4) + (t & 1) * 8;
-            if constexpr (ABL) {
-                const uint2 w = make_uint2(__builtin_bit_cast(unsigned, x[0]), __builtin_bit_cast(unsigned, x[2]));
-                *reinterpret_cast<uint2*>(dst) = w;
-                *reinterpret_cast<uint2*>(dst + HPLANE) = w;
-                return;
-            }
             // scalar fp32 arithmetic on purpose: v_pk_mul_f32 / v_pk_fma_f32 beside MFMAs cost ~20 cycles each (MI355X_MICROARCH.md,
             // 'price of one filler beside MFMAs'); only the two conversions are packed
             const float p0 = x[0] * f.x, p1 = x[1] * f.y, p2 = x[2] * f.z, p3 = x[3] * f.w;
@@ -1511,18 +1353,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         for (int q = 0; q < 2; ++q)
             dst[q] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, a16_off + (unsigned)mi * 256u, so + q * term_bytes, 0));
     };
-    // pixel fragment of tile n (tile row n >> 1, x half n & 1): lane (c16, kq) reads slot kq of its pixel's 64-byte row
-    // (PSL, column swizzle: lb16 = this lane's offset for the tap, the tile adds an immediate)
+    // pixel fragment of tile n (tile row n >> 1, x half n & 1): lane (c16, kq) reads slot kq of its pixel's 64-byte row (column swizzle:
+    // lb16 = this lane's offset for the tap, the tile adds an immediate)
     auto lane_b16 = [&](int shift, int dxp) -> int {
         return (shift + c16) * HPITCH + (((kq ^ ((((c16 + dxp) >> 2) & 1) << 1)) & 3) << 4);
     };
-    auto read_b16 = [&](const unsigned char* buf, int shift, int n, f16x8 (&dst)[2], int lb16 = 0) {
-        int o;
-        if constexpr (PSL) o = lb16 + ((n >> 1) * HALO_W + (n & 1) * 16) * HPITCH;
-        else {
-            const int p = (n >> 1) * HALO_W + shift + (n & 1) * 16 + c16;
-            o = p * HPITCH + (((kq ^ (((p >> 2) & 1) << 1)) & 3) << 4);
-        }
+    auto read_b16 = [&](const unsigned char* buf, int n, f16x8 (&dst)[2], int lb16) {
+        const int o = lb16 + ((n >> 1) * HALO_W + (n & 1) * 16) * HPITCH;
 #pragma unroll
         for (int q = 0; q < 2; ++q) dst[q] = *reinterpret_cast<const f16x8*>(buf + q * HPLANE + o);
     };
@@ -1537,83 +1374,49 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         const unsigned char* cur = smem + (cc & 1) * HBUF;
         unsigned char* nxt = smem + ((cc + 1) & 1) * HBUF;
         const bool has_next = cc + 1 < nck;
-        Slice sl;
-        sl.wr = -1;
-        sl.ok = false;
         float psx[4] = {0.f, 0.f, 0.f, 0.f};
-        int lb_cur = PSL ? lane_b16((int)(shpack & 127u), (int)(xpack & 3u)) : 0;
+        int lb_cur = lane_b16((int)(shpack & 127u), (int)(xpack & 3u));
 #pragma unroll
-        for (int n = 0; n < 4; ++n) read_b16(cur, (int)(shpack & 127u), n, b16[n], lb_cur);
+        for (int n = 0; n < 4; ++n) read_b16(cur, n, b16[n], lb_cur);
 #pragma unroll 1
         for (int t = 0; t < 9; ++t) {
-            const int shift = (int)((shpack >> (7 * t)) & 127u);
             const int tn = t + 1 < 9 ? t + 1 : 0;
             const int ccn = t + 1 < 9 ? cc : (has_next ? cc + 1 : 0);
             const int shift_n = (int)((shpack >> (7 * (t + 1 < 9 ? t + 1 : 8))) & 127u);
-            const int lb_nxt = PSL ? lane_b16(shift_n, (int)((xpack >> (2 * (t + 1 < 9 ? t + 1 : 8))) & 3u)) : 0;
+            const int lb_nxt = lane_b16(shift_n, (int)((xpack >> (2 * (t + 1 < 9 ? t + 1 : 8))) & 3u));
             float4 psf = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (PSL) { if (has_next && t >= 1) psf = ps_factors(cc + 1, t - 1); }
-            if constexpr (FR1) {
-                // every pixel fragment read ONCE per tap: four quarters (tiles 0-3 x rows 0-15, tiles 0-3 x rows 16-31, tiles 4-7 x rows 0-15,
-                // tiles 4-7 x rows 16-31); a slot is re-filled after its second use with the tile four steps ahead (tile k + 4 of this tap, then
-                // tile k of the next tap).  Half the LDS fragment traffic of the order below (the LDS pipe of a CU is busy 54-90 % under three
-                // workgroups, profiles/r05_pmc_halo_waits.txt) -- at the price of a QUARTER tap instead of half a tap for the next weights to land
+            if (has_next && t >= 1) psf = ps_factors(cc + 1, t - 1);
+            // every pixel fragment read ONCE per tap: four quarters (tiles 0-3 x rows 0-15, tiles 0-3 x rows 16-31, tiles 4-7 x rows 0-15,
+            // tiles 4-7 x rows 16-31); a slot is re-filled after its second use with the tile four steps ahead (tile k + 4 of this tap, then
+            // tile k of the next tap).  Half the LDS fragment traffic of walking all eight tiles per 16-row half (the LDS pipe of a CU is
+            // busy 54-90 % under three workgroups, profiles/r05_pmc_halo_waits.txt) -- at the price of a QUARTER tap instead of half a tap
+            // for the next weights to land
 #pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const int hf = q4 >> 1, mi = q4 & 1;
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const int hf = q4 >> 1, mi = q4 & 1;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int n = hf * 4 + k;
-                        f16x8 (&bs)[2] = b16[k];
-                        acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mi][1], bs[0], acc16[mi][n], 0, 0, 0);   // lh
-                        acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mi][0], bs[1], acc16[mi][n], 0, 0, 0);   // hl
-                        acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mi][0], bs[0], acc16[mi][n], 0, 0, 0);   // hh
-                        if (mi == 1) {
-                            if (hf == 0) read_b16(cur, shift, 4 + k, bs, lb_cur);
-                            else if (t + 1 < 9) read_b16(cur, shift_n, k, bs, lb_nxt);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if (q4 == 2) load_a16(ccn, tn, 0, a16[0]);      // rows 0-15 are done with this tap's weights: the next tap's, a quarter tap to land
-                    if (q4 == 3) load_a16(ccn, tn, 1, a16[1]);
-                    if (q4 == 1) {
-                        if (has_next && t >= 1) ps_write(nxt, t - 1, psx, psf);      // the slice loaded one tap ago
-                        ps_load(has_next ? cc + 1 : cc, t, psx);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            } else {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-                for (int n = 0; n < 8; ++n) {
-                    f16x8 (&bs)[2] = b16[n & 3];
+                for (int k = 0; k < 4; ++k) {
+                    const int n = hf * 4 + k;
+                    f16x8 (&bs)[2] = b16[k];
                     acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mi][1], bs[0], acc16[mi][n], 0, 0, 0);   // lh
                     acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mi][0], bs[1], acc16[mi][n], 0, 0, 0);   // hl
                     acc16[mi][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[mi][0], bs[0], acc16[mi][n], 0, 0, 0);   // hh
-                    // the slot is re-filled with the tile four steps ahead: (mi, n + 4), then (mi + 1, n - 4) of this tap (the same
-                    // pixels again for the other 16 rows), then tile n - 4 of the next tap (never across the chunk barrier)
-                    if (n < 4) read_b16(cur, shift, n + 4, bs, lb_cur);
-                    else if (mi == 0) read_b16(cur, shift, n - 4, bs, lb_cur);
-                    else if (t + 1 < 9) read_b16(cur, shift_n, n - 4, bs, lb_nxt);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                load_a16(ccn, tn, mi, a16[mi]);          // this half's weights of the next tap: half a tap to land
-                if (mi == 0) {
-                    if constexpr (PSL) {
-                        if (has_next && t >= 1) ps_write(nxt, t - 1, psx, psf);      // the slice loaded one tap ago
-                        ps_load(has_next ? cc + 1 : cc, t, psx);
-                    } else {
-                        slice_write(nxt, sl);
-                        slice_load(has_next ? cc + 1 : cc, t, sl, has_next);
+                    if (mi == 1) {
+                        if (hf == 0) read_b16(cur, 4 + k, bs, lb_cur);
+                        else if (t + 1 < 9) read_b16(cur, k, bs, lb_nxt);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-            }
+                if (q4 == 2) load_a16(ccn, tn, 0, a16[0]);      // rows 0-15 are done with this tap's weights: the next tap's, a quarter tap to land
+                if (q4 == 3) load_a16(ccn, tn, 1, a16[1]);
+                if (q4 == 1) {
+                    if (has_next && t >= 1) ps_write(nxt, t - 1, psx, psf);      // the slice loaded one tap ago
+                    ps_load(has_next ? cc + 1 : cc, t, psx);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
             lb_cur = lb_nxt;
         }
-        if constexpr (!PSL) slice_write(nxt, sl);      // (PSL: tap 8 loads nothing)
         LA_STAMP(2);
         __syncthreads();
         LA_STAMP(3);
@@ -1778,155 +1581,65 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
     la_conv_epilogue<MT, false, true, WM_>(a, acc, red, ntile, m0, G, G);
 }
 
+// > 64 KB of dynamic LDS needs the opt-in, and the attribute is per DEVICE: it is set once per (kernel, device) before the kernel's first
+// launch (atomic flags: the entry points may be entered from several host threads, one per device)
+#ifdef LA_DEV
+#define HALO_LDS_CAP (160 * 1024)      // (room for LA_KNOB_HALO_LDSPAD)
+#else
+#define HALO_LDS_CAP (2 * 3 * HALO_PX * HPITCH + 4096 * (int)sizeof(float))
+#endif
+template <int MT, int FMT, int WV, int MF>
+static int launch_halo(const LaConvArgs& as, dim3 grid, size_t lds, hipStream_t stream) {
+    static std::atomic<bool> cap_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!cap_set[dev].load(std::memory_order_acquire)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<MT, FMT, WV, MF>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, HALO_LDS_CAP);
+        if (e != hipSuccess) { la_set_error(hipGetErrorString(e)); return LA_ERR_HIP; }
+        cap_set[dev].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL((la_conv_bf16_halo_kernel<MT, FMT, WV, MF>), grid, dim3(256), lds, stream, as);
+    return LA_OK;
+}
+
 template <int FMT>
 static int launch_bf16(const LaConvArgs& as, int MTsel, dim3 grid, bool split, hipStream_t stream) {
     constexpr int NTERM = FMT == FMT_BF16X3 ? 3 : 2;
-    constexpr int W3 = NTERM == 2 ? 3 : 2;      // (the three-term format does not fit three waves: its W3 alias is the plain kernel)
-    const size_t lds128 = (size_t)2 * NTERM * NT * BPITCH, lds64 = lds128;     // two pixel buffers (>= the epilogue's 4 * MT floats)
     if (!split && la_conv_bf16_uses_halo(as)) {
         // two halo buffers (>= the epilogue's 4 * MT floats) + the per-channel factor table
-        size_t h128 = (size_t)(as.C > KCB ? 2 : 1) * NTERM * HALO_PX * HPITCH + (size_t)la_cdiv(as.C, KCB) * KCB * sizeof(float);
+        size_t lds = (size_t)(as.C > KCB ? 2 : 1) * NTERM * HALO_PX * HPITCH + (size_t)la_cdiv(as.C, KCB) * KCB * sizeof(float);
         const size_t epi = (size_t)160 * MTsel + (size_t)2048 * (MTsel / 32);      // what the epilogue addresses (row tables + fused-ToRGB partials)
-        if (h128 < epi) h128 = epi;
-        const size_t h64 = h128;
-        // > 64 KB of dynamic LDS needs the opt-in, and the attribute is per DEVICE: track it per device (atomic flags: the
-        // entry points may be entered from several host threads, one per device)
-        static std::atomic<bool> attr_done[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (!attr_done[dev].load(std::memory_order_acquire)) {
-            const int cap = 2 * 3 * HALO_PX * HPITCH + 4096 * (int)sizeof(float);
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<128, FMT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<128, FMT, W3>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<64, FMT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<32, FMT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-            if (e != hipSuccess) { la_set_error(hipGetErrorString(e)); return LA_ERR_HIP; }
-            attr_done[dev].store(true, std::memory_order_release);
-        }
-        // three-wave form for the fp16 x2 launches on 128-row tiles (see the kernel comment); dev knob LA_HALO_W3=0|1
-        static const int w3_knob = []() { const char* e = la_dev_env("LA_HALO_W3"); return e ? atoi(e) : -1; }();
-        const bool w3 = NTERM == 2 && MTsel == 128 && (w3_knob >= 0 ? w3_knob != 0 : true);
+        if (lds < epi) lds = epi;
         if constexpr (FMT == FMT_F16X2) {
-            // fp16 x2 launches on 128-row tiles with more than one chunk: the 16x16x32 / pixel-stationary form (MF 5, kernel comment).
-            // Dev knob (in-process A/B): 0 = this default, 8 = the round-2 form (MF 0), otherwise the MF bits to run.
-            const int knob = la_dev_knob(LA_KNOB_HALO_MF);
-            const int mf = knob == 0 ? 21 : (knob == 8 ? 0 : knob);      // (21 = MF 5 with every pixel fragment read once per tap, round 5)
-            if (MTsel == 128 && w3 && as.C > KCB && mf > 0) {
-                auto go = [&](auto tag) -> int {
-                    constexpr int MFV = decltype(tag)::value;
-                    static std::atomic<bool> done[64];
-                    if (!done[dev].load(std::memory_order_acquire)) {
-                        #ifdef LA_DEV
-                        const int cap = 160 * 1024;      // (room for LA_KNOB_HALO_LDSPAD)
-#else
-                        const int cap = 2 * 3 * HALO_PX * HPITCH + 4096 * (int)sizeof(float);
-#endif
-                        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<128, FMT_F16X2, 3, MFV>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
-                            la_set_error("halo MF: hipFuncSetAttribute failed"); return LA_ERR_HIP;
-                        }
-                        done[dev].store(true, std::memory_order_release);
-                    }
-                    // (dev knob LA_KNOB_HALO_LDSPAD: extra KB of dynamic LDS per workgroup -- fewer workgroups per CU, for scripts/halo_wave_timeline.py)
-                    hipLaunchKernelGGL((la_conv_bf16_halo_kernel<128, FMT_F16X2, 3, MFV>), grid, dim3(256), h128 + (size_t)la_dev_knob(LA_KNOB_HALO_LDSPAD) * 1024, stream, as);
-                    return LA_OK;
-                };
-                switch (mf) {
-#ifdef LA_DEV
-                    case 1: return go(std::integral_constant<int, 1>{});
-                    case 4: return go(std::integral_constant<int, 4>{});
-                    case 7: return go(std::integral_constant<int, 7>{});      // (loader ablation: wrong results, timing only)
-                    case 5: return go(std::integral_constant<int, 5>{});      // (round 4: every pixel fragment read twice per tap)
-#endif
-                    case 21: return go(std::integral_constant<int, 21>{});
-                    default: break;
-                }
-            }
-        }
-        if constexpr (FMT == FMT_F16X2) {
-            // every other fp16 x2 halo launch (64- / 32-row tiles, single-chunk launches): the pixel-stationary loader on the 32x32x16 form
-            // (MF 4); dev knob 8 = the round-2 loader
-            if (la_dev_knob(LA_KNOB_HALO_MF) != 8) {
-                auto attr = [&](const void* fn, std::atomic<bool>& flag) -> bool {
-                    if (!flag.load(std::memory_order_acquire)) {
-                        const int cap = 2 * 3 * HALO_PX * HPITCH + 4096 * (int)sizeof(float);
-                        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) { la_set_error("halo PSL: hipFuncSetAttribute failed"); return false; }
-                        flag.store(true, std::memory_order_release);
-                    }
-                    return true;
-                };
-                static std::atomic<bool> d128[64], d64[64], d32[64];
-                if (MTsel == 128 && w3) {
-                    if (!attr(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<128, FMT_F16X2, 3, 4>), d128[dev])) return LA_ERR_HIP;
-                    hipLaunchKernelGGL((la_conv_bf16_halo_kernel<128, FMT_F16X2, 3, 4>), grid, dim3(256), h128, stream, as);
-                    return LA_OK;
-                }
-                if (MTsel == 64) {
-                    if (!attr(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<64, FMT_F16X2, 2, 4>), d64[dev])) return LA_ERR_HIP;
-                    hipLaunchKernelGGL((la_conv_bf16_halo_kernel<64, FMT_F16X2, 2, 4>), grid, dim3(256), h64, stream, as);
-                    return LA_OK;
-                }
-                if (MTsel == 32) {
-                    if (!attr(reinterpret_cast<const void*>(&la_conv_bf16_halo_kernel<32, FMT_F16X2, 2, 4>), d32[dev])) return LA_ERR_HIP;
-                    hipLaunchKernelGGL((la_conv_bf16_halo_kernel<32, FMT_F16X2, 2, 4>), grid, dim3(256), h64, stream, as);
-                    return LA_OK;
-                }
-            }
-        }
-        if (MTsel == 128 && w3) hipLaunchKernelGGL((la_conv_bf16_halo_kernel<128, FMT, W3>), grid, dim3(256), h128, stream, as);
-        else if (MTsel == 128) hipLaunchKernelGGL((la_conv_bf16_halo_kernel<128, FMT, 2>), grid, dim3(256), h128, stream, as);
-        else if (MTsel == 64) hipLaunchKernelGGL((la_conv_bf16_halo_kernel<64, FMT, 2>), grid, dim3(256), h64, stream, as);
-        else hipLaunchKernelGGL((la_conv_bf16_halo_kernel<32, FMT, 2>), grid, dim3(256), h64, stream, as);
-        return LA_OK;
-    }
-    // three-wave form of the 128-row fp16 x2 launches (kernel comment); dev knob LA_FLAT_W3=0|1
-    static const int f3_knob = []() { const char* e = la_dev_env("LA_FLAT_W3"); return e ? atoi(e) : -1; }();
-    const bool f3 = FMT == FMT_F16X2  && MTsel == 128 && (f3_knob >= 0 ? f3_knob != 0 : true);
-    constexpr int FW3 = (FMT == FMT_F16X2 ) ? 3 : 2;
-    if constexpr (FMT == FMT_F16X2) {
-        // 16x16x32 form of the three-wave kernel (dev knob LA_KNOB_FLAT_MF: 8 = the 32x32x16 form); its accumulator hand-over needs 36 KB of LDS
-        const int fk = la_dev_knob(LA_KNOB_FLAT_MF);
-        if (MTsel == 128 && f3 && fk != 8) {
-            const size_t lds_mf = lds128 > (size_t)4 * 64 * 36 * 4 ? lds128 : (size_t)4 * 64 * 36 * 4;
-            const size_t lds_3 = (size_t)3 * NTERM * NT * BPITCH;      // three pixel buffers (>= the accumulator hand-over's 36 KB)
-            const bool three = fk == 2 || (fk == 0 && !split) || fk == 3;      // default: direct launches on three buffers (knob 2: both, 1: neither)
-#ifdef LA_DEV
-            if (fk >= 16 && !split) {      // ablations of the direct launches (kernel comment): 18 = no pixel re-reads, 34 = no weight re-reads, 50 = neither
-                if (fk == 18) hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 18>), grid, dim3(256), lds_3, stream, as);
-                else if (fk == 66) hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 66>), grid, dim3(256), lds_3, stream, as);       // no barrier
-                else if (fk == 130) hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 130>), grid, dim3(256), lds_3, stream, as);     // no LDS write
-                else if (fk == 242) hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 242>), grid, dim3(256), lds_3, stream, as);     // none of the four
-                else if (fk == 34) hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 34>), grid, dim3(256), lds_3, stream, as);
-                else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 50>), grid, dim3(256), lds_3, stream, as);
-                return LA_OK;
-            }
-#endif
-            if (three && !split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 2>), grid, dim3(256), lds_3, stream, as);
-            else if (fk == 2 && split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT_F16X2, 3, 2>), grid, dim3(256), lds_3, stream, as);
-#ifdef LA_DEV
-            else if (split && (fk == 11 || fk == 12)) {
-                // round-5 experiment, measured and NOT faster (profiles/r05_exp_splitk_prefetch.txt): weights three steps ahead (MF 3, two
-                // waves per SIMD; knob 11), and on top of it launches of at most one workgroup per CU whose slices are whole 9-tap chunks with a
-                // slice's first nine steps of weights requested up front, at one wave per SIMD (MF 4; knob 12).  Bit-identical to MF 1.
-                const long wgs = (long)grid.x * grid.y * grid.z;
-                const bool whole9 = as.nphase == 0 && as.ntaps == 9;
-                if (fk == 12 && wgs <= 256 && whole9) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT_F16X2, 1, 4>), grid, dim3(256), lds_mf, stream, as);
-                else hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT_F16X2, 2, 3>), grid, dim3(256), lds_mf, stream, as);
-            }
-#endif
-            else if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT_F16X2, 3, 1>), grid, dim3(256), lds_mf, stream, as);
-            else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT_F16X2, 3, 1>), grid, dim3(256), lds_mf, stream, as);
-            return LA_OK;
+            // the pixel-stationary loader (MF 4); on 128-row tiles with more than one chunk its 16x16x32 form (MF 21).  Dev knob
+            // LA_KNOB_HALO_LDSPAD: extra KB of dynamic LDS per workgroup of MF 21 -- fewer workgroups per CU, for scripts/halo_wave_timeline.py
+            if (MTsel == 128 && as.C > KCB) return launch_halo<128, FMT, 3, 21>(as, grid, lds + (size_t)la_dev_knob(LA_KNOB_HALO_LDSPAD) * 1024, stream);
+            if (MTsel == 128) return launch_halo<128, FMT, 3, 4>(as, grid, lds, stream);
+            if (MTsel == 64) return launch_halo<64, FMT, 2, 4>(as, grid, lds, stream);
+            return launch_halo<32, FMT, 2, 4>(as, grid, lds, stream);
+        } else {
+            // three waves per SIMD on 128-row tiles for the two-term format (the three-term one does not fit them)
+            if (MTsel == 128) return launch_halo<128, FMT, NTERM == 2 ? 3 : 2, 0>(as, grid, lds, stream);
+            if (MTsel == 64) return launch_halo<64, FMT, 2, 0>(as, grid, lds, stream);
+            return launch_halo<32, FMT, 2, 0>(as, grid, lds, stream);
         }
     }
-    if (MTsel == 128 && f3) {
-        if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, FW3>), grid, dim3(256), lds128, stream, as);
-        else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, FW3>), grid, dim3(256), lds128, stream, as);
-    } else if (MTsel == 128) {
-        if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, 2>), grid, dim3(256), lds128, stream, as);
-        else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, 2>), grid, dim3(256), lds128, stream, as);
+    const size_t lds = (size_t)2 * NTERM * NT * BPITCH;      // two pixel buffers (>= the epilogue's 4 * MT floats)
+    if (MTsel == 128) {
+        if constexpr (FMT == FMT_F16X2) {
+            // the three-wave 16x16x32 forms: split-K slices on two pixel buffers (MF 1; the accumulator hand-over needs 36 KB of LDS),
+            // direct launches on three (MF 2)
+            const size_t lds_mf = lds > (size_t)4 * 64 * 36 * 4 ? lds : (size_t)4 * 64 * 36 * 4;
+            if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, 3, 1>), grid, dim3(256), lds_mf, stream, as);
+            else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, 3, 2>), grid, dim3(256), (size_t)3 * NTERM * NT * BPITCH, stream, as);
+        } else {
+            if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, 2>), grid, dim3(256), lds, stream, as);
+            else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, 2>), grid, dim3(256), lds, stream, as);
+        }
     } else {
-        if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<64, true, FMT, 2>), grid, dim3(256), lds64, stream, as);
-        else hipLaunchKernelGGL((la_conv_bf16_kernel<64, false, FMT, 2>), grid, dim3(256), lds64, stream, as);
+        if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<64, true, FMT, 2>), grid, dim3(256), lds, stream, as);
+        else hipLaunchKernelGGL((la_conv_bf16_kernel<64, false, FMT, 2>), grid, dim3(256), lds, stream, as);
     }
     return LA_OK;
 }
