@@ -64,6 +64,19 @@ int la_bias_act_ex_f32(const float* x, const float* b, const float* xref, const 
                        long stepb, int nb, int grad, int act, float alpha, float gain, float clamp, la_stream_t stream);
 /* db [nb] = sum of dx over every axis but the bias axis (what bias_act.py:187,206 forms with Tensor.sum): element i -> (i / stepb) % nb. */
 int la_bias_sum_f32(const float* dx, float* db, long n, long stepb, int nb, la_stream_t stream);
+/* The same two entries for the reference plugin's other storage types (AT_DISPATCH_FLOATING_TYPES_AND_HALF, bias_act.cpp:77): argument
+ * order, (stepb, nb), grad, activation ids, NULL conventions and checks as la_bias_act_ex_f32 / la_bias_sum_f32.
+ *   _f16: IEEE binary16 storage (x, b, xref, yref, dy, out, db), fp32 arithmetic with one rounding on store (the plugin's
+ *         InternalType<half> = float), float scalars; db is summed in fp32 and rounded once.  With grad >= 1 the clamp test compares
+ *         yref with the clamp rounded to binary16, the value a clamped output holds.
+ *   _f64: double storage and arithmetic with DOUBLE alpha / gain / clamp (the reference's impl='ref' path applies them as doubles). */
+int la_bias_act_ex_f16(const unsigned short* x, const unsigned short* b, const unsigned short* xref, const unsigned short* yref,
+                       const unsigned short* dy, unsigned short* out, long n, long stepb, int nb, int grad, int act, float alpha, float gain,
+                       float clamp, la_stream_t stream);
+int la_bias_sum_f16(const unsigned short* dx, unsigned short* db, long n, long stepb, int nb, la_stream_t stream);
+int la_bias_act_ex_f64(const double* x, const double* b, const double* xref, const double* yref, const double* dy, double* out, long n,
+                       long stepb, int nb, int grad, int act, double alpha, double gain, double clamp, la_stream_t stream);
+int la_bias_sum_f64(const double* dx, double* db, long n, long stepb, int nb, la_stream_t stream);
 
 /* upfirdn2d.  Replaces upfirdn2d_plugin.upfirdn2d(x,f,upx,upy,downx,downy,padx0,padx1,pady0,pady1,flip,gain)
  * (upfirdn2d.cpp:16-98, kernels upfirdn2d.cu:29-200).  f_host: fh*fw taps in HOST memory (<= 8x8), as produced by
@@ -73,6 +86,15 @@ int la_upfirdn2d_out_size(int in_size, int up, int down, int pad0, int pad1, int
 int la_upfirdn2d_f32(const float* x, const float* f_host, float* y, int N, int C, int H, int W, int fh, int fw, int upx,
                      int upy, int downx, int downy, int padx0, int padx1, int pady0, int pady1, int flip, float gain,
                      la_stream_t stream);
+/* upfirdn2d for the plugin's other storage types (upfirdn2d.cpp:63); arguments, limits (<= 8x8 taps, or one separable pass of
+ * <= 32) and error messages as la_upfirdn2d_f32.  The taps stay float32 host values for every type (upfirdn2d.cpp:21).
+ *   _f16: binary16 x / y, fp32 accumulation, one rounding on store.
+ *   _f64: double x / y, the taps widened exactly, double arithmetic and a DOUBLE gain. */
+int la_upfirdn2d_f16(const unsigned short* x, const float* f_host, unsigned short* y, int N, int C, int H, int W, int fh, int fw,
+                     int upx, int upy, int downx, int downy, int padx0, int padx1, int pady0, int pady1, int flip, float gain,
+                     la_stream_t stream);
+int la_upfirdn2d_f64(const double* x, const float* f_host, double* y, int N, int C, int H, int W, int fh, int fw, int upx, int upy,
+                     int downx, int downy, int padx0, int padx1, int pady0, int pady1, int flip, double gain, la_stream_t stream);
 
 /* filtered_lrelu.  Replaces filtered_lrelu_plugin.filtered_lrelu(x,fu,fd,b,si,up,down,px0,px1,py0,py1,sx,sy,gain,slope,clamp,
  * flip_filters,writeSigns) (filtered_lrelu.cpp:16-18; the nine steps of filtered_lrelu.py:59-108): per (n, c) plane

@@ -34,6 +34,7 @@ _P = C.c_void_p
 _I = C.c_int
 _L = C.c_long
 _F = C.c_float
+_D = C.c_double
 _Z = C.c_size_t
 
 # name -> (restype, argtypes); kept in one table so tests can check every header symbol is exported
@@ -44,8 +45,14 @@ SIGNATURES = {
     'la_bias_act_grad_f32': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _F, _F, _F, _P]),
     'la_bias_act_ex_f32': (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _F, _F, _F, _P]),
     'la_bias_sum_f32': (_I, [_P, _P, _L, _L, _I, _P]),
+    'la_bias_act_ex_f16': (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _F, _F, _F, _P]),
+    'la_bias_sum_f16': (_I, [_P, _P, _L, _L, _I, _P]),
+    'la_bias_act_ex_f64': (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _D, _D, _D, _P]),
+    'la_bias_sum_f64': (_I, [_P, _P, _L, _L, _I, _P]),
     'la_upfirdn2d_out_size': (_I, [_I] * 6),
     'la_upfirdn2d_f32': (_I, [_P, _P, _P] + [_I] * 15 + [_F, _P]),
+    'la_upfirdn2d_f16': (_I, [_P, _P, _P] + [_I] * 15 + [_F, _P]),
+    'la_upfirdn2d_f64': (_I, [_P, _P, _P] + [_I] * 15 + [_D, _P]),
     'la_filtered_lrelu_f32': (_I, [_P] * 7 + [_I] * 16 + [_F, _F, _F, _I, _I, _P]),
     'la_filtered_lrelu_act_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P]),
     'la_filtered_lrelu_out_size': (_I, [_I] * 7),

@@ -8,6 +8,11 @@ Each op is a torch.autograd.Function whose forward AND backward are HIP launches
 table with first- and second-order gradients; upfirdn2d: first order, which is all the latent-optimisation path uses; filtered_lrelu: one
 fused launch whose backward is the same kernel reading the sign mask its forward wrote, so gradients of every order).  torch only owns the
 device memory and the stream.
+
+Dtypes of bias_act and the upfirdn2d family (upfirdn2d, filter2d, upsample2d, downsample2d), as the reference's plugins dispatch them
+(bias_act.cpp:77, upfirdn2d.cpp:63): float16, float32 and float64 run on kernels of their own and return their own dtype (float16 with
+fp32 arithmetic inside, float64 in double throughout).  Any other dtype (bfloat16, ...) is computed in float32 and returned as float32.
+A float16 or float64 x needs a bias of its own dtype (bias_act.cpp:36).  filtered_lrelu is float32 only.
 """
 import ctypes as C
 import math
@@ -26,10 +31,25 @@ _ACTS = {
 }
 
 
+# dtypes with entries of their own besides float32 (the C ABI's _f16 / _f64 forms); they keep their dtype through the op
+_OWN_DTYPES = {torch.float16: 'f16', torch.float64: 'f64'}
+
+
+def _op_input(x):
+    """x as the op's kernels read it: float16 / float64 / float32 as they are, every other dtype converted to float32 (as before)."""
+    return x.contiguous() if x.dtype in _OWN_DTYPES else x.contiguous().float()
+
+
 def _bias_act_launch(x, b, xref, yref, dy, grad, stepb, nb, act, alpha, gain, clamp):
-    """One launch of the general op (include/latentaug_hip.h: la_bias_act_ex_f32 = the plugin's bias_act(x, b, xref, yref, dy, grad, ...))."""
+    """One launch of the general op (include/latentaug_hip.h: la_bias_act_ex_f32 = the plugin's bias_act(x, b, xref, yref, dy, grad, ...));
+    float16 / float64 tensors go to its _f16 / _f64 form."""
     lib = _lib.load()
     out = torch.empty_like(x)
+    if x.dtype in _OWN_DTYPES:
+        fn = getattr(lib, 'la_bias_act_ex_' + _OWN_DTYPES[x.dtype])
+        _lib.check(fn(_lib.ptr(x), _lib.ptr(b), _lib.ptr(xref), _lib.ptr(yref), _lib.ptr(dy), _lib.ptr(out), x.numel(), stepb, nb, grad, act,
+                      alpha, gain, clamp, _lib.stream_ptr()), 'bias_act')
+        return out
     _lib.check(lib.la_bias_act_ex_f32(_lib.ptr(x), _lib.ptr(b), _lib.ptr(xref), _lib.ptr(yref), _lib.ptr(dy), _lib.ptr(out), x.numel(), stepb, nb,
                                       grad, act, alpha, gain, clamp, _lib.stream_ptr()), 'bias_act')
     return out
@@ -42,9 +62,14 @@ class _BiasSum(torch.autograd.Function):
     def forward(ctx, dx, stepb, nb):
         lib = _lib.load()
         dx = dx.contiguous()
-        db = torch.empty([nb], device=dx.device, dtype=torch.float32)
+        if dx.dtype in _OWN_DTYPES:
+            db = torch.empty([nb], device=dx.device, dtype=dx.dtype)
+            fn = getattr(lib, 'la_bias_sum_' + _OWN_DTYPES[dx.dtype])
+        else:
+            db = torch.empty([nb], device=dx.device, dtype=torch.float32)
+            fn = lib.la_bias_sum_f32
         if dx.numel():
-            _lib.check(lib.la_bias_sum_f32(_lib.ptr(dx), _lib.ptr(db), dx.numel(), stepb, nb, _lib.stream_ptr()), 'bias_sum')
+            _lib.check(fn(_lib.ptr(dx), _lib.ptr(db), dx.numel(), stepb, nb, _lib.stream_ptr()), 'bias_sum')
         else:
             db.zero_()
         ctx.meta = (tuple(dx.shape), stepb, nb)
@@ -63,11 +88,13 @@ class _BiasAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, b, dim, act, alpha, gain, clamp, ref, has2):
         _lib.require_gpu(x)
-        x = x.contiguous().float()
+        x = _op_input(x)
         stepb, nb = 1, 1
         if b is not None:
             assert b.ndim == 1 and 0 <= dim < x.ndim and b.shape[0] == x.shape[dim]
-            b = b.contiguous().float()
+            if x.dtype in _OWN_DTYPES and b.dtype != x.dtype:
+                raise _lib.LatentAugHipError(f'bias_act: b must have the dtype of x ({x.dtype}), got {b.dtype}')
+            b = b.contiguous() if x.dtype in _OWN_DTYPES else b.contiguous().float()
             nb = x.shape[dim]
             stepb = int(np.prod(x.shape[dim + 1:])) if dim + 1 < x.ndim else 1
         y = _bias_act_launch(x, b, None, None, None, 0, stepb, nb, act, alpha, gain, clamp)
@@ -116,7 +143,8 @@ class _BiasActGrad(torch.autograd.Function):
 
 def bias_act(x, b=None, dim=1, act='linear', alpha=None, gain=None, clamp=None, impl='hip'):
     """Fused bias + activation + gain + clamp (reference: bias_act.py:52-86); every activation of the reference's table, first- and
-    second-order gradients."""
+    second-order gradients.  float16 / float64 x (with b of the same dtype) returns its own dtype; float32 likewise; any other dtype
+    is computed and returned in float32."""
     assert isinstance(x, torch.Tensor)
     assert clamp is None or clamp >= 0
     if act not in _ACTS:
@@ -176,8 +204,14 @@ def _launch_upfirdn2d(x, f, upx, upy, dnx, dny, px0, px1, py0, py1, flip, gain):
     ow = lib.la_upfirdn2d_out_size(w, upx, dnx, px0, px1, fw)
     oh = lib.la_upfirdn2d_out_size(h, upy, dny, py0, py1, fh)
     assert ow >= 1 and oh >= 1
-    y = torch.empty([n, c, oh, ow], device=x.device, dtype=torch.float32)
     fh_ = np.ascontiguousarray(f.numpy(), dtype=np.float32)
+    if x.dtype in _OWN_DTYPES:
+        y = torch.empty([n, c, oh, ow], device=x.device, dtype=x.dtype)
+        fn = getattr(lib, 'la_upfirdn2d_' + _OWN_DTYPES[x.dtype])
+        _lib.check(fn(_lib.ptr(x), fh_.ctypes.data, _lib.ptr(y), n, c, h, w, fh, fw, upx, upy, dnx, dny, px0, px1, py0, py1, int(flip), float(gain),
+                      _lib.stream_ptr()), 'upfirdn2d')
+        return y
+    y = torch.empty([n, c, oh, ow], device=x.device, dtype=torch.float32)
     _lib.check(lib.la_upfirdn2d_f32(_lib.ptr(x), fh_.ctypes.data, _lib.ptr(y), n, c, h, w, fh, fw, upx, upy, dnx, dny,
                                     px0, px1, py0, py1, int(flip), float(gain), _lib.stream_ptr()), 'upfirdn2d')
     return y
@@ -187,7 +221,7 @@ class _Upfirdn2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, f, up, down, padding, flip_filter, gain):
         _lib.require_gpu(x)
-        x = x.contiguous().float()
+        x = _op_input(x)
         ctx.meta = (f, up, down, padding, flip_filter, gain, x.shape)
         return _launch_upfirdn2d(x, f, *up, *down, *padding, flip_filter, gain)
 
@@ -205,7 +239,9 @@ class _Upfirdn2d(torch.autograd.Function):
 
 def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1, impl='hip'):
     """Pad, upsample, filter, downsample (reference: upfirdn2d.py:118-162).  A 1-D (separable) filter runs as one pass per axis,
-    each with the square root of the gain, exactly as the reference's plugin path applies it (upfirdn2d.py:188-201)."""
+    each with the square root of the gain, exactly as the reference's plugin path applies it (upfirdn2d.py:188-201); the intermediate
+    keeps the dtype of the result.  float16 / float32 / float64 x returns its own dtype, any other dtype is computed and returned in
+    float32; the taps are float32 for every dtype (upfirdn2d.cpp:21)."""
     assert isinstance(x, torch.Tensor) and x.ndim == 4
     if f is None:
         f = torch.ones([1, 1], dtype=torch.float32)
