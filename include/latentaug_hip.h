@@ -350,6 +350,18 @@ size_t la_latent_opt_workspace_bytes(int img_resolution, int img_channels, int w
 int la_latent_opt_create(la_synth* g, int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
                          const float* bankW, long Mw, const float* bankXc, long Mx, int max_batch, void* workspace,
                          size_t workspace_bytes, la_latent_opt** out);
+/* The latent space the loop optimises in.  latent_space 0 = W: one w_dim row per sample, broadcast to every style slot (the reference's
+ * broadcasting(), util_latent_aug.py:493-494); the two entries above are these with 0.  1 = W+: one row per sample AND slot, w_opt
+ * [B][num_ws][w_dim] -- the reference's LatentAug.forward (:207-310) with broadcasting() the identity, hard_aug(w, w_tilde) = w_tilde,
+ * smooth_aug(w, w_tilde) = alpha * w_tilde + (1 - alpha) * w row by row; Adam, the criteria and the loss signs unchanged.  For a W+
+ * handle la_latent_opt_run's w0 is [B][num_ws][w_dim] (16-byte aligned), and the buffers of la_latent_opt_set_trace (w_trace) and
+ * la_latent_opt_set_grad_trace (dw_trace) are [steps][B][num_ws][w_dim].  W+ needs w_dim % 4 == 0.  Any other latent_space is
+ * LA_ERR_ARG (create_ex: before anything is allocated or launched; workspace_bytes_ex: 0 bytes). */
+size_t la_latent_opt_workspace_bytes_ex(int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg, long Mw,
+                                        long Mx, int max_batch, int latent_space);
+int la_latent_opt_create_ex(la_synth* g, int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
+                            const float* bankW, long Mw, const float* bankXc, long Mx, int max_batch, int latent_space,
+                            void* workspace, size_t workspace_bytes, la_latent_opt** out);
 void la_latent_opt_destroy(la_latent_opt* h);
 /* attach the discriminator used when cfg.w_disc != 0 (must outlive the loop handle) */
 int la_latent_opt_set_disc(la_latent_opt* h, la_disc* d);
@@ -373,10 +385,11 @@ int la_latent_opt_set_graph(la_latent_opt* h, int enable);
 int la_latent_opt_graph_state(const la_latent_opt* h);
 /* Per-step snapshots for the reference's verbose_log (util_latent_aug.py:292-295 snap_w / snap_img): device buffers (or NULL)
  * w_trace [steps][B][w_dim] = the optimised latent after every step, img_trace [steps][B][C][R][R] = the image synthesised in
- * every step.  While either is set the loop launches eagerly. */
+ * every step (W+ handle: w_trace [steps][B][num_ws][w_dim]).  While either is set the loop launches eagerly. */
 int la_latent_opt_set_trace(la_latent_opt* h, float* w_trace, float* img_trace);
 /* dw_trace [steps][B][w_dim] (device, or NULL) = dL/dw of every step, L = -latent - pix - lpips + disc (util_latent_aug.py:270):
- * the tensor `loss.backward()` leaves in w_opt.grad (:275) before Adam consumes it.  While set the loop launches eagerly. */
+ * the tensor `loss.backward()` leaves in w_opt.grad (:275) before Adam consumes it (W+ handle: [steps][B][num_ws][w_dim]).  While set
+ * the loop launches eagerly. */
 int la_latent_opt_set_grad_trace(la_latent_opt* h, float* dw_trace);
 /* 1 (default): with both the discriminator and the perceptual criterion active, the two run side by side inside a step -- the
  * discriminator branch on the launch stream, crop + feature net forward / backward on a stream of the handle's own, forked after the
@@ -402,7 +415,7 @@ int la_latent_opt_get_times(la_latent_opt* h, float* ms);
  * IMMUTABLE for the life of the handle: their column sums are reduced once (both criterion modes) and every later gradient uses
  * them.  A caller that does rewrite bank contents in place calls this before the next la_latent_opt_run. */
 int la_latent_opt_invalidate_banks(la_latent_opt* h);
-/* w0 [B][w_dim] -> img_out [B][C][R][R], w_aug_out [B][num_ws][w_dim]; losses_out (may be NULL) [steps][4] =
+/* w0 [B][w_dim] (W+ handle: [B][num_ws][w_dim]) -> img_out [B][C][R][R], w_aug_out [B][num_ws][w_dim]; losses_out (may be NULL) [steps][4] =
  * weighted {latent, pix, disc, lpips} per step. */
 int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const float* const* final_noises, float* img_out,
                       float* w_aug_out, float* losses_out, la_stream_t stream);

@@ -92,6 +92,8 @@ SIGNATURES = {
     'la_synth_style_rows': (_I, [_P]),
     'la_latent_opt_workspace_bytes': (_Z, [_I, _I, _I, _P, _L, _L, _I]),
     'la_latent_opt_create': (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _L, _I, _P, _Z, _P]),
+    'la_latent_opt_workspace_bytes_ex': (_Z, [_I, _I, _I, _P, _L, _L, _I, _I]),
+    'la_latent_opt_create_ex': (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _L, _I, _I, _P, _Z, _P]),
     'la_latent_opt_destroy': (None, [_P]),
     'la_latent_opt_run': (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     'la_fc_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _F, _P]),

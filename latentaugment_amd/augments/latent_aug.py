@@ -77,6 +77,9 @@ class LatentAugment(BaseAugment):
         parser.add_argument('--preprocess_aug', type=str, default='center_random_crop', help='window policy of the perceptual criterion: center_crop | random_crop | center_random_crop | original')
         parser.add_argument('--soft_aug', type=bool, default=False, help='return a blend of the inverted and the moved latent (see --alpha)')
         parser.add_argument('--verbose_log', type=bool, default=False, help='log losses / times of the first batch and write its snapshots')
+        # (this package's own option; the reference optimises in W only)
+        parser.add_argument('--latent_space', type=str, default='w', choices=['w', 'w+'],
+                            help="space the latent is optimised in: 'w' = one row broadcast to every style slot, 'w+' = one row per slot")
         return parser
 
     def __init__(self, opt):
@@ -90,6 +93,7 @@ class LatentAugment(BaseAugment):
         self.p_thres = opt.p_thres
         self.init_w = opt.init_w
         self.verbose_log = opt.verbose_log
+        self.latent_space = getattr(opt, 'latent_space', 'w')
         self.stats_time = []
 
         if self.phase == 'train':
@@ -156,7 +160,13 @@ class LatentAugment(BaseAugment):
         return {'w': w.detach().cpu().numpy().squeeze(), 'paths': '' if self.rand_aug else self.fname}
 
     def get_latent_output(self):
+        """W: the augmented latent's row 0 ([B, w_dim] after the squeeze); W+ (and rand_aug's mapped latents): [B, num_ws, w_dim]."""
+        if self._wplus():
+            return self._latent_dict(self.w_AB_aug)
         return self._latent_dict(reverse_broadcasting(self.w_AB_aug))
+
+    def _wplus(self):
+        return self.latent_space == 'w+' and not self.rand_aug
 
     def get_latent_input(self):
         return self._latent_dict(self.w_AB)
@@ -201,13 +211,22 @@ class LatentAugment(BaseAugment):
         return torch.randn([self.batch_size, self.z_dim])
 
     def sample_from_inversion(self, fname):
-        """Per-file inverted latent -> [len(fname), 1, w_dim] (reference :310-324; sized by the actual batch)."""
+        """Per-file inverted latent -> [len(fname), 1, w_dim] (reference :310-324; sized by the actual batch).  W+ (--latent_space w+):
+        [len(fname), num_ws, w_dim], the whole code of each file; a [w_dim] or [1, w_dim] code is broadcast to every row."""
         rows = []
         for fn in fname:
             code = np.asarray(self.stats_dataset_w.lookup(fn), dtype=np.float32)
-            rows.append(code.reshape(-1, self.w_dim)[:1])          # W space: row 0 of a [num_ws, w_dim] code, or the [w_dim] code itself
+            if not self._wplus():
+                rows.append(code.reshape(-1, self.w_dim)[:1])      # W space: row 0 of a [num_ws, w_dim] code, or the [w_dim] code itself
+                continue
+            if code.shape in ((self.w_dim,), (1, self.w_dim)):
+                code = np.broadcast_to(code.reshape(1, self.w_dim), (self.num_ws, self.w_dim))
+            elif code.shape != (self.num_ws, self.w_dim):
+                raise ValueError(f'latent_space w+: the inverted latent of {fn!r} has shape {code.shape}; expected '
+                                 f'[{self.num_ws}, {self.w_dim}], [1, {self.w_dim}] or [{self.w_dim}]')
+            rows.append(code)
         w = torch.from_numpy(np.ascontiguousarray(np.stack(rows)))
-        assert w.shape == (len(fname), 1, self.w_dim)
+        assert w.shape == (len(fname), self.num_ws if self._wplus() else 1, self.w_dim)
         return w
 
 

@@ -26,6 +26,13 @@ int la_step_advance(int* ctr, hipStream_t stream);
 int la_step_tail(const float* dws, const float* colsumW, float* dw, float* p, float* m, float* v, int B, int num_ws, int wdim, float lat2,
                  float mrows, float lr, float beta1, float beta2, float eps, const float* tab, int* ctr, int* ticket, hipStream_t stream);
 void la_adam_fill_table(float* tab_host, int steps, float beta1, float beta2);
+// W+ loop (la_wplus.hip): the step tail without the sum over the slots, and the gate without the broadcast; all of
+// [B][num_ws][w_dim], w_dim % 4 == 0, 16-byte aligned buffers
+int la_wplus_step_tail(const float* dws, const float* colsumW, float* dw, float* p, float* m, float* v, int B, int num_ws, int wdim,
+                       float lat2, float mrows, float lr, float beta1, float beta2, float eps, const float* tab, int* ctr, int* ticket,
+                       hipStream_t stream);
+int la_wplus_gate(const float* w_opt, const float* w0, float* w_aug, int B, int num_ws, int wdim, float alpha, int soft,
+                  hipStream_t stream);
 extern "C" {
 long la_pairwise_l2_workspace_floats(int n, long m);
 int la_pairwise_l2_f32(const float* X, int n, const float* Y, long m, long K, float* D, float* mean_out,

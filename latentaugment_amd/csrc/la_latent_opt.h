@@ -24,6 +24,12 @@ size_t la_latent_opt_workspace_bytes(int img_resolution, int img_channels, int w
 int la_latent_opt_create(la_synth* g, int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
                          const float* bankW, long Mw, const float* bankXc, long Mx, int max_batch, void* workspace,
                          size_t workspace_bytes, la_latent_opt** out);
+// latent_space: 0 W (the forms above), 1 W+ (la_wplus.hip)
+size_t la_latent_opt_workspace_bytes_ex(int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg, long Mw,
+                                        long Mx, int max_batch, int latent_space);
+int la_latent_opt_create_ex(la_synth* g, int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
+                            const float* bankW, long Mw, const float* bankXc, long Mx, int max_batch, int latent_space,
+                            void* workspace, size_t workspace_bytes, la_latent_opt** out);
 void la_latent_opt_destroy(la_latent_opt* h);
 struct la_disc;
 int la_latent_opt_set_disc(la_latent_opt* h, la_disc* d);

@@ -1,6 +1,7 @@
 // The latent-optimisation loop: LatentAug.forward (augments/utils/util_latent_aug.py:207-310) as one host-driven
 // launch sequence with no host<->device synchronisation inside the loop (the reference syncs 5x per step through
-// `.item()`, :234-271).  W-space optimisation: ws = w repeated num_ws times (:226, :493-494).
+// `.item()`, :234-271).  W-space optimisation: ws = w repeated num_ws times (:226, :493-494); a W+ handle (la_latent_opt_create_ex,
+// latent_space 1) optimises one row per slot instead (la_wplus.hip).
 #include "la_latent_opt.h"
 
 #include <math.h>
@@ -17,6 +18,7 @@ struct la_latent_opt {
     la_disc* d;
     la_opt_config cfg;
     int R, imgc, wdim, num_ws, maxB;
+    int wplus;              // latent space: 0 W (w_opt [B][w_dim], broadcast to the slots), 1 W+ (w_opt [B][num_ws][w_dim], la_wplus.hip)
     const float* bankW; long Mw;
     const float* bankX; long Mx;     // [imgc][Mx][cc*cc]
     float *w_opt, *m, *v, *dw, *dws, *g_img, *colsumW, *colsumX, *yx, *yy, *xx, *xc, *losses;
@@ -34,7 +36,7 @@ struct la_latent_opt {
     int adam_tab_valid;
     int* step_ctr;          // device (16 ints: [0] counter, [4..5] crop_dev, [8] ticket of la_step_tail)
     int* crop_dev;          // device {y0, x0}
-    float* trace_dw;        // optional [steps][B][w_dim]: dL/dw of every step (la_latent_opt_set_grad_trace); forces eager launches
+    float* trace_dw;        // optional [steps][B][w_dim] (W+: [steps][B][num_ws][w_dim]): dL/dw of every step (la_latent_opt_set_grad_trace); forces eager launches
     int graph_mode;         // 0 eager, 1 replay a captured step (default)
     int graph_B;            // batch the captured step was built for (0: none)
     int graph_win;          // ... and whether its synthesis passes were windowed
@@ -47,7 +49,7 @@ struct la_latent_opt {
     hipGraphExec_t seg_exec[4];
     int seg_valid;
     hipStream_t cap_stream; // capture needs a non-default stream; the replay goes to the caller's stream
-    float* trace_w;         // optional [steps][B][w_dim]: the latent after every step (verbose_log snapshots); forces eager launches
+    float* trace_w;         // optional [steps][B][w_dim] (W+: [steps][B][num_ws][w_dim]): the latent after every step (verbose_log snapshots); forces eager launches
     float* trace_img;       // optional [steps][B][C][R][R]: the image synthesised in every step
     // Independent image criteria side by side (round 4): the discriminator branch on the launch stream, the perceptual branch (crop,
     // feature net forward + backward) on a side stream, forked after the synthesis forward and joined before the crop gradient is
@@ -70,7 +72,8 @@ static size_t carve(la_latent_opt* h, char* base) {
     size_t off = 0;
     auto take = [&](size_t n) { float* p = base ? (float*)(base + off) : nullptr; off += al(n); return p; };
     const size_t B = h->maxB, wd = h->wdim, cc2 = (size_t)h->cfg.crop * h->cfg.crop;
-    h->w_opt = take(B * wd); h->m = take(B * wd); h->v = take(B * wd); h->dw = take(B * wd);
+    const size_t wl = h->wplus ? (size_t)h->num_ws * wd : wd;      // floats of one sample's optimised latent
+    h->w_opt = take(B * wl); h->m = take(B * wl); h->v = take(B * wl); h->dw = take(B * wl);
     h->dws = take(B * h->num_ws * wd);
     h->g_img = take(B * h->imgc * (size_t)h->R * h->R);
     h->colsumW = take((size_t)h->num_ws * wd);
@@ -85,18 +88,33 @@ static size_t carve(la_latent_opt* h, char* base) {
     return off;
 }
 
-extern "C" size_t la_latent_opt_workspace_bytes(int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
-                                                long Mw, long Mx, int max_batch) {
-    if (!cfg) return 0;
+// latent_space: 0 W, 1 W+ (anything else: 0 bytes, and la_latent_opt_create_ex refuses it)
+extern "C" size_t la_latent_opt_workspace_bytes_ex(int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
+                                                   long Mw, long Mx, int max_batch, int latent_space) {
+    if (!cfg || (latent_space != 0 && latent_space != 1)) return 0;
     la_latent_opt h; memset(&h, 0, sizeof(h));
     h.cfg = *cfg; h.R = img_resolution; h.imgc = img_channels; h.wdim = w_dim; h.num_ws = la_synth_num_ws(img_resolution);
-    h.maxB = max_batch; h.Mw = Mw; h.Mx = Mx;
+    h.maxB = max_batch; h.Mw = Mw; h.Mx = Mx; h.wplus = latent_space;
     return carve(&h, nullptr);
+}
+
+extern "C" size_t la_latent_opt_workspace_bytes(int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
+                                                long Mw, long Mx, int max_batch) {
+    return la_latent_opt_workspace_bytes_ex(img_resolution, img_channels, w_dim, cfg, Mw, Mx, max_batch, 0);
 }
 
 extern "C" int la_latent_opt_create(la_synth* g, int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
                                     const float* bankW, long Mw, const float* bankXc, long Mx, int max_batch,
                                     void* workspace, size_t workspace_bytes, la_latent_opt** out) {
+    return la_latent_opt_create_ex(g, img_resolution, img_channels, w_dim, cfg, bankW, Mw, bankXc, Mx, max_batch, 0, workspace,
+                                   workspace_bytes, out);
+}
+
+extern "C" int la_latent_opt_create_ex(la_synth* g, int img_resolution, int img_channels, int w_dim, const la_opt_config* cfg,
+                                       const float* bankW, long Mw, const float* bankXc, long Mx, int max_batch, int latent_space,
+                                       void* workspace, size_t workspace_bytes, la_latent_opt** out) {
+    LA_CHECK_ARG(latent_space == 0 || latent_space == 1, "latent_opt_create: latent_space must be 0 (W) or 1 (W+)");
+    LA_CHECK_ARG(latent_space == 0 || w_dim % 4 == 0, "latent_opt_create: W+ needs w_dim % 4 == 0");
     LA_CHECK_ARG(g && cfg && workspace && out, "latent_opt_create: null pointer");
     LA_CHECK_ARG(cfg->steps >= 0, "latent_opt_create: negative step count");
     LA_CHECK_ARG(cfg->w_latent == 0.f || (bankW && Mw >= 1), "latent_opt_create: w_latent > 0 needs the latent bank W");
@@ -108,7 +126,7 @@ extern "C" int la_latent_opt_create(la_synth* g, int img_resolution, int img_cha
     LA_CHECK_ARG(h, "latent_opt_create: out of host memory");
     memset(h, 0, sizeof(*h));
     h->g = g; h->cfg = *cfg; h->R = img_resolution; h->imgc = img_channels; h->wdim = w_dim;
-    h->num_ws = la_synth_num_ws(img_resolution); h->maxB = max_batch;
+    h->num_ws = la_synth_num_ws(img_resolution); h->maxB = max_batch; h->wplus = latent_space;
     h->bankW = bankW; h->Mw = cfg->w_latent != 0.f ? Mw : 0; h->bankX = bankXc; h->Mx = cfg->w_pix != 0.f ? Mx : 0;
     const size_t need = carve(h, (char*)workspace);
     if (need > workspace_bytes) { free(h); la_set_error("latent_opt_create: workspace too small"); return LA_ERR_WORKSPACE; }
@@ -336,7 +354,7 @@ extern "C" int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const
     LA_CHECK_ARG(c.final_noise_mode != 2 || final_noises, "latent_opt_run: explicit final noise requested but not given");
     const int wd = h->wdim, cc = c.crop, off = c.crop_off;
     const long cc2 = (long)cc * cc;
-    const long nw = (long)B * wd;
+    const long nw = (long)B * wd * (h->wplus ? h->num_ws : 1);      // floats of the optimised latents (and of one trace step)
     const float nb = (float)(c.norm_batch > 0 ? c.norm_batch : B);
     int rc;
     LA_HIP(hipMemcpyAsync(h->w_opt, w0, nw * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -410,12 +428,14 @@ extern "C" int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const
         const float* img = la_synth_image(h->g);      // (the loop's image buffer: fixed per handle, also before the first pass)
         if (segA) {
             mark(0);
-            if ((rc = la_synth_forward(h->g, h->w_opt, wd, 0, B, c.loop_noise_mode, nullptr, nullptr, st))) return rc;
+            // W: one row per sample read by every slot (ws = broadcasting(w_opt)); W+: the sample's own row per slot
+            const long wb = h->wplus ? (long)h->num_ws * wd : wd, wl = h->wplus ? wd : 0;
+            if ((rc = la_synth_forward(h->g, h->w_opt, wb, wl, B, c.loop_noise_mode, nullptr, nullptr, st))) return rc;
             img = la_synth_image(h->g);
             mark(1);
             if (L) {
-                if (h->Mw && (rc = la_l2_mean_from_bank(h->bankW, h->Mw, (long)h->num_ws * wd, h->w_opt, B, wd, wd, h->yx, h->yy,
-                                                        h->xx, lat_coef, L + 0, 0, st)))
+                if (h->Mw && (rc = la_l2_mean_from_bank(h->bankW, h->Mw, (long)h->num_ws * wd, h->w_opt, B, wb, h->wplus ? 0 : wd, h->yx,
+                                                        h->yy, h->xx, lat_coef, L + 0, 0, st)))
                     return rc;
             }
             // brackets of the per-criterion timers (la_latent_opt_get_times): [1,2) latent loss scalar, [2,3) pixel loss scalar + gradient,
@@ -489,9 +509,13 @@ extern "C" int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const
             dws = h->dws;
         } else if (segZ) { mark(3); mark(4); mark(5); }
         if (!segZ) return LA_OK;
-        // dw = sum_ws dws + latent gradient, Adam, step counter: one launch (la_step_tail)
-        rc = la_step_tail(dws, h->Mw ? h->colsumW : nullptr, h->dw, h->w_opt, h->m, h->v, B, h->num_ws, wd, -2.f * lat_coef, (float)h->Mw,
-                          c.lr, c.beta1, c.beta2, c.eps, h->adam_tab, h->step_ctr, h->step_ctr + 8, st);
+        // dw = sum_ws dws + latent gradient, Adam, step counter: one launch (la_step_tail; W+: la_wplus_step_tail, no sum over the slots)
+        if (h->wplus)
+            rc = la_wplus_step_tail(dws, h->Mw ? h->colsumW : nullptr, h->dw, h->w_opt, h->m, h->v, B, h->num_ws, wd, -2.f * lat_coef,
+                                    (float)h->Mw, c.lr, c.beta1, c.beta2, c.eps, h->adam_tab, h->step_ctr, h->step_ctr + 8, st);
+        else
+            rc = la_step_tail(dws, h->Mw ? h->colsumW : nullptr, h->dw, h->w_opt, h->m, h->v, B, h->num_ws, wd, -2.f * lat_coef, (float)h->Mw,
+                              c.lr, c.beta1, c.beta2, c.eps, h->adam_tab, h->step_ctr, h->step_ctr + 8, st);
         mark(6);
         return rc;
     };
@@ -550,7 +574,9 @@ extern "C" int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const
             if (h->trace_dw) LA_HIP(hipMemcpyAsync(h->trace_dw + (size_t)(step - 1) * nw, h->dw, sizeof(float) * nw, hipMemcpyDeviceToDevice, stream));
         }
     }
-    if ((rc = la_broadcast_mix(h->w_opt, w0, w_aug_out, B, h->num_ws, wd, c.alpha, c.soft_aug, stream))) return rc;
+    if ((rc = h->wplus ? la_wplus_gate(h->w_opt, w0, w_aug_out, B, h->num_ws, wd, c.alpha, c.soft_aug, stream)
+                       : la_broadcast_mix(h->w_opt, w0, w_aug_out, B, h->num_ws, wd, c.alpha, c.soft_aug, stream)))
+        return rc;
     if ((rc = la_synth_set_row_window(h->g, 0, 0)) || (rc = la_synth_set_col_window(h->g, 0, 0))) return rc;      // the augmented image: a whole frame
     if ((rc = la_synth_forward(h->g, w_aug_out, (long)h->num_ws * wd, wd, B, c.final_noise_mode, final_noises, img_out, stream)))
         return rc;

@@ -169,6 +169,9 @@ class InMemoryLatentCodes:
         return np.asarray(self.codes[fname], dtype=np.float32)
 
 
+LATENT_SPACES = {'w': 0, 'w+': 1}      # opt.latent_space -> latent_space of la_latent_opt_create_ex
+
+
 class LatentAug:
     def __init__(self, phase, opt, save_dir, gpu_ids, generator=None, discriminator=None, banks=None, latent_codes=None,
                  feature_net=None, group=None, _shared=None):
@@ -202,6 +205,13 @@ class LatentAug:
         # (3 fp16 MFMAs per product, fp32 accumulate); 'bf16x3' = 3 bf16 terms (6 MFMAs, no range scaling needed).  Both pass
         # every fp32 parity test at unchanged tolerances.  'f32' = exact fp32 MFMA; 'bf16x2' approximate.
         self.precision = getattr(opt, 'precision', 'f16x2')
+        # latent space of the optimisation: 'w' (default, the reference's: one row per sample, broadcast to every style slot) or 'w+'
+        # (one row per sample and slot: broadcasting() the identity, hard_aug / smooth_aug row by row -- DESIGN.md 'W+')
+        space = getattr(opt, 'latent_space', None)
+        self.latent_space = 'w' if space is None else str(space).lower()
+        if self.latent_space not in LATENT_SPACES:
+            raise _lib.LatentAugHipError(f'opt.latent_space = {space!r}: expected one of {sorted(LATENT_SPACES)}')
+        self.wplus = self.latent_space == 'w+'
         self._script_path = None
         if self.w_lpips > 0 and feature_net is None:
             # the reference's default perceptual net (`lpips_script`): NVIDIA's TorchScript vgg16.pt, fetched from a URL by load_vgg()
@@ -300,13 +310,14 @@ class LatentAug:
                              final_noise_mode={'none': 0, 'const': 1, 'random': 2}[self.final_noise_mode],
                              norm_batch=int(getattr(opt, 'norm_batch', 0) or 0), crop=crop, crop_off=off)
         self._cfg = cfg
-        nbytes = lib.la_latent_opt_workspace_bytes(self.res, self.engine.img_channels, self.w_dim, C.byref(cfg), Mw, Mx,
-                                                   max_local)
+        space = LATENT_SPACES[self.latent_space]
+        nbytes = lib.la_latent_opt_workspace_bytes_ex(self.res, self.engine.img_channels, self.w_dim, C.byref(cfg), Mw, Mx,
+                                                      max_local, space)
         self._workspace = torch.empty([max(nbytes, 64)], dtype=torch.uint8, device=self.device)
         h = C.c_void_p()
-        _lib.check(lib.la_latent_opt_create(self.engine.handle, self.res, self.engine.img_channels, self.w_dim,
-                                            C.byref(cfg), _lib.ptr(self.W), Mw, _lib.ptr(self.Xc), Mx, max_local,
-                                            _lib.ptr(self._workspace), self._workspace.numel(), C.byref(h)),
+        _lib.check(lib.la_latent_opt_create_ex(self.engine.handle, self.res, self.engine.img_channels, self.w_dim,
+                                               C.byref(cfg), _lib.ptr(self.W), Mw, _lib.ptr(self.Xc), Mx, max_local, space,
+                                               _lib.ptr(self._workspace), self._workspace.numel(), C.byref(h)),
                    'la_latent_opt_create')
         self._h = h
         self._max_local = max_local
@@ -452,11 +463,17 @@ class LatentAug:
         off = self.center_off if self.preprocess in ('center_crop', 'center_random_crop') else 0
         return off + int(x1), off + int(y1)
 
+    @property
+    def latent_rows(self):
+        """Rows of one sample's optimised latent: 1 in W space, num_ws in W+."""
+        return self.num_ws if self.wplus else 1
+
     def run_local(self, w, final_noises=None, want_losses=False, crop_pos=None, trace=None, out=None):
-        """w [b,1,w_dim] on this device -> (img [b,C,R,R], w_aug [b,num_ws,w_dim], losses or None).
+        """w [b,1,w_dim] on this device (W+: [b,num_ws,w_dim]) -> (img [b,C,R,R], w_aug [b,num_ws,w_dim], losses or None).
         out (optional): (img, w_aug) tensors to fill instead of allocating them on the current stream.
-        trace (optional): dict that receives the per-step snapshots 'w' [steps,b,w_dim] (latent after the step) and 'img'
-        [steps,b,C,R,R]; trace['want'] (default ('w', 'img')) selects them, and may name 'grad' [steps,b,w_dim] = dL/dw."""
+        trace (optional): dict that receives the per-step snapshots 'w' [steps,b,w_dim] (latent after the step; W+:
+        [steps,b,num_ws,w_dim]) and 'img' [steps,b,C,R,R]; trace['want'] (default ('w', 'img')) selects them, and may name 'grad'
+        (dL/dw, the shape of 'w')."""
         if self.feat is not None:
             if crop_pos is None:
                 crop_pos = getattr(self, 'crop_params', None)
@@ -465,7 +482,8 @@ class LatentAug:
             _lib.check(self._lib.la_latent_opt_set_crop_pos(self._h, ax, ay), 'la_latent_opt_set_crop_pos')
         w = w.to(device=self.device, dtype=torch.float32).contiguous()
         b = w.shape[0]
-        assert w.ndim == 3 and w.shape[1:] == (1, self.w_dim)
+        assert w.ndim == 3 and w.shape[1:] == (self.latent_rows, self.w_dim), \
+            f'latent_space {self.latent_space!r} takes w [b, {self.latent_rows}, {self.w_dim}], got {tuple(w.shape)}'
         if out is not None:
             img, w_aug = out
             assert img.shape == (b, self.engine.img_channels, self.res, self.res) and w_aug.shape == (b, self.num_ws, self.w_dim)
@@ -482,11 +500,12 @@ class LatentAug:
         tw = ti = tg = None
         want_img = trace is not None and 'img' in trace.get('want', ('w', 'img'))
         if trace is not None and self.num_epochs > 0:
-            tw = torch.empty([self.num_epochs, b, self.w_dim], device=self.device, dtype=torch.float32)
+            wshape = [self.num_epochs, b] + ([self.num_ws] if self.wplus else []) + [self.w_dim]
+            tw = torch.empty(wshape, device=self.device, dtype=torch.float32)
             if want_img:
                 ti = torch.empty([self.num_epochs, b, self.engine.img_channels, self.res, self.res], device=self.device, dtype=torch.float32)
             if 'grad' in trace.get('want', ()):
-                tg = torch.empty([self.num_epochs, b, self.w_dim], device=self.device, dtype=torch.float32)
+                tg = torch.empty(wshape, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             if tw is not None:
                 _lib.check(self._lib.la_latent_opt_set_trace(self._h, _lib.ptr(tw), _lib.ptr(ti)), 'la_latent_opt_set_trace')
@@ -771,9 +790,9 @@ class LatentAug:
         return self._mapping
 
     def z_to_w(self, z):
-        """reference :459-464: w = reverse_broadcasting(G.mapping(z, None, truncation_psi))."""
+        """reference :459-464: w = reverse_broadcasting(G.mapping(z, None, truncation_psi)); in W+ the mapping's per-row output."""
         ws = self.mapping.forward(z.to(self.device), self.num_ws, self.truncation_psi)
-        return self.reverse_broadcasting(ws)
+        return ws if self.wplus else self.reverse_broadcasting(ws)
 
     def forward_ganrand(self, z, noises=None):
         """reference :202-205: w_aug = G.mapping(z, c=None, truncation_psi); img = G.synthesis(w_aug)  (rand_aug mode)."""
