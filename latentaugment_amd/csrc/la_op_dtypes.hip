@@ -4,7 +4,7 @@
 //   float16: half storage, fp32 arithmetic, one rounding on store (the plugin's InternalType<half> = float); scalar fp32 math with
 //            conversions to and from half only (no packed arithmetic, see the Makefile)
 //   float64: double storage and arithmetic, double scalars (the parity target, the reference's impl='ref' path, applies gain / alpha /
-//            clamp as Python doubles)
+//            clamp of bias_act as Python doubles; upfirdn2d's gain is folded into the float32 taps first, see fir_op_fill)
 #include "la_common.h"
 
 #include <hip/hip_fp16.h>
@@ -420,9 +420,12 @@ static int fir_op_fill(LaFirOpArgs<T>& a, const T* in, T* out, int B, int C, int
     a.Hin = Hin; a.Win = Win; a.Wout = (upW - fw + dnx) / dnx; a.Hout = (upH - fh + dny) / dny;
     a.upx = upx; a.upy = upy; a.dnx = dnx; a.dny = dny; a.padx0 = padx0; a.pady0 = pady0;
     a.fw = fw; a.fh = fh;
-    for (int i = 0; i < fh; ++i)      // (float32 host taps widened exactly, times the gain in A)
+    // (the gain goes onto the float32 host taps IN float32 and the product is widened exactly: upfirdn2d.py:196-197 multiplies the float32
+    //  filter tensor by the gain before converting it to the dtype of x, so a float64 call sees a non-power-of-two gain rounded to float32)
+    const float gain32 = (float)gain;
+    for (int i = 0; i < fh; ++i)
         for (int j = 0; j < fw; ++j)
-            a.f[i * fw + j] = gain * (A)(flip_filter ? f_host[i * fw + j] : f_host[(fh - 1 - i) * fw + (fw - 1 - j)]);
+            a.f[i * fw + j] = (A)(gain32 * (flip_filter ? f_host[i * fw + j] : f_host[(fh - 1 - i) * fw + (fw - 1 - j)]));
     return LA_OK;
 }
 

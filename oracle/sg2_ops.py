@@ -107,7 +107,9 @@ def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1.0):
     # 2. pad (negative = crop)
     x = F.pad(x, [px0, px1, py0, py1])
     # 3. FIR.  True convolution unless flip_filter; conv2d correlates, hence the flip.
-    f = f.to(x.dtype) * (gain ** (f.ndim / 2))
+    #    The gain goes onto the taps in THEIR dtype (float32 from setup_filter), and only then are they widened (:196-197): in float64
+    #    a gain that is not a power of two reaches the result rounded to float32.
+    f = (f * (gain ** (f.ndim / 2))).to(x.dtype)
     if not flip_filter:
         f = f.flip(list(range(f.ndim)))
     if f.ndim == 2:
