@@ -43,16 +43,7 @@ SIGNATURES = {
     'la_abi_version': (_I, []),
     'la_bias_act_f32': (_I, [_P, _P, _P, _L, _L, _I, _I, _F, _F, _F, _P]),
     'la_bias_act_grad_f32': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _F, _F, _F, _P]),
-    'la_bias_act_ex_f32': (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _F, _F, _F, _P]),
-    'la_bias_sum_f32': (_I, [_P, _P, _L, _L, _I, _P]),
-    'la_bias_act_ex_f16': (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _F, _F, _F, _P]),
-    'la_bias_sum_f16': (_I, [_P, _P, _L, _L, _I, _P]),
-    'la_bias_act_ex_f64': (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _D, _D, _D, _P]),
-    'la_bias_sum_f64': (_I, [_P, _P, _L, _L, _I, _P]),
     'la_upfirdn2d_out_size': (_I, [_I] * 6),
-    'la_upfirdn2d_f32': (_I, [_P, _P, _P] + [_I] * 15 + [_F, _P]),
-    'la_upfirdn2d_f16': (_I, [_P, _P, _P] + [_I] * 15 + [_F, _P]),
-    'la_upfirdn2d_f64': (_I, [_P, _P, _P] + [_I] * 15 + [_D, _P]),
     'la_filtered_lrelu_f32': (_I, [_P] * 7 + [_I] * 16 + [_F, _F, _F, _I, _I, _P]),
     'la_filtered_lrelu_act_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P]),
     'la_filtered_lrelu_out_size': (_I, [_I] * 7),
@@ -143,6 +134,12 @@ SIGNATURES = {
     'la_prof_num_classes': (_I, []),
     'la_prof_end_classes': (_I, [_P, _P, _P, _P, _I]),
 }
+
+# the op layer's per-dtype entries: one row each, the scalars (alpha / gain / clamp) double for float64 and float otherwise
+for _sfx, _S in (('f16', _F), ('f32', _F), ('f64', _D)):
+    SIGNATURES['la_bias_act_ex_' + _sfx] = (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _S, _S, _S, _P])
+    SIGNATURES['la_bias_sum_' + _sfx] = (_I, [_P, _P, _L, _L, _I, _P])
+    SIGNATURES['la_upfirdn2d_' + _sfx] = (_I, [_P, _P, _P] + [_I] * 15 + [_S, _P])
 
 _lib = None
 LOADED_PATH = None

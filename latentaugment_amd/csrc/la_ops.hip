@@ -1,23 +1,28 @@
-// float16 and float64 forms of the op layer's bias_act, bias_sum and upfirdn2d: what the reference's plugins instantiate with
-// AT_DISPATCH_FLOATING_TYPES_AND_HALF (bias_act.cpp:77, upfirdn2d.cpp:63).  The float32 entries and their kernels (la_misc.hip,
-// la_upfirdn2d.hip) are the product path and stay as they are; this file holds the other two storage types only.
+// The op layer's bias_act, bias_sum and upfirdn2d over a storage type T and an arithmetic type A, instantiated for the three dtypes the
+// reference's plugins dispatch with AT_DISPATCH_FLOATING_TYPES_AND_HALF (bias_act.cpp:77, upfirdn2d.cpp:63):
 //   float16: half storage, fp32 arithmetic, one rounding on store (the plugin's InternalType<half> = float); scalar fp32 math with
 //            conversions to and from half only (no packed arithmetic, see the Makefile)
+//   float32: float storage and arithmetic (bias_act and bias_sum here; la_upfirdn2d_f32 is la_upfirdn2d.hip's, with the product path's
+//            4x4 kernels)
 //   float64: double storage and arithmetic, double scalars (the parity target, the reference's impl='ref' path, applies gain / alpha /
-//            clamp of bias_act as Python doubles; upfirdn2d's gain is folded into the float32 taps first, see fir_op_fill)
-#include "la_common.h"
+//            clamp of bias_act as Python doubles; upfirdn2d's gain is folded into the float32 taps first, see la_fir_setup)
+// The SG2 path's own linear / relu / lrelu forms of bias_act (la_bias_act_f32, la_bias_act_grad_f32) are in la_misc.hip.
+#include "la_upfirdn2d.h"
 
 #include <hip/hip_fp16.h>
 #include <type_traits>
 
 template <class T> struct LaOpType;
 template <> struct LaOpType<__half> { typedef float A; };
+template <> struct LaOpType<float> { typedef float A; };
 template <> struct LaOpType<double> { typedef double A; };
 
 __device__ __forceinline__ float la_op_load(__half v) { return __half2float(v); }
+__device__ __forceinline__ float la_op_load(float v) { return v; }
 __device__ __forceinline__ double la_op_load(double v) { return v; }
 template <class T> __device__ __forceinline__ T la_op_store(typename LaOpType<T>::A v);
 template <> __device__ __forceinline__ __half la_op_store<__half>(float v) { return __float2half(v); }      // (round to nearest even)
+template <> __device__ __forceinline__ float la_op_store<float>(float v) { return v; }
 template <> __device__ __forceinline__ double la_op_store<double>(double v) { return v; }
 
 __device__ __forceinline__ float la_op_exp(float v) { return expf(v); }
@@ -30,7 +35,14 @@ __device__ __forceinline__ float la_op_tanh(float v) { return tanhf(v); }
 __device__ __forceinline__ double la_op_tanh(double v) { return tanh(v); }
 
 // ------------------------------------------------------------------------------------------------------------
-// bias_act: la_bias_act_full_kernel (la_misc.hip) over storage T, arithmetic A -- the same activation table, the same grad 0 / 1 / 2 forms
+// The general bias_act op: the plugin entry point  bias_act(x, b, xref, yref, dy, grad, dim, act, alpha, gain, clamp)  of the reference
+// (bias_act.cpp:32; activation table bias_act.py:20-30: linear, relu, lrelu, tanh, sigmoid, elu, selu, softplus, swish = ids 1..9) with
+// all three values of `grad`:
+//   grad 0:  out = clamp(f(x + b) * gain)                         (dy, if given, multiplies before the clamp, as the plugin does)
+//   grad 1:  out = x * f'  * gain * dy,  zero where |yref| >= clamp      (x = the incoming gradient, f' from yref / gain or xref + b)
+//   grad 2:  out = x * f'' * gain * dy,  zero where |yref| >= clamp      (x = the gradient of the gradient)
+// Value, first and second derivative of each activation, the derivatives written in what the reference saves for it -- the OUTPUT
+// (bias_act.py `ref='y'`) or, for swish, the INPUT (`ref='x'`).
 #define LA_OP_SELU_SCALE 1.0507009873554804934193349852946
 #define LA_OP_SELU_ALPHA 1.6732632423543772848170429916717
 template <class A>
@@ -60,7 +72,7 @@ __device__ __forceinline__ void la_op_act_derivs(int act, A r, A alpha, A& d1, A
         case 6: d1 = r >= zero ? one : r + one; d2 = r >= zero ? zero : r + one; break;
         case 7: d1 = r >= zero ? (A)LA_OP_SELU_SCALE : r + sa; d2 = r >= zero ? zero : r + sa; break;
         case 8: { const A e = la_op_exp(-r); d1 = one - e; d2 = e * (one - e); break; }
-        case 9: {      // r = the pre-activation (as la_actfull_derivs)
+        case 9: {      // r = the pre-activation: sigma = 1 / (1 + e^-r);  f' = sigma (1 + r (1 - sigma));  f'' = sigma (1 - sigma) (2 + r (1 - 2 sigma))
             const A sg = one / (one + la_op_exp(-r));
             d1 = sg * (one + r * (one - sg));
             d2 = sg * (one - sg) * (two + r * (one - two * sg));
@@ -108,7 +120,7 @@ __device__ __forceinline__ typename LaOpType<T>::A la_op_bias_act_one(const LaBi
     return v;
 }
 
-// one work item = V = 16 / sizeof(T) consecutive elements (8 halves / 2 doubles): one 16-byte load per operand and one 16-byte store
+// one work item = V = 16 / sizeof(T) consecutive elements (8 halves / 4 floats / 2 doubles): one 16-byte load per operand and one 16-byte store
 template <class T, int V>
 struct alignas(16) LaOpVec { T v[V]; };
 
@@ -165,7 +177,8 @@ __device__ __forceinline__ typename LaOpType<T>::A la_op_block_sum_256(typename 
     return red[0] + red[1] + red[2] + red[3];
 }
 
-// db[c] = sum of dx over every axis but the bias axis, accumulated in A, one rounding into db (la_bias_grad_kernel's shape)
+// db[c] = sum of dx over every axis but the bias axis (bias_act.py:187, :206), accumulated in A, one rounding into db: element i belongs
+// to channel (i / stepb) % nb, one block per channel
 template <class T>
 __global__ __launch_bounds__(256) void la_bias_sum_op_kernel(const T* __restrict__ dx, T* __restrict__ db, long n, long stepb, int nb) {
     typedef typename LaOpType<T>::A A;
@@ -181,15 +194,14 @@ __global__ __launch_bounds__(256) void la_bias_sum_op_kernel(const T* __restrict
     if (threadIdx.x == 0) db[c] = la_op_store<T>(t);
 }
 
-static float la_op_round(float v) { return __half2float(__float2half(v)); }      // (host) v as float16 holds it
-static double la_op_round(double v) { return v; }
+template <class T> static typename LaOpType<T>::A la_op_round(typename LaOpType<T>::A v) { return v; }      // (host) v as storage type T holds it
+template <> float la_op_round<__half>(float v) { return __half2float(__float2half(v)); }
 
 template <class T>
 static int bias_act_op(const T* x, const T* b, const T* xref, const T* yref, const T* dy, T* out, long n, long stepb, int nb, int grad,
                        int act, typename LaOpType<T>::A alpha, typename LaOpType<T>::A gain, typename LaOpType<T>::A clamp, hipStream_t stream) {
     typedef typename LaOpType<T>::A A;
     if (n == 0) return LA_OK;
-    // (the checks and messages of la_bias_act_ex_f32)
     LA_CHECK_ARG(x && out && n > 0, "bias_act_ex: null pointer");
     LA_CHECK_ARG(act >= 1 && act <= 9, "bias_act_ex: activation id must be 1..9 (bias_act.py:20-30)");
     LA_CHECK_ARG(grad >= 0 && grad <= 2, "bias_act_ex: grad must be 0, 1 or 2");
@@ -202,7 +214,7 @@ static int bias_act_op(const T* x, const T* b, const T* xref, const T* yref, con
     p.n = n; p.stepb = stepb; p.nb = nb; p.grad = grad; p.act = act;
     p.vec = ((((size_t)x | (size_t)xref | (size_t)yref | (size_t)dy | (size_t)out) & 15) == 0);
     p.alpha = alpha; p.gain = gain; p.clamp = clamp;
-    p.clamp_s = clamp >= (A)0 ? la_op_round(clamp) : clamp;
+    p.clamp_s = clamp >= (A)0 ? la_op_round<T>(clamp) : clamp;
     constexpr int V = 16 / sizeof(T);
     long blocks = la_cdiv(la_cdiv(n, V), 256);
     if (blocks > 8192) blocks = 8192;
@@ -225,6 +237,10 @@ extern "C" int la_bias_act_ex_f16(const unsigned short* x, const unsigned short*
     typedef const __half* H;
     return bias_act_op<__half>(H(x), H(b), H(xref), H(yref), H(dy), (__half*)out, n, stepb, nb, grad, act, alpha, gain, clamp, stream);
 }
+extern "C" int la_bias_act_ex_f32(const float* x, const float* b, const float* xref, const float* yref, const float* dy, float* out, long n,
+                                  long stepb, int nb, int grad, int act, float alpha, float gain, float clamp, hipStream_t stream) {
+    return bias_act_op<float>(x, b, xref, yref, dy, out, n, stepb, nb, grad, act, alpha, gain, clamp, stream);
+}
 extern "C" int la_bias_act_ex_f64(const double* x, const double* b, const double* xref, const double* yref, const double* dy, double* out,
                                   long n, long stepb, int nb, int grad, int act, double alpha, double gain, double clamp, hipStream_t stream) {
     return bias_act_op<double>(x, b, xref, yref, dy, out, n, stepb, nb, grad, act, alpha, gain, clamp, stream);
@@ -232,15 +248,16 @@ extern "C" int la_bias_act_ex_f64(const double* x, const double* b, const double
 extern "C" int la_bias_sum_f16(const unsigned short* dx, unsigned short* db, long n, long stepb, int nb, hipStream_t stream) {
     return bias_sum_op<__half>((const __half*)dx, (__half*)db, n, stepb, nb, stream);
 }
+extern "C" int la_bias_sum_f32(const float* dx, float* db, long n, long stepb, int nb, hipStream_t stream) {
+    return bias_sum_op<float>(dx, db, n, stepb, nb, stream);
+}
 extern "C" int la_bias_sum_f64(const double* dx, double* db, long n, long stepb, int nb, hipStream_t stream) {
     return bias_sum_op<double>(dx, db, n, stepb, nb, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// upfirdn2d: la_upfirdn2d_kernel (la_upfirdn2d.hip) over storage T with the taps in A, plus a float16 form of the 4x4 filter at
+// upfirdn2d in float16 / float64: the generic gather (la_fir_gather, as la_upfirdn2d_kernel) over storage T with the taps in A, plus a float16 form of the 4x4 filter at
 // stride 1, up 2 and down 2 (setup_filter([1,3,3,1]) through filter2d / upsample2d / downsample2d and their adjoints)
-#define LA_OP_FIR_MAX 8
-
 template <class T>
 struct LaFirOpArgs {
     const T* in;
@@ -249,7 +266,7 @@ struct LaFirOpArgs {
     int Hin, Win, Hout, Wout;
     int upx, upy, dnx, dny, padx0, pady0;
     int fw, fh;
-    typename LaOpType<T>::A f[LA_OP_FIR_MAX * LA_OP_FIR_MAX];      // correlation taps (flipped as needed, gain folded in)
+    typename LaOpType<T>::A f[LA_FIR_MAX * LA_FIR_MAX];      // correlation taps (flipped as needed, gain folded in)
 };
 
 template <class T>
@@ -258,21 +275,9 @@ __global__ __launch_bounds__(256) void la_upfirdn2d_op_kernel(LaFirOpArgs<T> a) 
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.Wout || y >= a.Hout) return;
-    const int by = y * a.dny - a.pady0, bx = x * a.dnx - a.padx0;
-    const int iy_lo = (by >= 0) ? (by + a.upy - 1) / a.upy : -((-by) / a.upy);
-    const int ix_lo = (bx >= 0) ? (bx + a.upx - 1) / a.upx : -((-bx) / a.upx);
     const long HWin = (long)a.Hin * a.Win, HWout = (long)a.Hout * a.Wout;
     for (int p = blockIdx.z; p < a.P; p += gridDim.z) {
-        const T* ip = a.in + (long)p * HWin;
-        A v = 0;
-        for (int iy = iy_lo; iy * a.upy - by < a.fh; ++iy) {
-            if (iy < 0 || iy >= a.Hin) continue;
-            const int ta = iy * a.upy - by;
-            for (int ix = ix_lo; ix * a.upx - bx < a.fw; ++ix) {
-                if (ix < 0 || ix >= a.Win) continue;
-                v += la_op_load(ip[(long)iy * a.Win + ix]) * a.f[ta * a.fw + (ix * a.upx - bx)];
-            }
-        }
+        const A v = la_fir_gather<A>(a, a.in + (long)p * HWin, x, y);
         a.out[(long)p * HWout + (long)y * a.Wout + x] = la_op_store<T>(v);
     }
 }
@@ -407,25 +412,14 @@ __global__ __launch_bounds__(256) void la_fir4x4_h_kernel(LaFirOpArgs<__half> a)
 template <class T>
 static int fir_op_fill(LaFirOpArgs<T>& a, const T* in, T* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw, int upx,
                        int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter, typename LaOpType<T>::A gain) {
-    typedef typename LaOpType<T>::A A;
-    // (the checks and messages of fir_fill, la_upfirdn2d.hip)
-    LA_CHECK_ARG(in && out && f_host, "upfirdn2d: null pointer");
-    LA_CHECK_ARG(fh >= 1 && fw >= 1 && fh * fw <= LA_OP_FIR_MAX * LA_OP_FIR_MAX && fh <= 32 && fw <= 32,
-                 "upfirdn2d: filter larger than 8x8 (or than 32 taps in one separable pass)");
-    LA_CHECK_ARG(upx >= 1 && upy >= 1 && dnx >= 1 && dny >= 1, "upfirdn2d: bad up/down factor");
-    LA_CHECK_ARG(B >= 1 && C >= 1 && Hin >= 1 && Win >= 1, "upfirdn2d: empty input");
-    const int upW = Win * upx + padx0 + padx1, upH = Hin * upy + pady0 + pady1;
-    LA_CHECK_ARG(upW >= fw && upH >= fh, "upfirdn2d: upsampled image smaller than the filter");
+    LaFirSetup s;
+    const int rc = la_fir_setup(s, in, out, B, C, Hin, Win, f_host, fh, fw, upx, upy, dnx, dny, padx0, padx1, pady0, pady1, flip_filter, (float)gain);
+    if (rc) return rc;
     a.in = in; a.out = out; a.P = B * C;
-    a.Hin = Hin; a.Win = Win; a.Wout = (upW - fw + dnx) / dnx; a.Hout = (upH - fh + dny) / dny;
+    a.Hin = Hin; a.Win = Win; a.Wout = s.Wout; a.Hout = s.Hout;
     a.upx = upx; a.upy = upy; a.dnx = dnx; a.dny = dny; a.padx0 = padx0; a.pady0 = pady0;
     a.fw = fw; a.fh = fh;
-    // (the gain goes onto the float32 host taps IN float32 and the product is widened exactly: upfirdn2d.py:196-197 multiplies the float32
-    //  filter tensor by the gain before converting it to the dtype of x, so a float64 call sees a non-power-of-two gain rounded to float32)
-    const float gain32 = (float)gain;
-    for (int i = 0; i < fh; ++i)
-        for (int j = 0; j < fw; ++j)
-            a.f[i * fw + j] = (A)(gain32 * (flip_filter ? f_host[i * fw + j] : f_host[(fh - 1 - i) * fw + (fw - 1 - j)]));
+    for (int k = 0; k < fh * fw; ++k) a.f[k] = (typename LaOpType<T>::A)s.f[k];
     return LA_OK;
 }
 

@@ -2,6 +2,41 @@
 #pragma once
 #include "la_common.h"
 
+// What every upfirdn2d entry (float16 / float32 / float64) derives from its arguments: the argument checks, the output size
+// (upfirdn2d.cpp:35-36) and the correlation taps in float32 -- up to 8 x 8, or one separable pass of up to 32 (1 x fw / fh x 1, the
+// two-pass form of upfirdn2d.py:188-201 for 1-D filters); the op is a true convolution unless flip_filter, so the taps are the flipped
+// filter (upfirdn2d.py:198-199).  The gain goes onto the float32 taps IN float32 whatever the dtype of x: upfirdn2d.py:196-197
+// multiplies the float32 filter tensor by the gain before converting it to the dtype of x, so a float64 call sees a non-power-of-two
+// gain rounded to float32 and widens the product exactly.
+#define LA_FIR_MAX 8
+struct LaFirSetup {
+    int Hout, Wout;
+    float f[LA_FIR_MAX * LA_FIR_MAX];
+};
+int la_fir_setup(LaFirSetup& s, const void* in, const void* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw,
+                 int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter, float gain);
+
+// The generic kernels' gather of output (x, y) of one input plane `ip` (storage T, sum in A): the contributing input rows are
+// iy * upy = y * dny + ta - pady0 with ta in [0, fh), columns likewise; taps in ascending row, then column order.
+// Args: FirArgs (la_upfirdn2d.hip) or LaFirOpArgs<T> (la_ops.hip).
+template <class A, class T, class Args>
+__device__ __forceinline__ A la_fir_gather(const Args& a, const T* ip, int x, int y) {
+    const int by = y * a.dny - a.pady0, bx = x * a.dnx - a.padx0;
+    // smallest iy with iy * upy >= by  (floor division that is safe for negatives)
+    const int iy_lo = (by >= 0) ? (by + a.upy - 1) / a.upy : -((-by) / a.upy);
+    const int ix_lo = (bx >= 0) ? (bx + a.upx - 1) / a.upx : -((-bx) / a.upx);
+    A v = 0;
+    for (int iy = iy_lo; iy * a.upy - by < a.fh; ++iy) {
+        if (iy < 0 || iy >= a.Hin) continue;
+        const int ta = iy * a.upy - by;
+        for (int ix = ix_lo; ix * a.upx - bx < a.fw; ++ix) {
+            if (ix < 0 || ix >= a.Win) continue;
+            v += (A)ip[(long)iy * a.Win + ix] * a.f[ta * a.fw + (ix * a.upx - bx)];
+        }
+    }
+    return v;
+}
+
 // generic op, optional same-shape addend (skip connection add fused into the store)
 // optional tail of the 4x4 kernels: activation backward of the layer whose saved output `yref` has the shape of `out` (stride-1 kernel:
 // out = fir(in) * act'(yref), bias_act.py:170 with grad = 1) and / or the fp16 operand scale of `out` for the contraction that consumes

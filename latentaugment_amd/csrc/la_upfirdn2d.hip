@@ -5,8 +5,6 @@
 #include <atomic>
 #include <stdlib.h>
 
-#define FIR_MAX 8
-
 struct FirArgs {
     const float* in;
     float* out;
@@ -14,7 +12,7 @@ struct FirArgs {
     int Hin, Win, Hout, Wout;
     int upx, upy, dnx, dny, padx0, pady0;
     int fw, fh;
-    float f[FIR_MAX * FIR_MAX];  // effective correlation kernel (already flipped as needed, gain folded in)
+    float f[LA_FIR_MAX * LA_FIR_MAX];  // effective correlation kernel (already flipped as needed, gain folded in)
     int epi;                     // 0 plain, 1 modconv epilogue, 2 activation backward: out = fir(in) * act'(yref) (4x4 stride-1 scalar kernel)
     const float* yref;           // epi 2: saved output of the activation, same shape as `out`
     const float* demod; int demod_stride;   // [B][stride]
@@ -35,24 +33,9 @@ __global__ __launch_bounds__(256) void la_upfirdn2d_kernel(FirArgs a) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.Wout || y >= a.Hout) return;
-    // contributing input rows: iy*upy = y*dny + ta - pady0, ta in [0, fh)
-    const int by = y * a.dny - a.pady0, bx = x * a.dnx - a.padx0;
-    // smallest iy with iy*up >= by  (floor division that is safe for negatives)
-    int iy_lo = (by >= 0) ? (by + a.upy - 1) / a.upy : -((-by) / a.upy);
-    int ix_lo = (bx >= 0) ? (bx + a.upx - 1) / a.upx : -((-bx) / a.upx);
     const long HWin = (long)a.Hin * a.Win, HWout = (long)a.Hout * a.Wout;
     for (int p = blockIdx.z; p < a.P; p += gridDim.z) {
-        const float* ip = a.in + (long)p * HWin;
-        float v = 0.f;
-        for (int iy = iy_lo; iy * a.upy - by < a.fh; ++iy) {
-            if (iy < 0 || iy >= a.Hin) continue;
-            const int ta = iy * a.upy - by;
-            for (int ix = ix_lo; ix * a.upx - bx < a.fw; ++ix) {
-                if (ix < 0 || ix >= a.Win) continue;
-                const int tb = ix * a.upx - bx;
-                v += ip[(long)iy * a.Win + ix] * a.f[ta * a.fw + tb];
-            }
-        }
+        float v = la_fir_gather<float>(a, a.in + (long)p * HWin, x, y);
         const long o = (long)p * HWout + (long)y * a.Wout + x;
         if (a.epi == 1) {
             const int b = p / a.C, c = p - b * a.C;
@@ -159,27 +142,34 @@ __global__ __launch_bounds__(256) void la_fir4x4_s1_kernel(FirArgs a) {
     }
 }
 
-static int fir_fill(FirArgs& a, const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host,
-                    int fh, int fw, int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1,
-                    int flip_filter, float gain, int* Hout, int* Wout) {
+int la_fir_setup(LaFirSetup& s, const void* in, const void* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw,
+                 int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter, float gain) {
     LA_CHECK_ARG(in && out && f_host, "upfirdn2d: null pointer");
-    // (up to 8 x 8 taps, or one separable pass of up to 32: 1 x fw / fh x 1 -- the two-pass form of upfirdn2d.py:188-201 for 1-D filters)
-    LA_CHECK_ARG(fh >= 1 && fw >= 1 && fh * fw <= FIR_MAX * FIR_MAX && fh <= 32 && fw <= 32, "upfirdn2d: filter larger than 8x8 (or than 32 taps in one separable pass)");
+    LA_CHECK_ARG(fh >= 1 && fw >= 1 && fh * fw <= LA_FIR_MAX * LA_FIR_MAX && fh <= 32 && fw <= 32, "upfirdn2d: filter larger than 8x8 (or than 32 taps in one separable pass)");
     LA_CHECK_ARG(upx >= 1 && upy >= 1 && dnx >= 1 && dny >= 1, "upfirdn2d: bad up/down factor");
     LA_CHECK_ARG(B >= 1 && C >= 1 && Hin >= 1 && Win >= 1, "upfirdn2d: empty input");
     const int upW = Win * upx + padx0 + padx1, upH = Hin * upy + pady0 + pady1;
     LA_CHECK_ARG(upW >= fw && upH >= fh, "upfirdn2d: upsampled image smaller than the filter");
-    *Wout = (upW - fw + dnx) / dnx;   // upfirdn2d.cpp:35-36
-    *Hout = (upH - fh + dny) / dny;
-    a.in = in; a.out = out; a.P = B * C; a.C = C; a.pmax = nullptr; a.xs_out = nullptr; a.xs_mult = nullptr; a.row_lo = a.row_hi = 0; a.col_lo = a.col_hi = 0;
-    a.in_pitch = Win; a.in_plane = (long)Hin * Win; a.in_xhalf = 0;
-    a.Hin = Hin; a.Win = Win; a.Hout = *Hout; a.Wout = *Wout;
-    a.upx = upx; a.upy = upy; a.dnx = dnx; a.dny = dny; a.padx0 = padx0; a.pady0 = pady0;
-    a.fw = fw; a.fh = fh;
-    // the op is a true convolution unless flip_filter: correlation kernel = flipped filter (upfirdn2d.py:198-199)
+    s.Wout = (upW - fw + dnx) / dnx;
+    s.Hout = (upH - fh + dny) / dny;
     for (int i = 0; i < fh; ++i)
         for (int j = 0; j < fw; ++j)
-            a.f[i * fw + j] = gain * (flip_filter ? f_host[i * fw + j] : f_host[(fh - 1 - i) * fw + (fw - 1 - j)]);
+            s.f[i * fw + j] = gain * (flip_filter ? f_host[i * fw + j] : f_host[(fh - 1 - i) * fw + (fw - 1 - j)]);
+    return LA_OK;
+}
+
+static int fir_fill(FirArgs& a, const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host,
+                    int fh, int fw, int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1,
+                    int flip_filter, float gain) {
+    LaFirSetup s;
+    const int rc = la_fir_setup(s, in, out, B, C, Hin, Win, f_host, fh, fw, upx, upy, dnx, dny, padx0, padx1, pady0, pady1, flip_filter, gain);
+    if (rc) return rc;
+    a.in = in; a.out = out; a.P = B * C; a.C = C; a.pmax = nullptr; a.xs_out = nullptr; a.xs_mult = nullptr; a.row_lo = a.row_hi = 0; a.col_lo = a.col_hi = 0;
+    a.in_pitch = Win; a.in_plane = (long)Hin * Win; a.in_xhalf = 0;
+    a.Hin = Hin; a.Win = Win; a.Hout = s.Hout; a.Wout = s.Wout;
+    a.upx = upx; a.upy = upy; a.dnx = dnx; a.dny = dny; a.padx0 = padx0; a.pady0 = pady0;
+    a.fw = fw; a.fh = fh;
+    for (int k = 0; k < fh * fw; ++k) a.f[k] = s.f[k];
     a.epi = 0; a.demod = nullptr; a.noise = nullptr; a.bias = nullptr; a.addend = nullptr; a.yref = nullptr;
     a.demod_stride = 0; a.noise_bstride = 0; a.noise_strength = 0.f;
     a.act = LA_ACT_LINEAR; a.alpha = 0.f; a.gain = 1.f; a.clamp = -1.f;
@@ -508,8 +498,8 @@ __global__ __launch_bounds__(1024) void la_imgrad_pyramid_kernel(PyrArgs a) {
 // outs[l] = gradient planes at resolution R0 >> (l + 1), l = 0 .. nlev-1; needs (R0/2)^2 * 4 <= 64 KB (R0 <= 256)
 int la_image_grad_pyramid(const float* g_top, float* const* outs, int nlev, int planes, int R0, const float* f_host, hipStream_t stream) {
     LA_CHECK_ARG(g_top && outs && nlev >= 1 && nlev <= 12 && planes >= 1 && R0 >= 2 && R0 <= 256 && (R0 >> nlev) >= 1, "image_grad_pyramid: bad arguments");
-    FirArgs fa; int ho, wo;
-    int rc = fir_fill(fa, g_top, outs[0], planes, 1, R0, R0, f_host, 4, 4, 1, 1, 2, 2, 1, 1, 1, 1, 1, 4.f, &ho, &wo);      // (the taps as the per-level launches build them)
+    FirArgs fa;
+    int rc = fir_fill(fa, g_top, outs[0], planes, 1, R0, R0, f_host, 4, 4, 1, 1, 2, 2, 1, 1, 1, 1, 1, 4.f);      // (the taps as the per-level launches build them)
     if (rc) return rc;
     PyrArgs a;
     a.top = g_top; a.nlev = nlev; a.R0 = R0;
@@ -611,9 +601,9 @@ static int fir_launch_inner(const FirArgs& a, hipStream_t stream) {
 int la_upfirdn2d_ex(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw,
                     int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter,
                     float gain, const float* addend, hipStream_t stream, float* pmax, const LaFirTail* tail) {
-    FirArgs a; int ho, wo;
+    FirArgs a;
     int rc = fir_fill(a, in, out, B, C, Hin, Win, f_host, fh, fw, upx, upy, dnx, dny, padx0, padx1, pady0, pady1,
-                      flip_filter, gain, &ho, &wo);
+                      flip_filter, gain);
     if (rc) return rc;
     a.addend = addend;
     if (tail) {
@@ -639,9 +629,8 @@ int la_upfirdn2d_modconv_epilogue(const float* in, float* out, int B, int C, int
                                   float noise_strength, const float* bias, int act, float alpha, float gain,
                                   float clamp, hipStream_t stream, float* pmax, int in_pitch, long in_plane, int in_xhalf, float* xs_out,
                                   const float* xs_mult, int row_lo, int row_hi, int col_lo, int col_hi) {
-    FirArgs a; int ho, wo;
-    int rc = fir_fill(a, in, out, B, C, Hin, Win, f_host, fh, fw, 1, 1, 1, 1, padx0, padx1, pady0, pady1, 0, fir_gain,
-                      &ho, &wo);
+    FirArgs a;
+    int rc = fir_fill(a, in, out, B, C, Hin, Win, f_host, fh, fw, 1, 1, 1, 1, padx0, padx1, pady0, pady1, 0, fir_gain);
     if (rc) return rc;
     a.epi = 1; a.demod = demod; a.demod_stride = demod_stride; a.noise = noise; a.noise_bstride = noise_bstride;
     a.noise_strength = noise_strength; a.bias = bias; a.act = act; a.alpha = alpha; a.gain = gain; a.clamp = clamp;

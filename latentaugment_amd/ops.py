@@ -31,27 +31,22 @@ _ACTS = {
 }
 
 
-# dtypes with entries of their own besides float32 (the C ABI's _f16 / _f64 forms); they keep their dtype through the op
-_OWN_DTYPES = {torch.float16: 'f16', torch.float64: 'f64'}
+# dtypes of the C ABI's entries (suffix of la_bias_act_ex_* / la_bias_sum_* / la_upfirdn2d_*); they keep their dtype through the op
+_DTYPES = {torch.float16: 'f16', torch.float32: 'f32', torch.float64: 'f64'}
 
 
 def _op_input(x):
-    """x as the op's kernels read it: float16 / float64 / float32 as they are, every other dtype converted to float32 (as before)."""
-    return x.contiguous() if x.dtype in _OWN_DTYPES else x.contiguous().float()
+    """x as the op's kernels read it: float16 / float32 / float64 as they are, every other dtype converted to float32."""
+    return x.contiguous() if x.dtype in _DTYPES else x.contiguous().float()
 
 
 def _bias_act_launch(x, b, xref, yref, dy, grad, stepb, nb, act, alpha, gain, clamp):
-    """One launch of the general op (include/latentaug_hip.h: la_bias_act_ex_f32 = the plugin's bias_act(x, b, xref, yref, dy, grad, ...));
-    float16 / float64 tensors go to its _f16 / _f64 form."""
-    lib = _lib.load()
+    """One launch of the general op (include/latentaug_hip.h: la_bias_act_ex_f32 = the plugin's bias_act(x, b, xref, yref, dy, grad, ...),
+    or its _f16 / _f64 form)."""
+    fn = getattr(_lib.load(), 'la_bias_act_ex_' + _DTYPES[x.dtype])
     out = torch.empty_like(x)
-    if x.dtype in _OWN_DTYPES:
-        fn = getattr(lib, 'la_bias_act_ex_' + _OWN_DTYPES[x.dtype])
-        _lib.check(fn(_lib.ptr(x), _lib.ptr(b), _lib.ptr(xref), _lib.ptr(yref), _lib.ptr(dy), _lib.ptr(out), x.numel(), stepb, nb, grad, act,
-                      alpha, gain, clamp, _lib.stream_ptr()), 'bias_act')
-        return out
-    _lib.check(lib.la_bias_act_ex_f32(_lib.ptr(x), _lib.ptr(b), _lib.ptr(xref), _lib.ptr(yref), _lib.ptr(dy), _lib.ptr(out), x.numel(), stepb, nb,
-                                      grad, act, alpha, gain, clamp, _lib.stream_ptr()), 'bias_act')
+    _lib.check(fn(_lib.ptr(x), _lib.ptr(b), _lib.ptr(xref), _lib.ptr(yref), _lib.ptr(dy), _lib.ptr(out), x.numel(), stepb, nb, grad, act,
+                  alpha, gain, clamp, _lib.stream_ptr()), 'bias_act')
     return out
 
 
@@ -60,14 +55,9 @@ class _BiasSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dx, stepb, nb):
-        lib = _lib.load()
         dx = dx.contiguous()
-        if dx.dtype in _OWN_DTYPES:
-            db = torch.empty([nb], device=dx.device, dtype=dx.dtype)
-            fn = getattr(lib, 'la_bias_sum_' + _OWN_DTYPES[dx.dtype])
-        else:
-            db = torch.empty([nb], device=dx.device, dtype=torch.float32)
-            fn = lib.la_bias_sum_f32
+        db = torch.empty([nb], device=dx.device, dtype=dx.dtype)
+        fn = getattr(_lib.load(), 'la_bias_sum_' + _DTYPES[dx.dtype])
         if dx.numel():
             _lib.check(fn(_lib.ptr(dx), _lib.ptr(db), dx.numel(), stepb, nb, _lib.stream_ptr()), 'bias_sum')
         else:
@@ -92,9 +82,9 @@ class _BiasAct(torch.autograd.Function):
         stepb, nb = 1, 1
         if b is not None:
             assert b.ndim == 1 and 0 <= dim < x.ndim and b.shape[0] == x.shape[dim]
-            if x.dtype in _OWN_DTYPES and b.dtype != x.dtype:
+            if x.dtype != torch.float32 and b.dtype != x.dtype:
                 raise _lib.LatentAugHipError(f'bias_act: b must have the dtype of x ({x.dtype}), got {b.dtype}')
-            b = b.contiguous() if x.dtype in _OWN_DTYPES else b.contiguous().float()
+            b = b.contiguous().to(x.dtype)      # (a float32 x converts its bias, as it always has)
             nb = x.shape[dim]
             stepb = int(np.prod(x.shape[dim + 1:])) if dim + 1 < x.ndim else 1
         y = _bias_act_launch(x, b, None, None, None, 0, stepb, nb, act, alpha, gain, clamp)
@@ -205,15 +195,10 @@ def _launch_upfirdn2d(x, f, upx, upy, dnx, dny, px0, px1, py0, py1, flip, gain):
     oh = lib.la_upfirdn2d_out_size(h, upy, dny, py0, py1, fh)
     assert ow >= 1 and oh >= 1
     fh_ = np.ascontiguousarray(f.numpy(), dtype=np.float32)
-    if x.dtype in _OWN_DTYPES:
-        y = torch.empty([n, c, oh, ow], device=x.device, dtype=x.dtype)
-        fn = getattr(lib, 'la_upfirdn2d_' + _OWN_DTYPES[x.dtype])
-        _lib.check(fn(_lib.ptr(x), fh_.ctypes.data, _lib.ptr(y), n, c, h, w, fh, fw, upx, upy, dnx, dny, px0, px1, py0, py1, int(flip), float(gain),
-                      _lib.stream_ptr()), 'upfirdn2d')
-        return y
-    y = torch.empty([n, c, oh, ow], device=x.device, dtype=torch.float32)
-    _lib.check(lib.la_upfirdn2d_f32(_lib.ptr(x), fh_.ctypes.data, _lib.ptr(y), n, c, h, w, fh, fw, upx, upy, dnx, dny,
-                                    px0, px1, py0, py1, int(flip), float(gain), _lib.stream_ptr()), 'upfirdn2d')
+    y = torch.empty([n, c, oh, ow], device=x.device, dtype=x.dtype)
+    fn = getattr(lib, 'la_upfirdn2d_' + _DTYPES[x.dtype])
+    _lib.check(fn(_lib.ptr(x), fh_.ctypes.data, _lib.ptr(y), n, c, h, w, fh, fw, upx, upy, dnx, dny, px0, px1, py0, py1, int(flip), float(gain),
+                  _lib.stream_ptr()), 'upfirdn2d')
     return y
 
 

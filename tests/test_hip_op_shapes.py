@@ -4,7 +4,7 @@ loops, unequal x / y factors, every filter extent -- in float16, float32 and flo
 the CPU in float64.  Every case checks the forward and the input gradient (bias_act: also db, and the second order for swish), output
 shape and dtype.  Inputs come from a seeded CPU generator; a float16 (float32) case rounds x, b, dy to its dtype first and the oracle gets
 those rounded values widened, so input rounding is part of no error.  Each group of cases says which kernel form it reaches, read from
-the predicates in la_upfirdn2d.hip (fir_launch_inner), la_op_dtypes.hip (fir_h_mode, fir_op_launch, la_bias_act_op_kernel) and la_misc.hip.
+the predicates in la_upfirdn2d.hip (fir_launch_inner), la_ops.hip (fir_h_mode, fir_op_launch, la_bias_act_op_kernel).
 
 Tolerances (none tuned to the kernels):
   float64   |err| <= 1e-12 x max(1, max |expected|)                                             (test_hip_op_dtypes.py)
@@ -457,8 +457,8 @@ def _run_bias_act(dev, dtype, shape, dim, act, kw, seed, has_b=True, also_unalig
         _check(yu, ey, dtype, what + ('y, unaligned',))
 
 
-# Per-element bias branch of la_bias_act_op_kernel (stepb % V != 0; V = 8 halves / 2 doubles) and its scalar tail (numel % V != 0);
-# float32's la_bias_act_full_kernel takes one element per thread.  stepb = 21, 9, 25; [13] has no bias (stepb = nb = 1).
+# Per-element bias branch of la_bias_act_op_kernel (stepb % V != 0; V = 8 halves / 4 floats / 2 doubles) and its scalar tail
+# (numel % V != 0).  stepb = 21, 9, 25; [13] has no bias (stepb = nb = 1).
 @dtypes
 @acts
 @pytest.mark.parametrize('shape', [[3, 5, 7, 3], [2, 7, 1, 9], [1, 3, 5, 5], [13]], ids=lambda s: 'x'.join(str(v) for v in s))
