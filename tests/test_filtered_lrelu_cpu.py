@@ -25,6 +25,11 @@ def g(golden_dir):
     return np.load(os.path.join(golden_dir, 'filtered_lrelu.npz'))
 
 
+@pytest.fixture(scope='module')
+def gs(golden_dir):
+    return np.load(os.path.join(golden_dir, 'flrelu_shapes.npz'))
+
+
 def cases(g):
     for name in g['cases']:
         name = str(name)
@@ -147,3 +152,98 @@ def test_cpu_restatement_reproduces_goldens(g):
         for k, v in (('y', y), ('dx', grads[0]), ('g2', g2)) + ((('db', grads[1]),) if b is not None else ()):
             ref = g[f'{name}_{k}']
             np.testing.assert_allclose(v.detach().numpy(), ref, rtol=tol, atol=tol * max(1.0, np.abs(ref).max()), err_msg=f'{name} {k}')
+
+
+def _restated(g, name, m, dtype):
+    t = tensors(g, name)
+    kw = dict(up=m['up'], down=m['down'], padding=m['padding'], gain=m['gain'], slope=m['slope'], clamp=m['clamp'], flip_filter=m['flip_filter'])
+    x = t['x'].to(dtype).requires_grad_(True)
+    b = None if t['b'] is None else t['b'].to(dtype).requires_grad_(True)
+    dy = t['dy'].to(dtype).requires_grad_(True)
+    y = flrelu_cpu.filtered_lrelu(x, t['fu'], t['fd'], b, **kw, dtype=dtype)
+    assert y.dtype == dtype
+    grads = torch.autograd.grad(y, [x] + ([b] if b is not None else []), dy, create_graph=True)
+    (g2,) = torch.autograd.grad((grads[0] * t['v'].to(dtype)).sum(), [dy])
+    out = {'y': y, 'dx': grads[0], 'g2': g2}
+    if b is not None:
+        out['db'] = grads[1]
+    return t, kw, {k: v.detach().double().numpy() for k, v in out.items()}
+
+
+def test_cpu_restatement_reproduces_shape_goldens(gs):
+    """flrelu_shapes.npz (the three forms and the multi-tile sizes filtered_lrelu.npz lacks, clamp 0, slope 1.5): same bound."""
+    from test_hip_flrelu_shapes import taps_of, tile_plan
+    names = [n for n, _ in cases(gs)]
+    assert len(names) == 17
+    multi = set()
+    for name, m in cases(gs):
+        _, _, got = _restated(gs, name, m, torch.float64)
+        for k, v in got.items():
+            ref = gs[f'{name}_{k}']
+            np.testing.assert_allclose(v, ref, rtol=1e-9, atol=1e-9 * max(1.0, np.abs(ref).max()), err_msg=f'{name} {k}')
+        p = tile_plan(*gs[f'{name}_y'].shape[2:], m['up'], m['down'], taps_of(m['fu']), taps_of(m['fd']))
+        assert p is not None and (p['tiles_y'], p['tiles_x']) == m['tiles'], name
+        if min(m['tiles']) >= 2:
+            multi.add((m['up'], m['down']))
+    assert multi == {(u, d) for u in (1, 2, 4) for d in (1, 2, 4)}
+    assert {m['clamp'] for _, m in cases(gs)} >= {0.0, None} and 1.5 in {m['slope'] for _, m in cases(gs)}
+
+
+@pytest.mark.parametrize('which', ['g', 'gs'])
+def test_float32_restatement_is_as_good_as_the_reference_in_float32(which, request):
+    """The float32 mode of flrelu_cpu is the yardstick of the GPU sweep where no golden exists, so it is held to the reference here: its
+    error against the float64 golden is at most 4 x the reference's own float32 error + 2e-6 x the largest magnitude (the rule the GPU
+    tests apply to the kernel), kink cones excluded as there, and the reference's float32 error meets the same bound measured from the
+    restatement's -- neither yardstick is looser than the other by more than that."""
+    from test_hip_flrelu_shapes import masks
+    g = request.getfixturevalue(which)
+    for name, m in cases(g):
+        t, kw, got = _restated(g, name, m, torch.float32)
+        if kw['clamp'] == 0:
+            for k, v in got.items():
+                assert (v == 0).all() and (g[f'{name}_{k}'] == 0).all(), (name, k)
+            continue
+        ex = masks(t, kw)
+        for k, v in got.items():
+            ref64, ref32 = g[f'{name}_{k}'], g[f'{name}_{k}32'].astype(np.float64)
+            keep = ~ex[k]
+            scale = float(np.abs(ref64).max())
+            mine, theirs = np.abs(v - ref64)[keep].max(initial=0.0), np.abs(ref32 - ref64)[keep].max(initial=0.0)
+            assert mine <= 4 * theirs + 2e-6 * scale, (name, k, mine, theirs, scale)
+            assert theirs <= 4 * mine + 2e-6 * scale, (name, k, mine, theirs, scale)
+
+
+def test_sign_helpers_round_trip_and_layout(lib, g, gs):
+    """pack_signs / unpack_signs: the layout of include/latentaug_hip.h (sample t of a row at bits 2 * (t % 4) of byte t // 4), a round
+    trip at the rows / row_bytes la_filtered_lrelu_sign_shape gives for every golden case, and sign_bits over exactly the active extent."""
+    one = torch.zeros([1, 1, 2, 9], dtype=torch.uint8)
+    one[0, 0, 0, 0], one[0, 0, 0, 1], one[0, 0, 0, 6], one[0, 0, 1, 8] = 1, 2, 3, 2
+    buf = flrelu_cpu.pack_signs(one, 3, 4)
+    assert buf.shape == (1, 1, 3, 4) and buf.dtype == torch.uint8
+    assert buf[0, 0].tolist() == [[0x01 | 0x02 << 2, 0x03 << 4, 0, 0], [0, 0, 0x02, 0], [0, 0, 0, 0]]
+    gen = torch.Generator().manual_seed(4)
+    for gg in (g, gs):
+        for name, m in cases(gg):
+            t = tensors(gg, name)
+            (fu_h, fu_w), (fd_h, fd_w) = taps(t['fu']), taps(t['fd'])
+            n, c, h, w = t['x'].shape
+            rc, rows, row_bytes = sign_shape(lib, h, w, fu_h, fu_w, fd_h, fd_w, m['up'], m['down'], *m['padding'])
+            assert rc == 0
+            kw = dict(up=m['up'], down=m['down'], padding=m['padding'], gain=m['gain'], slope=m['slope'], clamp=m['clamp'], flip_filter=m['flip_filter'])
+            bits = flrelu_cpu.sign_bits(t['x'], t['fu'], t['fd'], t['b'], **kw)
+            ah, aw = flrelu_cpu.active_shape(gg[f'{name}_y'].shape, t['fd'], m['down'])
+            assert bits.shape == (n, c, ah, aw) and bits.dtype == torch.uint8 and int(bits.max()) <= 3, name
+            assert (m['clamp'] is None) == (int(bits.max()) <= 1), name
+            buf = flrelu_cpu.pack_signs(bits, rows, row_bytes)
+            assert buf.shape == (n, c, rows, row_bytes)
+            assert torch.equal(flrelu_cpu.unpack_signs(buf, ah, aw), bits), name
+            assert int(flrelu_cpu.unpack_signs(buf).sum()) == int(bits.sum()), name      # (nothing set past the active extent)
+            rnd = torch.randint(0, 4, [n, c, rows, 4 * row_bytes], generator=gen, dtype=torch.uint8)
+            assert torch.equal(flrelu_cpu.unpack_signs(flrelu_cpu.pack_signs(rnd, rows, row_bytes)), rnd), name
+            # the stored derivative: reading the written bits back at offset 0 differentiates the activation
+            mid = flrelu_cpu.up_stage(t['x'], t['fu'], t['b'], m['up'], m['padding'], m['flip_filter'])[:, :, :ah, :aw]
+            d = flrelu_cpu.act_read(torch.ones_like(mid), bits, 0, 0, m['gain'], m['slope'])
+            z = mid.clone().requires_grad_(True)
+            (want,) = torch.autograd.grad(flrelu_cpu.act_stage(z, m['gain'], m['slope'], m['clamp']).sum(), [z])
+            live = mid != 0      # (at an exact zero, padding only, the two conventions of lrelu'(0) differ and nothing depends on it)
+            assert torch.allclose(d[live], want[live], rtol=1e-7, atol=0), name      # (one of three well separated values)

@@ -39,6 +39,12 @@ def g(golden_dir):
     return np.load(os.path.join(golden_dir, 'filtered_lrelu.npz'))
 
 
+@pytest.fixture(scope='module')
+def gs(golden_dir):
+    """The forms and tile seams filtered_lrelu.npz has no case of (tests/golden/make_golden_flrelu_shapes.py)."""
+    return np.load(os.path.join(golden_dir, 'flrelu_shapes.npz'))
+
+
 def golden_case(g, name):
     m = ast.literal_eval(str(g[f'{name}_meta']))
     t = {k: torch.from_numpy(g[f'{name}_{k}']) if f'{name}_{k}' in g else None for k in ('x', 'b', 'fu', 'fd', 'dy', 'v')}
@@ -67,7 +73,11 @@ def run_hip(t, kw, dev, noncontig=False):
 
 
 def masks(t, kw):
-    """Excluded elements per quantity (bool arrays), from the float64 kink samples of the case."""
+    """Excluded elements per quantity (bool arrays), from the float64 kink samples of the case.  (clamp = 0: every result is an exact
+    zero in any precision, nothing is excluded.)"""
+    if kw['clamp'] == 0:
+        z = {'y': t['dy'], 'g2': t['dy'], 'dx': t['x'], 'db': t['b']}
+        return {k: np.zeros(tuple(v.shape), bool) for k, v in z.items() if v is not None}, 0
     mask, nk = flrelu_cpu.kink_mask(t['x'], t['fu'], t['fd'], t['b'], **kw, rtol=KINK_RTOL)
     y_aff, x_aff = flrelu_cpu.affected(mask, t['x'].shape, t['fu'], t['fd'], kw['up'], kw['down'], kw['padding'], kw['flip_filter'])
     tight, _ = flrelu_cpu.kink_mask(t['x'], t['fu'], t['fd'], t['b'], **kw, rtol=1e-6)
@@ -95,14 +105,19 @@ def check_case(g, name, dev):
     return m
 
 
-def test_fused_envelope_cases_match_goldens(g, dev):
-    names = [str(n) for n in g['cases'] if ast.literal_eval(str(g[f'{n}_meta']))['path'] == 'fused']
-    assert len(names) >= 10
-    seen = set()
-    for name in names:
-        m = check_case(g, name, dev)
-        seen.add((m['up'], m['down']))
+def test_fused_envelope_cases_match_goldens(g, gs, dev):
+    seen, multi = set(), set()
+    for gg, least in ((g, 10), (gs, 17)):
+        names = [str(n) for n in gg['cases'] if ast.literal_eval(str(gg[f'{n}_meta']))['path'] == 'fused']
+        assert len(names) >= least
+        for name in names:
+            m = check_case(gg, name, dev)
+            seen.add((m['up'], m['down']))
+            if min(m.get('tiles', (1, 1))) >= 2:
+                multi.add((m['up'], m['down']))
+    nine = {(u, d) for u in (1, 2, 4) for d in (1, 2, 4)}
     assert seen >= {(1, 1), (2, 1), (1, 2), (2, 2), (4, 2), (2, 4)}
+    assert seen == nine and multi == nine      # (every la_flrelu_fused_kernel<UP, DOWN>, each also with 2 x 2 tiles or more)
 
 
 def test_generic_path_cases_match_goldens(g, dev):
