@@ -134,6 +134,36 @@ int la_filtered_lrelu_sign_shape(int H, int W, int fu_h, int fu_w, int fd_h, int
                                  int* rows, int* row_bytes);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * conv2d / conv_transpose2d with data and weight gradients: the pair under conv2d_resample
+ * (torch_utils/ops/conv2d_gradfix.py:24-33, conv2d_resample.py:26-40).  float32, dense NCHW.
+ * ------------------------------------------------------------------------------------------------------------- */
+
+/* y = conv(x, w).  x [B][Cin][H][W], y [B][Cout][Hout][Wout], the same stride on both axes, padding pady / padx >= 0.
+ *   transpose == 0: w [Cout][Cin/groups][kh][kw], Hout = (H + 2 pady - kh) / stride + 1 (torch.nn.functional.conv2d)
+ *   transpose != 0: w [Cin][Cout/groups][kh][kw], (H-1) stride - 2 pady + kh <= Hout < that + stride: the excess is the output
+ *                   padding (torch.nn.functional.conv_transpose2d)
+ *   flip_weight != 0: correlation, w used as it is (what torch computes; the reference's flip_weight=True); 0: w flipped on both axes.
+ * The data gradient of a call is the same entry with `transpose` toggled, x := dy, the same w and the two shapes exchanged.
+ * Limits: kh, kw <= 7, stride <= 8; anything beyond is refused.  kh*kw <= 9, stride <= 2 and Cout/groups % 4 == 0 run on the MFMA
+ * contraction engine (la_conv2d_uses_engine), everything else on a direct-form kernel.
+ * ws: la_conv2d_workspace_bytes(0, ...) bytes of 16-byte aligned scratch (packed weights, split-K partials). */
+int la_conv2d_f32(const float* x, const float* w, float* y, void* ws, size_t ws_bytes, int B, int Cin, int H, int W, int Cout, int kh, int kw,
+                  int Hout, int Wout, int stride, int pady, int padx, int groups, int flip_weight, int transpose, la_stream_t stream);
+/* dw (the shape of w) = gradient of <dy, conv(x, w)> with respect to w; every argument means what it means in la_conv2d_f32, x and
+ * dy [B][Cout][Hout][Wout] being that call's input and output.  kh*kw <= 9 and stride <= 2: split-K fp32-MFMA kernel whose slices
+ * are summed in a fixed order; otherwise one workgroup per element with a fixed-order tree.  Bit-identical from run to run.
+ * ws: la_conv2d_workspace_bytes(1, ...) bytes. */
+int la_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int B, int Cin, int H, int W, int Cout,
+                        int kh, int kw, int Hout, int Wout, int stride, int pady, int padx, int groups, int flip_weight, int transpose,
+                        la_stream_t stream);
+/* pure host queries.  op: 0 = la_conv2d_f32, 1 = la_conv2d_wgrad_f32.  Scratch bytes of a call (never 0, non-decreasing in B);
+ * whether a call runs on the engine / MFMA path (1) or the direct-form one (0); K slices of an MFMA weight gradient (0: direct form). */
+size_t la_conv2d_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout, int kh, int kw, int Hout, int Wout, int stride, int groups,
+                                 int transpose);
+int la_conv2d_uses_engine(int op, int cout, int kh, int kw, int stride, int groups);
+int la_conv2d_wgrad_slices(int B, int Cin, int H, int W, int Cout, int kh, int kw, int Hout, int Wout, int stride, int groups, int transpose);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Modulated 3x3 convolution of a SynthesisLayer (the SG2 `modulated_conv2d` + `bias_act` pair that the reference
  * reaches through G.synthesis, util_latent_aug.py:227; resampling algebra conv2d_resample.py:82-134).
  * Non-fused formulation: y = act((W * (x.s)) . d + noise + bias); never materialises per-sample weights.

@@ -48,6 +48,11 @@ SIGNATURES = {
     'la_filtered_lrelu_act_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P]),
     'la_filtered_lrelu_out_size': (_I, [_I] * 7),
     'la_filtered_lrelu_sign_shape': (_I, [_I] * 12 + [_P, _P]),
+    'la_conv2d_f32': (_I, [_P, _P, _P, _P, _Z] + [_I] * 15 + [_P]),
+    'la_conv2d_wgrad_f32': (_I, [_P, _P, _P, _P, _Z] + [_I] * 15 + [_P]),
+    'la_conv2d_workspace_bytes': (_Z, [_I] * 13),
+    'la_conv2d_uses_engine': (_I, [_I] * 6),
+    'la_conv2d_wgrad_slices': (_I, [_I] * 12),
     'la_pack_conv_weights_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'la_modconv3x3_fwd_f32': (_I, [_P, _L, _P, _P, _I, _P, _I, _P, _I, _P, _L, _F, _P, _I, _F, _F, _F, _P, _P, _Z, _I, _I, _I, _I, _P]),
     'la_modconv3x3_up2_fwd_f32': (_I, [_P, _L, _P, _P, _I, _P, _I, _P, _I, _P, _L, _F, _P, _I, _F, _F, _F, _P, _P, _P, _P, _Z, _I,

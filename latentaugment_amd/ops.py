@@ -4,10 +4,14 @@ Same names, argument meaning and error behaviour as the reference's Python wrapp
   bias_act(x, b, dim, act, alpha, gain, clamp)                      bias_act.py:52-86
   setup_filter / upfirdn2d / filter2d / upsample2d / downsample2d   upfirdn2d.py:70-387
   filtered_lrelu(x, fu, fd, b, up, down, padding, gain, slope, clamp, flip_filter)   filtered_lrelu.py:59-108
+  conv2d / conv_transpose2d(x, w, stride, padding, groups)          conv2d_gradfix.py:24-33
+  conv2d_resample(x, w, f, up, down, padding, groups, flip_weight, flip_filter)       conv2d_resample.py:46-141
 Each op is a torch.autograd.Function whose forward AND backward are HIP launches (bias_act: every activation of the reference's
-table with first- and second-order gradients; upfirdn2d: first order, which is all the latent-optimisation path uses; filtered_lrelu: one
-fused launch whose backward is the same kernel reading the sign mask its forward wrote, so gradients of every order).  torch only owns the
-device memory and the stream.
+table with first- and second-order gradients; upfirdn2d: linear, its backward is the same op on the adjoint arguments, so gradients of
+every order; filtered_lrelu: one
+fused launch whose backward is the same kernel reading the sign mask its forward wrote, so gradients of every order; conv2d /
+conv_transpose2d: forward, data gradient and weight gradient are three bilinear maps that are each other's backward, so gradients of
+every order with respect to x, w and incoming gradients; float32 only).  torch only owns the device memory and the stream.
 
 Dtypes of bias_act and the upfirdn2d family (upfirdn2d, filter2d, upsample2d, downsample2d), as the reference's plugins dispatch them
 (bias_act.cpp:77, upfirdn2d.cpp:63): float16, float32 and float64 run on kernels of their own and return their own dtype (float16 with
@@ -218,7 +222,8 @@ class _Upfirdn2d(torch.autograd.Function):
         _, _, oh, ow = dy.shape
         fh, fw = f.shape
         p = [fw - px0 - 1, iw * upx - ow * dnx + px0 - upx + 1, fh - py0 - 1, ih * upy - oh * dny + py0 - upy + 1]
-        dx = _launch_upfirdn2d(dy.contiguous(), f, dnx, dny, upx, upy, *p, not flip, gain)
+        # (an apply, not a bare launch: the op is linear and its adjoint is the op itself, so gradients of every order exist)
+        dx = _Upfirdn2d.apply(dy, f, (dnx, dny), (upx, upy), tuple(p), not flip, gain)
         return dx, None, None, None, None, None, None
 
 
@@ -379,3 +384,201 @@ def l2_loss_vectorized(X, Y, compute_mean=True):
     _lib.check(lib.la_pairwise_l2_f32(_lib.ptr(Xf), n, _lib.ptr(Yf), m, K, _lib.ptr(D), _lib.ptr(mean), _lib.ptr(ws),
                                       _lib.stream_ptr()), 'pairwise_l2')
     return mean[0] if compute_mean else D
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# conv2d / conv_transpose2d / conv2d_resample
+
+def _conv_geo_toggle(geo):
+    """The convolution whose forward is the data gradient of `geo`: transpose toggled, the two image shapes exchanged, the same w."""
+    t, s, py, px, groups, corr, xs, ws, ys = geo
+    return (not t, s, py, px, groups, corr, ys, ws, xs)
+
+
+def _conv_dims(geo):
+    t, s, py, px, groups, corr, xs, ws, ys = geo
+    return (xs[0], xs[1], xs[2], xs[3], ys[1], ws[2], ws[3], ys[2], ys[3], s)
+
+
+def _conv_scratch(op, geo, dev):
+    t, s, py, px, groups = geo[:5]
+    n = _lib.load().la_conv2d_workspace_bytes(op, *_conv_dims(geo), groups, int(t))
+    return torch.empty([n], device=dev, dtype=torch.uint8)
+
+
+def _conv_launch_y(x, w, geo):
+    t, s, py, px, groups, corr, xs, ws, ys = geo
+    assert tuple(x.shape) == tuple(xs) and tuple(w.shape) == tuple(ws), (x.shape, w.shape, geo)
+    x, w = x.contiguous(), w.contiguous()
+    y = torch.empty(ys, device=x.device, dtype=torch.float32)
+    scratch = _conv_scratch(0, geo, x.device)
+    _lib.check(_lib.load().la_conv2d_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), _lib.ptr(scratch), scratch.numel(), *_conv_dims(geo), py, px, groups,
+                                         int(corr), int(t), _lib.stream_ptr()), 'conv2d')
+    return y
+
+
+def _conv_launch_w(x, dy, geo):
+    t, s, py, px, groups, corr, xs, ws, ys = geo
+    assert tuple(x.shape) == tuple(xs) and tuple(dy.shape) == tuple(ys), (x.shape, dy.shape, geo)
+    x, dy = x.contiguous(), dy.contiguous()
+    dw = torch.empty(ws, device=x.device, dtype=torch.float32)
+    scratch = _conv_scratch(1, geo, x.device)
+    _lib.check(_lib.load().la_conv2d_wgrad_f32(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(scratch), scratch.numel(), *_conv_dims(geo), py, px,
+                                               groups, int(corr), int(t), _lib.stream_ptr()), 'conv2d_wgrad')
+    return dw
+
+
+class _ConvY(torch.autograd.Function):
+    """y = conv(x, w) of a geometry (la_conv2d_f32).  Bilinear: its backward is the same map of the toggled geometry (data gradient) and
+    _ConvW (weight gradient), whose backwards are these maps again -- gradients of every order are launches of the same kernels."""
+
+    @staticmethod
+    def forward(ctx, x, w, geo):
+        ctx.save_for_backward(x, w)
+        ctx.geo = geo
+        return _conv_launch_y(x, w, geo)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        gx = _ConvY.apply(dy, w, _conv_geo_toggle(ctx.geo)) if ctx.needs_input_grad[0] else None
+        gw = _ConvW.apply(x, dy, ctx.geo) if ctx.needs_input_grad[1] else None
+        return gx, gw, None
+
+
+class _ConvW(torch.autograd.Function):
+    """dw = weight gradient of <dy, conv(x, w)> (la_conv2d_wgrad_f32), bilinear in (x, dy)."""
+
+    @staticmethod
+    def forward(ctx, x, dy, geo):
+        ctx.save_for_backward(x, dy)
+        ctx.geo = geo
+        return _conv_launch_w(x, dy, geo)
+
+    @staticmethod
+    def backward(ctx, ddw):
+        x, dy = ctx.saved_tensors
+        gx = _ConvY.apply(dy, ddw, _conv_geo_toggle(ctx.geo)) if ctx.needs_input_grad[0] else None
+        gdy = _ConvY.apply(x, ddw, ctx.geo) if ctx.needs_input_grad[1] else None
+        return gx, gdy, None
+
+
+def _conv_op(x, w, stride, padding, groups, transpose, flip_weight, name):
+    assert isinstance(x, torch.Tensor) and isinstance(w, torch.Tensor)
+    _lib.require_gpu(x)
+    _lib.require_gpu(w)
+    assert x.ndim == 4 and w.ndim == 4
+    assert w.dtype == x.dtype
+    if x.dtype != torch.float32:
+        raise _lib.LatentAugHipError(f'{name}: x and w must be float32 (got {x.dtype}); there is no other-precision kernel')
+    assert isinstance(stride, (int, np.integer)) and isinstance(groups, (int, np.integer)) and groups >= 1
+    py, px = (padding, padding) if isinstance(padding, (int, np.integer)) else padding
+    s, py, px, groups = int(stride), int(py), int(px), int(groups)
+    n, cin, h, wd = x.shape
+    kh, kw = w.shape[2:]
+    if s < 1:
+        raise _lib.LatentAugHipError(f'{name}: stride must be at least 1')
+    if transpose:
+        assert w.shape[0] == cin, (x.shape, w.shape)
+        cout, oh, ow = w.shape[1] * groups, (h - 1) * s - 2 * py + kh, (wd - 1) * s - 2 * px + kw
+    else:
+        assert w.shape[1] * groups == cin, (x.shape, w.shape)
+        cout, oh, ow = w.shape[0], (h + 2 * py - kh) // s + 1, (wd + 2 * px - kw) // s + 1
+    if oh < 1 or ow < 1:
+        raise _lib.LatentAugHipError(f'{name}: output smaller than 1x1 (got {oh}x{ow})')
+    geo = (bool(transpose), s, py, px, groups, bool(flip_weight), tuple(x.shape), tuple(w.shape), (n, cout, oh, ow))
+    return _ConvY.apply(x, w, geo)
+
+
+def conv2d(x, w, stride=1, padding=0, groups=1):
+    """torch.nn.functional.conv2d(x, w, None, stride, padding, 1, groups) as conv2d_gradfix.py:24 provides it: float32 device tensors,
+    one stride for both axes, padding an int or (py, px).  Gradients of every order with respect to x and w."""
+    return _conv_op(x, w, stride, padding, groups, False, True, 'conv2d')
+
+
+def conv_transpose2d(x, w, stride=1, padding=0, groups=1):
+    """torch.nn.functional.conv_transpose2d(x, w, None, stride, padding, 0, groups) (conv2d_gradfix.py:29); w [Cin][Cout/groups][kh][kw]."""
+    return _conv_op(x, w, stride, padding, groups, True, True, 'conv_transpose2d')
+
+
+def _conv2d_wrapper(x, w, stride=1, padding=0, groups=1, transpose=False, flip_weight=True):
+    """conv2d_resample.py:26-40.  flip_weight=True is correlation; False runs on the flipped kernel -- the kernels index it that
+    way themselves, no flipped copy of w is made."""
+    return _conv_op(x, w, stride, padding, groups, transpose, flip_weight, 'conv2d_resample')
+
+
+def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight=True, flip_filter=False, impl='hip'):
+    """2-D convolution with optional up / down-sampling (reference: conv2d_resample.py:46-141): x [N][Cin][H][W], w
+    [Cout][Cin/groups][kh][kw], f a filter of setup_filter() or None, up / down integer factors, padding with respect to the upsampled
+    image (an int, [x, y] or [x0, x1, y0, y1]), flip_weight=False for a true convolution.  float32 device tensors; composed of
+    conv2d / conv_transpose2d and upfirdn2d, with gradients of every order with respect to x and w."""
+    assert isinstance(x, torch.Tensor) and x.ndim == 4
+    assert isinstance(w, torch.Tensor) and w.ndim == 4 and w.dtype == x.dtype
+    assert f is None or (isinstance(f, torch.Tensor) and f.ndim in [1, 2] and f.dtype == torch.float32)
+    assert isinstance(up, (int, np.integer)) and up >= 1
+    assert isinstance(down, (int, np.integer)) and down >= 1
+    assert isinstance(groups, (int, np.integer)) and groups >= 1
+    _lib.require_gpu(x)
+    _lib.require_gpu(w)
+    if x.dtype != torch.float32:
+        raise _lib.LatentAugHipError(f'conv2d_resample: x and w must be float32 (got {x.dtype}); there is no other-precision kernel')
+    up, down, groups = int(up), int(down), int(groups)
+    cout, cin_g, kh, kw = (int(v) for v in w.shape)
+    fh, fw = (1, 1) if f is None else _fshape(f)
+    px0, px1, py0, py1 = _parse_padding(padding)
+
+    # padding with respect to the upsampled image -> padding of the resampling steps
+    if up > 1:
+        px0 += (fw + up - 1) // 2
+        px1 += (fw - up) // 2
+        py0 += (fh + up - 1) // 2
+        py1 += (fh - up) // 2
+    if down > 1:
+        px0 += (fw - down + 1) // 2
+        px1 += (fw - down) // 2
+        py0 += (fh - down + 1) // 2
+        py1 += (fh - down) // 2
+
+    # 1x1 kernel and downsampling only: filter and decimate first, convolve the small image
+    if kw == 1 and kh == 1 and down > 1 and up == 1:
+        x = upfirdn2d(x, f, down=down, padding=[px0, px1, py0, py1], flip_filter=flip_filter)
+        return _conv2d_wrapper(x, w, groups=groups, flip_weight=flip_weight)
+
+    # 1x1 kernel and upsampling only: convolve the small image first
+    if kw == 1 and kh == 1 and up > 1 and down == 1:
+        x = _conv2d_wrapper(x, w, groups=groups, flip_weight=flip_weight)
+        return upfirdn2d(x, f, up=up, padding=[px0, px1, py0, py1], gain=up ** 2, flip_filter=flip_filter)
+
+    # downsampling only: filter, then a strided convolution
+    if down > 1 and up == 1:
+        x = upfirdn2d(x, f, padding=[px0, px1, py0, py1], flip_filter=flip_filter)
+        return _conv2d_wrapper(x, w, stride=down, groups=groups, flip_weight=flip_weight)
+
+    # upsampling (and possibly downsampling after it): transposed strided convolution, then the filter
+    if up > 1:
+        if groups == 1:
+            wt = w.transpose(0, 1)
+        else:
+            wt = w.reshape(groups, cout // groups, cin_g, kh, kw).transpose(1, 2).reshape(groups * cin_g, cout // groups, kh, kw)
+        px0 -= kw - 1
+        px1 -= kw - up
+        py0 -= kh - 1
+        py1 -= kh - up
+        pxt = max(min(-px0, -px1), 0)
+        pyt = max(min(-py0, -py1), 0)
+        x = _conv2d_wrapper(x, wt, stride=up, padding=[pyt, pxt], groups=groups, transpose=True, flip_weight=(not flip_weight))
+        x = upfirdn2d(x, f, padding=[px0 + pxt, px1 + pxt, py0 + pyt, py1 + pyt], gain=up ** 2, flip_filter=flip_filter)
+        if down > 1:
+            x = upfirdn2d(x, f, down=down, flip_filter=flip_filter)
+        return x
+
+    # no resampling and a symmetric non-negative padding: the convolution pads itself
+    if up == 1 and down == 1 and px0 == px1 and py0 == py1 and px0 >= 0 and py0 >= 0:
+        return _conv2d_wrapper(x, w, padding=[py0, px0], groups=groups, flip_weight=flip_weight)
+
+    # anything else: pad / crop through upfirdn2d, convolve, decimate
+    x = upfirdn2d(x, (f if up > 1 else None), up=up, padding=[px0, px1, py0, py1], gain=up ** 2, flip_filter=flip_filter)
+    x = _conv2d_wrapper(x, w, groups=groups, flip_weight=flip_weight)
+    if down > 1:
+        x = upfirdn2d(x, f, down=down, flip_filter=flip_filter)
+    return x
