@@ -3,6 +3,11 @@
  * Drop-in boundary for the latent-optimisation hot path of ltronchin/LatentAugment.  Every entry point names the
  * reference interface it replaces (paths relative to the reference repository root).
  *
+ * This file is the only copy of the ABI: the library's sources are compiled against it (a definition that disagrees does not build)
+ * and the Python binding (latentaugment_amd/_lib.py) reads its prototypes and structs from it.  Keep the style it parses: C comments
+ * only, one `ret name(type name, ...);` per entry with every parameter named, scalars of int / long / float / double / size_t /
+ * unsigned / unsigned long long.
+ *
  * Conventions
  *   - plain pointers and sizes only; every data pointer is DEVICE memory (fp32, contiguous NCHW) unless its name ends
  *     in `_host`; the caller has selected the device and owns every buffer; nothing here allocates device memory.
@@ -28,9 +33,9 @@ typedef struct ihipStream_t* la_stream_t; /* == hipStream_t */
 #endif
 
 #define LA_OK 0
-#define LA_ERR_ARG (-1)
-#define LA_ERR_HIP (-2)
-#define LA_ERR_WORKSPACE (-3)
+#define LA_ERR_ARG (-1)       /* bad argument / unsupported configuration */
+#define LA_ERR_HIP (-2)       /* a HIP runtime call failed (see la_last_error) */
+#define LA_ERR_WORKSPACE (-3) /* caller-provided workspace too small */
 
 /* activation ids = the reference's cuda_idx (torch_utils/ops/bias_act.py:20-30) */
 #define LA_ACT_LINEAR 1
@@ -361,14 +366,15 @@ int la_crop_repeat_grad_f32(const float* gxc, float* g_img, int B, int imgc, int
 typedef struct la_opt_config {
     int steps;              /* opt_num_epochs (latent_aug.py:81) */
     float lr;               /* opt_lr (latent_aug.py:82) */
-    float beta1, beta2, eps;
+    float beta1, beta2, eps; /* Adam (0.9, 0.999, 1e-8) (util_latent_aug.py:213) */
     float w_latent, w_pix, w_disc, w_lpips; /* latent_aug.py:88-91 */
     int criterion_mode;     /* 0 | 1, kept for ABI stability: both use bank column sums reduced once per handle for the gradient;
                                loss scalars (only when losses_out is given) always use the reference's GEMM form over the banks */
     int soft_aug;           /* latent_aug.py:94 */
     float alpha;            /* latent_aug.py:95 */
     int loop_noise_mode;    /* 1 = 'const' (util_latent_aug.py:227) */
-    int final_noise_mode;   /* util_latent_aug.py:488 uses the generator default ('random'): pass 2 + tensors */
+    int final_noise_mode;   /* 0 none / 1 const / 2 explicit tensors; util_latent_aug.py:488 uses the generator default ('random'):
+                               pass 2 + tensors */
     int norm_batch;         /* n of the criteria's 1/(m*n); 0 = local batch (what a DataParallel replica sees) */
     int crop, crop_off;     /* util_dataset.py:317-323: int(sqrt(R*R/2)), round((R-crop)/2) */
 } la_opt_config;

@@ -1,150 +1,83 @@
-"""ctypes binding of liblatentaug_hip.so (the C ABI declared in include/latentaug_hip.h).
+"""ctypes binding of liblatentaug_hip.so.  The C ABI is written down once, in include/latentaug_hip.h: the library is compiled
+against that header and this module reads its prototypes and structs from it (`parse_header`), so there is no second table here.
 
 The library is the product: there is no CPU or PyTorch fallback.  If it is missing, or a call fails, this module
 raises (`LatentAugHipError`) -- it never silently computes elsewhere.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblatentaug_hip.so')
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'latentaug_hip.h')
 
 
 class LatentAugHipError(RuntimeError):
     pass
 
 
-class FeatOp(C.Structure):
-    """Mirror of `la_feat_op`."""
-    _fields_ = [('kind', C.c_int), ('cin', C.c_int), ('cout', C.c_int)]
-
-
-class OptConfig(C.Structure):
-    """Mirror of `la_opt_config` (include/latentaug_hip.h)."""
-    _fields_ = [
-        ('steps', C.c_int), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
-        ('w_latent', C.c_float), ('w_pix', C.c_float), ('w_disc', C.c_float), ('w_lpips', C.c_float),
-        ('criterion_mode', C.c_int), ('soft_aug', C.c_int), ('alpha', C.c_float),
-        ('loop_noise_mode', C.c_int), ('final_noise_mode', C.c_int), ('norm_batch', C.c_int),
-        ('crop', C.c_int), ('crop_off', C.c_int),
-    ]
-
-
-_P = C.c_void_p
 _I = C.c_int
-_L = C.c_long
-_F = C.c_float
-_D = C.c_double
-_Z = C.c_size_t
+_SCALARS = {'void': None, 'int': _I, 'long': C.c_long, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t,
+            'unsigned': C.c_uint, 'unsigned long long': C.c_ulonglong, 'la_stream_t': C.c_void_p}
+_TYPE_WORDS = {w for k in _SCALARS for w in k.split()} | {'char', 'short', 'signed'}
 
-# name -> (restype, argtypes); kept in one table so tests can check every header symbol is exported
-SIGNATURES = {
-    'la_last_error': (C.c_char_p, []),
-    'la_abi_version': (_I, []),
-    'la_bias_act_f32': (_I, [_P, _P, _P, _L, _L, _I, _I, _F, _F, _F, _P]),
-    'la_bias_act_grad_f32': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _F, _F, _F, _P]),
-    'la_upfirdn2d_out_size': (_I, [_I] * 6),
-    'la_filtered_lrelu_f32': (_I, [_P] * 7 + [_I] * 16 + [_F, _F, _F, _I, _I, _P]),
-    'la_filtered_lrelu_act_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P]),
-    'la_filtered_lrelu_out_size': (_I, [_I] * 7),
-    'la_filtered_lrelu_sign_shape': (_I, [_I] * 12 + [_P, _P]),
-    'la_conv2d_f32': (_I, [_P, _P, _P, _P, _Z] + [_I] * 15 + [_P]),
-    'la_conv2d_wgrad_f32': (_I, [_P, _P, _P, _P, _Z] + [_I] * 15 + [_P]),
-    'la_conv2d_workspace_bytes': (_Z, [_I] * 13),
-    'la_conv2d_uses_engine': (_I, [_I] * 6),
-    'la_conv2d_wgrad_slices': (_I, [_I] * 12),
-    'la_pack_conv_weights_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    'la_modconv3x3_fwd_f32': (_I, [_P, _L, _P, _P, _I, _P, _I, _P, _I, _P, _L, _F, _P, _I, _F, _F, _F, _P, _P, _Z, _I, _I, _I, _I, _P]),
-    'la_modconv3x3_up2_fwd_f32': (_I, [_P, _L, _P, _P, _I, _P, _I, _P, _I, _P, _L, _F, _P, _I, _F, _F, _F, _P, _P, _P, _P, _Z, _I,
-                                       _I, _I, _I, _P]),
-    'la_modconv3x3_bwd_f32': (_I, [_P, _P, _P, _I, _P, _I, _P, _L, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
-    'la_modconv3x3_up2_bwd_f32': (_I, [_P, _P, _P, _I, _P, _I, _P, _L, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
-    'la_modconv_ds_tiles': (_I, [_I]),
-    'la_modconv_workspace_bytes': (_Z, [_I, _I, _I, _I, _I]),
-    'la_modconv_bf16_pack_bytes': (_Z, [_I, _I, _I, _I]),
-    'la_pack_conv_weights_bf16_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    'la_pairwise_l2_workspace_floats': (_L, [_I, _L]),
-    'la_pairwise_l2_f32': (_I, [_P, _I, _P, _L, _L, _P, _P, _P, _P]),
-    'la_center_crop_f32': (_I, [_P, _P, _L, _I, _I, _I, _P]),
-    'la_adam_step_f32': (_I, [_P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _P]),
-    'la_noise_normal_f32': (_I, [_P, _L, _L, C.c_ulonglong, C.c_uint, _L, _P]),
-    'la_synth_num_ws': (_I, [_I]),
-    'la_synth_num_params': (_I, [_I]),
-    'la_synth_workspace_bytes': (_Z, [_I, _I, _I, _P, _I]),
-    'la_synth_create': (_I, [_I, _I, _I, _P, _F, _P, _I, _P, _I, _P, _I, _I, _I, _P, _Z, _P, _P]),
-    'la_synth_destroy': (None, [_P]),
-    'la_synth_set_precision': (_I, [_P, _I]),
-    'la_synth_set_operand_scale': (_I, [_P, _I]),
-    'la_synth_set_row_window': (_I, [_P, _I, _I]),
-    'la_synth_set_col_window': (_I, [_P, _I, _I]),
-    'la_synth_get_precision': (_I, [_P]),
-    'la_synth_forward': (_I, [_P, _P, _L, _L, _I, _I, _P, _P, _P]),
-    'la_synth_backward': (_I, [_P, _P, _P, _P]),
-    'la_synth_image': (_P, [_P]),
-    'la_synth_block_image': (_P, [_P, _I]),
-    'la_synth_layer_output': (_P, [_P, _I]),
-    'la_synth_styles': (_P, [_P]),
-    'la_synth_style_grads': (_P, [_P]),
-    'la_synth_style_rows': (_I, [_P]),
-    'la_latent_opt_workspace_bytes': (_Z, [_I, _I, _I, _P, _L, _L, _I]),
-    'la_latent_opt_create': (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _L, _I, _P, _Z, _P]),
-    'la_latent_opt_workspace_bytes_ex': (_Z, [_I, _I, _I, _P, _L, _L, _I, _I]),
-    'la_latent_opt_create_ex': (_I, [_P, _I, _I, _I, _P, _P, _L, _P, _L, _I, _I, _P, _Z, _P]),
-    'la_latent_opt_destroy': (None, [_P]),
-    'la_latent_opt_run': (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
-    'la_fc_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _F, _P]),
-    'la_mapping_forward_f32': (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _F, _I, _P, _P, _P]),
-    'la_feature_moments_f64': (_I, [_P, _L, _I, _P, _P, _P]),
-    'la_pr_workspace_floats': (_Z, [_L, _L]),
-    'la_cdist_f16': (_I, [_P, _L, _P, _L, _I, _P, _P, _P]),
-    'la_pr_kth_f16': (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _P]),
-    'la_pr_member_f16': (_I, [_P, _L, _P, _L, _I, _P, _P, _P, _P]),
-    'la_disc_num_params': (_I, [_I]),
-    'la_disc_workspace_bytes': (_Z, [_I, _I, _P, _I]),
-    'la_disc_create': (_I, [_I, _I, _P, _F, _P, _I, _P, _I, _I, _P, _Z, _P, _P]),
-    'la_disc_destroy': (None, [_P]),
-    'la_disc_set_precision': (_I, [_P, _I]),
-    'la_disc_forward': (_I, [_P, _P, _I, _P]),
-    'la_disc_loss': (_I, [_P, _F, _I, _P, _P]),
-    'la_disc_backward': (_I, [_P, _P, _P, _I, _P]),
-    'la_disc_logits': (_P, [_P]),
-    'la_latent_opt_set_disc': (_I, [_P, _P]),
-    'la_feat_workspace_bytes': (_Z, [_I, _P, _I, _I, _I]),
-    'la_feat_create': (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _Z, _P, _P]),
-    'la_feat_destroy': (None, [_P]),
-    'la_feat_num_features': (_I, [_P]),
-    'la_feat_set_precision': (_I, [_P, _I]),
-    'la_feat_forward': (_I, [_P, _P, _I, _P, _P]),
-    'la_feat_backward': (_I, [_P, _P, _P, _P]),
-    'la_crop_repeat_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
-    'la_crop_repeat_grad_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
-    'la_latent_opt_lpips_workspace_bytes': (_Z, [_I, _I, _I, _L, _I]),
-    'la_latent_opt_set_lpips': (_I, [_P, _P, _P, _L, _I, _F, _F, _P, _Z]),
-    'la_latent_opt_set_crop_pos': (_I, [_P, _I, _I]),
-    'la_latent_opt_set_graph': (_I, [_P, _I]),
-    'la_latent_opt_graph_state': (_I, [_P]),
-    'la_latent_opt_set_trace': (_I, [_P, _P, _P]),
-    'la_latent_opt_set_grad_trace': (_I, [_P, _P]),
-    'la_latent_opt_set_overlap': (_I, [_P, _I]),
-    'la_latent_opt_set_row_window': (_I, [_P, _I, _I]),
-    'la_latent_opt_set_col_window': (_I, [_P, _I, _I]),
-    'la_latent_opt_set_time_trace': (_I, [_P, _I]),
-    'la_latent_opt_get_times': (_I, [_P, _P]),
-    'la_latent_opt_set_lpips_preproc': (_I, [_P, _P, _P, _I]),
-    'la_latent_opt_invalidate_banks': (_I, [_P]),
-    'la_prof_begin': (_I, []),
-    'la_prof_end': (_I, [_P, _P, _P, _P]),
-    'la_prof_set_stride': (_I, [_I]),
-    'la_prof_total_launches': (_L, []),
-    'la_prof_num_classes': (_I, []),
-    'la_prof_end_classes': (_I, [_P, _P, _P, _P, _I]),
-}
 
-# the op layer's per-dtype entries: one row each, the scalars (alpha / gain / clamp) double for float64 and float otherwise
-for _sfx, _S in (('f16', _F), ('f32', _F), ('f64', _D)):
-    SIGNATURES['la_bias_act_ex_' + _sfx] = (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _S, _S, _S, _P])
-    SIGNATURES['la_bias_sum_' + _sfx] = (_I, [_P, _P, _L, _L, _I, _P])
-    SIGNATURES['la_upfirdn2d_' + _sfx] = (_I, [_P, _P, _P] + [_I] * 15 + [_S, _P])
+def _ctype(decl, named=True):
+    """ctypes type of one C declarator: a named parameter or struct field ('const float* x', 'unsigned long long seed'), or with
+    named=False a return type.  Every pointer is c_void_p (a `const char*` return: c_char_p); a scalar must be in _SCALARS."""
+    if '*' in decl:
+        return C.c_char_p if not named and decl.replace(' ', '') == 'constchar*' else C.c_void_p
+    words = [w for w in decl.split() if w != 'const']
+    if named:
+        if len(words) < 2 or words[-1] in _TYPE_WORDS:
+            raise LatentAugHipError(f'C header: parameter or field without a name: {decl!r}')
+        words.pop()
+    if ' '.join(words) not in _SCALARS or (named and words == ['void']):
+        raise LatentAugHipError(f'C header: unknown type {" ".join(words)!r} in {decl!r}')
+    return _SCALARS[' '.join(words)]
+
+
+def parse_header(text):
+    """The C ABI as ctypes: ({entry: (restype, argtypes)}, {struct: ctypes.Structure subclass}) from the text of the public header.
+    Its style is regular -- /* */ comments, one `ret la_name(type name, ...);` per entry, `typedef struct tag { fields } name;` -- and
+    whatever is left over after those (and the opaque-handle typedefs) is an error, never skipped or guessed at."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+    structs, sigs = {}, {}
+
+    def take_struct(m):
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(';'))):
+            if '*' in decl:
+                raise LatentAugHipError(f'C header: pointer field in struct {m.group(2)}: {decl!r}')
+            first, *more = [s.strip() for s in decl.split(',')]
+            fields += [(n, _ctype(first)) for n in [first.split()[-1]] + more]
+        structs[m.group(2)] = type(m.group(2), (C.Structure,), {'_fields_': fields})
+        return ''
+    text = re.sub(r'typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;', take_struct, text, flags=re.S)
+    text = re.sub(r'typedef\s+struct\s+\w+\s*\*?\s*\w+\s*;', '', text)      # opaque handles, la_stream_t
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r'\1', text, flags=re.S)
+    for stmt in filter(None, (' '.join(s.split()) for s in text.split(';'))):
+        m = re.fullmatch(r'(.+?)\s*\b(la_\w+)\s*\(([^()]*)\)', stmt)
+        if not m or m.group(2) in sigs:
+            raise LatentAugHipError(f'C header: not a prototype, or declared twice: {stmt!r}')
+        ret, name, args = m.groups()
+        sigs[name] = (_ctype(ret, named=False), [] if args.strip() == 'void' else [_ctype(a) for a in args.split(',')])
+    return sigs, structs
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise LatentAugHipError(f'{HEADER_PATH}: the public header is the source of this binding and could not be read ({e})')
+
+
+# name -> (restype, argtypes) of every entry of the header; la_feat_op / la_opt_config as ctypes structures
+SIGNATURES, _structs = _read_header()
+FeatOp, OptConfig = _structs['la_feat_op'], _structs['la_opt_config']
 
 _lib = None
 LOADED_PATH = None

@@ -3,10 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define LA_OK 0
-#define LA_ERR_ARG (-1)        // bad argument / unsupported configuration
-#define LA_ERR_HIP (-2)        // a HIP runtime call failed (see la_last_error)
-#define LA_ERR_WORKSPACE (-3)  // caller-provided workspace too small
+// The public C ABI: every translation unit sees the prototypes, structs and LA_* constants it defines or calls from the one header
+// that callers get, so a definition that disagrees with it does not compile.  (la_stream_t there is hipStream_t.)
+#include "latentaug_hip.h"
 
 #define LA_WAVE 64
 
@@ -127,11 +126,6 @@ __device__ __forceinline__ float la_xs_get(const float* p, int b, int fan) {
     for (int i = 1; i < LA_XS_SUBS; ++i) m = fminf(m, v[i]);
     return m;
 }
-
-// activation ids follow the reference's cuda_idx (bias_act.py:20-30): 1 linear, 2 relu, 3 lrelu
-#define LA_ACT_LINEAR 1
-#define LA_ACT_RELU 2
-#define LA_ACT_LRELU 3
 
 // y = clamp(act(v) * gain)  (bias_act.cu:23-147 semantics, grad=0)
 __device__ __forceinline__ float la_act_fwd(float v, int act, float alpha, float gain, float clamp) {

@@ -16,12 +16,6 @@
 #define LA_CONV_MAX_PHASES 4
 #define LA_CONV_PHASE_TAPS 4
 
-// contraction arithmetic: exact fp32 MFMA, or fp32 operands split into 3 / 2 bf16 terms on the bf16 MFMA (la_conv_bf16.hip)
-#define LA_PREC_F32 0
-#define LA_PREC_BF16X3 1
-#define LA_PREC_BF16X2 2
-#define LA_PREC_F16X2 3     // fp32 operands scaled by a power of two and split into 2 fp16 terms, 3 fp16 MFMAs per product
-
 struct LaConvArgs {
     const float* in;         // [B][C][Hin][Win]; in_bstride == 0 broadcasts one sample over the batch
     const float* wgt;        // [slabs][C][M]

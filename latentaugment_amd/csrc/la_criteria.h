@@ -33,11 +33,3 @@ int la_wplus_step_tail(const float* dws, const float* colsumW, float* dw, float*
                        hipStream_t stream);
 int la_wplus_gate(const float* w_opt, const float* w0, float* w_aug, int B, int num_ws, int wdim, float alpha, int soft,
                   hipStream_t stream);
-extern "C" {
-long la_pairwise_l2_workspace_floats(int n, long m);
-int la_pairwise_l2_f32(const float* X, int n, const float* Y, long m, long K, float* D, float* mean_out,
-                       float* workspace, hipStream_t stream);
-int la_center_crop_f32(const float* src, float* dst, long planes, int R, int cc, int off, hipStream_t stream);
-int la_adam_step_f32(float* p, const float* g, float* m, float* v, long n, int step, float lr, float beta1, float beta2,
-                     float eps, hipStream_t stream);
-}

@@ -5,7 +5,7 @@
 //
 // Every 3x3 / 1x1 contraction reuses the implicit-GEMM kernels of la_conv*.hip (shared weights: no modulation);
 // FIR stages reuse la_upfirdn2d.hip; what is new here: fromrgb (K = img_channels, HBM-bound), MinibatchStd, the FC tail.
-#include "la_disc.h"
+#include "la_common.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -15,11 +15,6 @@
 #include "la_modconv.h"
 #include "la_style.h"
 #include "la_upfirdn2d.h"
-
-extern "C" int la_bias_act_grad_f32(const float* dy, const float* yref, float* dx, float* db, long n, long stepb, int nb, int act,
-                                    float alpha, float gain, float clamp, hipStream_t stream);
-extern "C" int la_fc_f32(const float* x, const float* W, const float* bias, float* y, int B, int in, int out, float lr_mul, int act,
-                         float alpha, float gain, hipStream_t stream);
 
 #define DMAX_BLOCKS 12
 

@@ -17,9 +17,6 @@
 #include "la_modconv.h"
 #include "la_style.h"
 
-extern "C" int la_bias_act_grad_f32(const float* dy, const float* yref, float* dx, float* db, long n, long stepb, int nb, int act,
-                                    float alpha, float gain, float clamp, hipStream_t stream);
-
 #define FEAT_MAX_OPS 48
 
 struct FOp {

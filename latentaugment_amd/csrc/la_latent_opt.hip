@@ -2,7 +2,7 @@
 // launch sequence with no host<->device synchronisation inside the loop (the reference syncs 5x per step through
 // `.item()`, :234-271).  W-space optimisation: ws = w repeated num_ws times (:226, :493-494); a W+ handle (la_latent_opt_create_ex,
 // latent_space 1) optimises one row per slot instead (la_wplus.hip).
-#include "la_latent_opt.h"
+#include "la_common.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -10,7 +10,6 @@
 
 #include "la_conv.h"
 #include "la_criteria.h"
-#include "la_disc.h"
 #include "la_feat.h"
 
 struct la_latent_opt {

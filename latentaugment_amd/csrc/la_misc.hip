@@ -61,7 +61,6 @@ extern "C" int la_bias_act_f32(const float* x, const float* b, float* y, long n,
     return LA_OK;
 }
 
-extern "C" int la_bias_sum_f32(const float* dx, float* db, long n, long stepb, int nb, hipStream_t stream);
 extern "C" int la_bias_act_grad_f32(const float* dy, const float* yref, float* dx, float* db, long n, long stepb, int nb,
                                     int act, float alpha, float gain, float clamp, hipStream_t stream) {
     if (n == 0) return LA_OK;

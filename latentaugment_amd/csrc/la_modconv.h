@@ -1,6 +1,5 @@
-// Modulated 3x3 conv entry points (C ABI; citations in include/latentaug_hip.h).
+// Modulated 3x3 conv: the internal (C++) variants of the entry points of include/latentaug_hip.h.
 #pragma once
-#include <stddef.h>
 #include "la_common.h"
 #include "la_style.h"
 
@@ -74,25 +73,3 @@ int la_modconv3x3_up2_bwd_ex(const float* gz, const float* gz_pmax, int gz_nseg,
 // its (res+1)-row result that can be non-zero, [in_lo - 2, in_hi + 2), and the contraction reads the others as zeros      // seam of the block BELOW (its conv1 output is xin), incl. its ToRGB backward
 
 float la_modconv_up2_bwd_xs_mult(const float* fir_host);      // the `mult` of the operand scale an up layer's backward expects (LaSeamFuse::xs_mult)
-
-extern "C" {
-int la_pack_conv_weights_f32(const float* w, float* wf, float* wb, float* wsq, int cout, int cin, int ktaps, hipStream_t);
-int la_modconv3x3_fwd_f32(const float* x, long x_bstride, const float* wf, const void* wq, int precision, const float* s, int s_stride, const float* d,
-                          int d_stride, const float* noise, long noise_bstride, float noise_strength, const float* bias,
-                          int act, float alpha, float gain, float clamp, float* y, void* ws, size_t ws_bytes, int B, int cin, int cout, int res,
-                          hipStream_t stream);
-int la_modconv3x3_up2_fwd_f32(const float* x, long x_bstride, const float* wf, const void* wq, int precision, const float* s, int s_stride,
-                              const float* d, int d_stride, const float* noise, long noise_bstride, float noise_strength,
-                              const float* bias, int act, float alpha, float gain, float clamp, const float* fir_host,
-                              float* scratch, float* y, void* ws, size_t ws_bytes, int B, int cin, int cout, int res, hipStream_t stream);
-int la_modconv3x3_bwd_f32(const float* gz, const float* wb, const void* wq, int precision, const float* s, int s_stride, const float* xin,
-                          long xin_bstride, float* gx, float* ds_part, void* ws, size_t ws_bytes, int B, int cin, int cout, int res, hipStream_t);
-int la_modconv3x3_up2_bwd_f32(const float* gz, const float* wb, const void* wq, int precision, const float* s, int s_stride, const float* xin,
-                              long xin_bstride, const float* fir_host, float* scratch, float* gx, float* ds_part, void* ws, size_t ws_bytes, int B,
-                              int cin, int cout, int res, hipStream_t stream);
-int la_modconv_ds_tiles(int grid_res);
-size_t la_modconv_workspace_bytes(int B, int cin, int cout, int res, int up);
-size_t la_modconv_bf16_pack_bytes(int cin, int cout, int transpose, int nterm);
-int la_pack_conv_weights_bf16_f32(const float* w, void* out, int cout, int cin, int ktaps, int transpose, int nterm,
-                                  hipStream_t stream);
-}

@@ -2,7 +2,7 @@
 // Mirrors the call  G.synthesis(ws, noise_mode=...)  at augments/utils/util_latent_aug.py:227,488 and the autograd
 // backward of it that loss.backward() at :275 performs, restricted to d/d(ws) (G is frozen: :480).
 // Formulation: non-fused modulated conv (x*s -> shared-weight contraction -> *demod), see DESIGN.md.
-#include "la_synth.h"
+#include "la_common.h"
 
 #include <math.h>
 #include <stdlib.h>

@@ -34,6 +34,81 @@ def test_header_symbols_exported(lib):
     assert lib.la_abi_version() == 1
 
 
+def _header():
+    return open(os.path.join(ROOT, 'include', 'latentaug_hip.h')).read()
+
+
+def test_binding_is_parsed_from_every_header_prototype():
+    """The ctypes table is read from the header: one row per entry it declares, none missing, none extra."""
+    from latentaugment_amd import _lib
+    declared = set(re.findall(r'\b(la_[a-z0-9_]+)\s*\(', _header()))
+    assert len(declared) >= 100
+    assert set(_lib.SIGNATURES) == declared and len(_lib.SIGNATURES) == len(declared)
+    sigs, structs = _lib.parse_header(_header())
+    assert sigs == _lib.SIGNATURES and set(structs) == {'la_feat_op', 'la_opt_config'}
+
+
+def test_binding_type_map_pins():
+    """One entry per scalar kind of the parser's type map, written out by hand."""
+    import ctypes as C
+    from latentaugment_amd._lib import SIGNATURES as S
+    P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
+    assert S['la_noise_normal_f32'] == (I, [P, L, L, C.c_ulonglong, C.c_uint, L, P])
+    assert S['la_conv2d_workspace_bytes'] == (C.c_size_t, [I] * 13)
+    assert S['la_last_error'] == (C.c_char_p, [])
+    assert S['la_synth_image'] == (P, [P])
+    assert S['la_synth_destroy'] == (None, [P])
+    assert S['la_pairwise_l2_workspace_floats'] == (L, [I, L])
+    assert S['la_bias_act_ex_f64'] == (I, [P] * 6 + [L, L, I, I, I] + [C.c_double] * 3 + [P])
+    assert S['la_bias_act_ex_f32'] == (I, [P] * 6 + [L, L, I, I, I] + [F] * 3 + [P])
+    assert S['la_filtered_lrelu_f32'] == (I, [P] * 7 + [I] * 16 + [F, F, F, I, I, P])
+
+
+def test_binding_structs_follow_the_header():
+    import ctypes as C
+    from latentaugment_amd import _lib
+    hdr = re.sub(r'/\*.*?\*/', ' ', _header(), flags=re.S)
+    for cname, cls in (('la_opt_config', _lib.OptConfig), ('la_feat_op', _lib.FeatOp)):
+        body = re.search(r'typedef\s+struct\s+%s\s*\{(.*?)\}' % cname, hdr, re.S).group(1)
+        names = [n for n in re.findall(r'[A-Za-z_]\w*', body) if n not in ('int', 'float')]
+        assert [f[0] for f in cls._fields_] == names, cname
+        assert all(t in (C.c_int, C.c_float) for _, t in cls._fields_)
+    assert C.sizeof(_lib.OptConfig) == 17 * 4 and C.sizeof(_lib.FeatOp) == 3 * 4
+    assert dict(_lib.OptConfig._fields_)['lr'] is C.c_float and dict(_lib.OptConfig._fields_)['crop_off'] is C.c_int
+    cfg = _lib.OptConfig(steps=5, lr=0.5, crop=181, crop_off=38)
+    assert (cfg.steps, cfg.lr, cfg.crop, cfg.crop_off, cfg.w_pix) == (5, 0.5, 181, 38, 0.0)
+    op = _lib.FeatOp(1, 2, 3)
+    assert (op.kind, op.cin, op.cout) == (1, 2, 3)
+
+
+@pytest.mark.parametrize('text', [
+    'int la_x(int a, int b;',                       # cannot be split
+    'int la_x(int a) int la_y(int b);',
+    'int la_x(long long n);',                       # scalar types the map does not have
+    'int la_x(short n);',
+    'wchar_t la_x(void);',
+    'int la_x(int);',                               # no parameter name: `unsigned long` could not be told from `unsigned x`
+    'int la_x();',
+    'int la_x(void); int la_x(void);',              # declared twice
+    'int some_global;',
+    'typedef struct s { char c; } s;',
+    'typedef struct s { int* p; } s;',
+])
+def test_binding_parser_refuses_what_it_does_not_know(text):
+    from latentaugment_amd import _lib
+    with pytest.raises(_lib.LatentAugHipError) as e:
+        _lib.parse_header(text)
+    assert 'C header' in str(e.value)
+    _lib.parse_header('int la_x(int a);')           # (the well-formed neighbour of these parses)
+
+
+def test_binding_needs_the_header(monkeypatch, tmp_path):
+    from latentaugment_amd import _lib
+    monkeypatch.setattr(_lib, 'HEADER_PATH', str(tmp_path / 'latentaug_hip.h'))
+    with pytest.raises(_lib.LatentAugHipError, match='latentaug_hip.h'):
+        _lib._read_header()
+
+
 def test_product_library_has_no_development_switches(lib):
     """Kernel-variant knobs and LA_* environment switches exist in the development build (-DLA_DEV) only: the product library neither
     exports la_dev_knob_set nor contains the names of the environment variables the development build reads."""
