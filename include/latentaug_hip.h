@@ -465,6 +465,7 @@ int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const float* con
  *                           dist float32 [nr][nc].  rows/cols: float16 [n][D] row-major, D % 16 == 0, 16-byte aligned.
  *   la_pr_kth_f16           precision_recall.py:75-79: kth[i] = (nhood_size+1)-th smallest distance of row i.
  *   la_pr_member_f16        precision_recall.py:80-84: member[i] = any_j dist(i, j) <= radius[j].
+ *   la_kid_poly3_f32        Kernel Inception Distance of two feature sets (described at its prototype below).
  * ws: la_pr_workspace_floats(nr, nc) floats.  The [nr][nc] matrix is not materialised by the last two.
  * ------------------------------------------------------------------------------------------------------------- */
 int la_feature_moments_f64(const float* x, long n, int D, double* raw_mean, double* raw_cov, la_stream_t stream);
@@ -474,6 +475,24 @@ int la_pr_kth_f16(const void* rows, long nr, const void* cols, long nc, int D, i
                   la_stream_t stream);
 int la_pr_member_f16(const void* rows, long nr, const void* cols, long nc, int D, const float* radius, unsigned char* member,
                      float* ws, la_stream_t stream);
+
+/* Kernel Inception Distance (no reference counterpart; the community's kid50k_full recipe): the unbiased MMD^2 estimator with the
+ * cubic polynomial kernel k(a, b) = (a.b / D + 1)^3 over detector features, averaged over S subsets.  For subset s, with
+ * x_i = x[ix[s][i]] (i < mx, the generated side) and y_j = y[iy[s][j]] (j < my, the real side):
+ *   sums[s] = { sum_{i != j} k(x_i, x_j),  sum_{i != j} k(y_i, y_j),  sum_{i, j} k(x_i, y_j) }
+ *   mmd2[s] = sums[s][0] / (mx (mx - 1)) + sums[s][1] / (my (my - 1)) - 2 sums[s][2] / (mx my);    kid[0] = mean_s mmd2[s]
+ * x float32 [nx][D], y float32 [ny][D], row-major, any D >= 1 (no padding; float4 loads when D % 4 == 0 and both are 16-byte
+ * aligned).  ix int32 [S][mx], iy int32 [S][my]: row numbers, gathered while loading (no gathered copy is made); the caller
+ * draws them, and a value outside [0, n) is clamped into it rather than read out of bounds.  mx, my >= 2; they differ only for the
+ * full-set estimator (S = 1, ix = 0..nx-1, iy = 0..ny-1).  sums float64 [S][3], mmd2 float64 [S], kid float64 [1]: device memory.
+ * Dot products on the exact fp32 MFMA, in fp32 chains of 128 terms added in fp32; (dot / D + 1)^3 in fp32 per element; every sum
+ * of kernel values in float64.  The kernel matrices are never written out: ws holds one float64 partial per 128 x 128 tile and
+ * subset, la_kid_workspace_bytes(S, mx, my) bytes (8-byte aligned; 0 for sizes the launch refuses), about 109 KB at S = 100,
+ * mx = my = 1000.  A smaller ws_bytes is LA_ERR_WORKSPACE, checked with the other arguments before anything is launched.
+ * Deterministic: partials are added in index order by a second launch, no atomics; two runs give the same bits. */
+size_t la_kid_workspace_bytes(long S, long mx, long my);
+int la_kid_poly3_f32(const float* x, long nx, const float* y, long ny, int D, const int* ix, const int* iy, long S, long mx, long my,
+                     double* sums, double* mmd2, double* kid, void* ws, size_t ws_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Opt-in profiler for the contraction launches (HIP events on the launch stream).  No reference counterpart: the

@@ -4,6 +4,7 @@
 //   la_pr_kth_f16             metrics/precision_recall.py:75-79 k-th neighbour radius of every manifold point
 //   la_pr_member_f16          metrics/precision_recall.py:80-84 is a probe inside any manifold point's radius
 //   la_cdist_f16              metrics/precision_recall.py:19-32 the distance matrix itself (torch.cdist)
+//   la_kid_poly3_f32          (no reference counterpart) Kernel Inception Distance: unbiased MMD^2, cubic polynomial kernel, per subset
 // Distances follow torch.cdist's GEMM form |a|^2 + |b|^2 - 2 a.b, clamped at 1e-30, square root.  The reference hands
 // cdist float16 features; their products are exact on the fp16 MFMA (v_mfma_f32_32x32x16_f16, fp32 accumulate), so the dot
 // products here are fp32 sums of exact terms.  The [rows, cols] matrix is never materialised for the radii / membership
@@ -227,6 +228,249 @@ extern "C" int la_feature_moments_f64(const float* x, long n, int D, double* raw
     LA_CHECK_ARG(x && raw_mean && raw_cov && n >= 0 && D >= 1, "feature_moments: bad args");
     if (n == 0) return LA_OK;
     hipLaunchKernelGGL(la_feature_moments_kernel, dim3(la_cdiv(D, 16), la_cdiv(D, 16)), dim3(256), 0, stream, x, n, D, raw_mean, raw_cov);
+    LA_CHECK_LAUNCH();
+    return LA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Kernel Inception Distance: per subset s the three sums of k(a, b) = (a.b / D + 1)^3 that the unbiased MMD^2 estimator needs,
+//   sxx = sum_{i != j} k(x_i, x_j),  syy = sum_{i != j} k(y_i, y_j),  sxy = sum_{i, j} k(x_i, y_j),
+// over the rows x_i = X[ix[s][i]] (mx of them) and y_j = Y[iy[s][j]] (my).  The rows are gathered by index while the tiles are loaded;
+// the m x m kernel matrices live in accumulator registers only: one float64 partial per 128 x 128 tile is all that reaches memory.
+// Arithmetic: the exact fp32 MFMA (v_mfma_f32_32x32x2_f32), as la_conv_wgrad_mfma_kernel: 4 waves (2 x 2) of 64 x 64 = 2 x 2 MFMA tiles,
+// K walked in chunks of 16 through two LDS buffers [k][128 + 4] with the next chunk's global loads in flight, one barrier per chunk.
+// An MFMA accumulator is one k-ordered fp32 fma chain, whose rounding error grows like sqrt(chain length); with m as small as 2 nothing
+// averages it out, so a chain runs over KID_SEG chunks (128 k) only and is then added into a second fp32 accumulator (two-level
+// summation: ~2.4e-7 relative on a D = 2048 dot product of non-negative features instead of ~9e-7).
+// The xx and yy Grams are symmetric: only tiles with tj >= ti are computed; an off-diagonal tile counts twice, a diagonal tile sums
+// both of its triangles and drops i == j.  Epilogue per element in fp32, (dot / D + 1)^3, summed in float64 per lane, then over the
+// workgroup by a fixed tree.  A second launch adds the tile partials of each subset in index order: no atomics, the same bits every run.
+#define KID_T 128
+#define KID_KC 16
+#define KID_LD (KID_T + 4)
+#define KID_SEG 8
+
+struct KidArgs {
+    const float *x, *y;
+    const int *ix, *iy;
+    long nx, ny, mx, my;
+    int D, vec;          // vec: rows are 16-byte aligned (D % 4 == 0 and aligned bases): float4 loads
+    int tx, ty;          // 128-row tiles per side
+    int nxx, nyy, tiles; // tiles per subset: xx upper triangle, yy upper triangle, then tx * ty of xy
+    double* part;        // [S][tiles]
+};
+
+// fixed-order sum over the 256 threads of a workgroup; the result is in red[0]
+__device__ __forceinline__ void kid_block_sum(double v, double* red) {
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void la_kid_tile_kernel(KidArgs a) {
+    __shared__ __attribute__((aligned(16))) float As[2][KID_KC][KID_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[2][KID_KC][KID_LD];
+    __shared__ double red[256];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    const int l31 = lane & 31, lh = lane >> 5;
+
+    // blockIdx.x = subset * tiles + tile (the x axis carries the subset: no 65 535 limit)
+    const long s = blockIdx.x / (unsigned)a.tiles;
+    int t = (int)(blockIdx.x - (unsigned)(s * a.tiles));
+    const int kind = t < a.nxx ? 0 : (t < a.nxx + a.nyy ? 1 : 2);      // 0 xx, 1 yy, 2 xy
+    t -= kind == 0 ? 0 : (kind == 1 ? a.nxx : a.nxx + a.nyy);
+    const float* A = kind == 1 ? a.y : a.x;
+    const float* B = kind == 0 ? a.x : a.y;
+    const int* ia = kind == 1 ? a.iy + s * a.my : a.ix + s * a.mx;
+    const int* ib = kind == 0 ? a.ix + s * a.mx : a.iy + s * a.my;
+    const long ma = kind == 1 ? a.my : a.mx, mb = kind == 0 ? a.mx : a.my;
+    const long na = kind == 1 ? a.ny : a.nx, nb = kind == 0 ? a.nx : a.ny;
+    int ti, tj;
+    if (kind == 2) {
+        ti = t / a.ty;
+        tj = t - ti * a.ty;
+    } else {
+        const int T = kind == 0 ? a.tx : a.ty;
+        ti = 0;
+        while (t >= T - ti) { t -= T - ti; ++ti; }
+        tj = ti + t;
+    }
+    const long i0 = (long)ti * KID_T, j0 = (long)tj * KID_T;
+    const int D = a.D;
+
+    // loader roles: 4 threads per row (4 consecutive k each), rows tid / 4 and tid / 4 + 64 of both operands.  Rows past the end of
+    // the subset load zeros; an index outside the matrix is clamped into it, so nothing is ever read out of bounds.
+    const int kq = (tid & 3) * 4, lr = tid >> 2;
+    const float *pa[2], *pb[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const long i = i0 + lr + 64 * j, c = j0 + lr + 64 * j;
+        pa[j] = pb[j] = nullptr;
+        if (i < ma) { long r = ia[i]; r = r < 0 ? 0 : (r >= na ? na - 1 : r); pa[j] = A + r * D; }
+        if (c < mb) { long r = ib[c]; r = r < 0 ? 0 : (r >= nb ? nb - 1 : r); pb[j] = B + r * D; }
+    }
+    float4 areg[2], breg[2];
+    auto fetch = [&](const float* p, int k) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p && k < D) {
+            if (a.vec) {
+                v = *reinterpret_cast<const float4*>(p + k);      // D % 4 == 0: k + 3 < D
+            } else {
+                v.x = p[k];
+                if (k + 1 < D) v.y = p[k + 1];
+                if (k + 2 < D) v.z = p[k + 2];
+                if (k + 3 < D) v.w = p[k + 3];
+            }
+        }
+        return v;
+    };
+    auto prefetch = [&](int ci) {
+        const int k = ci * KID_KC + kq;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { areg[j] = fetch(pa[j], k); breg[j] = fetch(pb[j], k); }
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int r = lr + 64 * j;
+            As[buf][kq][r] = areg[j].x; As[buf][kq + 1][r] = areg[j].y; As[buf][kq + 2][r] = areg[j].z; As[buf][kq + 3][r] = areg[j].w;
+            Bs[buf][kq][r] = breg[j].x; Bs[buf][kq + 1][r] = breg[j].y; Bs[buf][kq + 2][r] = breg[j].z; Bs[buf][kq + 3][r] = breg[j].w;
+        }
+    };
+
+    f32x16 acc[2][2], tot[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = tot[i][j][r] = 0.f;
+
+    const int nchunk = (D + KID_KC - 1) / KID_KC;
+    prefetch(0);
+    stage(0);
+    __syncthreads();
+    for (int ci = 0; ci < nchunk; ++ci) {
+        const int buf = ci & 1;
+        if (ci + 1 < nchunk) prefetch(ci + 1);
+#pragma unroll
+        for (int kp = 0; kp < KID_KC / 2; ++kp) {
+            float av[2], bv[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) av[i] = As[buf][2 * kp + lh][wm * 64 + i * 32 + l31];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bv[j] = Bs[buf][2 * kp + lh][wn * 64 + j * 32 + l31];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        if ((ci & (KID_SEG - 1)) == KID_SEG - 1 || ci + 1 == nchunk) {      // end of a chain: fold it into the second level
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.f; }
+        }
+        if (ci + 1 < nchunk) stage(buf ^ 1);
+        __syncthreads();
+    }
+
+    const bool diag = kind != 2 && ti == tj;
+    const float fD = (float)D;
+    double dsum = 0.0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const long n = j0 + wn * 64 + j * 32 + l31;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long m = i0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (m < ma && n < mb && !(diag && m == n)) {
+                    const float v = tot[i][j][r] / fD + 1.f;
+                    dsum += (double)(v * v * v);
+                }
+            }
+        }
+    kid_block_sum(dsum, red);
+    if (tid == 0) a.part[blockIdx.x] = (kind != 2 && ti != tj) ? 2.0 * red[0] : red[0];
+}
+
+// one workgroup per subset: the tile partials of each of the three sums in index order (thread-strided, then the fixed tree)
+__global__ __launch_bounds__(256) void la_kid_finish_kernel(const double* __restrict__ part, int nxx, int nyy, int tiles, long mx, long my,
+                                                           double* __restrict__ sums, double* __restrict__ mmd2) {
+    __shared__ double red[256];
+    const long s = blockIdx.x;
+    const double* p = part + s * tiles;
+    const int beg[4] = {0, nxx, nxx + nyy, tiles};
+    double v[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        double acc = 0.0;
+        for (int t = beg[q] + (int)threadIdx.x; t < beg[q + 1]; t += 256) acc += p[t];
+        kid_block_sum(acc, red);
+        v[q] = red[0];
+    }
+    if (threadIdx.x == 0) {
+        sums[s * 3 + 0] = v[0];
+        sums[s * 3 + 1] = v[1];
+        sums[s * 3 + 2] = v[2];
+        mmd2[s] = v[0] / ((double)mx * (double)(mx - 1)) + v[1] / ((double)my * (double)(my - 1)) - 2.0 * v[2] / ((double)mx * (double)my);
+    }
+}
+
+__global__ __launch_bounds__(256) void la_kid_mean_kernel(const double* __restrict__ mmd2, long S, double* __restrict__ kid) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (long s = threadIdx.x; s < S; s += 256) acc += mmd2[s];
+    kid_block_sum(acc, red);
+    if (threadIdx.x == 0) kid[0] = red[0] / (double)S;
+}
+
+static inline long kid_tiles(long mx, long my) {
+    const long tx = (mx + KID_T - 1) / KID_T, ty = (my + KID_T - 1) / KID_T;
+    return tx * (tx + 1) / 2 + ty * (ty + 1) / 2 + tx * ty;
+}
+
+// one float64 partial per tile and subset (0 for sizes the launch refuses)
+extern "C" size_t la_kid_workspace_bytes(long S, long mx, long my) {
+    if (S < 1 || mx < 2 || my < 2 || mx > 0x7fffffffL || my > 0x7fffffffL) return 0;
+    return (size_t)S * (size_t)kid_tiles(mx, my) * sizeof(double);
+}
+
+extern "C" int la_kid_poly3_f32(const float* x, long nx, const float* y, long ny, int D, const int* ix, const int* iy, long S, long mx,
+                                long my, double* sums, double* mmd2, double* kid, void* ws, size_t ws_bytes, hipStream_t stream) {
+    LA_CHECK_ARG(x && y && ix && iy && sums && mmd2 && kid && ws, "kid: null pointer");
+    LA_CHECK_ARG(mx >= 2 && my >= 2, "kid: a subset needs at least 2 rows per side (the estimator divides by m (m - 1))");
+    LA_CHECK_ARG(D >= 1 && S >= 1 && nx >= 1 && ny >= 1, "kid: D, the number of subsets and the row counts must be positive");
+    LA_CHECK_ARG(mx <= 0x7fffffffL && my <= 0x7fffffffL && nx <= 0x7fffffffL && ny <= 0x7fffffffL, "kid: sizes beyond int32 indices");
+    const long tiles = kid_tiles(mx, my);
+    LA_CHECK_ARG(tiles <= 0x7fffffffL / S, "kid: num_subsets x tiles exceeds the grid");
+    if (ws_bytes < la_kid_workspace_bytes(S, mx, my)) {
+        la_set_error("kid: workspace smaller than la_kid_workspace_bytes(S, mx, my)");
+        return LA_ERR_WORKSPACE;
+    }
+    LA_CHECK_ARG(((size_t)ws & 7) == 0, "kid: the workspace must be 8-byte aligned");
+    KidArgs a;
+    a.x = x; a.y = y; a.ix = ix; a.iy = iy;
+    a.nx = nx; a.ny = ny; a.mx = mx; a.my = my;
+    a.D = D;
+    a.vec = (D % 4 == 0 && (((size_t)x | (size_t)y) & 15) == 0) ? 1 : 0;
+    a.tx = (int)((mx + KID_T - 1) / KID_T); a.ty = (int)((my + KID_T - 1) / KID_T);
+    a.nxx = (int)((long)a.tx * (a.tx + 1) / 2); a.nyy = (int)((long)a.ty * (a.ty + 1) / 2); a.tiles = (int)tiles;
+    a.part = (double*)ws;
+    hipLaunchKernelGGL(la_kid_tile_kernel, dim3((unsigned)(S * tiles)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(la_kid_finish_kernel, dim3((unsigned)S), dim3(256), 0, stream, (const double*)a.part, a.nxx, a.nyy, a.tiles, mx, my,
+                       sums, mmd2);
+    hipLaunchKernelGGL(la_kid_mean_kernel, dim3(1), dim3(256), 0, stream, (const double*)mmd2, S, kid);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }

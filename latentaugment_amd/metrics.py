@@ -6,10 +6,11 @@ detector features.
   compute_fid_from_stats       metrics/frechet_inception_distance.py:41-45
   compute_distances            metrics/precision_recall.py:19-32
   compute_pr_from_features     metrics/precision_recall.py:72-85
+  compute_kid_from_features    (not in the reference) Kernel Inception Distance, the community's kid50k_full recipe
 
 The detectors themselves (Inception-v3 and VGG16 pickles hosted by NVIDIA, metric_utils.py:46-60) cannot be fetched offline:
 callers supply the features, e.g. from `synthesis.FeatureEngine` or from a detector they have on disk.
-torch only owns the device memory; the moments, distances, radii and membership tests are HIP kernels (la_metrics.hip).
+torch only owns the device memory; the moments, distances, radii, membership tests and kernel sums are HIP kernels (la_metrics.hip).
 """
 import pickle
 
@@ -178,3 +179,76 @@ def compute_pr_from_features(real_features, gen_features, nhood_size=3, row_batc
     if return_details:
         return results['precision'], results['recall'], details
     return results['precision'], results['recall']
+
+
+def kid_subset_indices(num_real, num_gen, num_subsets=100, max_subset_size=1000, seed=0):
+    """(ix [S][mx] into the generated rows, iy [S][my] into the real rows), int32: per subset m = min(num_real, num_gen,
+    max_subset_size) rows of each side without replacement from numpy.random.RandomState(seed), the generated side drawn first.
+    max_subset_size=None with num_subsets=1 is the full-set estimator: every row once, in its given order (mx != my allowed)."""
+    if num_subsets < 1:
+        raise ValueError('num_subsets must be at least 1')
+    if max_subset_size is None:
+        if num_subsets != 1:
+            raise ValueError('max_subset_size=None is the full-set estimator: it needs num_subsets=1')
+        ix, iy = np.arange(num_gen, dtype=np.int32)[None], np.arange(num_real, dtype=np.int32)[None]
+    else:
+        m = min(num_real, num_gen, max_subset_size)
+        if m < 2:
+            raise ValueError(f'KID needs at least 2 rows per side in a subset (got m = {m})')
+        rs = np.random.RandomState(seed)
+        ix, iy = np.empty([num_subsets, m], np.int32), np.empty([num_subsets, m], np.int32)
+        for s in range(num_subsets):
+            ix[s] = rs.choice(num_gen, m, replace=False)
+            iy[s] = rs.choice(num_real, m, replace=False)
+    if min(ix.shape[1], iy.shape[1]) < 2:
+        raise ValueError(f'KID needs at least 2 rows per side (got {ix.shape[1]} generated, {iy.shape[1]} real)')
+    return ix, iy
+
+
+def _f32_features(x, dev):
+    x = torch.as_tensor(x)
+    if x.ndim != 2 or not x.is_floating_point():
+        raise ValueError('features must be a [N, D] array of a float dtype')
+    return x.detach().to(dev).to(torch.float32).contiguous()
+
+
+def compute_kid_from_features(real_features, gen_features, num_subsets=100, max_subset_size=1000, seed=0, device='cuda:0',
+                              return_details=False, indices=None):
+    """Kernel Inception Distance of `gen_features` against `real_features` ([N, D] numpy arrays or torch tensors of any float dtype,
+    computed from their float32 values; FeatureStats(capture_all=True).get_all() is such an array): the mean over `num_subsets`
+    subsets of the unbiased MMD^2 estimator with k(a, b) = (a.b / D + 1)^3.  The subsets are those of `kid_subset_indices`;
+    `indices=(ix, iy)` supplies them instead ([S][mx] generated rows, [S][my] real rows).  The rows are gathered by the kernel and the
+    kernel matrices never leave it (la_kid_poly3_f32); the result is the same bits on every run.
+    return_details=True: (kid, {'mmd2': float64 [S], 'sums': float64 [S][3] (xx and yy off-diagonal, xy), 'ix', 'iy'})."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); got device ' + str(dev))
+    nr, ng = np.shape(real_features)[0], np.shape(gen_features)[0]
+    if indices is None:
+        ix, iy = kid_subset_indices(nr, ng, num_subsets, max_subset_size, seed)
+    else:
+        ix, iy = (np.ascontiguousarray(i, dtype=np.int32) for i in indices)
+        if ix.ndim != 2 or iy.ndim != 2 or ix.shape[0] != iy.shape[0] or ix.shape[0] < 1 or min(ix.shape[1], iy.shape[1]) < 2:
+            raise ValueError('indices: ([S][mx], [S][my]) with S >= 1 and at least 2 rows per side')
+        if ix.min() < 0 or ix.max() >= ng or iy.min() < 0 or iy.max() >= nr:
+            raise ValueError('indices: a row number outside its feature matrix')
+    if not torch.cuda.is_available():
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); none is available')
+    lib = _lib.load()
+    real, gen = _f32_features(real_features, dev), _f32_features(gen_features, dev)
+    if real.shape[1] != gen.shape[1] or real.shape[1] < 1:
+        raise ValueError(f'feature dimensions differ or are empty: real {tuple(real.shape)}, generated {tuple(gen.shape)}')
+    S, mx, my = ix.shape[0], ix.shape[1], iy.shape[1]
+    ixd, iyd = torch.from_numpy(ix).to(dev), torch.from_numpy(iy).to(dev)
+    out = torch.empty([S * 4 + 1], dtype=torch.float64, device=dev)          # sums [S][3], mmd2 [S], kid [1]
+    ws_bytes = lib.la_kid_workspace_bytes(S, mx, my)
+    ws = torch.empty([ws_bytes // 8], dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
+        _lib.check(lib.la_kid_poly3_f32(_lib.ptr(gen), gen.shape[0], _lib.ptr(real), real.shape[0], gen.shape[1], _lib.ptr(ixd),
+                                        _lib.ptr(iyd), S, mx, my, _lib.ptr(out), _lib.ptr(out[S * 3:]), _lib.ptr(out[S * 4:]),
+                                        _lib.ptr(ws), ws_bytes, _lib.stream_ptr()), 'kid_poly3')
+    out = out.cpu().numpy()
+    kid = float(out[S * 4])
+    if return_details:
+        return kid, dict(mmd2=out[S * 3:S * 4].copy(), sums=out[:S * 3].reshape(S, 3).copy(), ix=ix, iy=iy)
+    return kid
