@@ -134,6 +134,7 @@ extern "C" int la_mapping_forward_f32(const float* z, int B, int z_dim, int w_di
                                       hipStream_t stream) {
     LA_CHECK_ARG(z && weights && biases && tmp && ws_out, "mapping: null pointer");
     LA_CHECK_ARG(B >= 1 && z_dim >= 1 && w_dim >= 1 && num_layers >= 0 && num_ws >= 1, "mapping: bad shape");
+    LA_CHECK_ARG(num_layers >= 1 || z_dim == w_dim, "mapping: without a layer z_dim must equal w_dim");
     const int mx = z_dim > w_dim ? z_dim : w_dim;
     float* a = tmp;
     float* b = tmp + (long)B * mx;
