@@ -78,7 +78,7 @@ __device__ __forceinline__ float la_block_sum_256(float v, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
-// power-of-two operand scale of the fp16 split (la_conv_bf16.hip): brings a tensor's max magnitude into [2^14, 2^15)
+// power-of-two operand scale of the fp16 split (la_conv_operand.hip): brings a tensor's max magnitude into [2^14, 2^15)
 __device__ __forceinline__ float la_pow2_scale(float amax) {
     if (!(amax > 0.f) || !isfinite(amax)) return 1.f;
     int e;

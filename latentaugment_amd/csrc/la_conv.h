@@ -123,7 +123,7 @@ struct LaConvArgs {
     // gradient there is exactly zero.  (Flat kernel: rows of the pre-split operand's grid.)
     int in_row_lo, in_row_hi;
 #ifdef LA_DEV
-    int dbg_stamp;                 // development build: per-wave segment clocks of the MF 21 halo kernel (la_conv_bf16.hip, LA_STAMP)
+    int dbg_stamp;                 // development build: per-wave segment clocks of the MF 21 halo kernel (la_conv_halo.hip, LA_STAMP)
 #endif
     int nphase;
     struct Phase {
@@ -132,6 +132,12 @@ struct LaConvArgs {
         long ws_off;         // ... and the float offset of its slice partials inside splitk_ws
     } ph[LA_CONV_MAX_PHASES];
 };
+
+// ---- 16-bit split path, three units: la_conv_operand.hip (weight packs, operand scales, pre-split copy, kernel selection),
+// la_conv_flat.hip (la_conv_bf16_kernel) and la_conv_halo.hip (la_conv_bf16_halo_kernel)
+// the launches of the two kernels for as.precision (la_conv_bf16_dispatch picks one)
+int la_conv_flat_launch(const LaConvArgs& as, int MTsel, dim3 grid, bool split, hipStream_t stream);
+int la_conv_halo_launch(const LaConvArgs& as, int MTsel, dim3 grid, hipStream_t stream);
 
 long la_conv_bf16_pack_elems(int M, int C, int ktaps);   // elements per term
 int la_pack_conv_weights_bf16(const float* w, void* out, int cout, int cin, int ktaps, int transpose, int nterm,

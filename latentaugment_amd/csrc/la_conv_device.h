@@ -1,4 +1,5 @@
-// Device-side pieces shared by the contraction kernels (fp32 MFMA and split-bf16 MFMA): the fused epilogue.
+// Device-side pieces shared by the contraction kernels (fp32 MFMA and split-bf16 MFMA): the fused epilogue, and the fragments that
+// the two 16-bit kernels (la_conv_flat.hip, la_conv_halo.hip) have in common.
 // Both kernel families leave the same kind of accumulator fragment: acc[i][j][r] of a 32x32 MFMA tile.  The 4 waves of a
 // workgroup form a WM_ x (4/WM_) grid over the MT x 128 tile (2x2: fp32 kernel and the 64-row 16-bit tiles; 4x1: the
 // 128-row 16-bit tiles, where every wave owns 32 rows x all 128 pixels so that no weight fragment is loaded twice):
@@ -10,7 +11,7 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Development build: per-wave segment clocks (s_memtime differences in scalar registers) of a kernel that passes a LaStamp to its epilogue
-// (la_conv_bf16.hip, dev knob LA_KNOB_HALO_STAMP; scripts/halo_wave_timeline.py).  Segments 0-5 belong to the kernel, 6.. to the epilogue.
+// (la_conv_halo.hip, dev knob LA_KNOB_HALO_STAMP; scripts/halo_wave_timeline.py).  Segments 0-5 belong to the kernel, 6.. to the epilogue.
 #ifdef LA_DEV
 struct LaStamp { unsigned long long last, seg[12]; bool on; };
 #define LA_ESTAMP(k) do { if (stp && stp->on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); stp->seg[k] += t_ - stp->last; stp->last = t_; } } while (0)
@@ -601,5 +602,132 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
         if (lane == 0) red[0][wid] = ymax;
         __syncthreads();
         if (tid == 0) la_xs_lower(fxs_row, fxs_seen, a.fwd_xs_mult ? a.fwd_xs_mult[b] : 1.f, fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3])));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Fragments of the two 16-bit kernels.  Both read their weights straight from the fragment-order pack (la_pack_*_kernel) and issue
+// the products of a K step in the same term order; their pixel loaders differ and stay with the kernels.  A kernel uses a function
+// from here where that leaves its register counts as they were (profiles/conv_units_codegen.md): the halo kernel the weight
+// loader, the MMA step and the zeroing, the flat kernel the quarter walk; both the 16x16x32 product and the step advance.
+// FMT template parameter of the two kernels
+#define FMT_BF16X3 3
+#define FMT_BF16X2 2
+#define FMT_F16X2 16
+#define KCB 32                 // channels per chunk
+// weight pack (la_pack_conv_weights_bf16): [3 bf16 terms][2 fp16 terms][pad to 16 B][wscale float], rows padded to whole 32-row blocks
+__host__ __device__ static inline int pack_mp(int M) { return (M + 31) & ~31; }
+__host__ __device__ static inline size_t pack_f16_offset(long term_elems) { return (size_t)3 * term_elems * 2; }
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// MF template parameter of la_conv_bf16_kernel (flat): the form of the step
+constexpr int FLAT_MF_32 = 0;           // v_mfma_f32_32x32x16, two pixel buffers: every format, both tile heights
+constexpr int FLAT_MF_16 = 1;           // v_mfma_f32_16x16x32_f16 on two pixel buffers: the fp16 x2 split-K launches on 128-row tiles
+constexpr int FLAT_MF_16_3BUF = 2;      // ... on three pixel buffers: the direct fp16 x2 launches on 128-row tiles
+// MF template parameter of la_conv_bf16_halo_kernel: a bit mask.  Only HALO_MF_M16 and HALO_MF_PSL are tested by the kernel;
+// bit 16 ("every pixel fragment read once per tap") selects nothing -- the 16x16x32 tap loop has that one form -- and is kept
+// in HALO_MF_F16_16 because the value is part of the kernel's name.
+constexpr int HALO_MF_M16 = 1;          // v_mfma_f32_16x16x32_f16
+constexpr int HALO_MF_PSL = 4;          // pixel-stationary halo loader
+constexpr int HALO_MF_BF16 = 0;         // the form of the bf16 formats: slice loader, 32x32x16
+constexpr int HALO_MF_F16_32 = HALO_MF_PSL;                        // fp16 x2: the loader on the 32x32x16 form
+constexpr int HALO_MF_F16_16 = 16 | HALO_MF_PSL | HALO_MF_M16;     // fp16 x2, 128-row tiles, more than one chunk (= 21)
+
+template <bool F16>
+__device__ __forceinline__ f32x16 la_mma(bf16x8 a, bf16x8 b, f32x16 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+// the products of one K step of a 32x32 tile: smallest first, so they are not swamped by the leading term inside the accumulator
+template <bool F16, int NTERM, int NJ>
+__device__ __forceinline__ f32x16 la_mma_terms(const bf16x8 (&af)[NTERM], const bf16x8 (&bf)[NTERM][NJ], int j, f32x16 c) {
+    if constexpr (NTERM == 3) {
+        c = la_mma<F16>(af[2], bf[0][j], c);   // lh
+        c = la_mma<F16>(af[0], bf[2][j], c);   // hl
+        c = la_mma<F16>(af[1], bf[1][j], c);   // mm
+    }
+    c = la_mma<F16>(af[1], bf[0][j], c);       // mh
+    c = la_mma<F16>(af[0], bf[1][j], c);       // hm
+    return la_mma<F16>(af[0], bf[0][j], c);    // hh
+}
+// ... and of a 16x16 tile over the whole 32-channel chunk (fp16 x2)
+__device__ __forceinline__ f32x4 la_mma16_terms(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], c, 0, 0, 0);      // lh
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], c, 0, 0, 0);      // hl
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], c, 0, 0, 0);   // hh
+}
+
+template <int NJ>
+__device__ __forceinline__ void la_acc_zero(f32x16 (&acc)[1][NJ]) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
+}
+
+// Weight fragments of one wave (wave-uniform part of the addressing).  A 32-row x 16-channel block of a (tap, chunk) slab is 1 KB in MFMA
+// fragment order; `off` is the byte offset of the wave's 32-row block (blocks past M are clamped: their rows are never stored), to
+// which a lane adds lane * 16 for a 32-row fragment, or (kq * 32 + c16) * 16 + mi * 256 for the 16-row half mi of the 16x16x32 forms
+struct LaWgt {
+    __amdgpu_buffer_rsrc_t rs;             // the terms of this format
+    unsigned off, slab_bytes, term_bytes;  // one (tap, chunk) slab of one term; one term
+    unsigned long long wpack;              // weight-slab index of every tap, 4 bits each (packed by the kernel beside its other tap tables)
+    int nck;
+};
+template <int FMT>
+__device__ __forceinline__ LaWgt la_wgt_setup(const LaConvArgs& a, int row0, unsigned long long wpack) {
+    const int Mp = pack_mp(a.M);
+    const long term_elems = a.wgt_bf16_term_elems;
+    int mblk = row0 >> 5;
+    mblk = mblk < (Mp >> 5) ? mblk : (Mp >> 5) - 1;
+    LaWgt w;
+    w.rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(static_cast<const char*>(a.wgt_bf16)) + (FMT == FMT_F16X2 ? pack_f16_offset(term_elems) : 0), 0,
+        (int)((FMT == FMT_BF16X3 ? 3 : 2) * term_elems * 2), 0x00020000);
+    w.off = (unsigned)mblk * 2048u;
+    w.slab_bytes = (unsigned)Mp * KCB * 2u;
+    w.term_bytes = (unsigned)term_elems * 2u;
+    w.wpack = wpack;
+    w.nck = (a.C + KCB - 1) / KCB;
+    return w;
+}
+// the NTERM terms of one fragment of (chunk cc, tap t): lane offset voff, byte `sub` inside the slab
+template <int NTERM, typename V>
+__device__ __forceinline__ void la_wgt_load(const LaWgt& w, int cc, int t, unsigned voff, unsigned sub, V (&dst)[NTERM]) {
+    const unsigned tw = (unsigned)((w.wpack >> (4 * t)) & 15u);
+    const unsigned so = (tw * w.nck + cc) * w.slab_bytes + sub;
+#pragma unroll
+    for (int q = 0; q < NTERM; ++q)
+        dst[q] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(w.rs, voff, so + q * w.term_bytes, 0));
+}
+
+// next (chunk, tap) step of a K loop that ends with chunk ck_end - 1; past the end it stays on the last valid step (harmless re-loads)
+__device__ __forceinline__ void la_step_adv(int& c, int& t, int ntaps, int ck_end) {
+    if (t + 1 < ntaps) ++t;
+    else if (c + 1 < ck_end) { ++c; t = 0; }
+}
+
+// One (chunk, tap) step of the 16x16x32 forms on a wave tile of 32 rows x 128 pixels = 2 x 8 tiles of 16 x 16, walked in quarters: tiles
+// 0-3 x rows 0-15, tiles 0-3 x rows 16-31, tiles 4-7 x rows 0-15, tiles 4-7 x rows 16-31, so that every pixel fragment is read ONCE per
+// step.  Slot k of b16 holds tile k, then tile k + 4: after its second use (mi == 1) the caller re-fills it -- refill(hf, k, slot) --
+// with the tile four sub-steps ahead (tile k + 4 of this step, then tile k of the next one); after(q4) follows every quarter (the
+// weights of the next step: rows 0-15 are done with theirs after quarter 2, rows 16-31 after quarter 3).
+template <typename Refill, typename After>
+__device__ __forceinline__ void la_quarter_walk(f16x8 (&a16)[2][2], f16x8 (&b16)[4][2], f32x4 (&acc16)[2][8], Refill refill, After after) {
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const int hf = q4 >> 1, mi = q4 & 1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int n = hf * 4 + k;
+            acc16[mi][n] = la_mma16_terms(a16[mi], b16[k], acc16[mi][n]);
+            if (mi == 1) refill(hf, k, b16[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        after(q4);
     }
 }

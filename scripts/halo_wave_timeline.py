@@ -1,5 +1,5 @@
-"""Dev tool: where a wave of the 128-row (MF 5) halo kernel spends its life.  The development build stamps s_memtime per segment in every wave
-(la_conv_bf16.hip, LA_STAMP; dev knob LA_KNOB_HALO_STAMP) -- prologue issue / prologue wait + first stage / tap loops / chunk barriers /
+"""Dev tool: where a wave of the 128-row (MF 21) halo kernel spends its life.  The development build stamps s_memtime per segment in every wave
+(la_conv_halo.hip, LA_STAMP; dev knob LA_KNOB_HALO_STAMP) -- prologue issue / prologue wait + first stage / tap loops / chunk barriers /
 accumulator hand-over / epilogue -- and this script runs ONE stride-1 layer call with the knob on and prints the distribution per segment.
     python scripts/halo_wave_timeline.py --res 256 --ch 128 [--batch 8] [--bwd]"""
 import argparse

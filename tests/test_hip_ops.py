@@ -286,6 +286,7 @@ def test_modconv_vs_oracle(dev, case):
     dict(B=2, cin=48, cout=32, res=128, up=True, noise_strength=0.1),      # 64x64 input: the four phases run as ONE merged launch
     dict(B=1, cin=128, cout=40, res=128, up=True, noise_strength=0.0),     # 128-row backward tile over a 129^2 gradient scratch, ragged channel chunk
     dict(B=2, cin=512, cout=512, res=4, up=False, noise_strength=0.0),
+    dict(B=1, cin=32, cout=128, res=64, up=False, noise_strength=0.0),     # 128-row halo tile over ONE channel chunk (fp16 x2: one halo buffer, 32x32x16 form)
 ])
 def test_modconv_split_bf16_vs_oracle(dev, case):
     """Split-bf16 contraction: x3 (6 MFMAs) must hold the SAME tolerance as the exact fp32 path; x2 (3 MFMAs) 10x looser."""
