@@ -169,6 +169,47 @@ int la_conv2d_uses_engine(int op, int cout, int kh, int kw, int stride, int grou
 int la_conv2d_wgrad_slices(int B, int Cin, int H, int W, int Cout, int kh, int kw, int Hout, int Wout, int stride, int groups, int transpose);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * grid_sample and fma: the last two modules of torch_utils/ops/ (grid_sample_gradfix.py, fma.py).
+ * ------------------------------------------------------------------------------------------------------------- */
+
+/* torch.nn.functional.grid_sample(x, grid, mode='bilinear', padding_mode='zeros', align_corners=False) in 2-D, the only form
+ * grid_sample_gradfix.py:28-31 provides.  x [N][C][H][W], grid [N][Ho][Wo][2] = (x, y) in [-1, 1], y [N][C][Ho][Wo], contiguous.
+ * Pixel position of a grid value g along an axis of `size` pixels: ((g + 1) * size - 1) / 2; the four neighbouring pixels are read, one
+ * outside the image contributes nothing.  A position outside [-1, size) -- huge, infinite or NaN included -- is tested in floating
+ * point before any integer is formed from it: it reads and writes no memory, y = 0 and dgrid = 0 there.
+ * Every tensor of a call must have at most INT_MAX elements; a larger shape is LA_ERR_ARG, never truncated.
+ *   _f16: binary16 storage, fp32 arithmetic, one rounding on store.   _f64: double throughout. */
+int la_grid_sample_f32(const float* x, const float* grid, float* y, int N, int C, int H, int W, int Ho, int Wo, la_stream_t stream);
+int la_grid_sample_f16(const unsigned short* x, const unsigned short* grid, unsigned short* y, int N, int C, int H, int W, int Ho, int Wo,
+                       la_stream_t stream);
+int la_grid_sample_f64(const double* x, const double* grid, double* y, int N, int C, int H, int W, int Ho, int Wo, la_stream_t stream);
+/* aten::grid_sampler_2d_backward(dy, x, grid, 0, 0, False, output_mask) (grid_sample_gradfix.py:60-63) as one launch.  dx (the shape of
+ * x) and dgrid (the shape of grid) may each be NULL: that output is then not computed (torch's output_mask); x may be NULL when dgrid
+ * is.  dgrid is summed over the channels in registers: bit-identical from run to run.  dx is zeroed by the entry and then summed with
+ * global float atomic adds, so its last bits can depend on arrival order (no other sum of this library does).  The gradient of dx with
+ * respect to dy is la_grid_sample_* applied to the incoming gradient; nothing is defined for second derivatives that involve grid
+ * (grid_sample_gradfix.py:70-81).
+ *   _f16: dx is accumulated in ws, la_grid_sample_grad_workspace_floats(N, C, H, W) = N*C*H*W floats of device memory (0: the shape
+ *   is refused), and rounded to binary16 once by a second launch; ws may be NULL when dx is. */
+int la_grid_sample_grad_f32(const float* dy, const float* x, const float* grid, float* dx, float* dgrid, int N, int C, int H, int W, int Ho,
+                            int Wo, la_stream_t stream);
+int la_grid_sample_grad_f16(const unsigned short* dy, const unsigned short* x, const unsigned short* grid, unsigned short* dx,
+                            unsigned short* dgrid, float* ws, int N, int C, int H, int W, int Ho, int Wo, la_stream_t stream);
+int la_grid_sample_grad_f64(const double* dy, const double* x, const double* grid, double* dx, double* dgrid, int N, int C, int H, int W,
+                            int Ho, int Wo, la_stream_t stream);
+long la_grid_sample_grad_workspace_floats(int N, int C, int H, int W);
+
+/* fma.py:15 `fma(a, b, c)`: y = a * b + c (one fused multiply-add per element) over the broadcast shape shape_host[4] (HOST memory,
+ * operands of lower rank left-padded with 1s).  astride_host / bstride_host / cstride_host [4] (HOST): element strides of each operand,
+ * 0 along an axis it broadcasts; y is contiguous.  c NULL = 0 (cstride_host is then ignored).  At most INT_MAX elements. */
+int la_fma_f32(const float* a, const float* b, const float* c, float* y, const long* shape_host, const long* astride_host,
+               const long* bstride_host, const long* cstride_host, la_stream_t stream);
+/* _unbroadcast of fma.py:49-58: x contiguous of shape_host[4] -> out contiguous of out_shape_host[4] (both HOST), every axis of which is
+ * either the input's (kept) or 1 (summed).  Terms are added in double, in an order that depends on the shapes alone, and rounded once:
+ * bit-identical from run to run.  At most INT_MAX elements. */
+int la_unbroadcast_sum_f32(const float* x, float* out, const long* shape_host, const long* out_shape_host, la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Modulated 3x3 convolution of a SynthesisLayer (the SG2 `modulated_conv2d` + `bias_act` pair that the reference
  * reaches through G.synthesis, util_latent_aug.py:227; resampling algebra conv2d_resample.py:82-134).
  * Non-fused formulation: y = act((W * (x.s)) . d + noise + bias); never materialises per-sample weights.

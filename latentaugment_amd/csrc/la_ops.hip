@@ -7,23 +7,11 @@
 //   float64: double storage and arithmetic, double scalars (the parity target, the reference's impl='ref' path, applies gain / alpha /
 //            clamp of bias_act as Python doubles; upfirdn2d's gain is folded into the float32 taps first, see la_fir_setup)
 // The SG2 path's own linear / relu / lrelu forms of bias_act (la_bias_act_f32, la_bias_act_grad_f32) are in la_misc.hip.
+#include "la_op_types.h"
 #include "la_upfirdn2d.h"
 
 #include <hip/hip_fp16.h>
 #include <type_traits>
-
-template <class T> struct LaOpType;
-template <> struct LaOpType<__half> { typedef float A; };
-template <> struct LaOpType<float> { typedef float A; };
-template <> struct LaOpType<double> { typedef double A; };
-
-__device__ __forceinline__ float la_op_load(__half v) { return __half2float(v); }
-__device__ __forceinline__ float la_op_load(float v) { return v; }
-__device__ __forceinline__ double la_op_load(double v) { return v; }
-template <class T> __device__ __forceinline__ T la_op_store(typename LaOpType<T>::A v);
-template <> __device__ __forceinline__ __half la_op_store<__half>(float v) { return __float2half(v); }      // (round to nearest even)
-template <> __device__ __forceinline__ float la_op_store<float>(float v) { return v; }
-template <> __device__ __forceinline__ double la_op_store<double>(double v) { return v; }
 
 __device__ __forceinline__ float la_op_exp(float v) { return expf(v); }
 __device__ __forceinline__ double la_op_exp(double v) { return exp(v); }

@@ -6,17 +6,22 @@ Same names, argument meaning and error behaviour as the reference's Python wrapp
   filtered_lrelu(x, fu, fd, b, up, down, padding, gain, slope, clamp, flip_filter)   filtered_lrelu.py:59-108
   conv2d / conv_transpose2d(x, w, stride, padding, groups)          conv2d_gradfix.py:24-33
   conv2d_resample(x, w, f, up, down, padding, groups, flip_weight, flip_filter)       conv2d_resample.py:46-141
+  grid_sample(input, grid)                                          grid_sample_gradfix.py:28-31
+  fma(a, b, c)                                                      fma.py:15
 Each op is a torch.autograd.Function whose forward AND backward are HIP launches (bias_act: every activation of the reference's
 table with first- and second-order gradients; upfirdn2d: linear, its backward is the same op on the adjoint arguments, so gradients of
 every order; filtered_lrelu: one
 fused launch whose backward is the same kernel reading the sign mask its forward wrote, so gradients of every order; conv2d /
 conv_transpose2d: forward, data gradient and weight gradient are three bilinear maps that are each other's backward, so gradients of
-every order with respect to x, w and incoming gradients; float32 only).  torch only owns the device memory and the stream.
+every order with respect to x, w and incoming gradients; float32 only; grid_sample: forward and a one-launch backward for input and
+grid, the backward's own backward being the forward again, so gradients of every order between input and output; fma: one launch, its
+gradients the same launch and a fixed-order un-broadcast sum).  torch only owns the device memory and the stream.
 
 Dtypes of bias_act and the upfirdn2d family (upfirdn2d, filter2d, upsample2d, downsample2d), as the reference's plugins dispatch them
 (bias_act.cpp:77, upfirdn2d.cpp:63): float16, float32 and float64 run on kernels of their own and return their own dtype (float16 with
 fp32 arithmetic inside, float64 in double throughout).  Any other dtype (bfloat16, ...) is computed in float32 and returned as float32.
-A float16 or float64 x needs a bias of its own dtype (bias_act.cpp:36).  filtered_lrelu is float32 only.
+A float16 or float64 x needs a bias of its own dtype (bias_act.cpp:36).  filtered_lrelu is float32 only.  grid_sample has float16 /
+float32 / float64 kernels too; fma has a float32 kernel, other float dtypes are computed in float32 and cast back to their own dtype.
 """
 import ctypes as C
 import math
@@ -582,3 +587,183 @@ def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight
     if down > 1:
         x = upfirdn2d(x, f, down=down, flip_filter=flip_filter)
     return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# grid_sample (grid_sample_gradfix.py) and fma (fma.py)
+
+def _grid_sample_dims(x, grid):
+    n, c, h, w = x.shape
+    return n, c, h, w, grid.shape[1], grid.shape[2]
+
+
+def _grid_sample_launch(x, grid):
+    n, c, h, w, ho, wo = _grid_sample_dims(x, grid)
+    y = torch.empty([n, c, ho, wo], device=x.device, dtype=x.dtype)
+    if y.numel() and x.numel():
+        fn = getattr(_lib.load(), 'la_grid_sample_' + _DTYPES[x.dtype])
+        _lib.check(fn(_lib.ptr(x), _lib.ptr(grid), _lib.ptr(y), n, c, h, w, ho, wo, _lib.stream_ptr()), 'grid_sample')
+    else:
+        y.zero_()
+    return y
+
+
+class _GridSampleForward(torch.autograd.Function):
+    """y = grid_sample(input, grid) (la_grid_sample_*); the reference's _GridSample2dForward (grid_sample_gradfix.py:40-53)."""
+
+    @staticmethod
+    def forward(ctx, input, grid):
+        ctx.save_for_backward(input, grid)
+        return _grid_sample_launch(input, grid)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, grid = ctx.saved_tensors
+        return _GridSampleBackward.apply(grad_output, input, grid, (ctx.needs_input_grad[0], ctx.needs_input_grad[1]))
+
+
+class _GridSampleBackward(torch.autograd.Function):
+    """(grad_input, grad_grid) of one launch of la_grid_sample_grad_*; `mask` is torch's output_mask, an output not asked for is None.
+    grad_input is linear in grad_output and does not depend on input: its gradient with respect to grad_output is the forward op on the
+    incoming gradient (grid_sample_gradfix.py:70-81), which is again differentiable, so every order between input and output exists.
+    Nothing is defined for second derivatives that involve grid -- asking for one raises."""
+
+    @staticmethod
+    def forward(ctx, grad_output, input, grid, mask):
+        ctx.set_materialize_grads(False)
+        grad_output = grad_output.contiguous()
+        n, c, h, w, ho, wo = _grid_sample_dims(input, grid)
+        assert tuple(grad_output.shape) == (n, c, ho, wo) and grad_output.dtype == input.dtype
+        dx = torch.empty_like(input) if mask[0] else None
+        dgrid = torch.empty_like(grid) if mask[1] else None
+        if input.numel() and grad_output.numel() and (mask[0] or mask[1]):
+            lib = _lib.load()
+            args = [_lib.ptr(grad_output), _lib.ptr(input), _lib.ptr(grid), _lib.ptr(dx), _lib.ptr(dgrid)]
+            if input.dtype == torch.float16:
+                ws = torch.empty([lib.la_grid_sample_grad_workspace_floats(n, c, h, w)], device=input.device, dtype=torch.float32) if mask[0] else None
+                args.append(_lib.ptr(ws))
+            fn = getattr(lib, 'la_grid_sample_grad_' + _DTYPES[input.dtype])
+            _lib.check(fn(*args, n, c, h, w, ho, wo, _lib.stream_ptr()), 'grid_sample_grad')
+        else:
+            for t in (dx, dgrid):
+                if t is not None:
+                    t.zero_()
+        ctx.save_for_backward(grid)
+        return dx, dgrid
+
+    @staticmethod
+    def backward(ctx, grad2_grad_input, grad2_grad_grid):
+        grid, = ctx.saved_tensors
+        if grad2_grad_grid is not None or ctx.needs_input_grad[2]:
+            raise _lib.LatentAugHipError(
+                'grid_sample: second derivatives that involve grid are not defined (as in the reference, grid_sample_gradfix.py:70-81): '
+                'a gradient of grad_grid, or a gradient with respect to a grid that requires grad, was asked for. Detach the grid '
+                'where gradients of gradients are taken.')
+        grad2_grad_output = None
+        if ctx.needs_input_grad[0] and grad2_grad_input is not None:
+            grad2_grad_output = _GridSampleForward.apply(grad2_grad_input.contiguous(), grid)
+        return grad2_grad_output, None, None, None
+
+
+def grid_sample(input, grid):
+    """torch.nn.functional.grid_sample(input, grid, mode='bilinear', padding_mode='zeros', align_corners=False) for 2-D images, as the
+    reference's grid_sample_gradfix.grid_sample (grid_sample_gradfix.py:28-31): input [N, C, H, W], grid [N, Ho, Wo, 2] of (x, y) in
+    [-1, 1] -> [N, C, Ho, Wo] in the input's dtype.  float16 (fp32 arithmetic inside), float32 and float64 run on kernels of their own;
+    any other dtype is computed and returned in float32.  Gradients of every order between input and output; first-order gradients
+    with respect to grid; a second derivative that involves grid raises LatentAugHipError."""
+    assert isinstance(input, torch.Tensor) and isinstance(grid, torch.Tensor)
+    _lib.require_gpu(input)
+    _lib.require_gpu(grid)
+    assert input.ndim == 4
+    assert grid.ndim == 4
+    assert grid.shape[0] == input.shape[0] and grid.shape[3] == 2, (input.shape, grid.shape)
+    if grid.dtype != input.dtype:
+        raise _lib.LatentAugHipError(f'grid_sample: input and grid must have the same dtype, got {input.dtype} and {grid.dtype}')
+    return _GridSampleForward.apply(_op_input(input), _op_input(grid))
+
+
+def _pad4(shape):
+    return (1,) * (4 - len(shape)) + tuple(int(v) for v in shape)
+
+
+def _long4(v):
+    return (C.c_long * 4)(*v)
+
+
+def _fma_launch(a, b, c, shape):
+    """a * b + c (c None: a * b) of contiguous float32 operands over the broadcast `shape` (rank <= 4), one launch of la_fma_f32."""
+    s4 = _pad4(shape)
+
+    def strides(t):
+        ts = _pad4(t.shape)
+        st = (0,) * (4 - t.ndim) + tuple(t.stride())
+        return _long4([0 if ts[k] == 1 else st[k] for k in range(4)])
+    y = torch.empty(shape, device=a.device, dtype=torch.float32)
+    if y.numel():
+        _lib.check(_lib.load().la_fma_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(c), _lib.ptr(y), _long4(s4), strides(a), strides(b),
+                                          strides(c) if c is not None else None, _lib.stream_ptr()), 'fma')
+    return y
+
+
+class _Unbroadcast(torch.autograd.Function):
+    """x summed over the axes along which `shape` was broadcast to x.shape (fma.py:49-58), one launch of la_unbroadcast_sum_f32 with
+    a fixed summation order; its own gradient is a broadcast view."""
+
+    @staticmethod
+    def forward(ctx, x, shape):
+        x = x.contiguous()
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+        ctx.xshape = tuple(x.shape)
+        if x.numel():
+            _lib.check(_lib.load().la_unbroadcast_sum_f32(_lib.ptr(x), _lib.ptr(out), _long4(_pad4(x.shape)), _long4(_pad4(shape)),
+                                                          _lib.stream_ptr()), 'unbroadcast_sum')
+        else:
+            out.zero_()
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return d_out.expand(ctx.xshape), None
+
+
+def _unbroadcast(x, shape):
+    shape = tuple(shape)
+    return x if tuple(x.shape) == shape else _Unbroadcast.apply(x, shape)
+
+
+class _Fma(torch.autograd.Function):
+    """a * b + c; the gradients are the same Function (and _Unbroadcast) applied to the incoming gradient (fma.py:20-45), so autograd
+    gives every higher order."""
+
+    @staticmethod
+    def forward(ctx, a, b, c, shape):
+        ctx.save_for_backward(a, b)
+        ctx.shapes = (tuple(a.shape), tuple(b.shape), None if c is None else tuple(c.shape))
+        return _fma_launch(a.contiguous(), b.contiguous(), None if c is None else c.contiguous(), shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, b = ctx.saved_tensors
+        sa, sb, sc = ctx.shapes
+        shape = tuple(dout.shape)
+        da = _unbroadcast(_Fma.apply(dout, b, None, shape), sa) if ctx.needs_input_grad[0] else None
+        db = _unbroadcast(_Fma.apply(dout, a, None, shape), sb) if ctx.needs_input_grad[1] else None
+        dc = _unbroadcast(dout, sc) if ctx.needs_input_grad[2] else None
+        return da, db, dc, None
+
+
+def fma(a, b, c):
+    """a * b + c with un-broadcast gradients (reference: fma.py:15): the operands broadcast against each other (rank <= 4), one fused
+    multiply-add per element.  float32 kernels; other floating dtypes are computed in float32 and returned in the operands' promoted
+    dtype."""
+    assert all(isinstance(t, torch.Tensor) for t in (a, b, c))
+    for t in (a, b, c):
+        _lib.require_gpu(t)
+    shape = tuple(torch.broadcast_shapes(a.shape, b.shape, c.shape))
+    if len(shape) > 4:
+        raise _lib.LatentAugHipError(f'fma: at most 4 dimensions, got {len(shape)}')
+    dtype = torch.promote_types(torch.promote_types(a.dtype, b.dtype), c.dtype)
+    if not dtype.is_floating_point:
+        raise _lib.LatentAugHipError(f'fma: floating-point operands only, got {dtype}')
+    y = _Fma.apply(a.float(), b.float(), c.float(), shape)
+    return y if dtype == torch.float32 else y.to(dtype)
