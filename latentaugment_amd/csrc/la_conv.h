@@ -7,7 +7,11 @@
 //   B2  backward-data of F2 (stride-2 gather over the (2h+1)^2 gradient)
 // expressed as  out[b, m, g*os+oo] = sum_{t, c} wgt[tap_w[t]][c][m] * scale[b][c] * in[b, c, g*is + tap_d[t]]
 #pragma once
+#include <stddef.h>
+#include <string.h>
+
 #include "la_common.h"
+#include "la_launch_args.h"
 
 #define LA_EPI_RAW 0
 #define LA_EPI_FWD 1
@@ -15,6 +19,33 @@
 #define LA_CONV_MAX_TAPS 9
 #define LA_CONV_MAX_PHASES 4
 #define LA_CONV_PHASE_TAPS 4
+
+// Fused ToRGB of a block inside the epilogue of its conv1 (LaConvArgs::rgb): possible where one row tile of the halo kernel holds every
+// output channel (la_modconv3x3_fwd_fuses_rgb); weights [imgc][cout], styles [B][s_stride] (already * weight_gain), bias [imgc],
+// skip [B][imgc][res^2] or null, outputs rgb_pre / img [B][imgc][res^2]
+struct LaRgbFuse {
+    int imgc;                // 0: none
+    const float* w; const float* s; int s_stride; const float* bias; const float* skip;
+    float* rgb_pre; float* img; float clamp;
+};
+// Backward seam of the layer that produced `xin`, applied inside the backward contraction's epilogue (LaConvArgs::seam): its demod /
+// bias / noise / activation (la_seam_set_epi), and where its demod-gradient partials and plane maxima go ([B][cin][la_modconv_ds_tiles(res)]).
+struct LaSeamFuse {
+    const float* demod; int demod_stride;
+    const float* bias;
+    const float* noise; long noise_bstride; float noise_strength;
+    int act; float alpha, gain, clamp;
+    float* ddn_part;         // [B][M][tiles_per_sample]
+    float* pmax;             // [B][M][tiles_per_sample] or null
+    float* xs_out;           // [B][LA_XS_FAN] or null: slot rows of the fp16 operand scale of `out` for its consumer = pow2 scale of
+    float xs_mult;           //   xs_mult * max|out| over the sample, final when the launch has run: every kernel form (direct epilogues,
+                             //   split-K finish pass) lowers the row itself (la_xs_lower, la_common.h; it must hold LA_XS_INIT before)
+    // ToRGB backward of that block (imgc > 0): image gradient, ToRGB pre-clamp output, weights [imgc][C], styles, partial outputs
+    int imgc;
+    const float* g_img; const float* rgb_pre; float rgb_clamp;
+    const float* wrgb; const float* s_rgb; int s_rgb_stride;
+    float* dweff_part;       // [B][imgc][M][tiles_per_sample]
+};
 
 struct LaConvArgs {
     const float* in;         // [B][C][Hin][Win]; in_bstride == 0 broadcasts one sample over the batch
@@ -61,34 +92,16 @@ struct LaConvArgs {
     long xin_bstride;
     float* ds_part;          // [B][M][tiles_per_sample]
     int tiles_per_sample;
-    // LA_EPI_BWD with seam_ddn_part != null (16-bit kernels and the split-K finish pass only): the backward "seam" of the layer
+    // LA_EPI_BWD with seam.ddn_part != null (16-bit kernels and the split-K finish pass only): the backward "seam" of the layer
     // that PRODUCED xin is applied to the outgoing gradient in the same epilogue -- xin is that layer's saved output y, which the
     // epilogue loads anyway for ds_part -- instead of a separate pass over y and the gradient (la_seam_bwd_kernel<0>):
-    //   g = acc * out_scale;  g1 = g * act'(y);  seam_ddn_part[b][m][tile] = sum_px g1 * (act^-1(y) - seam_bias[m] - noise*strength);
-    //   out = g1 * seam_demod[b][m];  seam_pmax[b][m][tile] = max_px |out|   (plane maxima for the next contraction's operand scale)
-    const float* seam_demod; int seam_demod_stride;
-    const float* seam_bias;
-    const float* seam_noise; long seam_noise_bstride; float seam_noise_strength;
-    int seam_act; float seam_alpha, seam_gain, seam_clamp;
-    float* seam_ddn_part;    // [B][M][tiles_per_sample]
-    float* seam_pmax;        // [B][M][tiles_per_sample] or null
-    float* seam_xs_out;      // [B][LA_XS_FAN] or null: slot rows of the fp16 operand scale of `out` for its consumer = pow2 scale of
-    float seam_xs_mult;      //   seam_xs_mult * max|out| over the sample, final when the launch has run: every kernel form (direct epilogues,
-                             //   split-K finish pass) lowers the row itself (la_xs_lower, la_common.h; it must hold LA_XS_INIT before)
-    // ... and, with seam_imgc > 0, the ToRGB backward of the block whose conv1 output xin is (la_seam_bwd_kernel<imgc>):
-    //   g += sum_c seam_wrgb[c][m] * seam_srgb[b][m] * gr_c,  gr_c = seam_gimg[b][c][px] where |seam_rgbpre[b][c][px]| <= seam_rgb_clamp;
-    //   seam_dweff_part[b][c][m][tile] = sum_px gr_c * y
-    int seam_imgc;
-    const float* seam_gimg; const float* seam_rgbpre; float seam_rgb_clamp;
-    const float* seam_wrgb; const float* seam_srgb; int seam_srgb_stride;
-    float* seam_dweff_part;  // [B][imgc][M][tiles_per_sample]
+    //   g = acc * out_scale;  g1 = g * act'(y);  seam.ddn_part[b][m][tile] = sum_px g1 * (act^-1(y) - seam.bias[m] - noise*strength);
+    //   out = g1 * seam.demod[b][m];  seam.pmax[b][m][tile] = max_px |out|   (plane maxima for the next contraction's operand scale)
+    LaSeamFuse seam;
     // Fused ToRGB of the block (LA_EPI_FWD, 16-bit halo launches whose ONE row tile holds every output channel, M == tile rows):
-    //   rgb_pre[b][c][px] = sum_m rgb_w[c][m] * rgb_s[b][m] * out[b][m][px] + rgb_bias[c];  rgb_img = clamp(rgb_pre) + rgb_skip
+    //   rgb.rgb_pre[b][c][px] = sum_m rgb.w[c][m] * rgb.s[b][m] * out[b][m][px] + rgb.bias[c];  rgb.img = clamp(rgb.rgb_pre) + rgb.skip
     // (la_torgb_fwd_kernel's arithmetic on the epilogue's registers: the block's conv1 output is not streamed a second time)
-    int rgb_imgc;            // 0: none
-    const float* rgb_w; const float* rgb_s; int rgb_s_stride; const float* rgb_bias;
-    const float* rgb_skip;   // [B][imgc][Hout*Wout] or null
-    float* rgb_pre; float* rgb_img; float rgb_clamp;
+    LaRgbFuse rgb;
     // optional caller-provided scratch (la_conv_workspace_bytes): [fp16 scale header | pre-split input | split-K slice partials]
     void* ws;
     size_t ws_bytes;
@@ -132,6 +145,45 @@ struct LaConvArgs {
         long ws_off;         // ... and the float offset of its slice partials inside splitk_ws
     } ph[LA_CONV_MAX_PHASES];
 };
+// Kernel parameter: the byte layout is pinned (numbers of the flat struct before the seam / ToRGB records became members).
+static_assert(sizeof(LaConvArgs) == 1096 && offsetof(LaConvArgs, seam) == 416 && offsetof(LaConvArgs, rgb) == 568 && offsetof(LaConvArgs, ws) == 640,
+              "LaConvArgs: an embedded record moved a kernel-parameter field");
+
+// every launch starts from this: zeros, unit strides, a linear epilogue without clamp
+static inline void la_conv_args_init(LaConvArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.in_sy = a.in_sx = a.out_sy = a.out_sx = 1;
+    a.clamp = -1.f; a.gain = 1.f; a.act = LA_ACT_LINEAR;
+}
+// k x k taps around the centre (pad k / 2); backward: the flipped taps of the backward-data contraction
+static inline void la_conv_taps_kxk(LaConvArgs& a, int k, bool backward) {
+    a.ntaps = k * k;
+    for (int t = 0; t < a.ntaps; ++t) {
+        const int dy = t / k - k / 2, dx = t % k - k / 2;
+        a.tap_dy[t] = backward ? -dy : dy; a.tap_dx[t] = backward ? -dx : dx; a.tap_w[t] = t;
+    }
+}
+static inline void la_conv_taps_3x3(LaConvArgs& a, bool backward) { la_conv_taps_kxk(a, 3, backward); }
+// 3 x 3 taps from the corner (offsets 0 .. 2): the stride-2 gathers over a (2h+1)^2 input
+static inline void la_conv_taps_3x3_corner(LaConvArgs& a) {
+    a.ntaps = 9;
+    for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3; a.tap_dx[t] = t % 3; a.tap_w[t] = t; }
+}
+// Output phase (py, px) of the transposed stride-2 3x3 conv over an hin^2 input: row Y = 2 * qy + py receives the taps ky with
+// (Y - ky) even.  Sets the launch-wide grid, offset (column phase px at out_ox = px * ox_step) and taps; merged: also appends them
+// as the next phase of a one-launch form (LaConvArgs::nphase).
+static inline void la_conv_up2_phase(LaConvArgs& a, int hin, int py, int px, int ox_step, bool merged) {
+    a.out_oy = py; a.out_ox = px * ox_step;
+    a.Gy = py ? hin : hin + 1; a.Gx = px ? hin : hin + 1;
+    int nt = 0;
+    for (int ky = py; ky < 3; ky += 2)
+        for (int kx = px; kx < 3; kx += 2) { a.tap_dy[nt] = -(ky / 2); a.tap_dx[nt] = -(kx / 2); a.tap_w[nt] = ky * 3 + kx; ++nt; }
+    a.ntaps = nt;
+    if (!merged) return;
+    LaConvArgs::Phase& P = a.ph[a.nphase++];
+    P.Gy = a.Gy; P.Gx = a.Gx; P.out_oy = py; P.out_ox = a.out_ox; P.ntaps = nt;
+    for (int t = 0; t < nt; ++t) { P.tap_dy[t] = a.tap_dy[t]; P.tap_dx[t] = a.tap_dx[t]; P.tap_w[t] = a.tap_w[t]; }
+}
 
 // ---- 16-bit split path, three units: la_conv_operand.hip (weight packs, operand scales, pre-split copy, kernel selection),
 // la_conv_flat.hip (la_conv_bf16_kernel) and la_conv_halo.hip (la_conv_bf16_halo_kernel)

@@ -227,20 +227,20 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
     const float bv = (a.epi == LA_EPI_FWD && a.bias) ? a.bias[m] : 0.f;
     const float sc = (a.epi == LA_EPI_BWD && a.out_scale) ? a.out_scale[(long)b * a.oscale_stride + m] : 1.f;
     const float* xin_p = (a.epi == LA_EPI_BWD && a.xin) ? a.xin + (long)b * a.xin_bstride + (long)m * HWout : nullptr;
-    // fused seam of the layer that produced xin (LaConvArgs::seam_*): same arithmetic as the direct kernels' epilogue
-    const bool seam = a.epi == LA_EPI_BWD && a.seam_ddn_part != nullptr && xin_p != nullptr;
-    const float dm0 = (seam && a.seam_demod) ? a.seam_demod[(long)b * a.seam_demod_stride + m] : 1.f;
-    const float b0 = (seam && a.seam_bias) ? a.seam_bias[m] : 0.f;
+    // fused seam of the layer that produced xin (LaConvArgs::seam): same arithmetic as the direct kernels' epilogue
+    const bool seam = a.epi == LA_EPI_BWD && a.seam.ddn_part != nullptr && xin_p != nullptr;
+    const float dm0 = (seam && a.seam.demod) ? a.seam.demod[(long)b * a.seam.demod_stride + m] : 1.f;
+    const float b0 = (seam && a.seam.bias) ? a.seam.bias[m] : 0.f;
     float part = 0.f, dd = 0.f, mx = 0.f;
     // (the sub-slot of the consumer's scale row this plane lowers, read early: the round trip hides under the slice loads)
-    float* xs_row = (seam && a.seam_xs_out && lane == 0 && (PPB > 1 || threadIdx.x == 0)) ? a.seam_xs_out + (long)b * LA_XS_FAN + la_xs_sub((int)(threadIdx.x >> 6) * 5) : nullptr;
+    float* xs_row = (seam && a.seam.xs_out && lane == 0 && (PPB > 1 || threadIdx.x == 0)) ? a.seam.xs_out + (long)b * LA_XS_FAN + la_xs_sub((int)(threadIdx.x >> 6) * 5) : nullptr;
     // (forward epilogue: the same for LaConvArgs::fwd_xs_out, one atomic per wave)
     float ymax = 0.f;
     if (a.epi == LA_EPI_FWD && a.fwd_xs_out && lane == 0) xs_row = a.fwd_xs_out + (long)b * LA_XS_FAN + la_xs_sub((int)(threadIdx.x >> 6) * 5);
     const float xs_seen = xs_row ? la_xs_peek(xs_row) : 0.f;
-    const int imgc = seam ? (a.seam_imgc < 4 ? a.seam_imgc : 4) : 0;
+    const int imgc = seam ? (a.seam.imgc < 4 ? a.seam.imgc : 4) : 0;
     float we[4] = {0.f, 0.f, 0.f, 0.f}, dwe[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < imgc; ++c) we[c] = a.seam_wrgb[(long)c * a.M + m] * a.seam_srgb[(long)b * a.seam_srgb_stride + m];
+    for (int c = 0; c < imgc; ++c) we[c] = a.seam.wrgb[(long)c * a.M + m] * a.seam.s_rgb[(long)b * a.seam.s_rgb_stride + m];
     // VEC consecutive grid positions per thread and step (4: 16-byte loads / stores when the rows allow it, else 1)
     auto run = [&](auto vec_tag) {
         constexpr int VEC = decltype(vec_tag)::value;
@@ -303,18 +303,18 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
                     gv[c] = 0.f;
                     if (c < imgc) {
                         const long o = ((long)b * imgc + c) * HWout + pos;
-                        gv[c] = ld(a.seam_gimg + o);
-                        if (a.seam_rgb_clamp >= 0.f) {
-                            const vf pre = ld(a.seam_rgbpre + o);
+                        gv[c] = ld(a.seam.g_img + o);
+                        if (a.seam.rgb_clamp >= 0.f) {
+                            const vf pre = ld(a.seam.rgb_pre + o);
 #pragma unroll
-                            for (int e = 0; e < VEC; ++e) if (fabsf(pre[e]) > a.seam_rgb_clamp) gv[c][e] = 0.f;
+                            for (int e = 0; e < VEC; ++e) if (fabsf(pre[e]) > a.seam.rgb_clamp) gv[c][e] = 0.f;
                         }
                     }
                 }
-                if (seam && a.seam_noise) {
-                    nz0 = ld(a.seam_noise + (long)b * a.seam_noise_bstride + pos);
+                if (seam && a.seam.noise) {
+                    nz0 = ld(a.seam.noise + (long)b * a.seam.noise_bstride + pos);
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) nz0[e] *= a.seam_noise_strength;
+                    for (int e = 0; e < VEC; ++e) nz0[e] *= a.seam.noise_strength;
                 }
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
@@ -324,8 +324,8 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
                     for (int c = 0; c < 4; ++c)
                         if (c < imgc) { v[e] += we[c] * gv[c][e]; dwe[c] += gv[c][e] * y[e]; }
                     if (seam) {
-                        const float g1 = v[e] * la_act_bwd_from_y(y[e], a.seam_act, a.seam_alpha, a.seam_gain, a.seam_clamp);
-                        dd += g1 * (la_act_inv(y[e], a.seam_act, a.seam_alpha, a.seam_gain) - b0 - nz0[e]);
+                        const float g1 = v[e] * la_act_bwd_from_y(y[e], a.seam.act, a.seam.alpha, a.seam.gain, a.seam.clamp);
+                        dd += g1 * (la_act_inv(y[e], a.seam.act, a.seam.alpha, a.seam.gain) - b0 - nz0[e]);
                         v[e] = g1 * dm0;
                         mx = fmaxf(mx, fabsf(v[e]));
                     }
@@ -339,8 +339,8 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
     };
     {
         size_t al = (size_t)a.splitk_ws | (size_t)a.out | (size_t)a.out2 | (size_t)a.addend | (size_t)a.noise | (size_t)a.xin;
-        if (seam) al |= (size_t)a.seam_noise | (size_t)(imgc ? a.seam_gimg : nullptr) | (size_t)(imgc ? a.seam_rgbpre : nullptr);
-        const bool vec4 = a.out_sx == 1 && ((a.Gx | wpitch | a.out_ox) & 3) == 0 && ((HWout | a.noise_bstride | a.seam_noise_bstride | a.xin_bstride) & 3) == 0 &&
+        if (seam) al |= (size_t)a.seam.noise | (size_t)(imgc ? a.seam.g_img : nullptr) | (size_t)(imgc ? a.seam.rgb_pre : nullptr);
+        const bool vec4 = a.out_sx == 1 && ((a.Gx | wpitch | a.out_ox) & 3) == 0 && ((HWout | a.noise_bstride | a.seam.noise_bstride | a.xin_bstride) & 3) == 0 &&
                           (al & 15) == 0 && (a_in.nphase == 0 || (a_in.ph[blockIdx.z].ws_off & 3) == 0);
         if (vec4) run(std::integral_constant<int, 4>{});
         else run(std::integral_constant<int, 1>{});
@@ -373,15 +373,15 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
             for (int c = 0; c < 4; ++c) dwe[c] = (wdw[c][0] + wdw[c][1]) + (wdw[c][2] + wdw[c][3]);
         }
         // operand scale of the output for its consumer: one atomic per plane (wave) on a sub-slot of the sample's row
-        if (xs_row) la_xs_lower(xs_row, xs_seen, a.seam_xs_mult, mx);
+        if (xs_row) la_xs_lower(xs_row, xs_seen, a.seam.xs_mult, mx);
         if (tp < a.tiles_per_sample) {
             const long slot = ((long)b * a.M + m) * a.tiles_per_sample + tp;
             for (int c = 0; c < imgc; ++c)
-                a.seam_dweff_part[(((long)b * imgc + c) * a.M + m) * a.tiles_per_sample + tp] = tp == 0 ? dwe[c] : 0.f;
+                a.seam.dweff_part[(((long)b * imgc + c) * a.M + m) * a.tiles_per_sample + tp] = tp == 0 ? dwe[c] : 0.f;
             if (a.ds_part) a.ds_part[slot] = tp == 0 ? part : 0.f;
             if (seam) {
-                a.seam_ddn_part[slot] = tp == 0 ? dd : 0.f;
-                if (a.seam_pmax) a.seam_pmax[slot] = tp == 0 ? mx : 0.f;
+                a.seam.ddn_part[slot] = tp == 0 ? dd : 0.f;
+                if (a.seam.pmax) a.seam.pmax[slot] = tp == 0 ? mx : 0.f;
             }
         }
     }
@@ -453,7 +453,7 @@ int la_conv_launch(const LaConvArgs& a, hipStream_t stream) {
         pflops = 2.0 * a.B * gt * a.M * (double)a.C;
         pbytes = 4.0 * ((double)a.B * a.C * a.Hin * a.Win * (a.in_bstride ? 1.0 : 1.0 / a.B) + (double)a.B * a.M * gout + ntw * a.C * a.M);
     }
-    if (as.seam_xs_out) as.seam_pmax = nullptr;      // every kernel form lowers the consumer's slot row itself: no plane maxima
+    if (as.seam.xs_out) as.seam.pmax = nullptr;      // every kernel form lowers the consumer's slot row itself: no plane maxima
     as.splitk_ws = nullptr;
     long splitk_floats = 0;
     if (as.ws && as.ws_bytes >= sizeof(float)) {
@@ -493,7 +493,7 @@ int la_conv_launch(const LaConvArgs& a, hipStream_t stream) {
                 // one wave per (b, m) plane, four planes per workgroup, at every split-K size (<= 34x34): a whole workgroup per plane
                 // (the <1> form) measured 21 against 13 us on the 8 x 512 x 32^2 launches
                 hipLaunchKernelGGL(la_conv_splitk_finish_kernel<4>, dim3(la_cdiv(a.M, 4), a.B, nz), dim3(256), 0, stream, as);
-                // (the consumer's operand scale, LaConvArgs::seam_xs_out: the finish workgroups lower the sample's slot row themselves)
+                // (the consumer's operand scale, LaConvArgs::seam.xs_out: the finish workgroups lower the sample's slot row themselves)
             }
         }
     }

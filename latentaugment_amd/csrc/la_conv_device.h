@@ -37,11 +37,11 @@ __device__ __forceinline__ void la_conv_zero_partials(const LaConvArgs& a, int b
     if (a.epi != LA_EPI_BWD || tid >= MT || m0 + tid >= a.M) return;
     const long slot = ((long)b * a.M + m0 + tid) * a.tiles_per_sample + tile;
     if (a.ds_part) a.ds_part[slot] = 0.f;
-    if (a.seam_ddn_part) {
-        a.seam_ddn_part[slot] = 0.f;
-        if (a.seam_pmax) a.seam_pmax[slot] = 0.f;
-        if (a.seam_dweff_part)
-            for (int c = 0; c < a.seam_imgc && c < 4; ++c) a.seam_dweff_part[(((long)b * a.seam_imgc + c) * a.M + m0 + tid) * a.tiles_per_sample + tile] = 0.f;
+    if (a.seam.ddn_part) {
+        a.seam.ddn_part[slot] = 0.f;
+        if (a.seam.pmax) a.seam.pmax[slot] = 0.f;
+        if (a.seam.dweff_part)
+            for (int c = 0; c < a.seam.imgc && c < 4; ++c) a.seam.dweff_part[(((long)b * a.seam.imgc + c) * a.M + m0 + tid) * a.tiles_per_sample + tile] = 0.f;
     }
 }
 
@@ -105,21 +105,21 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
             if (tid < MT) prm[tid] = os_b ? os_b[m0 + tid] : 1.f;
             const float* x0 = a.xin ? a.xin + (long)b * a.xin_bstride + (long)(m0 + mw) * HWo : nullptr;
             // fused seam of the layer that produced xin (see LaConvArgs): LDS rows 6, 7 = its demod / bias, 8.. = ddn partials,
-            // 12.. = maxima (the 16-bit kernels' LDS is large enough; the fp32 kernel never sets seam_ddn_part)
-            const bool seam = a.seam_ddn_part != nullptr && x0 != nullptr;
-            const float xs_seen = (seam && a.seam_xs_out) ? la_xs_peek(a.seam_xs_out + (long)b * LA_XS_FAN + la_xs_sub()) : 0.f;      // (early: its latency hides under the epilogue)
+            // 12.. = maxima (the 16-bit kernels' LDS is large enough; the fp32 kernel never sets seam.ddn_part)
+            const bool seam = a.seam.ddn_part != nullptr && x0 != nullptr;
+            const float xs_seen = (seam && a.seam.xs_out) ? la_xs_peek(a.seam.xs_out + (long)b * LA_XS_FAN + la_xs_sub()) : 0.f;      // (early: its latency hides under the epilogue)
             // (activation backward from the saved output as straight-line selects with reciprocals: same values as
             //  la_act_bwd_from_y / la_act_inv up to the rounding of 1/gain, 1/alpha)
-            const float s_pos = a.seam_gain, s_neg = a.seam_act == LA_ACT_LRELU ? a.seam_gain * a.seam_alpha : (a.seam_act == LA_ACT_RELU ? 0.f : a.seam_gain);
-            const float i_gain = 1.f / a.seam_gain, i_neg = a.seam_act == LA_ACT_LRELU ? 1.f / (a.seam_gain * a.seam_alpha) : 1.f / a.seam_gain;
-            const float s_cl = a.seam_clamp >= 0.f ? a.seam_clamp : __builtin_huge_valf();
+            const float s_pos = a.seam.gain, s_neg = a.seam.act == LA_ACT_LRELU ? a.seam.gain * a.seam.alpha : (a.seam.act == LA_ACT_RELU ? 0.f : a.seam.gain);
+            const float i_gain = 1.f / a.seam.gain, i_neg = a.seam.act == LA_ACT_LRELU ? 1.f / (a.seam.gain * a.seam.alpha) : 1.f / a.seam.gain;
+            const float s_cl = a.seam.clamp >= 0.f ? a.seam.clamp : __builtin_huge_valf();
             float nz0[NJ];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) nz0[j] = 0.f;
-            // ToRGB part of the fused seam (seam_imgc image channels): per-pixel image gradients (masked by the ToRGB clamp) in
+            // ToRGB part of the fused seam (seam.imgc image channels): per-pixel image gradients (masked by the ToRGB clamp) in
             // registers, per-row effective ToRGB weights in LDS rows 16.., weight-gradient partials in rows 20..
             constexpr int SEAM_MAXC = 4;
-            const int imgc = seam ? a.seam_imgc : 0;
+            const int imgc = seam ? a.seam.imgc : 0;
             float gr[SEAM_MAXC][NJ];
 #pragma unroll
             for (int c = 0; c < SEAM_MAXC; ++c)
@@ -127,15 +127,15 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                 for (int j = 0; j < NJ; ++j) gr[c][j] = 0.f;
             if (seam) {
                 if (tid < MT) {
-                    red[6][tid] = a.seam_demod ? a.seam_demod[(long)b * a.seam_demod_stride + m0 + tid] : 1.f;
-                    red[7][tid] = a.seam_bias ? a.seam_bias[m0 + tid] : 0.f;
+                    red[6][tid] = a.seam.demod ? a.seam.demod[(long)b * a.seam.demod_stride + m0 + tid] : 1.f;
+                    red[7][tid] = a.seam.bias ? a.seam.bias[m0 + tid] : 0.f;
 #pragma unroll
                     for (int c = 0; c < SEAM_MAXC; ++c)
-                        if (c < imgc) red[16 + c][tid] = a.seam_wrgb[(long)c * a.M + m0 + tid] * a.seam_srgb[(long)b * a.seam_srgb_stride + m0 + tid];
+                        if (c < imgc) red[16 + c][tid] = a.seam.wrgb[(long)c * a.M + m0 + tid] * a.seam.s_rgb[(long)b * a.seam.s_rgb_stride + m0 + tid];
                 }
-                if (a.seam_noise) {
+                if (a.seam.noise) {
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) nz0[j] = a.seam_noise[(long)b * a.seam_noise_bstride + np[j]] * a.seam_noise_strength;
+                    for (int j = 0; j < NJ; ++j) nz0[j] = a.seam.noise[(long)b * a.seam.noise_bstride + np[j]] * a.seam.noise_strength;
                 }
 #pragma unroll
                 for (int c = 0; c < SEAM_MAXC; ++c)
@@ -143,8 +143,8 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) {
                             const long o = ((long)b * imgc + c) * HWo + np[j];
-                            float gv = a.seam_gimg[o];
-                            if (a.seam_rgb_clamp >= 0.f && fabsf(a.seam_rgbpre[o]) > a.seam_rgb_clamp) gv = 0.f;
+                            float gv = a.seam.g_img[o];
+                            if (a.seam.rgb_clamp >= 0.f && fabsf(a.seam.rgb_pre[o]) > a.seam.rgb_clamp) gv = 0.f;
                             gr[c][j] = gv;
                         }
                     }
@@ -263,7 +263,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                         float t = red[20 + c * 4][tid];
 #pragma unroll
                         for (int w = 1; w < WN_; ++w) t += red[20 + c * 4 + w][tid];
-                        a.seam_dweff_part[(((long)b * imgc + c) * a.M + m0 + tid) * a.tiles_per_sample + ntile] = t;
+                        a.seam.dweff_part[(((long)b * imgc + c) * a.M + m0 + tid) * a.tiles_per_sample + ntile] = t;
                     }
                     if (a.ds_part) {
                         float t = red[0][tid];
@@ -275,12 +275,12 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                         float t = red[8][tid], m = red[12][tid];
 #pragma unroll
                         for (int w = 1; w < WN_; ++w) { t += red[8 + w][tid]; m = fmaxf(m, red[12 + w][tid]); }
-                        a.seam_ddn_part[slot] = t;
-                        if (a.seam_pmax) a.seam_pmax[slot] = m;
+                        a.seam.ddn_part[slot] = t;
+                        if (a.seam.pmax) a.seam.pmax[slot] = m;
                         red[12][tid] = m;
                     }
                 }
-                if (seam && a.seam_xs_out) {      // this workgroup's maximum lowers the running operand scale of the sample (wave 0)
+                if (seam && a.seam.xs_out) {      // this workgroup's maximum lowers the running operand scale of the sample (wave 0)
                     __syncthreads();
                     if (tid < 64) {
                         float m = 0.f;
@@ -288,7 +288,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                         for (int k = tid; k < MT; k += 64) m = fmaxf(m, red[12][k]);
 #pragma unroll
                         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-                        if (tid == 0) la_xs_lower(a.seam_xs_out + (long)b * LA_XS_FAN + la_xs_sub(), xs_seen, a.seam_xs_mult, m);
+                        if (tid == 0) la_xs_lower(a.seam.xs_out + (long)b * LA_XS_FAN + la_xs_sub(), xs_seen, a.seam.xs_mult, m);
                     }
                 }
             }
@@ -318,7 +318,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
         // fused ToRGB (LaConvArgs::rgb_*): effective weights of this tile's rows in LDS rows 16.., per-lane partial sums over the
         // lane's 16 rows, then over the two half-waves and the waves along M (LDS, floats [wm][c][128 pixels] behind the row tables)
         constexpr int RGB_MAXC = 4;
-        const int rgbc = (fwd && TILE2D && a.rgb_imgc > 0 && MT == a.M) ? a.rgb_imgc : 0;
+        const int rgbc = (fwd && TILE2D && a.rgb.imgc > 0 && MT == a.M) ? a.rgb.imgc : 0;
         float* rgbp = &red[0][0] + 40 * MT;
         float pr[RGB_MAXC][NJ];
 #pragma unroll
@@ -329,7 +329,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
             if (tid < MT) {
 #pragma unroll
                 for (int c = 0; c < RGB_MAXC; ++c)
-                    red[16 + c][tid] = c < rgbc ? a.rgb_w[(long)c * a.M + tid] * a.rgb_s[(long)b * a.rgb_s_stride + tid] : 0.f;
+                    red[16 + c][tid] = c < rgbc ? a.rgb.w[(long)c * a.M + tid] * a.rgb.s[(long)b * a.rgb.s_stride + tid] : 0.f;
             }
             __syncthreads();
         }
@@ -411,13 +411,13 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                 float t = rgbp[c * NT + tp];
 #pragma unroll
                 for (int w = 1; w < WM_; ++w) t += rgbp[(w * RGB_MAXC + c) * NT + tp];
-                t += a.rgb_bias ? a.rgb_bias[c] : 0.f;
+                t += a.rgb.bias ? a.rgb.bias[c] : 0.f;
                 const int tpr = a.Gx >> 5;
                 const int tyb = ntile / tpr, txb = ntile - tyb * tpr;
                 const long pos = ((long)b * rgbc + c) * HWo + (long)(tyb * 4 + (tp >> 5)) * a.Wout + txb * 32 + (tp & 31);
-                a.rgb_pre[pos] = t;
-                if (a.rgb_clamp >= 0.f) t = fminf(fmaxf(t, -a.rgb_clamp), a.rgb_clamp);
-                a.rgb_img[pos] = t + (a.rgb_skip ? a.rgb_skip[pos] : 0.f);
+                a.rgb.rgb_pre[pos] = t;
+                if (a.rgb.clamp >= 0.f) t = fminf(fmaxf(t, -a.rgb.clamp), a.rgb.clamp);
+                a.rgb.img[pos] = t + (a.rgb.skip ? a.rgb.skip[pos] : 0.f);
             }
         }
         if (fwd && a.fwd_xs_out) {      // (block-uniform)
@@ -457,8 +457,8 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
     if (a.epi == LA_EPI_BWD) {
         const float* xin_b = a.xin ? a.xin + (long)b * a.xin_bstride : nullptr;
         const float* os_b = a.out_scale ? a.out_scale + (long)b * a.oscale_stride : nullptr;
-        const bool seam = a.seam_ddn_part != nullptr && xin_b != nullptr;      // fused seam of the layer that produced xin (LaConvArgs)
-        const float xs_seen = (seam && a.seam_xs_out) ? la_xs_peek(a.seam_xs_out + (long)b * LA_XS_FAN + la_xs_sub()) : 0.f;
+        const bool seam = a.seam.ddn_part != nullptr && xin_b != nullptr;      // fused seam of the layer that produced xin (LaConvArgs)
+        const float xs_seen = (seam && a.seam.xs_out) ? la_xs_peek(a.seam.xs_out + (long)b * LA_XS_FAN + la_xs_sub()) : 0.f;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -467,8 +467,8 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                 const int m = m0 + ml;
                 const bool mok = m < a.M;
                 const float sc = (os_b && mok) ? os_b[m] : 1.f;
-                const float dm0 = (seam && mok && a.seam_demod) ? a.seam_demod[(long)b * a.seam_demod_stride + m] : 1.f;
-                const float b0 = (seam && mok && a.seam_bias) ? a.seam_bias[m] : 0.f;
+                const float dm0 = (seam && mok && a.seam.demod) ? a.seam.demod[(long)b * a.seam.demod_stride + m] : 1.f;
+                const float b0 = (seam && mok && a.seam.bias) ? a.seam.bias[m] : 0.f;
                 float part = 0.f, dd = 0.f, mx = 0.f;
                 float dwe[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -478,16 +478,16 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                         const float y = xin_b ? xin_b[(long)m * HWout + npos[j]] : 0.f;
                         float g = v * sc;
                         if (seam) {
-                            for (int c = 0; c < a.seam_imgc && c < 4; ++c) {
-                                const long o = ((long)b * a.seam_imgc + c) * HWout + npos[j];
-                                float gv = a.seam_gimg[o];
-                                if (a.seam_rgb_clamp >= 0.f && fabsf(a.seam_rgbpre[o]) > a.seam_rgb_clamp) gv = 0.f;
-                                g += a.seam_wrgb[(long)c * a.M + m] * a.seam_srgb[(long)b * a.seam_srgb_stride + m] * gv;
+                            for (int c = 0; c < a.seam.imgc && c < 4; ++c) {
+                                const long o = ((long)b * a.seam.imgc + c) * HWout + npos[j];
+                                float gv = a.seam.g_img[o];
+                                if (a.seam.rgb_clamp >= 0.f && fabsf(a.seam.rgb_pre[o]) > a.seam.rgb_clamp) gv = 0.f;
+                                g += a.seam.wrgb[(long)c * a.M + m] * a.seam.s_rgb[(long)b * a.seam.s_rgb_stride + m] * gv;
                                 dwe[c] += gv * y;
                             }
-                            const float nz0 = a.seam_noise ? a.seam_noise[(long)b * a.seam_noise_bstride + npos[j]] * a.seam_noise_strength : 0.f;
-                            const float g1 = g * la_act_bwd_from_y(y, a.seam_act, a.seam_alpha, a.seam_gain, a.seam_clamp);
-                            dd += g1 * (la_act_inv(y, a.seam_act, a.seam_alpha, a.seam_gain) - b0 - nz0);
+                            const float nz0 = a.seam.noise ? a.seam.noise[(long)b * a.seam.noise_bstride + npos[j]] * a.seam.noise_strength : 0.f;
+                            const float g1 = g * la_act_bwd_from_y(y, a.seam.act, a.seam.alpha, a.seam.gain, a.seam.clamp);
+                            dd += g1 * (la_act_inv(y, a.seam.act, a.seam.alpha, a.seam.gain) - b0 - nz0);
                             g = g1 * dm0;
                             mx = fmaxf(mx, fabsf(g));
                         }
@@ -507,7 +507,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                     if (l31 == 0) { red[8 + wn][ml] = dd; red[12 + wn][ml] = mx; }
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
-                        if (c < a.seam_imgc) {
+                        if (c < a.seam.imgc) {
                             float t = dwe[c];
 #pragma unroll
                             for (int o = 16; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
@@ -520,11 +520,11 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
             __syncthreads();
             if (tid < MT && m0 + tid < a.M) {
                 const long slot = ((long)b * a.M + m0 + tid) * a.tiles_per_sample + ntile;
-                for (int c = 0; seam && c < a.seam_imgc && c < 4; ++c) {
+                for (int c = 0; seam && c < a.seam.imgc && c < 4; ++c) {
                     float t = red[20 + c * 4][tid];
 #pragma unroll
                     for (int w = 1; w < WN_; ++w) t += red[20 + c * 4 + w][tid];
-                    a.seam_dweff_part[(((long)b * a.seam_imgc + c) * a.M + m0 + tid) * a.tiles_per_sample + ntile] = t;
+                    a.seam.dweff_part[(((long)b * a.seam.imgc + c) * a.M + m0 + tid) * a.tiles_per_sample + ntile] = t;
                 }
                 if (a.ds_part) {
                     float t = red[0][tid];
@@ -536,12 +536,12 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                     float t = red[8][tid], mm = red[12][tid];
 #pragma unroll
                     for (int w = 1; w < WN_; ++w) { t += red[8 + w][tid]; mm = fmaxf(mm, red[12 + w][tid]); }
-                    a.seam_ddn_part[slot] = t;
-                    if (a.seam_pmax) a.seam_pmax[slot] = mm;
+                    a.seam.ddn_part[slot] = t;
+                    if (a.seam.pmax) a.seam.pmax[slot] = mm;
                     red[12][tid] = mm;
                 }
             }
-            if (seam && a.seam_xs_out) {
+            if (seam && a.seam.xs_out) {
                 __syncthreads();
                 if (tid < 64) {
                     float m = 0.f;
@@ -549,7 +549,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                         if (m0 + k < a.M) m = fmaxf(m, red[12][k]);
 #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-                    if (tid == 0) la_xs_lower(a.seam_xs_out + (long)b * LA_XS_FAN + la_xs_sub(), xs_seen, a.seam_xs_mult, m);
+                    if (tid == 0) la_xs_lower(a.seam.xs_out + (long)b * LA_XS_FAN + la_xs_sub(), xs_seen, a.seam.xs_mult, m);
                 }
             }
         }

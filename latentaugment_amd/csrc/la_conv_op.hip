@@ -348,13 +348,6 @@ size_t workspace_bytes(int op, const Geo& g) {
     return (size_t)ks * a.groups * a.Ag * a.N * sizeof(float) + 16;
 }
 
-void base_args(LaConvArgs& a) {
-    memset(&a, 0, sizeof(a));
-    a.in_sy = a.in_sx = a.out_sy = a.out_sx = 1;
-    a.clamp = -1.f; a.gain = 1.f; a.act = LA_ACT_LINEAR;
-    a.epi = LA_EPI_RAW; a.precision = LA_PREC_F32;
-}
-
 int engine_forward(const Geo& g, const float* x, const float* w, float* y, void* ws, size_t ws_bytes, hipStream_t stream) {
     const int Cg = g.Cin / g.groups, Mg = g.Cout / g.groups, taps = g.kh * g.kw;
     float* wp = static_cast<float*>(ws);
@@ -370,7 +363,7 @@ int engine_forward(const Geo& g, const float* x, const float* w, float* y, void*
     for (int grp = 0; grp < g.groups; ++grp)
         for (int bs = 0; bs < nb; ++bs) {
             LaConvArgs a;
-            base_args(a);
+            la_conv_args_init(a);      // (epi = LA_EPI_RAW, precision = LA_PREC_F32: both zero)
             a.in = x + ((long)bs * g.Cin + (long)grp * Cg) * HWi;
             a.in_bstride = (long)g.Cin * HWi;
             a.wgt = wp + (long)grp * taps * Cg * Mg;

@@ -465,11 +465,6 @@ __global__ void la_disc_loss_kernel(const float* __restrict__ logits, float* __r
     }
 }
 
-static void cbase(LaConvArgs& a) {
-    memset(&a, 0, sizeof(a));
-    a.in_sy = a.in_sx = a.out_sy = a.out_sx = 1; a.clamp = -1.f; a.gain = 1.f; a.act = LA_ACT_LINEAR;
-}
-
 static void set_w(LaConvArgs& a, la_disc* h, const DConv& L, bool backward) {
     a.wgt = backward ? L.wb : L.wf;
     a.precision = h->precision; a.wgt_bf16 = backward ? L.wqb : L.wqf;
@@ -481,7 +476,7 @@ static void set_w(LaConvArgs& a, la_disc* h, const DConv& L, bool backward) {
 static int conv_same(la_disc* h, const DConv& L, bool backward, const float* in, float* out, int B, int res, int act, float gain,
                      float clamp, const float* addend, float* out2, hipStream_t stream, const float* in_pmax = nullptr, int in_nseg = 0,
                      const float* xs_rows = nullptr, float in_gain = 1.f, float* xs_out = nullptr) {
-    LaConvArgs a; cbase(a);
+    LaConvArgs a; la_conv_args_init(a);
     set_w(a, h, L, backward);
     a.in = in; a.out = out; a.B = B; a.in_pmax = in_pmax; a.in_pmax_nseg = in_nseg;
     if (xs_rows) { a.acc_scale_x = xs_rows; a.acc_scale_fan = LA_XS_FAN; a.in_pmax = nullptr; }      // slot rows left by the producer of `in`
@@ -489,11 +484,7 @@ static int conv_same(la_disc* h, const DConv& L, bool backward, const float* in,
     a.C = backward ? L.cout : L.cin; a.M = backward ? L.mb_ : L.cout;      // (padded channels of a backward come out as zeros)
     a.in_bstride = (long)a.C * res * res;
     a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
-    a.ntaps = L.k * L.k;
-    for (int t = 0; t < a.ntaps; ++t) {
-        const int ky = t / L.k, kx = t % L.k, pad = L.k / 2;
-        a.tap_dy[t] = backward ? pad - ky : ky - pad; a.tap_dx[t] = backward ? pad - kx : kx - pad; a.tap_w[t] = t;
-    }
+    la_conv_taps_kxk(a, L.k, backward);
     if (backward) { a.epi = LA_EPI_BWD; }
     else {
         a.epi = LA_EPI_FWD; a.bias = L.bias; a.act = act; a.alpha = 0.2f; a.gain = gain; a.clamp = clamp; a.addend = addend; a.out2 = out2;
@@ -531,7 +522,7 @@ extern "C" int la_disc_forward(la_disc* h, const float* img, int B, hipStream_t 
             LA_CHECK_LAUNCH();
         }
         // skip: FIR (pad 1,1,1,1) + decimate 2, then 1x1 conv, linear * sqrt(1/2)      (conv2d_resample.py:94-97)
-        if ((rc = la_upfirdn2d_ex(b.xin, h->scrB, B, b.cin, res, res, h->fir, 4, 4, 1, 1, 2, 2, 1, 1, 1, 1, 0, 1.f, nullptr, stream))) return rc;
+        if ((rc = la_upfirdn2d_ex(b.xin, h->scrB, B, b.cin, res, res, h->fir, la_fir_down2(), stream))) return rc;
         if ((rc = conv_same(h, b.skip, false, h->scrB, b.ysk, B, hq, LA_ACT_LINEAR, rs2, -1.f, nullptr, nullptr, stream, nullptr, 0, rows_x(k)))) return rc;
         // conv0
         if ((rc = conv_same(h, b.conv0, false, b.xin, b.y0, B, res, LA_ACT_LRELU, sq2, h->clamp, nullptr, nullptr, stream, nullptr, 0, rows_x(k), 1.f, rows_y(k)))) return rc;
@@ -541,9 +532,9 @@ extern "C" int la_disc_forward(la_disc* h, const float* img, int B, hipStream_t 
         // (res+1)^2 fp32 scratch + the pre-split copy of that scratch
         const size_t qbytes = (size_t)B * la_cdiv(b.cin, 32) * 32 * (res + 1) * (res + 1) * 4;
         const bool fir_pack = slots && res % 4 == 0 && h->cws_bytes > qbytes + 1024;
-        if (!fir_pack && (rc = la_upfirdn2d_ex(b.y0, h->scrA, B, b.cin, res, res, h->fir, 4, 4, 1, 1, 1, 1, 2, 2, 2, 2, 0, 1.f, nullptr, stream))) return rc;
+        if (!fir_pack && (rc = la_upfirdn2d_ex(b.y0, h->scrA, B, b.cin, res, res, h->fir, la_fir_same_pad2(0, 1.f), stream))) return rc;
         {
-            LaConvArgs a; cbase(a);
+            LaConvArgs a; la_conv_args_init(a);
             set_w(a, h, b.conv1, false);
             if (fir_pack) {
                 unsigned* q = reinterpret_cast<unsigned*>(h->cws);
@@ -553,8 +544,8 @@ extern "C" int la_disc_forward(la_disc* h, const float* img, int B, hipStream_t 
             }
             a.in = h->scrA; a.in_bstride = (long)b.cin * (res + 1) * (res + 1); a.out = b.x1;
             a.B = B; a.C = b.cin; a.M = b.cout; a.Hin = a.Win = res + 1; a.Hout = a.Wout = a.Gy = a.Gx = hq;
-            a.in_sy = a.in_sx = 2; a.ntaps = 9;
-            for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3; a.tap_dx[t] = t % 3; a.tap_w[t] = t; }
+            a.in_sy = a.in_sx = 2;
+            la_conv_taps_3x3_corner(a);
             a.epi = LA_EPI_FWD; a.bias = b.conv1.bias; a.act = LA_ACT_LRELU; a.alpha = 0.2f; a.gain = sq2 * rs2;
             a.clamp = h->clamp >= 0.f ? h->clamp * rs2 : -1.f;
             a.addend = b.ysk; a.out2 = b.sum;
@@ -632,7 +623,7 @@ extern "C" int la_disc_backward(la_disc* h, const float* dlogits, float* g_img, 
         if (!gs && (rc = la_conv_act_grad_pmax(g_sum, b.x1, h->scrB, h->pm, B, b.cout, (long)hq * hq, LA_ACT_LRELU, 0.2f, sq2 * rs2,
                                                h->clamp >= 0.f ? h->clamp * rs2 : -1.f, stream))) return rc;
         {
-            LaConvArgs a; cbase(a);
+            LaConvArgs a; la_conv_args_init(a);
             set_w(a, h, b.conv1, true);
             a.in = gs ? g_sum : h->scrB; a.in_bstride = (long)b.cout * hq * hq; a.out = h->scrA;
             a.B = B; a.C = b.cout; a.M = b.cin; a.Hin = a.Win = hq; a.Hout = a.Wout = res + 1;
@@ -648,36 +639,25 @@ extern "C" int la_disc_backward(la_disc* h, const float* dlogits, float* g_img, 
             } else { a.in_pmax = h->pm; a.in_pmax_nseg = nsq; }
             if (h->precision != LA_PREC_F32 && (rc = la_conv_prepare_input(a, stream))) return rc;   // split once for the four phases
             const bool merged = h->precision != LA_PREC_F32;      // 16-bit kernels: the four phases in ONE launch (as the generator's up layers)
-            int np = 0;
             for (int py = 0; py < 2; ++py)
                 for (int px = 0; px < 2; ++px) {
-                    a.out_oy = py; a.out_ox = zx ? px * zx : px; a.Gy = py ? hq : hq + 1; a.Gx = px ? hq : hq + 1;
-                    int nt = 0;
-                    for (int ky = py; ky < 3; ky += 2)
-                        for (int kx = px; kx < 3; kx += 2) { a.tap_dy[nt] = -(ky / 2); a.tap_dx[nt] = -(kx / 2); a.tap_w[nt] = ky * 3 + kx; ++nt; }
-                    a.ntaps = nt;
-                    if (merged) {
-                        LaConvArgs::Phase& P = a.ph[np++];
-                        P.Gy = a.Gy; P.Gx = a.Gx; P.out_oy = py; P.out_ox = a.out_ox; P.ntaps = nt;
-                        for (int t = 0; t < nt; ++t) { P.tap_dy[t] = a.tap_dy[t]; P.tap_dx[t] = a.tap_dx[t]; P.tap_w[t] = a.tap_w[t]; }
-                        continue;
-                    }
-                    if ((rc = la_conv_launch(a, stream))) return rc;
+                    la_conv_up2_phase(a, hq, py, px, zx ? zx : 1, merged);
+                    if (!merged && (rc = la_conv_launch(a, stream))) return rc;
                 }
             if (merged) {
-                a.nphase = np;
                 a.out_oy = a.out_ox = 0; a.Gy = a.Gx = hq + 1; a.ntaps = 4;      // launch-wide fields = the largest phase (checks only)
                 if ((rc = la_conv_launch(a, stream))) return rc;
             }
         }
         if (fuse) {
             // FIR adjoint + act'(y0) + the slot rows of conv0's backward contraction in one kernel
-            LaFirTail tail{b.y0, LA_ACT_LRELU, 0.2f, sq2, h->clamp, rows_c0(k)};
+            LaFirTail tail;
+            tail.yref = b.y0; tail.act = LA_ACT_LRELU; tail.alpha = 0.2f; tail.gain = sq2; tail.clamp = h->clamp; tail.xs_out = rows_c0(k);
             if (zx_of(res)) { tail.in_pitch = 2 * zx_of(res); tail.in_plane = (long)tail.in_pitch * (res + 1); tail.in_xhalf = zx_of(res); }
-            if ((rc = la_upfirdn2d_ex(h->scrA, other, B, b.cin, res + 1, res + 1, h->fir, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1.f, nullptr, stream, nullptr, &tail))) return rc;
+            if ((rc = la_upfirdn2d_ex(h->scrA, other, B, b.cin, res + 1, res + 1, h->fir, la_fir_same_pad1(1, 1.f), stream, tail))) return rc;
             if ((rc = conv_same(h, b.conv0, true, other, h->scrA, B, res, 0, 0.f, 0.f, nullptr, nullptr, stream, nullptr, 0, rows_c0(k)))) return rc;
         } else {
-            if ((rc = la_upfirdn2d_ex(h->scrA, other, B, b.cin, res + 1, res + 1, h->fir, 4, 4, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1.f, nullptr, stream))) return rc;
+            if ((rc = la_upfirdn2d_ex(h->scrA, other, B, b.cin, res + 1, res + 1, h->fir, la_fir_same_pad1(1, 1.f), stream))) return rc;
             // ---- conv0: act' then backward-data
             if ((rc = la_conv_act_grad_pmax(other, b.y0, other, h->pm, B, b.cin, (long)res * res, LA_ACT_LRELU, 0.2f, sq2, h->clamp, stream))) return rc;
             if ((rc = conv_same(h, b.conv0, true, other, h->scrA, B, res, 0, 0.f, 0.f, nullptr, nullptr, stream, h->pm, nsf))) return rc;   // scrA >= B*cin*res^2
@@ -691,8 +671,9 @@ extern "C" int la_disc_backward(la_disc* h, const float* dlogits, float* g_img, 
             if ((rc = conv_same(h, b.skip, true, h->scrB, g_sum, B, hq, 0, 0.f, 0.f, nullptr, nullptr, stream, h->pm, nsq))) return rc;       // reuse g_sum buffer: [B][cin][hq^2]
         }
         {
-            LaFirTail tail{nullptr, 0, 0.f, 0.f, 0.f, (fuse && k > 0) ? rows_g(k - 1) : nullptr};
-            if ((rc = la_upfirdn2d_ex(g_sum, other, B, b.cin, hq, hq, h->fir, 4, 4, 2, 2, 1, 1, 2, 1, 2, 1, 1, 1.f, h->scrA, stream, nullptr, &tail))) return rc;
+            LaFirTail tail;
+            tail.addend = h->scrA; tail.xs_out = (fuse && k > 0) ? rows_g(k - 1) : nullptr;
+            if ((rc = la_upfirdn2d_ex(g_sum, other, B, b.cin, hq, hq, h->fir, la_fir_up2(1, 1.f), stream, tail))) return rc;
         }
         // `other` now holds d/d(xin) of this block
         float* t = g_sum; g_sum = other; other = t;
@@ -700,12 +681,12 @@ extern "C" int la_disc_backward(la_disc* h, const float* dlogits, float* g_img, 
     // fromrgb backward: act' then the 1x1 adjoint onto the image channels (streams the gradient once)
     DBlock& b0 = h->blk[0];
     const long n0 = (long)B * b0.cin * h->R * h->R;
+    // (unmodulated 1x1 with the transposed FromRGB weights, no bias, no clamp; accumulate: g_img is its own skip)
+    const LaRgbFuse r{h->imgc, b0.frgb_wt, nullptr, 0, nullptr, accumulate ? g_img : nullptr, nullptr, g_img, -1.f};
     if (fuse && (long)h->R * h->R > 4096) {      // act' inside the 1x1's stream of the gradient
         const LaTorgbMask mk{b0.xin, LA_ACT_LRELU, 0.2f, sq2, h->clamp};
-        return la_torgb_forward(g_sum, b0.frgb_wt, nullptr, 0, nullptr, accumulate ? g_img : nullptr, nullptr, g_img, B, b0.cin, h->imgc, h->R,
-                                h->R, -1.f, stream, &mk);
+        return la_torgb_forward(g_sum, r, B, b0.cin, h->R, h->R, stream, &mk);
     }
     if ((rc = la_bias_act_grad_f32(g_sum, b0.xin, g_sum, nullptr, n0, 1, 1, LA_ACT_LRELU, 0.2f, sq2, h->clamp, stream))) return rc;
-    return la_torgb_forward(g_sum, b0.frgb_wt, nullptr, 0, nullptr, accumulate ? g_img : nullptr, nullptr, g_img, B, b0.cin, h->imgc, h->R,
-                            h->R, -1.f, stream);
+    return la_torgb_forward(g_sum, r, B, b0.cin, h->R, h->R, stream);
 }

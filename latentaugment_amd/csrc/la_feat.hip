@@ -321,17 +321,12 @@ __global__ __launch_bounds__(256) void la_tap_bwd_kernel(const float* __restrict
 // pixel lanes of a tap workgroup: the largest power of two <= min(64, HW)
 static inline int tap_lanes(int HW) { int pl = 1; while (pl * 2 <= HW && pl < 64) pl *= 2; return pl; }
 
-static void fbase(LaConvArgs& a) {
-    memset(&a, 0, sizeof(a));
-    a.in_sy = a.in_sx = a.out_sy = a.out_sx = 1; a.clamp = -1.f; a.gain = 1.f; a.act = LA_ACT_LINEAR;
-}
-
 // slot-row hand-over of the fp16 operand scales (f16x2 mode): xs_in = rows of this launch's input (null: absmax / plane-maxima passes),
 // xs_out = rows the epilogue lowers for the contraction that consumes the output (forward: the next conv's; backward: those of the conv
-// whose ReLU output `mask_y` is -- the epilogue then also applies that ReLU's mask to the outgoing gradient, LaConvArgs::seam_*)
+// whose ReLU output `mask_y` is -- the epilogue then also applies that ReLU's mask to the outgoing gradient, LaConvArgs::seam)
 static int f_conv(la_feat* h, const FOp& o, bool backward, const float* in, float* out, int N, hipStream_t stream, const float* in_pmax = nullptr,
                   int in_nseg = 0, const float* xs_in = nullptr, float* xs_out = nullptr, const float* mask_y = nullptr) {
-    LaConvArgs a; fbase(a);
+    LaConvArgs a; la_conv_args_init(a);
     a.wgt = backward ? o.wb : o.wf;
     a.precision = h->precision; a.wgt_bf16 = backward ? o.wqb : o.wqf;
     a.wgt_bf16_term_elems = la_conv_bf16_pack_elems(backward ? o.mb_ : o.cout, backward ? o.cout : o.cin, 9);
@@ -341,17 +336,14 @@ static int f_conv(la_feat* h, const FOp& o, bool backward, const float* in, floa
     const int res = o.res_in;
     a.in_bstride = (long)a.C * res * res;
     a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
-    a.ntaps = 9;
-    for (int t = 0; t < 9; ++t) {
-        a.tap_dy[t] = backward ? 1 - t / 3 : t / 3 - 1; a.tap_dx[t] = backward ? 1 - t % 3 : t % 3 - 1; a.tap_w[t] = t;
-    }
+    la_conv_taps_3x3(a, backward);
     if (xs_in) { a.acc_scale_x = xs_in; a.acc_scale_fan = LA_XS_FAN; a.in_pmax = nullptr; }
     if (backward) {
         a.epi = LA_EPI_BWD;
         if (mask_y) {      // activation backward of the layer below, fused (its saved output is the epilogue's xin)
             a.xin = mask_y; a.xin_bstride = (long)a.M * res * res; a.tiles_per_sample = la_conv_tiles_per_sample(res, res);
-            a.seam_ddn_part = h->seam_scr; a.seam_act = LA_ACT_RELU; a.seam_alpha = 0.f; a.seam_gain = 1.f; a.seam_clamp = -1.f;
-            a.seam_xs_out = xs_out; a.seam_xs_mult = 1.f;
+            a.seam.ddn_part = h->seam_scr; a.seam.act = LA_ACT_RELU; a.seam.alpha = 0.f; a.seam.gain = 1.f; a.seam.clamp = -1.f;
+            a.seam.xs_out = xs_out; a.seam.xs_mult = 1.f;
         }
     } else { a.epi = LA_EPI_FWD; a.bias = o.bias; a.act = LA_ACT_RELU; a.gain = 1.f; a.fwd_xs_out = xs_out; }
     return la_conv_launch(a, stream);
@@ -406,7 +398,7 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
     int rc;
     // fp16 x2 mode: the ReLU mask of conv k and the operand scale of the masked gradient come from the kernel that WRITES that gradient
     // last -- the tap behind conv k (la_tap_bwd_kernel, mask fused), or the backward contraction of conv k+1 when it follows directly
-    // (its epilogue applies the mask of its xin = y_k, LaConvArgs::seam_*) -- instead of an activation-backward sweep with plane maxima
+    // (its epilogue applies the mask of its xin = y_k, LaConvArgs::seam) -- instead of an activation-backward sweep with plane maxima
     // and a scale-reduction launch per conv.  `masked`: g already carries op k's mask and its slot rows are final.
     const bool slots = h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS");      // (dev knob: the round-3 passes)
     if (slots) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_b), (int)LA_XS_INIT, (size_t)h->nops * h->maxN * LA_XS_FAN, stream));

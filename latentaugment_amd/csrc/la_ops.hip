@@ -401,7 +401,7 @@ template <class T>
 static int fir_op_fill(LaFirOpArgs<T>& a, const T* in, T* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw, int upx,
                        int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter, typename LaOpType<T>::A gain) {
     LaFirSetup s;
-    const int rc = la_fir_setup(s, in, out, B, C, Hin, Win, f_host, fh, fw, upx, upy, dnx, dny, padx0, padx1, pady0, pady1, flip_filter, (float)gain);
+    const int rc = la_fir_setup(s, in, out, B, C, Hin, Win, f_host, LaFirGeom{fh, fw, upx, upy, dnx, dny, padx0, padx1, pady0, pady1, flip_filter, (float)gain});
     if (rc) return rc;
     a.in = in; a.out = out; a.P = B * C;
     a.Hin = Hin; a.Win = Win; a.Wout = s.Wout; a.Hout = s.Hout;

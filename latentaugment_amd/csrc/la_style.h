@@ -1,6 +1,7 @@
 // Internal (C++) interface of la_style.hip.
 #pragma once
 #include "la_common.h"
+#include "la_conv.h"
 
 #define LA_MAX_STYLE_LAYERS 40
 
@@ -30,7 +31,7 @@ struct LaSeamArgs {
     float* gz;               // [B][C][HW] (may alias gx_next)
     long HW;
     int C;
-    const float* demod; int demod_stride;
+    const float* demod; int demod_stride;      // the layer's epilogue, in the seam order (la_seam_set_epi)
     const float* bias;
     const float* noise; long noise_bstride; float noise_strength;
     int act; float alpha, gain, clamp;
@@ -44,7 +45,7 @@ struct LaSeamArgs {
     float* dweff_part;       // [B][imgc][C][slabs]
     float* pmax_out;         // optional [B][C][slabs]: partial max |gz| per plane (one per workgroup)
     float* xs_out; float xs_mult;      // optional slot rows [B][LA_XS_FAN] (la_common.h): fp16 operand scale of gz for its consumer, pow2 scale of xs_mult * max|gz|
-    long p_lo, p_hi;         // pixel window (multiples of 4; 0 / 0 = the whole plane): only pixels [p_lo, p_hi) of every plane are read and written --
+    long p_lo, p_hi;         // pixel window, not a LaWindow: a range of flattened pixels (multiples of 4; 0 / 0 = the whole plane): only pixels [p_lo, p_hi) of every plane are read and written --
                              // the incoming gradient is zero outside them (la_synth.hip: row windows); the slabs share the window
 };
 
@@ -61,10 +62,9 @@ int la_demod_forward(const LaDemodTable& t, const float* s_all, int s_stride, in
 // mask (optional, planes above 64x64): x is a gradient still to be taken through an activation -- x[b][i][p] * act'(mask.y[b][i][p]) is what
 // the 1x1 reads (the discriminator's FromRGB backward: one stream of the gradient and the saved output instead of a sweep + a stream)
 struct LaTorgbMask { const float* y; int act; float alpha, gain, clamp; };
-int la_torgb_forward(const float* x, const float* wrgb, const float* s, int s_stride, const float* bias,
-                     const float* skip, float* rgb_pre, float* img, int B, int C, int imgc, int H, int W, float clamp,
-                     hipStream_t, const LaTorgbMask* mask = nullptr, int row_lo = 0, int row_hi = 0, const float* skip_lo = nullptr,
-                     const float* fir_host = nullptr);      // skip_lo + fir_host: the block below's image, up-sampled inside the kernel
+// r: the ToRGB layer as LaRgbFuse describes it (la_conv.h; s null = no modulation, rgb_pre null = not kept)
+int la_torgb_forward(const float* x, const LaRgbFuse& r, int B, int C, int H, int W, hipStream_t, const LaTorgbMask* mask = nullptr, int row_lo = 0,
+                     int row_hi = 0, const float* skip_lo = nullptr, const float* fir_host = nullptr);      // skip_lo + fir_host: the block below's image, up-sampled inside the kernel
 // row_lo / row_hi (planes above 64x64; 0 / 0 = all): only these rows of rgb_pre / img are computed and written
 int la_seam_slabs(long HW);
 int la_seam_backward(const LaSeamArgs& a, int B, int imgc, hipStream_t);

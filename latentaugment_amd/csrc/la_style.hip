@@ -384,9 +384,12 @@ __global__ __launch_bounds__(256) void la_torgb_fwd_small_kernel(const float* __
     }
 }
 
-int la_torgb_forward(const float* x, const float* wrgb, const float* s, int s_stride, const float* bias,
-                     const float* skip, float* rgb_pre, float* img, int B, int C, int imgc, int H, int W, float clamp,
-                     hipStream_t stream, const LaTorgbMask* mask, int row_lo, int row_hi, const float* skip_lo, const float* fir_host) {
+int la_torgb_forward(const float* x, const LaRgbFuse& r, int B, int C, int H, int W, hipStream_t stream, const LaTorgbMask* mask, int row_lo,
+                     int row_hi, const float* skip_lo, const float* fir_host) {
+    const float *wrgb = r.w, *s = r.s, *bias = r.bias, *skip = r.skip;
+    float *rgb_pre = r.rgb_pre, *img = r.img;
+    const int s_stride = r.s_stride, imgc = r.imgc;
+    const float clamp = r.clamp;
     // skip_lo (instead of skip): the image of the block below [B][imgc][H/2][W/2]; its upsample2d (up 2, pad (2,1,2,1), gain 4, upfirdn2d.py:342-348)
     // is computed inside the kernel (la_up2_quad) with the 4x4 filter fir_host
     LaSkipUp su; su.lo = nullptr; su.Hl = H / 2; su.Wl = W / 2;

@@ -69,6 +69,19 @@ struct la_synth {
     int fw_lo[2 * MAX_BLOCKS], fw_hi[2 * MAX_BLOCKS];      // row windows of the conv outputs in the LAST forward pass (0 / 0 = whole plane)
 };
 
+// a layer's epilogue (SynthesisLayer.forward: lrelu, gain sqrt(2), conv_clamp) with the noise the last forward pass used ...
+static LaLayerEpi layer_epi(const la_synth* h, const ConvLayer& L) {
+    return LaLayerEpi{h->d_all + L.d_off, h->Dt, L.noise_used, L.noise_bstride, L.noise_strength, L.bias, LA_ACT_LRELU, 0.2f, sqrtf(2.f), h->clamp};
+}
+// ... and its contraction, forward or backward
+static LaModconv layer_conv(const la_synth* h, const ConvLayer& L, int B, bool backward) {
+    return LaModconv{backward ? L.wb : L.wf, backward ? L.wqb : L.wqf, h->precision, h->s_all + L.s_off, h->S, B, L.cin, L.cout, L.res, h->cws, h->cws_bytes};
+}
+// the block's ToRGB layer writing its image to `img`
+static LaRgbFuse layer_rgb(const la_synth* h, const RgbLayer& T, const float* skip, float* img) {
+    return LaRgbFuse{h->imgc, T.weight, h->s_all + T.s_off, h->S, T.bias, skip, T.rgb_pre, img, h->clamp};
+}
+
 static size_t align_up(size_t v) { return (v + 63) & ~(size_t)63; }
 
 struct Carver {
@@ -368,12 +381,12 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
             if (res < 64) break;
             int lo = img_lo, hi = img_hi;
             if (up_hi > 0) { lo = up_lo < lo ? up_lo : lo; hi = up_hi > hi ? up_hi : hi; }
-            lo &= ~3; hi = (hi + 3) & ~3;
-            if (hi > res) hi = res;
+            la_span_tiles(lo, hi, 4, res);
             if (lo <= 0 && hi >= res) break;                      // everything is needed from here down
             wlo[c1] = lo; whi[c1] = hi;
             ilo[k] = img_lo; ihi[k] = img_hi;
-            const int l0 = lo - 1 > 0 ? lo - 1 : 0, h0 = hi + 1 < res ? hi + 1 : res;
+            int l0 = lo, h0 = hi;
+            la_span_grow(l0, h0, 1, 1, res);
             wlo[c1 - 1] = l0; whi[c1 - 1] = h0;
             la_modconv3x3_up2_fwd_rows(res, l0, h0, &up_lo, &up_hi);
             img_lo = (img_lo - 2) >> 1; if (img_lo < 0) img_lo = 0;
@@ -386,9 +399,11 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
     int c1lo = 0, c1hi = 0, c0lo = 0, c0hi = 0;
     h->fw_c0 = h->fw_c1 = 0;
     if (h->wcol_hi > 0 && whi[h->nconv - 1] > 0 && h->R >= 64) {
-        c1lo = h->wcol_lo & ~31; c1hi = (h->wcol_hi + 31) & ~31; if (c1hi > h->R) c1hi = h->R;
+        c1lo = h->wcol_lo; c1hi = h->wcol_hi;
+        la_span_tiles(c1lo, c1hi, 32, h->R);
         if (h->wcol_lo - 1 >= c1lo && h->wcol_hi + 1 <= c1hi && (c1lo > 0 || c1hi < h->R)) {
-            c0lo = c1lo - 1 > 0 ? c1lo - 1 : 0; c0hi = c1hi + 1 < h->R ? c1hi + 1 : h->R;
+            c0lo = c1lo; c0hi = c1hi;
+            la_span_grow(c0lo, c0hi, 1, 1, h->R);
             h->fw_c0 = c1lo; h->fw_c1 = c1hi;
         } else c1lo = c1hi = 0;
     }
@@ -406,7 +421,7 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
         const float* skip = nullptr;
         if (k > 0 && fuse_rgb) {      // (the skip image has to exist before conv1 runs)
             RgbLayer& P = h->rgb[k - 1];
-            if ((rc = la_upfirdn2d_ex(P.img, T.g_img, B, h->imgc, res / 2, res / 2, h->fir, 4, 4, 2, 2, 1, 1, 2, 1, 2, 1, 0, 4.f, nullptr, stream)))
+            if ((rc = la_upfirdn2d_ex(P.img, T.g_img, B, h->imgc, res / 2, res / 2, h->fir, la_fir_up2(), stream)))
                 return rc;
             skip = T.g_img;
         }
@@ -417,23 +432,18 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
                 if (noise_mode == 1) L.noise_used = L.noise_const;
                 else if (noise_mode == 2) { L.noise_used = noises[ci]; L.noise_bstride = (long)res * res; LA_CHECK_ARG(L.noise_used, "synth_forward: missing noise tensor"); }
             }
-            const float sq2 = sqrtf(2.f);
-            LaRgbFuse rf;
-            rf.imgc = h->imgc; rf.w = T.weight; rf.s = h->s_all + T.s_off; rf.s_stride = h->S; rf.bias = T.bias; rf.skip = skip;
-            rf.rgb_pre = T.rgb_pre; rf.img = rgb_dst; rf.clamp = h->clamp;
+            const LaRgbFuse rf = layer_rgb(h, T, skip, rgb_dst);
+            LaModconvFwdOpts o;
+            o.xscale = fwd_row(ci); o.xs_out = fwd_row(ci + 1); o.xs_mult = fwd_mult(ci + 1);
+            o.win.row_lo = wlo[ci]; o.win.row_hi = whi[ci];
             if (!L.up) {
-                rc = la_modconv3x3_fwd_ex(x, x_bstride, nullptr, 0, L.wf, L.wqf, h->precision, h->s_all + L.s_off, h->S, h->d_all + L.d_off, h->Dt,
-                                          L.noise_used, L.noise_bstride, L.noise_strength, L.bias, LA_ACT_LRELU, 0.2f, sq2,
-                                          h->clamp, L.y, h->cws, h->cws_bytes, B, L.cin, L.cout, res, stream, fwd_row(ci),
-                                          (fuse_rgb && q == nl - 1) ? &rf : nullptr, fwd_row(ci + 1), fwd_mult(ci + 1), wlo[ci], whi[ci],
-                                          ci == h->nconv - 1 ? c1lo : 0, ci == h->nconv - 1 ? c1hi : 0);
+                if (fuse_rgb && q == nl - 1) o.rgb = &rf;
+                if (ci == h->nconv - 1) { o.win.col_lo = c1lo; o.win.col_hi = c1hi; }
+                rc = la_modconv3x3_fwd_ex(x, x_bstride, layer_conv(h, L, B, false), layer_epi(h, L), L.y, stream, o);
             } else {
-                rc = la_modconv3x3_up2_fwd_ex(x, x_bstride, L.wf, L.wqf, h->precision, h->s_all + L.s_off, h->S, h->d_all + L.d_off, h->Dt,
-                                              L.noise_used, L.noise_bstride, L.noise_strength, L.bias, LA_ACT_LRELU, 0.2f,
-                                              sq2, h->clamp, h->fir, h->zT, L.y, nullptr, h->cws, h->cws_bytes, B, L.cin,
-                                              L.cout, res, stream, fwd_row(ci),
-                                              zt_dense ? 0 : 2 * zt_xhalf(res), zt_dense ? 0 : zt_xhalf(res), fwd_row(ci + 1), fwd_mult(ci + 1),
-                                              wlo[ci], whi[ci], ci == h->nconv - 2 ? c0lo : 0, ci == h->nconv - 2 ? c0hi : 0);
+                if (!zt_dense) { o.scratch_pitch = 2 * zt_xhalf(res); o.scratch_xhalf = zt_xhalf(res); }
+                if (ci == h->nconv - 2) { o.win.col_lo = c0lo; o.win.col_hi = c0hi; }
+                rc = la_modconv3x3_up2_fwd_ex(x, x_bstride, layer_conv(h, L, B, false), layer_epi(h, L), h->fir, h->zT, L.y, stream, o);
             }
             if (rc) return rc;
             x = L.y; x_bstride = (long)L.cout * res * res;
@@ -443,8 +453,8 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
             // below is computed inside the ToRGB kernel (la_up2_quad; round 4: a launch of its own per block, parked in g_img)
             const float* skip_lo = k > 0 ? h->rgb[k - 1].img : nullptr;
             const bool iw = ihi[k] > 0 && (long)res * res > 4096;      // (windowed block: only the image rows somebody reads)
-            if ((rc = la_torgb_forward(x, T.weight, h->s_all + T.s_off, h->S, T.bias, nullptr, T.rgb_pre, rgb_dst, B, T.cin, h->imgc,
-                                       res, res, h->clamp, stream, nullptr, iw ? ilo[k] : 0, iw ? ihi[k] : 0, skip_lo, h->fir)))
+            if ((rc = la_torgb_forward(x, layer_rgb(h, T, nullptr, rgb_dst), B, T.cin, res, res, stream, nullptr, iw ? ilo[k] : 0, iw ? ihi[k] : 0,
+                                       skip_lo, h->fir)))
                 return rc;
         }
         if (k == h->nblocks - 1) h->final_img = rgb_dst;
@@ -487,22 +497,22 @@ extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hi
     // a producer writes its window, its consumer reads everything outside it as zeros (LaBwdRows) -- the ping-pong buffers G0 / G1 hold
     // older contents there.  Default path only (fused seams, slot rows); needs an image gradient that is zero outside the image window.
     const bool bw = xs_hand && !no_fuse && !no_fuse2 && h->precision != LA_PREC_F32;
-    auto r4 = [](int lo, int hi, int res, int* o_lo, int* o_hi) { *o_lo = lo & ~3; *o_hi = (hi + 3) & ~3; if (*o_hi > res) *o_hi = res; };
     for (int k = h->nblocks - 1; k >= 0; --k) {
         const int res = 4 << k;
         const long HW = (long)res * res;
         // W1 = window of this block's conv1 output (= valid rows of the gradient G0 that reaches it), R1 = the 4-row tiles around the
         // window of conv0's output (what conv1's backward contraction writes into G1), Wb = window of the block below's conv1 output
         const bool win = bw && k > 0 && h->fw_hi[ci] > 0;
-        LaBwdRows rw1{0, 0, 0, 0, 0, 0, 0, 0}, rw0{0, 0, 0, 0, 0, 0, 0, 0};
+        LaBwdRows rw1 = {}, rw0 = {};
         if (win && k == h->nblocks - 1 && h->fw_c1 > 0) {      // top block: conv1's backward contraction writes the window's tile columns, the FIR adjoint reads the others as zeros
-            rw1.out_c0 = h->fw_c0; rw1.out_c1 = h->fw_c1; rw0.in_c0 = h->fw_c0; rw0.in_c1 = h->fw_c1;
+            rw1.out.col_lo = rw0.in.col_lo = h->fw_c0; rw1.out.col_hi = rw0.in.col_hi = h->fw_c1;
         }
         if (win) {
-            rw1.in_lo = h->fw_lo[ci]; rw1.in_hi = h->fw_hi[ci];
-            r4(h->fw_lo[ci - 1], h->fw_hi[ci - 1], res, &rw1.out_lo, &rw1.out_hi);
-            rw0.in_lo = rw1.out_lo; rw0.in_hi = rw1.out_hi;
-            if (ci - 2 >= 0 && h->fw_hi[ci - 2] > 0) { rw0.out_lo = h->fw_lo[ci - 2]; rw0.out_hi = h->fw_hi[ci - 2]; }
+            rw1.in.row_lo = h->fw_lo[ci]; rw1.in.row_hi = h->fw_hi[ci];
+            rw1.out.row_lo = h->fw_lo[ci - 1]; rw1.out.row_hi = h->fw_hi[ci - 1];
+            la_span_tiles(rw1.out.row_lo, rw1.out.row_hi, 4, res);
+            rw0.in.row_lo = rw1.out.row_lo; rw0.in.row_hi = rw1.out.row_hi;
+            if (ci - 2 >= 0 && h->fw_hi[ci - 2] > 0) { rw0.out.row_lo = h->fw_lo[ci - 2]; rw0.out.row_hi = h->fw_hi[ci - 2]; }
         }
         RgbLayer& T = h->rgb[k];
         ConvLayer& L1 = h->conv[ci];
@@ -514,15 +524,13 @@ extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hi
         if (!seam2_done) {
             memset(&s, 0, sizeof(s));
             s.y = L1.y; s.gx_next = gx_next; s.gz = h->G0; s.HW = HW; s.C = L1.cout;
-            s.demod = h->d_all + L1.d_off; s.demod_stride = h->Dt; s.bias = L1.bias;
-            s.noise = L1.noise_used; s.noise_bstride = L1.noise_bstride; s.noise_strength = L1.noise_strength;
-            s.act = LA_ACT_LRELU; s.alpha = 0.2f; s.gain = sqrtf(2.f); s.clamp = h->clamp;
+            la_seam_set_epi(s, layer_epi(h, L1));
             s.ddn_part = L1.ddnp;
             s.g_img = gi; s.rgb_pre = T.rgb_pre; s.rgb_clamp = h->clamp; s.wrgb = T.weight;
             s.s_rgb = h->s_all + T.s_off; s.s_stride = h->S; s.dweff_part = T.dwep;
             if (xs_hand) { s.xs_out = xs_slot(ci); s.xs_mult = 1.f; }      // the seam kernel lowers the slot row of the contraction that follows ...
             else if (f16) s.pmax_out = h->pmax;                              // ... or leaves the plane maxima of gz for it
-            if (win) { s.p_lo = (long)rw1.in_lo * res; s.p_hi = (long)rw1.in_hi * res; }
+            if (win) { s.p_lo = (long)rw1.in.row_lo * res; s.p_hi = (long)rw1.in.row_hi * res; }
             if ((rc = la_seam_backward(s, B, h->imgc, stream))) return rc;
         }
         {
@@ -539,17 +547,15 @@ extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hi
             LaSeamFuse sf; memset(&sf, 0, sizeof(sf));
             if (fuse_seam) {
                 const ConvLayer& L0f = h->conv[ci - 1];
-                sf.demod = h->d_all + L0f.d_off; sf.demod_stride = h->Dt; sf.bias = L0f.bias;
-                sf.noise = L0f.noise_used; sf.noise_bstride = L0f.noise_bstride; sf.noise_strength = L0f.noise_strength;
-                sf.act = LA_ACT_LRELU; sf.alpha = 0.2f; sf.gain = sqrtf(2.f); sf.clamp = h->clamp;
-                sf.ddn_part = h->conv[ci - 1].ddnp;
+                la_seam_set_epi(sf, layer_epi(h, L0f));
+                sf.ddn_part = L0f.ddnp;
                 sf.pmax = f16 ? h->pmax2 : nullptr;
                 if (xs_hand) { sf.xs_out = xs_slot(ci - 1); sf.xs_mult = up_mult; }
             }
-            if ((rc = la_modconv3x3_bwd_ex(h->G0, f16 ? (seam2_done ? h->pmax3 : h->pmax) : nullptr, nseg1, L1.wb, L1.wqb, h->precision, h->s_all + L1.s_off,
-                                           h->S, xin, xin_bs, h->G1, L1.dsp, h->cws, h->cws_bytes, B, L1.cin, L1.cout, res, stream,
-                                           fuse_seam ? &sf : nullptr, xs_slot(ci), win ? &rw1 : nullptr)))
-                return rc;
+            LaModconvBwdOpts o;
+            o.in_pmax = f16 ? (seam2_done ? h->pmax3 : h->pmax) : nullptr; o.in_nseg = nseg1;
+            o.seam = fuse_seam ? &sf : nullptr; o.xscale = xs_slot(ci); o.rows = win ? &rw1 : nullptr;
+            if ((rc = la_modconv3x3_bwd_ex(h->G0, layer_conv(h, L1, B, true), xin, xin_bs, h->G1, L1.dsp, stream, o))) return rc;
             fin_conv(L1, tiles1, nseg1);
         }
         --ci;
@@ -559,9 +565,7 @@ extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hi
         if (!fuse_seam) {
             memset(&s, 0, sizeof(s));
             s.y = L0.y; s.gx_next = h->G1; s.gz = h->G1; s.HW = HW; s.C = L0.cout;
-            s.demod = h->d_all + L0.d_off; s.demod_stride = h->Dt; s.bias = L0.bias;
-            s.noise = L0.noise_used; s.noise_bstride = L0.noise_bstride; s.noise_strength = L0.noise_strength;
-            s.act = LA_ACT_LRELU; s.alpha = 0.2f; s.gain = sqrtf(2.f); s.clamp = h->clamp;
+            la_seam_set_epi(s, layer_epi(h, L0));
             s.ddn_part = L0.ddnp;
             if (xs_hand) { s.xs_out = xs_slot(ci); s.xs_mult = up_mult; }
             else if (f16) s.pmax_out = h->pmax;      // plane maxima of gz: bound for the operand scale of the fused FIR-adjoint + split pass
@@ -571,9 +575,7 @@ extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hi
         // (before the up layer's backward contraction: its epilogue may apply the block below's ToRGB backward)
         RgbLayer& P = h->rgb[k - 1];
         if (!pyramid_done) {
-            if ((rc = la_upfirdn2d_ex(gi, P.g_img, B, h->imgc, res, res, h->fir, 4, 4, 1, 1, 2, 2, 1, 1, 1, 1, 1, 4.f, nullptr,
-                                      stream)))
-                return rc;
+            if ((rc = la_upfirdn2d_ex(gi, P.g_img, B, h->imgc, res, res, h->fir, la_fir_down2_adjoint(), stream))) return rc;
             // every level below in ONE launch (la_image_grad_pyramid: the levels depend on the image gradient only), from <= 256^2 inputs
             if (k >= 2 && res / 2 <= 256) {
                 float* outs[MAX_BLOCKS];
@@ -591,18 +593,18 @@ extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hi
             if (fuse_seam2) {
                 // the conv1 seam of the block BELOW (its saved output is this contraction's xin), incl. its ToRGB backward
                 const ConvLayer& Lb = h->conv[ci - 1];
-                sf2.demod = h->d_all + Lb.d_off; sf2.demod_stride = h->Dt; sf2.bias = Lb.bias;
-                sf2.noise = Lb.noise_used; sf2.noise_bstride = Lb.noise_bstride; sf2.noise_strength = Lb.noise_strength;
-                sf2.act = LA_ACT_LRELU; sf2.alpha = 0.2f; sf2.gain = sqrtf(2.f); sf2.clamp = h->clamp;
+                la_seam_set_epi(sf2, layer_epi(h, Lb));
                 sf2.ddn_part = Lb.ddnp;
                 sf2.pmax = f16 ? h->pmax3 : nullptr;
                 if (xs_hand) { sf2.xs_out = xs_slot(ci - 1); sf2.xs_mult = 1.f; }
                 sf2.imgc = h->imgc; sf2.g_img = P.g_img; sf2.rgb_pre = P.rgb_pre; sf2.rgb_clamp = h->clamp;
                 sf2.wrgb = P.weight; sf2.s_rgb = h->s_all + P.s_off; sf2.s_rgb_stride = h->S; sf2.dweff_part = P.dwep;
             }
-            if ((rc = la_modconv3x3_up2_bwd_ex(h->G1, f16 ? (fuse_seam ? h->pmax2 : h->pmax) : nullptr, nseg0, L0.wb, L0.wqb, h->precision, h->s_all + L0.s_off, h->S,
-                                               h->conv[ci - 1].y, (long)L0.cin * hin * hin, h->fir, h->zT, h->G0, L0.dsp, h->cws, h->cws_bytes, B,
-                                               L0.cin, L0.cout, res, stream, fuse_seam2 ? &sf2 : nullptr, xs_slot(ci), win ? &rw0 : nullptr)))
+            LaModconvBwdOpts o;
+            o.in_pmax = f16 ? (fuse_seam ? h->pmax2 : h->pmax) : nullptr; o.in_nseg = nseg0;
+            o.seam = fuse_seam2 ? &sf2 : nullptr; o.xscale = xs_slot(ci); o.rows = win ? &rw0 : nullptr;
+            if ((rc = la_modconv3x3_up2_bwd_ex(h->G1, layer_conv(h, L0, B, true), h->conv[ci - 1].y, (long)L0.cin * hin * hin, h->fir, h->zT, h->G0, L0.dsp,
+                                               stream, o)))
                 return rc;
             fin_conv(L0, tiles, nseg0);
         }

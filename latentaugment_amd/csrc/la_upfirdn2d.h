@@ -1,6 +1,7 @@
 // Internal (C++) entry points of the FIR resampling kernels; the public C ABI is in include/latentaug_hip.h.
 #pragma once
 #include "la_common.h"
+#include "la_launch_args.h"
 
 // What every upfirdn2d entry (float16 / float32 / float64) derives from its arguments: the argument checks, the output size
 // (upfirdn2d.cpp:35-36) and the correlation taps in float32 -- up to 8 x 8, or one separable pass of up to 32 (1 x fw / fh x 1, the
@@ -13,8 +14,7 @@ struct LaFirSetup {
     int Hout, Wout;
     float f[LA_FIR_MAX * LA_FIR_MAX];
 };
-int la_fir_setup(LaFirSetup& s, const void* in, const void* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw,
-                 int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter, float gain);
+int la_fir_setup(LaFirSetup& s, const void* in, const void* out, int B, int C, int Hin, int Win, const float* f_host, const LaFirGeom& g);
 
 // The generic kernels' gather of output (x, y) of one input plane `ip` (storage T, sum in A): the contributing input rows are
 // iy * upy = y * dny + ta - pady0 with ta in [0, fh), columns likewise; taps in ascending row, then column order.
@@ -37,43 +37,44 @@ __device__ __forceinline__ A la_fir_gather(const Args& a, const T* ip, int x, in
     return v;
 }
 
-// generic op, optional same-shape addend (skip connection add fused into the store)
-// optional tail of the 4x4 kernels: activation backward of the layer whose saved output `yref` has the shape of `out` (stride-1 kernel:
-// out = fir(in) * act'(yref), bias_act.py:170 with grad = 1) and / or the fp16 operand scale of `out` for the contraction that consumes
-// it (slot rows [B][LA_XS_FAN], la_common.h; stride-1 and up-2 kernels)
+// The options of a FIR launch, all off by default:
+//   addend   same-shape tensor added to the result (skip connection add fused into the store); plain launches only
+//   pmax     [B*C][la_fir4x4_segments(Hout, Wout)]: partial max |out| of every plane, one per workgroup (4x4 stride-1 scalar kernel) -- lets
+//            the contraction that consumes `out` skip its own absmax pass (fp16 operand scale)
+//   yref ..  activation backward of the layer whose saved output `yref` has the shape of `out` (4x4 stride-1 kernels: out = fir(in) *
+//            act'(yref), bias_act.py:170 with grad = 1)
+//   xs_out / xs_mult  slot rows [B][LA_XS_FAN] of the fp16 operand scale of `out` for the contraction that consumes it (la_common.h),
+//            lowered by the producing workgroups to pow2(xs_mult[b] * max |out|), xs_mult null = 1 (4x4 stride-1 and up-2 kernels)
+//   in_pitch / in_plane  (floats, 0 = dense; 4x4 stride-1 only) padded row pitch / plane stride of `in` (multiples of 4 select the vector kernel)
+//   in_xhalf (> 0, needs in_pitch) column-planar rows -- even columns of the image at [0, ceil(Win/2)), odd columns from in_xhalf on
+//   win      (column-planar input only) only these output rows / 4-column groups are computed and written
 struct LaFirTail {
-    const float* yref; int act; float alpha, gain, clamp;
-    float* xs_out;
-    int in_pitch = 0; long in_plane = 0; int in_xhalf = 0;      // (4x4 stride-1 only) padded / column-planar input rows, as la_upfirdn2d_modconv_epilogue takes them
+    const float* yref = nullptr; int act = LA_ACT_LINEAR; float alpha = 0.f, gain = 1.f, clamp = -1.f;
+    float* xs_out = nullptr; const float* xs_mult = nullptr;
+    int in_pitch = 0; long in_plane = 0; int in_xhalf = 0;
+    const float* addend = nullptr;
+    float* pmax = nullptr;
+    LaWindow win = {};
 };
-int la_upfirdn2d_ex(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw,
-                    int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter,
-                    float gain, const float* addend, hipStream_t stream, float* pmax = nullptr, const LaFirTail* tail = nullptr);
-// pmax (optional, [B*C][la_fir4x4_segments(Hout, Wout)]): partial max |out| of every plane, one per workgroup -- lets the
-// contraction that consumes `out` skip its own absmax pass (fp16 operand scale).
+int la_upfirdn2d_ex(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, const LaFirGeom& g, hipStream_t stream,
+                    const LaFirTail& opts = LaFirTail());
 int la_fir4x4_segments(int Hout, int Wout);
 
 // FIR (up=down=1) followed by the modulated-conv epilogue: *demod[b][c] + noise*strength + bias[c] -> act -> clamp.
-// Used after the transposed stride-2 conv of an up-sampling SynthesisLayer (conv2d_resample.py:126).
-int la_upfirdn2d_modconv_epilogue(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host,
-                                  int fh, int fw, int padx0, int padx1, int pady0, int pady1, float fir_gain,
-                                  const float* demod, int demod_stride, const float* noise, long noise_bstride,
-                                  float noise_strength, const float* bias, int act, float alpha, float gain,
-                                  float clamp, hipStream_t stream, float* pmax = nullptr, int in_pitch = 0, long in_plane = 0, int in_xhalf = 0,
-                                  float* xs_out = nullptr, const float* xs_mult = nullptr, int row_lo = 0, int row_hi = 0, int col_lo = 0, int col_hi = 0);
-// row_lo / row_hi (column-planar input only; 0 / 0 = all): only output rows [row_lo, row_hi) are computed and written
-// xs_out / xs_mult (optional): slot rows [B][LA_XS_FAN] of the fp16 operand scale of `out` for the contraction that consumes it
-// (la_common.h): lowered by the producing workgroups to pow2(xs_mult[b] * max |out|)
-// in_pitch / in_plane (floats, 0 = dense): padded row pitch / plane stride of `in` (multiples of 4 select the vector kernel)
-// in_xhalf (> 0, needs in_pitch): column-planar rows -- even columns of the image at [0, ceil(Win/2)), odd columns from in_xhalf on
+// Used after the transposed stride-2 conv of an up-sampling SynthesisLayer (conv2d_resample.py:126).  opts: pmax, xs_out / xs_mult, the
+// input layout and the window (yref and addend do not apply).
+int la_upfirdn2d_modconv_epilogue(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, const LaFirGeom& g,
+                                  const LaLayerEpi& epi, hipStream_t stream, const LaFirTail& opts = LaFirTail());
 
 // FIR adjoint of an up-sampling layer written straight into the stride-2 backward contraction's operand format (fp16 mode):
 // q [B][ceil(C/32)][(H+1)*(W+1)][32 channels] = {h | l << 16} of xscale[b] * adjoint(in); see la_upfirdn2d.hip
-int la_fir4x4_adjoint_pack_f16(const float* in, unsigned* q, const float* xscale, int xs_fan, int B, int C, int H, int W, const float* f_host,
-                               float gain, hipStream_t stream, int flip_taps = 0, int in_lo = 0, int in_hi = 0, int out_lo = 0, int out_hi = 0, int in_c0 = 0, int in_c1 = 0);
-// in_lo / in_hi: valid rows of `in` (the others read as zeros); out_lo / out_hi: row window of the (H+1)-row output (0 / 0 = all)
+// in_win: valid rows / columns of `in` (the others read as zeros); out_win: row window of the (H+1)-row output (its columns are not used)
 // flip_taps = 1: the forward 4x4 FIR with pad 2 (same geometry: (H+1) x (W+1) outputs) instead of the adjoint of the pad-1 FIR
+int la_fir4x4_adjoint_pack_f16(const float* in, unsigned* q, const float* xscale, int xs_fan, int B, int C, int H, int W, const float* f_host,
+                               float gain, hipStream_t stream, int flip_taps = 0, const LaWindow& in_win = LaWindow{},
+                               const LaWindow& out_win = LaWindow{});
 
 // The image-gradient pyramid of a synthesis backward pass in one launch: outs[l] [planes][R0 >> (l+1)]^2 = adjoint of upsample2d applied l + 1
-// times to g_top [planes][R0]^2 (per level exactly la_upfirdn2d_ex(.., down 2, pad (1,1,1,1), flip, gain 4)); R0 <= 256.
+// times to g_top [planes][R0]^2 (per level exactly la_upfirdn2d_ex(.., la_fir_down2_adjoint())); R0 <= 256: the kernel keeps two levels in LDS,
+// ((R0/2)^2 + (R0/4)^2) * 4 bytes = 80 KB at R0 = 256, and raises its dynamic-LDS limit to 96 KB for that.
 int la_image_grad_pyramid(const float* g_top, float* const* outs, int nlev, int planes, int R0, const float* f_host, hipStream_t stream);

@@ -142,34 +142,32 @@ __global__ __launch_bounds__(256) void la_fir4x4_s1_kernel(FirArgs a) {
     }
 }
 
-int la_fir_setup(LaFirSetup& s, const void* in, const void* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw,
-                 int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter, float gain) {
+int la_fir_setup(LaFirSetup& s, const void* in, const void* out, int B, int C, int Hin, int Win, const float* f_host, const LaFirGeom& g) {
+    const int fh = g.fh, fw = g.fw, upx = g.upx, upy = g.upy, dnx = g.dnx, dny = g.dny;
     LA_CHECK_ARG(in && out && f_host, "upfirdn2d: null pointer");
     LA_CHECK_ARG(fh >= 1 && fw >= 1 && fh * fw <= LA_FIR_MAX * LA_FIR_MAX && fh <= 32 && fw <= 32, "upfirdn2d: filter larger than 8x8 (or than 32 taps in one separable pass)");
     LA_CHECK_ARG(upx >= 1 && upy >= 1 && dnx >= 1 && dny >= 1, "upfirdn2d: bad up/down factor");
     LA_CHECK_ARG(B >= 1 && C >= 1 && Hin >= 1 && Win >= 1, "upfirdn2d: empty input");
-    const int upW = Win * upx + padx0 + padx1, upH = Hin * upy + pady0 + pady1;
+    const int upW = Win * upx + g.padx0 + g.padx1, upH = Hin * upy + g.pady0 + g.pady1;
     LA_CHECK_ARG(upW >= fw && upH >= fh, "upfirdn2d: upsampled image smaller than the filter");
     s.Wout = (upW - fw + dnx) / dnx;
     s.Hout = (upH - fh + dny) / dny;
     for (int i = 0; i < fh; ++i)
         for (int j = 0; j < fw; ++j)
-            s.f[i * fw + j] = gain * (flip_filter ? f_host[i * fw + j] : f_host[(fh - 1 - i) * fw + (fw - 1 - j)]);
+            s.f[i * fw + j] = g.gain * (g.flip_filter ? f_host[i * fw + j] : f_host[(fh - 1 - i) * fw + (fw - 1 - j)]);
     return LA_OK;
 }
 
-static int fir_fill(FirArgs& a, const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host,
-                    int fh, int fw, int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1,
-                    int flip_filter, float gain) {
+static int fir_fill(FirArgs& a, const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, const LaFirGeom& g) {
     LaFirSetup s;
-    const int rc = la_fir_setup(s, in, out, B, C, Hin, Win, f_host, fh, fw, upx, upy, dnx, dny, padx0, padx1, pady0, pady1, flip_filter, gain);
+    const int rc = la_fir_setup(s, in, out, B, C, Hin, Win, f_host, g);
     if (rc) return rc;
     a.in = in; a.out = out; a.P = B * C; a.C = C; a.pmax = nullptr; a.xs_out = nullptr; a.xs_mult = nullptr; a.row_lo = a.row_hi = 0; a.col_lo = a.col_hi = 0;
     a.in_pitch = Win; a.in_plane = (long)Hin * Win; a.in_xhalf = 0;
     a.Hin = Hin; a.Win = Win; a.Hout = s.Hout; a.Wout = s.Wout;
-    a.upx = upx; a.upy = upy; a.dnx = dnx; a.dny = dny; a.padx0 = padx0; a.pady0 = pady0;
-    a.fw = fw; a.fh = fh;
-    for (int k = 0; k < fh * fw; ++k) a.f[k] = s.f[k];
+    a.upx = g.upx; a.upy = g.upy; a.dnx = g.dnx; a.dny = g.dny; a.padx0 = g.padx0; a.pady0 = g.pady0;
+    a.fw = g.fw; a.fh = g.fh;
+    for (int k = 0; k < g.fh * g.fw; ++k) a.f[k] = s.f[k];
     a.epi = 0; a.demod = nullptr; a.noise = nullptr; a.bias = nullptr; a.addend = nullptr; a.yref = nullptr;
     a.demod_stride = 0; a.noise_bstride = 0; a.noise_strength = 0.f;
     a.act = LA_ACT_LINEAR; a.alpha = 0.f; a.gain = 1.f; a.clamp = -1.f;
@@ -495,11 +493,12 @@ __global__ __launch_bounds__(1024) void la_imgrad_pyramid_kernel(PyrArgs a) {
     }
 }
 
-// outs[l] = gradient planes at resolution R0 >> (l + 1), l = 0 .. nlev-1; needs (R0/2)^2 * 4 <= 64 KB (R0 <= 256)
+// outs[l] = gradient planes at resolution R0 >> (l + 1), l = 0 .. nlev-1; LDS = two levels, ((R0/2)^2 + (R0/4)^2) * 4 bytes: 80 KB at
+// R0 = 256 (the limit), above the 64 KB default -- hence the 96 KB attribute below
 int la_image_grad_pyramid(const float* g_top, float* const* outs, int nlev, int planes, int R0, const float* f_host, hipStream_t stream) {
     LA_CHECK_ARG(g_top && outs && nlev >= 1 && nlev <= 12 && planes >= 1 && R0 >= 2 && R0 <= 256 && (R0 >> nlev) >= 1, "image_grad_pyramid: bad arguments");
     FirArgs fa;
-    int rc = fir_fill(fa, g_top, outs[0], planes, 1, R0, R0, f_host, 4, 4, 1, 1, 2, 2, 1, 1, 1, 1, 1, 4.f);      // (the taps as the per-level launches build them)
+    int rc = fir_fill(fa, g_top, outs[0], planes, 1, R0, R0, f_host, la_fir_down2_adjoint());      // (the taps as the per-level launches build them)
     if (rc) return rc;
     PyrArgs a;
     a.top = g_top; a.nlev = nlev; a.R0 = R0;
@@ -598,48 +597,42 @@ static int fir_launch_inner(const FirArgs& a, hipStream_t stream) {
     return LA_OK;
 }
 
-int la_upfirdn2d_ex(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, int fh, int fw,
-                    int upx, int upy, int dnx, int dny, int padx0, int padx1, int pady0, int pady1, int flip_filter,
-                    float gain, const float* addend, hipStream_t stream, float* pmax, const LaFirTail* tail) {
+int la_upfirdn2d_ex(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, const LaFirGeom& g, hipStream_t stream,
+                    const LaFirTail& o) {
     FirArgs a;
-    int rc = fir_fill(a, in, out, B, C, Hin, Win, f_host, fh, fw, upx, upy, dnx, dny, padx0, padx1, pady0, pady1,
-                      flip_filter, gain);
+    int rc = fir_fill(a, in, out, B, C, Hin, Win, f_host, g);
     if (rc) return rc;
-    a.addend = addend;
-    if (tail) {
-        const bool s1 = upx == 1 && upy == 1 && dnx == 1 && dny == 1 && fw == 4 && fh == 4;
-        const bool up2 = upx == 2 && upy == 2 && dnx == 1 && dny == 1 && fw == 4 && fh == 4 && padx0 == 2 && pady0 == 2;
-        LA_CHECK_ARG(!tail->yref || (s1 && !addend), "upfirdn2d: the fused activation backward exists for the 4x4 stride-1 kernel");
-        LA_CHECK_ARG(!tail->xs_out || s1 || up2, "upfirdn2d: the operand-scale hand-over exists for the 4x4 stride-1 and up-2 kernels");
-        if (tail->yref) { a.epi = 2; a.yref = tail->yref; a.act = tail->act; a.alpha = tail->alpha; a.gain = tail->gain; a.clamp = tail->clamp; }
-        a.xs_out = tail->xs_out; a.xs_mult = nullptr;
-        if (tail->in_pitch > 0) {      // padded / column-planar input rows (the transposed conv's intermediate): the planar vector kernel
-            LA_CHECK_ARG(s1, "upfirdn2d: a padded input layout needs the 4x4 stride-1 kernel");
-            a.in_pitch = tail->in_pitch; a.in_plane = tail->in_plane; a.in_xhalf = tail->in_xhalf;
-        }
+    a.addend = o.addend;
+    const bool s1 = g.upx == 1 && g.upy == 1 && g.dnx == 1 && g.dny == 1 && g.fw == 4 && g.fh == 4;
+    const bool up2 = g.upx == 2 && g.upy == 2 && g.dnx == 1 && g.dny == 1 && g.fw == 4 && g.fh == 4 && g.padx0 == 2 && g.pady0 == 2;
+    LA_CHECK_ARG(!o.yref || (s1 && !o.addend), "upfirdn2d: the fused activation backward exists for the 4x4 stride-1 kernel");
+    LA_CHECK_ARG(!o.xs_out || s1 || up2, "upfirdn2d: the operand-scale hand-over exists for the 4x4 stride-1 and up-2 kernels");
+    if (o.yref) { a.epi = 2; a.yref = o.yref; a.act = o.act; a.alpha = o.alpha; a.gain = o.gain; a.clamp = o.clamp; }
+    a.xs_out = o.xs_out; a.xs_mult = o.xs_mult;
+    if (o.in_pitch > 0) {      // padded / column-planar input rows (the transposed conv's intermediate): the planar vector kernel
+        LA_CHECK_ARG(s1, "upfirdn2d: a padded input layout needs the 4x4 stride-1 kernel");
+        a.in_pitch = o.in_pitch; a.in_plane = o.in_plane; a.in_xhalf = o.in_xhalf;
     }
-    if (pmax && upx == 1 && upy == 1 && dnx == 1 && dny == 1 && fw == 4 && fh == 4) a.pmax = pmax;
-    else LA_CHECK_ARG(!pmax, "upfirdn2d: plane maxima are produced by the 4x4 stride-1 kernel only");
+    LA_CHECK_ARG(!o.pmax || s1, "upfirdn2d: plane maxima are produced by the 4x4 stride-1 kernel only");
+    a.pmax = o.pmax;
     return fir_launch(a, stream);
 }
 
-int la_upfirdn2d_modconv_epilogue(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host,
-                                  int fh, int fw, int padx0, int padx1, int pady0, int pady1, float fir_gain,
-                                  const float* demod, int demod_stride, const float* noise, long noise_bstride,
-                                  float noise_strength, const float* bias, int act, float alpha, float gain,
-                                  float clamp, hipStream_t stream, float* pmax, int in_pitch, long in_plane, int in_xhalf, float* xs_out,
-                                  const float* xs_mult, int row_lo, int row_hi, int col_lo, int col_hi) {
+int la_upfirdn2d_modconv_epilogue(const float* in, float* out, int B, int C, int Hin, int Win, const float* f_host, const LaFirGeom& g,
+                                  const LaLayerEpi& e, hipStream_t stream, const LaFirTail& o) {
+    LA_CHECK_ARG(g.upx == 1 && g.upy == 1 && g.dnx == 1 && g.dny == 1 && !g.flip_filter, "upfirdn2d: the modconv epilogue follows a plain stride-1 FIR");
     FirArgs a;
-    int rc = fir_fill(a, in, out, B, C, Hin, Win, f_host, fh, fw, 1, 1, 1, 1, padx0, padx1, pady0, pady1, 0, fir_gain);
+    int rc = fir_fill(a, in, out, B, C, Hin, Win, f_host, g);
     if (rc) return rc;
-    a.epi = 1; a.demod = demod; a.demod_stride = demod_stride; a.noise = noise; a.noise_bstride = noise_bstride;
-    a.noise_strength = noise_strength; a.bias = bias; a.act = act; a.alpha = alpha; a.gain = gain; a.clamp = clamp;
-    if (fw == 4 && fh == 4) a.pmax = pmax;
-    else LA_CHECK_ARG(!pmax, "upfirdn2d: plane maxima are produced by the 4x4 stride-1 kernel only");
-    if (in_pitch > 0) { a.in_pitch = in_pitch; a.in_plane = in_plane; a.in_xhalf = in_xhalf; }
-    LA_CHECK_ARG(!xs_out || (fw == 4 && fh == 4), "upfirdn2d: the operand-scale hand-over exists for the 4x4 stride-1 kernels only");
-    a.xs_out = xs_out; a.xs_mult = xs_mult;
-    if (in_xhalf > 0) { a.row_lo = row_lo; a.row_hi = row_hi; a.col_lo = col_lo; a.col_hi = col_hi; }      // (the planar vector kernel honours the window; the others compute everything)
+    const bool f4 = g.fw == 4 && g.fh == 4;
+    a.epi = 1; a.demod = e.demod; a.demod_stride = e.demod_stride; a.noise = e.noise; a.noise_bstride = e.noise_bstride;
+    a.noise_strength = e.noise_strength; a.bias = e.bias; a.act = e.act; a.alpha = e.alpha; a.gain = e.gain; a.clamp = e.clamp;
+    LA_CHECK_ARG(!o.pmax || f4, "upfirdn2d: plane maxima are produced by the 4x4 stride-1 kernel only");
+    a.pmax = o.pmax;
+    if (o.in_pitch > 0) { a.in_pitch = o.in_pitch; a.in_plane = o.in_plane; a.in_xhalf = o.in_xhalf; }
+    LA_CHECK_ARG(!o.xs_out || f4, "upfirdn2d: the operand-scale hand-over exists for the 4x4 stride-1 kernels only");
+    a.xs_out = o.xs_out; a.xs_mult = o.xs_mult;
+    if (o.in_xhalf > 0) { a.row_lo = o.win.row_lo; a.row_hi = o.win.row_hi; a.col_lo = o.win.col_lo; a.col_hi = o.win.col_hi; }      // (the planar vector kernel honours the window; the others compute everything)
     return fir_launch(a, stream);
 }
 
@@ -762,12 +755,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void l
 
 // in [B][C][H][W] -> q [B][ceil(C/32)][(H+1)*(W+1)][32] packed fp16 pairs of  xscale[b] * (FIR adjoint of `in`)
 int la_fir4x4_adjoint_pack_f16(const float* in, unsigned* q, const float* xscale, int xs_fan, int B, int C, int H, int W, const float* f_host,
-                               float gain, hipStream_t stream, int flip_taps, int in_lo, int in_hi, int out_lo, int out_hi, int in_c0, int in_c1) {
+                               float gain, hipStream_t stream, int flip_taps, const LaWindow& in_win, const LaWindow& out_win) {
+    const int in_c0 = in_win.col_lo, in_c1 = in_win.col_hi, out_lo = out_win.row_lo, out_hi = out_win.row_hi;
     LA_CHECK_ARG(in && q && xscale && f_host, "fir_adjoint_pack: null pointer");
     LA_CHECK_ARG(W % 4 == 0 && (((size_t)in | (size_t)q) & 15) == 0, "fir_adjoint_pack: rows must be 16-byte aligned");
     FirPackArgs a;
     a.in = in; a.out = q; a.xscale = xscale; a.xs_fan = xs_fan; a.B = B; a.C = C; a.H = H; a.W = W; a.Hz = H + 1; a.Wz = W + 1; a.nck = la_cdiv(C, 32);
-    a.in_lo = in_lo; a.in_hi = in_hi; a.out_lo = out_lo; a.out_hi = out_hi; a.in_c0 = in_c0; a.in_c1 = in_c1;
+    a.in_lo = in_win.row_lo; a.in_hi = in_win.row_hi; a.out_lo = out_lo; a.out_hi = out_hi; a.in_c0 = in_c0; a.in_c1 = in_c1;
     LA_CHECK_ARG(in_c0 % 4 == 0 && in_c1 % 4 == 0, "fir_adjoint_pack: the column mask is in groups of 4");
     a.pad = 2;         // adjoint of pad (1,1,1,1): fw - 1 - pad = 2 per side (upfirdn2d.py:255-266)
     // adjoint = correlation with the flipped filter = flip_filter of the forward op negated; the forward (flip_filter = False)
@@ -792,6 +786,5 @@ extern "C" int la_upfirdn2d_out_size(int in_size, int up, int down, int pad0, in
 extern "C" int la_upfirdn2d_f32(const float* x, const float* f_host, float* y, int N, int C, int H, int W, int fh,
                                 int fw, int upx, int upy, int downx, int downy, int padx0, int padx1, int pady0,
                                 int pady1, int flip, float gain, hipStream_t stream) {
-    return la_upfirdn2d_ex(x, y, N, C, H, W, f_host, fh, fw, upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip,
-                           gain, nullptr, stream);
+    return la_upfirdn2d_ex(x, y, N, C, H, W, f_host, LaFirGeom{fh, fw, upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, gain}, stream);
 }
