@@ -378,7 +378,9 @@ const float* la_disc_logits(const la_disc* h);
  * calc_loss_lpips_torchscript (util_latent_aug.py:387-409).  The network is described by the caller as a list of ops
  * (VGG16 = 13 x conv3x3+ReLU, 4 x max-pool, 5 taps); a tap emits f * rsqrt(sum_c f^2 + 1e-10) * sqrt(lin[c]) / sqrt(H*W),
  * so squared L2 between two outputs is their LPIPS distance.  params: per op in order -- conv: weight [cout][cin][3][3],
- * bias [cout]; tap: lin [C]; pools: none.  la_crop_repeat_f32: the crop + `.repeat([1,3,1,1])` of :394 for every modality
+ * bias [cout]; tap: lin [C]; pools: none.  Every conv needs cout % 4 == 0, and cin % 4 == 0 unless it is the first op of
+ * the list; a pool needs an even resolution; the list must hold a tap.  A list that breaks one of these is refused by
+ * la_feat_workspace_bytes (0) and la_feat_create (LA_ERR_ARG), before any launch.  la_crop_repeat_f32: the crop + `.repeat([1,3,1,1])` of :394 for every modality
  * (rows ordered modality-major: row = c*B + b) with an affine preprocess; la_crop_repeat_grad_f32: its adjoint, ADDED to
  * g_img.
  * ------------------------------------------------------------------------------------------------------------- */

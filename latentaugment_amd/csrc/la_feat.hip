@@ -60,6 +60,8 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
         switch (o.kind) {
             case LA_FEAT_CONV_RELU:
                 LA_CHECK_ARG(ops[k].cin == c && ops[k].cout >= 4 && ops[k].cout % 4 == 0, "feat: conv channels mismatch / not a multiple of 4");
+                // (the backward pads the gradient of a conv's input to a multiple of 4 channels and copies the real ones out: only into gx)
+                LA_CHECK_ARG(c % 4 == 0 || k == 0, "feat: only the first conv may have cin % 4 != 0");
                 o.cout = ops[k].cout; o.res_out = r; c = o.cout; break;
             case LA_FEAT_MAXPOOL2: case LA_FEAT_AVGPOOL2:
                 LA_CHECK_ARG(r % 2 == 0, "feat: pooling needs an even resolution");
@@ -445,7 +447,6 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
                                         hipMemcpyDeviceToDevice, stream));
             }
             float* t = g; g = other; other = t;
-            if (o.mb_ != o.cin && k != 0) { la_set_error("feat_backward: only the first conv may have cin % 4 != 0"); return LA_ERR_ARG; }
         } else {
             LA_CHECK_ARG(have, "feat_backward: the op list must end with a tap");
             const long planes = (long)N * o.cout;

@@ -299,11 +299,16 @@ class Discriminator(nn.Module):
     """D(img, c=None) -> logits [N,1]  (call: util_latent_aug.py:367)."""
 
     def __init__(self, img_resolution=256, img_channels=2, channel_base=32768, channel_max=512, conv_clamp=256,
-                 mbstd_group_size=4):
+                 mbstd_group_size=4, channels=None):
+        """channels: optional explicit table {resolution: channels} for 4, 8, ..., img_resolution (test shapes the
+        channel_base / channel_max rule cannot produce); None: the rule."""
         super().__init__()
         self.img_resolution, self.img_channels = img_resolution, img_channels
         self.block_resolutions = [2 ** i for i in range(int(math.log2(img_resolution)), 2, -1)]
         ch = channels_dict(img_resolution, channel_base, channel_max)
+        if channels is not None:
+            assert sorted(channels) == sorted(ch), 'the channel table needs one entry per resolution 4..img_resolution'
+            ch = {int(r): int(c) for r, c in channels.items()}
         for res in self.block_resolutions:
             first = res == img_resolution
             setattr(self, f'b{res}', DiscriminatorBlock(0 if first else ch[res], ch[res], ch[res // 2], res,
@@ -340,11 +345,12 @@ def make_generator(img_resolution=256, img_channels=2, channel_base=32768, chann
 
 
 def make_discriminator(img_resolution=256, img_channels=2, channel_base=32768, channel_max=512, seed=0,
-                       conv_clamp=256):
+                       conv_clamp=256, mbstd_group_size=4, channels=None):
     state = torch.random.get_rng_state()
     torch.manual_seed(seed + 1000)
     try:
-        D = Discriminator(img_resolution, img_channels, channel_base, channel_max, conv_clamp)
+        D = Discriminator(img_resolution, img_channels, channel_base, channel_max, conv_clamp,
+                          mbstd_group_size=mbstd_group_size, channels=channels)
     finally:
         torch.random.set_rng_state(state)
     return D.eval().requires_grad_(False)
