@@ -287,6 +287,41 @@ int la_adam_step_f32(float* p, const float* g, float* m, float* v, long n, int s
 int la_noise_normal_f32(float* out, long rows, long row_elems, unsigned long long seed, unsigned layer, long row0, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * GeometricAugment (augments/geometric_aug.py): flip, affine and elastic warps of a float32 [B][C][H][W] batch.  x is the column index,
+ * y the row index, pixel centres sit at integer coordinates.  S(img, px, py, mode) is bilinear sampling at pixel position (px, py),
+ * per axis: a position that is not finite or beyond 2^23 in magnitude is refused in floating point (the output element is 0, nothing
+ * is addressed); mode 0 'zeros' = the rule of la_grid_sample_* applied to the position; 1 'border' = the position clipped to
+ * [0, size - 1]; 2 'reflection' = torch's for align_corners=False: reflected about -0.5 and size - 0.5 as often as needed, then
+ * clipped.  No atomics anywhere: bit-identical from run to run.  Every tensor of a call has at most INT_MAX elements, B at most 65535.
+ * ------------------------------------------------------------------------------------------------------------- */
+
+/* Uniform noise of the elastic field (geometric_aug.py:122, kornia's RandomElasticTransform draws torch.rand * 2 - 1): out
+ * [rows][row_elems]; element e of GLOBAL row row0 + r of `stream_id` is a pure function of (seed, stream_id, row0 + r, e) --
+ * Philox4x32-10 with the counter and key layout of la_noise_normal_f32 -- so a shard draws only its rows.  The value is
+ * (k + 0.5) * 2^-22 - 1 with k the top 23 bits of the word: exact in float32 and strictly inside (-1, 1). */
+int la_noise_uniform_f32(float* out, long rows, long row_elems, unsigned long long seed, unsigned stream_id, long row0, la_stream_t stream);
+
+/* Displacement field of the elastic warp (geometric_aug.py:122, kornia's elastic_transform2d): noise [B][2][H][W] -> disp [B][2][H][W],
+ * disp[b][p][y][x] = alpha_p * sum_i sum_j taps[i] taps[j] noise[b][p][y + i - r][x + j - r] with r = (ntaps - 1) / 2 and noise outside
+ * the image = 0; plane 0 (alpha_x) is the x displacement, plane 1 (alpha_y) the y displacement, in normalised units.  taps_host: ntaps
+ * floats in HOST memory, ntaps odd and at most 63, applied in ascending order.  One launch, the row pass kept in LDS: ws is not used and
+ * may be NULL.  noise and disp must not alias. */
+int la_elastic_field_f32(const float* noise, const float* taps_host, int ntaps, float alpha_x, float alpha_y, float* disp, float* ws, int B, int H,
+                         int W, la_stream_t stream);
+
+/* Flip and affine as one resampling (geometric_aug.py:112,117): y[b][c][oy][ox] = S(x[b][c], Minv[b] (ox, oy, 1), mode) with minv [B][6]
+ * float32 in device memory, the rows (m0 m1 m2), (m3 m4 m5) of the inverse map in pixel coordinates: px = m0 ox + m1 oy + m2,
+ * py = m3 ox + m4 oy + m5.  apply [B] bytes in device memory: a sample whose byte is 0 is copied bit for bit.  x and y must not alias. */
+int la_warp_affine_f32(const float* x, const float* minv, const unsigned char* apply, float* y, int B, int C, int H, int W, int mode,
+                       la_stream_t stream);
+
+/* The elastic resampling (geometric_aug.py:122): gx = clamp(-1 + 2 ox / (W - 1) + disp[b][0][oy][ox], -1, 1), gy likewise with H and plane 1
+ * (0 along a one-pixel axis), position ((g + 1) * size - 1) / 2, y[b][c][oy][ox] = S(x[b][c], px, py, mode).  A NaN displacement passes
+ * the clamp and is refused by S.  apply as above.  x and y must not alias. */
+int la_warp_elastic_f32(const float* x, const float* disp, const unsigned char* apply, float* y, int B, int C, int H, int W, int mode,
+                        la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Synthesis network engine: replaces  G.synthesis(ws, noise_mode=...)  (call sites util_latent_aug.py:227,488) and the
  * autograd backward to ws that loss.backward() (:275) runs through it.  Architecture 'skip', fp32
  * (models/stylegan3/legacy.py:122-144).
