@@ -228,14 +228,18 @@ int la_modconv3x3_fwd_f32(const float* x, long x_bstride, const float* wf, const
                           la_stream_t stream);
 
 /* up-sampling layer (conv0): x [B][cin][res/2][res/2] -> y [B][cout][res][res];
- * scratch: B*cout*(res+1)^2 floats (the transposed-conv intermediate of conv2d_resample.py:125). */
+ * scratch: B*cout*(res+1)^2 floats (the transposed-conv intermediate of conv2d_resample.py:125).
+ * All four entries: square images of any resolution >= 1 for the same-resolution calls, of any EVEN resolution >= 2 for the two
+ * up-sampling calls (an odd one is LA_ERR_ARG); cout (forward) / cin (backward), the row count of the contraction, must be a multiple of 4. */
 int la_modconv3x3_up2_fwd_f32(const float* x, long x_bstride, const float* wf, const void* wq, int precision, const float* s, int s_stride,
                               const float* d, int d_stride, const float* noise, long noise_bstride, float noise_strength,
                               const float* bias, int act, float alpha, float gain, float clamp, const float* fir_host,
                               float* scratch, float* y, void* ws, size_t ws_bytes, int B, int cin, int cout, int res, la_stream_t stream);
 
 /* backward-data + style-gradient partials.  gz [B][cout][res][res] = gradient w.r.t. the raw contraction (already
- * multiplied by d and by act').  gx = (W^T * gz) . s ;  ds_part[b][i][tile] = partial sums of sum_p (W^T*gz) . xin. */
+ * multiplied by d and by act').  gx = (W^T * gz) . s ;  ds_part[b][i][tile] = partial sums of sum_p (W^T*gz) . xin.
+ * ds_part [B][cin][la_modconv_ds_tiles(grid)] (grid = res, up-sampling call: res / 2) needs no initialisation: every kernel form writes
+ * every slot (the split-K finish pass puts the sum into tile 0 and zeros into the others). */
 int la_modconv3x3_bwd_f32(const float* gz, const float* wb, const void* wq, int precision, const float* s, int s_stride, const float* xin,
                           long xin_bstride, float* gx, float* ds_part, void* ws, size_t ws_bytes, int B, int cin, int cout, int res,
                           la_stream_t stream);
@@ -243,9 +247,12 @@ int la_modconv3x3_up2_bwd_f32(const float* gz, const float* wb, const void* wq, 
                               long xin_bstride, const float* fir_host, float* scratch, float* gx, float* ds_part, void* ws, size_t ws_bytes, int B,
                               int cin, int cout, int res, la_stream_t stream);
 int la_modconv_ds_tiles(int grid_res); /* leading dimension of ds_part for a backward over a grid_res^2 grid */
-/* ws (may be NULL for precision 0): scratch of la_modconv_workspace_bytes() bytes.  With it, layers of <= 34x34 split
+/* ws (may be NULL for precision 0): scratch of la_modconv_workspace_bytes() bytes, 16-byte aligned.  With it, layers of <= 34x34 split
  * their K loop over workgroups (deterministic slice sum) instead of serialising it on a few CUs; the split-bf16
- * precisions also park the pre-split copy of the launch input there. */
+ * precisions also park the pre-split copy of the launch input there.  Precisions 1-3 REQUIRE it wherever that copy is made -- every
+ * call except the same-resolution ones at res % 32 == 0, res >= 64 (precision 3 keeps its operand scales there even then) -- and take
+ * at most 64 samples per call: a NULL or too small ws, or B > 64, is LA_ERR_ARG.  A ws that holds the copy but not the slice partials
+ * is valid: the call then runs its direct kernels. */
 size_t la_modconv_workspace_bytes(int B, int cin, int cout, int res, int up);
 /* Contraction precision (the `precision` argument of the la_modconv3x3_* calls; `wq` = weights packed for it or NULL):
  *   0 LA_PREC_F32     exact fp32 MFMA (v_mfma_f32_32x32x2_f32)

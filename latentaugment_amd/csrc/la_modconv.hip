@@ -193,6 +193,7 @@ int la_modconv3x3_up2_bwd_ex(const float* gz, const LaModconv& m, const float* x
     void* ws = m.ws;
     size_t ws_bytes = m.ws_bytes;
     LA_CHECK_ARG(gz && m.w && gx && scratch && fir_host, "modconv_up2_bwd: null pointer");
+    LA_CHECK_ARG(res >= 2 && res % 2 == 0, "modconv_up2_bwd: output resolution must be even");
     LA_CHECK_ARG(!seam || (m.precision != LA_PREC_F32 && xin && seam->ddn_part && (seam->imgc == 0 || (seam->g_img && seam->wrgb && seam->s_rgb && seam->dweff_part))),
                  "modconv_up2_bwd: the fused seam needs a 16-bit contraction, xin and its output buffers");
     const int hin = res / 2;
