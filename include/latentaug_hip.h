@@ -551,6 +551,7 @@ int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const float* con
  *   la_pr_kth_f16           precision_recall.py:75-79: kth[i] = (nhood_size+1)-th smallest distance of row i.
  *   la_pr_member_f16        precision_recall.py:80-84: member[i] = any_j dist(i, j) <= radius[j].
  *   la_kid_poly3_f32        Kernel Inception Distance of two feature sets (described at its prototype below).
+ *   la_dc_count_f16         density and coverage of two feature sets (described at its prototype below).
  * ws: la_pr_workspace_floats(nr, nc) floats.  The [nr][nc] matrix is not materialised by the last two.
  * ------------------------------------------------------------------------------------------------------------- */
 int la_feature_moments_f64(const float* x, long n, int D, double* raw_mean, double* raw_cov, la_stream_t stream);
@@ -578,6 +579,28 @@ int la_pr_member_f16(const void* rows, long nr, const void* cols, long nc, int D
 size_t la_kid_workspace_bytes(long S, long mx, long my);
 int la_kid_poly3_f32(const float* x, long nx, const float* y, long ny, int D, const int* ix, const int* iy, long S, long mx, long my,
                      double* sums, double* mmd2, double* kid, void* ws, size_t ws_bytes, la_stream_t stream);
+
+/* Density and coverage (no reference counterpart; Naeem et al., "Reliable Fidelity and Diversity Metrics for Generative Models",
+ * ICML 2020, the `prdc` package).  Both use the balls of the REAL samples only.  With real features X [nr][D], generated features
+ * Y [ng][D] (float16, row-major, D % 16 == 0, D >= 16, 16-byte aligned, as the entries above), k = nhood_size,
+ * dist(a, b) = sqrt(max(|a|^2 + |b|^2 - 2 a.b, 1e-30)) with fp32 accumulation (the torch.cdist form of the entries above) and
+ * radius[i] = the (k+1)-th smallest distance from real i to all reals, its own zero included -- la_pr_kth_f16(real, real), kept in
+ * float32 (not rounded to float16: no reference keeps these radii in float16):
+ *   count[j]   = #{ i : dist(Y_j, X_i) <= radius[i] }      int32 [ng];     density  = sum_j count[j] / (k ng)
+ *   nearest[i] = min_j dist(Y_j, X_i)                       float32 [nr];   coverage = mean_i (nearest[i] <= radius[i])
+ * The comparison is <=, as the library's precision (precision_recall.py:83); prdc uses <.  They differ at exact ties only.
+ * la_dc_count_f16 makes one tiled pass over the ng x nr pairs (exact float16 products on v_mfma_f32_32x32x16_f16) for both outputs;
+ * the distance matrix is never written.  The grid is blocks of 128 generated rows x la_dc_col_splits(ng, nr) chunks of real
+ * columns (a host rule that brings the launch to about 512 workgroups; 0 for sizes the launch refuses).  Row counts stay in
+ * registers over a chunk; column minima are reduced in the wave and the workgroup first.  Chunks and row blocks are combined with
+ * integer atomics only (atomicAdd on count, atomicMin on the bit pattern of the positive distances): order-independent, two runs give
+ * the same bits.  count and nearest are initialised by a kernel on `stream` inside the entry, which can be captured in a graph.
+ * ws: la_dc_workspace_bytes(ng, nr) bytes (the squared norms of both sides; 0 for sizes the launch refuses).  A smaller ws_bytes
+ * is LA_ERR_WORKSPACE, checked with the other arguments before anything is launched. */
+size_t la_dc_workspace_bytes(long ng, long nr);
+int la_dc_col_splits(long ng, long nr);
+int la_dc_count_f16(const void* gen, long ng, const void* real, long nr, int D, const float* radius, int* count, float* nearest,
+                    void* ws, size_t ws_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Opt-in profiler for the contraction launches (HIP events on the launch stream).  No reference counterpart: the

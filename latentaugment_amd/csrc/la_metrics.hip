@@ -5,6 +5,8 @@
 //   la_pr_member_f16          metrics/precision_recall.py:80-84 is a probe inside any manifold point's radius
 //   la_cdist_f16              metrics/precision_recall.py:19-32 the distance matrix itself (torch.cdist)
 //   la_kid_poly3_f32          (no reference counterpart) Kernel Inception Distance: unbiased MMD^2, cubic polynomial kernel, per subset
+//   la_dc_count_f16           (no reference counterpart) density and coverage: per generated row the number of real balls that hold it,
+//                             per real sample the distance to its nearest generated row, one pass over the pair grid
 // Distances follow torch.cdist's GEMM form |a|^2 + |b|^2 - 2 a.b, clamped at 1e-30, square root.  The reference hands
 // cdist float16 features; their products are exact on the fp16 MFMA (v_mfma_f32_32x32x16_f16, fp32 accumulate), so the dot
 // products here are fp32 sums of exact terms.  The [rows, cols] matrix is never materialised for the radii / membership
@@ -471,6 +473,205 @@ extern "C" int la_kid_poly3_f32(const float* x, long nx, const float* y, long ny
     hipLaunchKernelGGL(la_kid_finish_kernel, dim3((unsigned)S), dim3(256), 0, stream, (const double*)a.part, a.nxx, a.nyy, a.tiles, mx, my,
                        sums, mmd2);
     hipLaunchKernelGGL(la_kid_mean_kernel, dim3(1), dim3(256), 0, stream, (const double*)mmd2, S, kid);
+    LA_CHECK_LAUNCH();
+    return LA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Density and coverage (Naeem et al., ICML 2020): one tiled pass over the ng x nr grid of (generated row j, real column i) pairs,
+//   count[j]   = #{ i : dist(Y_j, X_i) <= radius[i] }      (int32; density = sum_j count[j] / (k ng))
+//   nearest[i] = min_j dist(Y_j, X_i)                        (float32; covered[i] = nearest[i] <= radius[i])
+// with dist and the fragments exactly as la_pr_tile_kernel has them.  Only the real samples' balls are used: radius[i] is the
+// (k+1)-th smallest distance from real i to the reals (la_pr_kth_f16(real, real)), kept in float32.
+// Grid: x = blocks of 128 generated rows (4 waves x 32), y = column chunks of `chunk` (a multiple of 128) real columns; the number
+// of chunks is the host rule dc_col_splits.  A workgroup walks its chunk in steps of 128 columns, and each step's K range in chunks
+// of DC_KC = 64: the 128 x 64 tiles of both operands go through LDS (two buffers each, the next chunk's global loads in flight during
+// the MFMAs, one barrier per chunk, as la_kid_tile_kernel).  Eight lanes load 128 contiguous bytes of a row, so every cache line that
+// is touched is used whole, and the four waves share one copy of the column tile; rows of 64 + 8 halves (144 bytes) keep the 16-byte
+// fragment reads of 16 consecutive rows on distinct banks.  K past D is filled with zeros (an exact no-op in the accumulator).
+// Every accumulator is the same k-ordered chain as in la_pr_tile_kernel, so a distance has the same bits here and in la_pr_kth_f16.
+// Row side: every lane counts, for its 16 rows, the columns it sees (one per MFMA tile) in 16 integer registers over the whole chunk;
+// the 32 lanes of a half are summed once at the end and one lane adds the row's total into count[] with an integer atomicAdd.
+// Column side: per step of 128 columns a lane takes the minimum over its 16 rows, the two lane halves are combined by a shuffle, the
+// four waves through LDS (two buffers, one barrier per step), and 128 threads fold the workgroup's minimum into nearest[] with
+// atomicMin on the bit pattern (the distances are positive floats, whose order is the order of their bits as unsigned integers).
+// Integer adds and minima do not depend on their order: two runs give the same bits.
+// count[] and nearest[] are initialised by la_dc_init_kernel on the same stream.
+#define DC_TARGET_WG 512      // about two workgroups per CU of a 256-CU device
+#define DC_KC 64
+#define DC_LD (DC_KC + 8)
+
+__global__ __launch_bounds__(256) void la_dc_init_kernel(int* __restrict__ count, long ng, unsigned* __restrict__ nearest, long nr) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < ng) count[i] = 0;
+    if (i < nr) nearest[i] = 0x7f800000u;      // +inf
+}
+
+__global__ __launch_bounds__(256) void la_dc_tile_kernel(const _Float16* __restrict__ rows, const float* __restrict__ rown, long ng,
+                                                        const _Float16* __restrict__ cols, const float* __restrict__ coln, long nr,
+                                                        int D, long chunk, const float* __restrict__ radius, int* __restrict__ count,
+                                                        unsigned* __restrict__ nearest) {
+    __shared__ __attribute__((aligned(16))) _Float16 As[2][128][DC_LD];
+    __shared__ __attribute__((aligned(16))) _Float16 Bs[2][128][DC_LD];
+    __shared__ float smin[2][4][128];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const long b0 = (long)blockIdx.x * 128;                     // b0 < ng: the grid has no empty row block
+    const long r0 = b0 + wid * 32;                              // a wave past the end works on clamped rows and contributes nothing
+    const long cbeg = (long)blockIdx.y * chunk;
+    const long cend = cbeg + chunk < nr ? cbeg + chunk : nr;
+    // rows held by this lane: m(r) = (r&3) + 8*(r>>2) + 4*lh
+    float na[16];
+    int cnt[16];
+    unsigned rowok = 0u;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long m = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        na[r] = rown[m < ng ? m : ng - 1];
+        cnt[r] = 0;
+        if (m < ng) rowok |= 1u << r;
+    }
+    // loader roles: 8 threads per tile row (8 halves = 16 bytes each), tile rows tid / 8 + 32 p of both operands.  A row past the end
+    // of its matrix is clamped into it, so nothing is read out of bounds; what it yields is masked in the epilogue.
+    const int lrow = tid >> 3, lk = (tid & 7) * 8;
+    const _Float16 *pa[4], *pb[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const long m = b0 + p * 32 + lrow;
+        pa[p] = rows + (m < ng ? m : ng - 1) * D + lk;
+    }
+    f16x8 areg[4], breg[4];
+    auto prefetch = [&](int kc) {
+        const int k = kc * DC_KC;
+        const bool in = k + lk < D;                             // D % 16 == 0: the 8 halves are inside or outside together
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) areg[p][q] = breg[p][q] = (_Float16)0.f;
+            if (in) {
+                areg[p] = *reinterpret_cast<const f16x8*>(pa[p] + k);
+                breg[p] = *reinterpret_cast<const f16x8*>(pb[p] + k);
+            }
+        }
+    };
+    auto stage = [&](int b) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            *reinterpret_cast<f16x8*>(&As[b][p * 32 + lrow][lk]) = areg[p];
+            *reinterpret_cast<f16x8*>(&Bs[b][p * 32 + lrow][lk]) = breg[p];
+        }
+    };
+    const int nkc = (D + DC_KC - 1) / DC_KC;
+    int sbuf = 0;
+    for (long c0 = cbeg; c0 < cend; c0 += 128, sbuf ^= 1) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const long c = c0 + p * 32 + lrow;
+            pb[p] = cols + (c < nr ? c : nr - 1) * D + lk;
+        }
+        f32x16 acc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+        // every read of LDS buffer 0 by the previous step was followed by a barrier
+        prefetch(0);
+        stage(0);
+        __syncthreads();
+        for (int kc = 0; kc < nkc; ++kc) {
+            const int b = kc & 1;
+            if (kc + 1 < nkc) prefetch(kc + 1);
+#pragma unroll
+            for (int ks = 0; ks < DC_KC / 16; ++ks) {
+                const f16x8 af = *reinterpret_cast<const f16x8*>(&As[b][wid * 32 + l31][ks * 16 + lh * 8]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f16x8 bf = *reinterpret_cast<const f16x8*>(&Bs[b][j * 32 + l31][ks * 16 + lh * 8]);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[j], 0, 0, 0);
+                }
+            }
+            if (kc + 1 < nkc) stage(b ^ 1);      // last read in iteration kc - 1, before its barrier
+            __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long c = c0 + j * 32 + l31;
+            const bool cok = c < cend;
+            const float nb = coln[c < nr ? c : nr - 1];
+            const float rad = radius[c < nr ? c : nr - 1];
+            float cm = __builtin_huge_valf();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float d = sqrtf(fmaxf(na[r] + nb - 2.f * acc[j][r], 1e-30f));
+                const bool ok = cok && ((rowok >> r) & 1u);
+                if (ok && d <= rad) ++cnt[r];
+                cm = fminf(cm, ok ? d : __builtin_huge_valf());
+            }
+            cm = fminf(cm, __shfl_xor(cm, 32, 64));          // the other 16 rows of the same column
+            if (lh == 0) smin[sbuf][wid][j * 32 + l31] = cm;
+        }
+        // One barrier per step: buffer `sbuf` is next written two steps on, after the barriers of the step between, which its readers
+        // below reach only when they have read it.
+        __syncthreads();
+        if (tid < 128 && c0 + tid < cend) {
+            const float m = fminf(fminf(smin[sbuf][0][tid], smin[sbuf][1][tid]), fminf(smin[sbuf][2][tid], smin[sbuf][3][tid]));
+            atomicMin(nearest + c0 + tid, __float_as_uint(m));
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        int s = cnt[r];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);      // stays inside each 32-lane half
+        const long mrow = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (l31 == 0 && mrow < ng && s) atomicAdd(count + mrow, s);
+    }
+}
+
+// columns per chunk (a multiple of 128): enough chunks that row blocks x chunks reaches DC_TARGET_WG workgroups, never more chunks
+// than there are 128-column steps
+static inline long dc_chunk_cols(long ng, long nr) {
+    const long rb = (ng + 127) / 128, ct = (nr + 127) / 128;
+    long want = (DC_TARGET_WG + rb - 1) / rb;
+    if (want > ct) want = ct;
+    return (ct + want - 1) / want * 128;
+}
+
+// number of column chunks of the launch (0 for sizes it refuses)
+extern "C" int la_dc_col_splits(long ng, long nr) {
+    if (ng < 1 || nr < 1) return 0;
+    const long chunk = dc_chunk_cols(ng, nr);
+    return (int)((nr + chunk - 1) / chunk);
+}
+
+// the squared norms of both sides, fp32 (0 for sizes the launch refuses)
+extern "C" size_t la_dc_workspace_bytes(long ng, long nr) {
+    if (ng < 1 || nr < 1) return 0;
+    return ((size_t)ng + (size_t)nr) * sizeof(float);
+}
+
+extern "C" int la_dc_count_f16(const void* gen, long ng, const void* real, long nr, int D, const float* radius, int* count,
+                               float* nearest, void* ws, size_t ws_bytes, hipStream_t stream) {
+    LA_CHECK_ARG(gen && real && radius && count && nearest && ws, "dc: null pointer");
+    LA_CHECK_ARG(ng >= 1 && nr >= 1, "dc: both feature sets need at least one row");
+    LA_CHECK_ARG(D >= 16 && D % 16 == 0, "dc: the feature dimension must be a multiple of 16 (pad with zeros)");
+    LA_CHECK_ARG((((size_t)gen | (size_t)real) & 15) == 0, "dc: feature matrices must be 16-byte aligned");
+    LA_CHECK_ARG((((size_t)radius | (size_t)count | (size_t)nearest | (size_t)ws) & 3) == 0, "dc: radius, count, nearest and ws must be 4-byte aligned");
+    const long chunk = dc_chunk_cols(ng, nr);
+    const long rb = (ng + 127) / 128, splits = (nr + chunk - 1) / chunk;
+    LA_CHECK_ARG(rb <= 0x7fffffffL && splits <= 65535, "dc: sizes exceed the grid");
+    if (ws_bytes < la_dc_workspace_bytes(ng, nr)) {
+        la_set_error("dc: workspace smaller than la_dc_workspace_bytes(ng, nr)");
+        return LA_ERR_WORKSPACE;
+    }
+    float* gn = (float*)ws;
+    float* rn = gn + ng;
+    const long nmax = ng > nr ? ng : nr;
+    hipLaunchKernelGGL(la_dc_init_kernel, dim3((unsigned)la_cdiv(nmax, 256)), dim3(256), 0, stream, count, ng, (unsigned*)nearest, nr);
+    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(ng, 4)), dim3(256), 0, stream, (const _Float16*)gen, ng, D, gn);
+    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nr, 4)), dim3(256), 0, stream, (const _Float16*)real, nr, D, rn);
+    hipLaunchKernelGGL(la_dc_tile_kernel, dim3((unsigned)rb, (unsigned)splits), dim3(256), 0, stream, (const _Float16*)gen, (const float*)gn,
+                       ng, (const _Float16*)real, (const float*)rn, nr, D, chunk, radius, count, (unsigned*)nearest);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }

@@ -7,6 +7,8 @@ detector features.
   compute_distances            metrics/precision_recall.py:19-32
   compute_pr_from_features     metrics/precision_recall.py:72-85
   compute_kid_from_features    (not in the reference) Kernel Inception Distance, the community's kid50k_full recipe
+  compute_dc_from_features     (not in the reference) density and coverage, Naeem et al., ICML 2020 (the `prdc` package)
+  compute_prdc_from_features   precision, recall, density and coverage in one dict
 
 The detectors themselves (Inception-v3 and VGG16 pickles hosted by NVIDIA, metric_utils.py:46-60) cannot be fetched offline:
 callers supply the features, e.g. from `synthesis.FeatureEngine` or from a detector they have on disk.
@@ -252,3 +254,59 @@ def compute_kid_from_features(real_features, gen_features, num_subsets=100, max_
     if return_details:
         return kid, dict(mmd2=out[S * 3:S * 4].copy(), sums=out[:S * 3].reshape(S, 3).copy(), ix=ix, iy=iy)
     return kid
+
+
+def compute_dc_from_features(real_features, gen_features, nhood_size=5, device='cuda:0', return_details=False):
+    """(density, coverage) of `gen_features` against `real_features` ([N, D] arrays or tensors, rounded to float16 as the precision /
+    recall path does): Naeem et al., "Reliable Fidelity and Diversity Metrics for Generative Models", ICML 2020.  Only the balls of the
+    real samples are used.  With r_i the (nhood_size + 1)-th smallest distance from real i to all reals, its own zero included
+    (la_pr_kth_f16(real, real), kept in float32 -- unlike compute_pr_from_features, whose radii pass through float16 as the
+    reference's do):
+        count[j] = #{ i : dist(gen_j, real_i) <= r_i },   density  = sum_j count[j] / (nhood_size * ng)   (the sum in integers)
+        nearest[i] = min_j dist(gen_j, real_i),           coverage = mean_i (nearest[i] <= r_i)
+    The comparison is <=, as in compute_pr_from_features (precision_recall.py:83); the `prdc` package uses <.  The two differ only
+    where a distance equals a radius exactly.  One pass over the pair grid (la_dc_count_f16) gives count and nearest; the distance
+    matrix is never built and two runs give the same bits.  nhood_size must lie in 1 .. min(7, nr - 1): the radii kernel keeps 8
+    candidates per row.  There is no CPU fallback.
+    return_details=True: (density, coverage, {'radii': float32 [nr], 'count': int32 [ng], 'nearest': float32 [nr], 'covered': bool [nr]})."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); got device ' + str(dev))
+    rshape, gshape = tuple(np.shape(real_features)), tuple(np.shape(gen_features))
+    if len(rshape) != 2 or len(gshape) != 2 or rshape[1] != gshape[1] or rshape[1] < 1 or rshape[0] < 1 or gshape[0] < 1:
+        raise ValueError(f'features must be two non-empty [N, D] arrays of one D: real {rshape}, generated {gshape}')
+    nr, ng = rshape[0], gshape[0]
+    if int(nhood_size) != nhood_size or not 1 <= nhood_size <= min(7, nr - 1):
+        raise ValueError(f'nhood_size must lie in 1 .. min(7, nr - 1) = {min(7, nr - 1)} (got {nhood_size} with nr = {nr})')
+    k = int(nhood_size)
+    if not torch.cuda.is_available():
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); none is available')
+    lib = _lib.load()
+    real, gen = _f16_padded(real_features, dev), _f16_padded(gen_features, dev)
+    D = real.shape[1]
+    radii = torch.empty([nr], dtype=torch.float32, device=dev)
+    count = torch.empty([ng], dtype=torch.int32, device=dev)
+    nearest = torch.empty([nr], dtype=torch.float32, device=dev)
+    ws_bytes = max(lib.la_dc_workspace_bytes(ng, nr), 4 * lib.la_pr_workspace_floats(nr, nr))
+    ws = torch.empty([ws_bytes // 4], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
+        _lib.check(lib.la_pr_kth_f16(_lib.ptr(real), nr, _lib.ptr(real), nr, D, k, _lib.ptr(radii), _lib.ptr(ws), _lib.stream_ptr()),
+                   'pr_kth')
+        _lib.check(lib.la_dc_count_f16(_lib.ptr(gen), ng, _lib.ptr(real), nr, D, _lib.ptr(radii), _lib.ptr(count), _lib.ptr(nearest),
+                                       _lib.ptr(ws), ws_bytes, _lib.stream_ptr()), 'dc_count')
+    covered = nearest <= radii
+    density = int(count.sum(dtype=torch.int64)) / (k * ng)
+    coverage = int(covered.sum()) / nr
+    if return_details:
+        return density, coverage, dict(radii=radii.cpu().numpy(), count=count.cpu().numpy(), nearest=nearest.cpu().numpy(),
+                                       covered=covered.cpu().numpy())
+    return density, coverage
+
+
+def compute_prdc_from_features(real_features, gen_features, nhood_size=5, device='cuda:0'):
+    """{'precision', 'recall', 'density', 'coverage'} with one nhood_size: compute_pr_from_features (radii of the real and of the
+    generated manifold, rounded to float16 as the reference keeps them) and compute_dc_from_features (radii of the real samples only,
+    float32), each with its own documented convention."""
+    precision, recall = compute_pr_from_features(real_features, gen_features, nhood_size=nhood_size, device=device)
+    density, coverage = compute_dc_from_features(real_features, gen_features, nhood_size=nhood_size, device=device)
+    return dict(precision=precision, recall=recall, density=density, coverage=coverage)
