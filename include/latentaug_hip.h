@@ -421,15 +421,23 @@ const float* la_disc_logits(const la_disc* h);
  * (VGG16 = 13 x conv3x3+ReLU, 4 x max-pool, 5 taps); a tap emits f * rsqrt(sum_c f^2 + 1e-10) * sqrt(lin[c]) / sqrt(H*W),
  * so squared L2 between two outputs is their LPIPS distance.  params: per op in order -- conv: weight [cout][cin][3][3],
  * bias [cout]; tap: lin [C]; pools: none.  Every conv needs cout % 4 == 0, and cin % 4 == 0 unless it is the first op of
- * the list; a pool needs an even resolution; the list must hold a tap.  A list that breaks one of these is refused by
+ * the list; a pool needs an even resolution; the list must hold a tap (or end in an FC op, below).  A list that breaks one of these is refused by
  * la_feat_workspace_bytes (0) and la_feat_create (LA_ERR_ARG), before any launch.  la_crop_repeat_f32: the crop + `.repeat([1,3,1,1])` of :394 for every modality
  * (rows ordered modality-major: row = c*B + b) with an affine preprocess; la_crop_repeat_grad_f32: its adjoint, ADDED to
  * g_img.
+ * Detector lists: LA_FEAT_FC_RELU / LA_FEAT_FC are fully connected layers, y = act(flatten(x) W^T + b), for the
+ * `return_features=True` branch of the same net (metrics/metric_utils.py:264-328).  cin is the flattened C*res*res of what
+ * precedes (NCHW order, torch's flatten), cout the number of outputs; params: weight [cout][cin], bias [cout].  A list that
+ * ends in an FC op is a detector list: forward only (la_feat_backward refuses it), its feature vector is the last FC's output,
+ * it holds no tap (a list with both is refused), and only FC ops may follow the first FC.  Its convolutions run in the engine's
+ * precision mode; the FC ops are always exact fp32 (la_fc_bias_act_f32).
  * ------------------------------------------------------------------------------------------------------------- */
 #define LA_FEAT_CONV_RELU 0
 #define LA_FEAT_TAP 1
 #define LA_FEAT_MAXPOOL2 2
 #define LA_FEAT_AVGPOOL2 3
+#define LA_FEAT_FC_RELU 4
+#define LA_FEAT_FC 5
 typedef struct la_feat_op { int kind, cin, cout; } la_feat_op;
 typedef struct la_feat la_feat;
 size_t la_feat_workspace_bytes(int nops, const la_feat_op* ops, int in_ch, int in_res, int max_batch);
@@ -444,6 +452,31 @@ int la_crop_repeat_f32(const float* img, float* xc, int B, int imgc, int R, int 
                        float shift, la_stream_t stream);
 int la_crop_repeat_grad_f32(const float* gxc, float* g_img, int B, int imgc, int R, int S, int y0, int x0, int rep,
                             float scale, la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Detector features: the steps of the reference's image -> VGG16 feature path (metrics/metric_utils.py:314-318 and the scripted
+ * module's own resize and fully connected layers) that the feature engine does not hold.
+ *   la_detector_prep_f32  img [N][C][H][W] -> out [N][rep*C][S][S] in one launch, rep * C == 3 (rep = 3: x.repeat([1,3,1,1]),
+ *                         output channel r*C + c).  In this order: quantize != 0: q = floor(clamp(x*127.5 + 128, 0, 255)), the
+ *                         bits of torch's (x * 127.5 + 128).clamp(0, 255).to(torch.uint8) (product and sum rounded separately);
+ *                         resampling (H, W) -> (S, S), mode LA_DET_AREA: F.interpolate(mode='area') == adaptive_avg_pool2d
+ *                         (bins floor(i*H/S) .. ceil((i+1)*H/S); non-integer ratios, up-sampling and H != W allowed), mode
+ *                         LA_DET_BILINEAR: align_corners=False, no antialiasing; H == S && W == S is a copy; then the
+ *                         per-channel affine v * scale[k] + shift[k], k < 3 (scale / shift: host arrays of 3).
+ *   la_fc_bias_act_f32    y [N][O] = act(x [N][K] . W [O][K]^T + b [O]), act LA_ACT_LINEAR | LA_ACT_RELU, float32 with exact
+ *                         fp32 products (fp32 MFMA).  A weight stream: every batch of up to 64 rows reads each weight element
+ *                         from memory once.  K is split over workgroups; the partial sums are added in a fixed order (no float
+ *                         atomics), so two runs give the same bits.  workspace: la_fc_workspace_bytes(N, K, O) bytes, which also
+ *                         serve every smaller N; 0 means the shape was refused.  Bad arguments: LA_ERR_ARG, a workspace that is
+ *                         too small: LA_ERR_WORKSPACE, both before any launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define LA_DET_AREA 0
+#define LA_DET_BILINEAR 1
+int la_detector_prep_f32(const float* img, float* out, int N, int C, int H, int W, int S, int rep, int mode, int quantize,
+                         const float* scale, const float* shift, la_stream_t stream);
+size_t la_fc_workspace_bytes(long N, long K, long O);
+int la_fc_bias_act_f32(const float* x, const float* w, const float* b, float* y, long N, long K, long O, int act,
+                       void* workspace, size_t workspace_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The loop: replaces LatentAug.forward(w, fname) (augments/utils/util_latent_aug.py:207-310) for 3-D w input.

@@ -7,6 +7,8 @@
 //       f[n][c][p] * rsqrt(sum_c f^2 + 1e-10) * sqrt(lin[c]) / sqrt(H*W)
 // to the output vector, so that squared L2 distance of two vectors is their LPIPS distance.
 // Contractions reuse la_conv*.hip (shared weights); pools / taps are small HBM-bound kernels.
+// Detector lists (the `return_features=True` branch of the same net, metrics/metric_utils.py:264-328) end in fully connected ops
+// instead of taps: forward only, the feature vector is the last FC's output (la_fc_bias_act_f32, la_detector.hip).
 #include "la_feat.h"
 
 #include <math.h>
@@ -23,7 +25,7 @@ struct FOp {
     int kind, cin, cout, res_in, res_out;
     const float *w, *bias, *lin;
     float *wf, *wb; void *wqf, *wqb; int mb_;
-    float* y;          // output activation [maxN][cout][res_out^2] (conv, pools); taps have none
+    float* y;          // output activation [maxN][cout][res_out^2] (conv, pools, fc: res_out = 1); taps have none
     long feat_off;     // taps: offset of the slice inside the feature vector
 };
 
@@ -39,7 +41,11 @@ struct la_feat {
     void* cws; size_t cws_bytes;
     const float* x_in;   // input of the last forward
     int lastN;
+    int detector;        // the list ends in an FC op: forward only, F = the last FC's outputs
+    void* fcws; size_t fcws_bytes;      // la_fc_bias_act_f32's workspace (detector lists only)
 };
+
+static inline bool f_is_fc(int kind) { return kind == LA_FEAT_FC_RELU || kind == LA_FEAT_FC; }
 
 static size_t falign(size_t v) { return (v + 63) & ~(size_t)63; }
 struct FCarver {
@@ -54,9 +60,11 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
     h->nops = nops; h->in_ch = in_ch; h->in_res = in_res; h->maxN = maxN;
     int c = in_ch, r = in_res;
     long F = 0;
+    int ntap = 0, nfc = 0;
     for (int k = 0; k < nops; ++k) {
         FOp& o = h->op[k];
         o.kind = ops[k].kind; o.cin = c; o.res_in = r;
+        if (nfc) LA_CHECK_ARG(f_is_fc(o.kind), "feat: only fc ops may follow an fc op");
         switch (o.kind) {
             case LA_FEAT_CONV_RELU:
                 LA_CHECK_ARG(ops[k].cin == c && ops[k].cout >= 4 && ops[k].cout % 4 == 0, "feat: conv channels mismatch / not a multiple of 4");
@@ -67,11 +75,17 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
                 LA_CHECK_ARG(r % 2 == 0, "feat: pooling needs an even resolution");
                 o.cout = c; o.res_out = r / 2; r /= 2; break;
             case LA_FEAT_TAP:
-                o.cout = c; o.res_out = r; o.feat_off = F; F += (long)c * r * r; break;
+                o.cout = c; o.res_out = r; o.feat_off = F; F += (long)c * r * r; ++ntap; break;
+            case LA_FEAT_FC_RELU: case LA_FEAT_FC:
+                LA_CHECK_ARG(ntap == 0, "feat: taps and fc ops cannot be mixed in one list");
+                LA_CHECK_ARG((long)ops[k].cin == (long)c * r * r, "feat: fc cin must be C*res*res of what precedes it");
+                LA_CHECK_ARG(ops[k].cout >= 1, "feat: fc needs at least one output");
+                o.cin = ops[k].cin; o.cout = ops[k].cout; o.res_out = 1; c = o.cout; r = 1; ++nfc; break;
             default:
                 la_set_error("feat: unknown op kind"); return LA_ERR_ARG;
         }
     }
+    if (nfc) { h->detector = 1; F = c; }
     LA_CHECK_ARG(F > 0 && F < (1L << 31), "feat: no tap op / feature vector too long");
     h->F = (int)F;
     return LA_OK;
@@ -97,6 +111,16 @@ static size_t f_layout(la_feat* h, void* ws) {
             if (pmn > pmax) pmax = pmn;
         }
         if (o.kind != LA_FEAT_TAP) { o.y = c.take(n_out); if (n_out > gmax) gmax = n_out; }
+    }
+    if (h->detector) {      // forward only: no gradient buffers; the FC kernel's K-slice partials instead
+        gmax = 0; pmax = 0;
+        size_t fb = 0;
+        for (int k = 0; k < h->nops; ++k)
+            if (f_is_fc(h->op[k].kind)) {
+                const size_t b = la_fc_workspace_bytes((long)mn, h->op[k].cin, h->op[k].cout);
+                if (b > fb) fb = b;
+            }
+        h->fcws = c.take((fb + 3) / 4); h->fcws_bytes = fb;
     }
     h->gA = c.take(gmax); h->gB = c.take(gmax);
     h->pm = c.take(pmax);
@@ -144,6 +168,9 @@ extern "C" int la_feat_create(int nops, const la_feat_op* ops, const float* cons
         } else if (o.kind == LA_FEAT_TAP) {
             if (p + 1 > nparams || !params[p]) { rc = LA_ERR_ARG; la_set_error("feat_create: missing tap weights"); break; }
             o.lin = params[p++];
+        } else if (f_is_fc(o.kind)) {      // used in place: weight [cout][cin], bias [cout]
+            if (p + 2 > nparams || !params[p] || !params[p + 1]) { rc = LA_ERR_ARG; la_set_error("feat_create: missing fc tensors"); break; }
+            o.w = params[p++]; o.bias = params[p++];
         }
     }
     if (!rc && p != nparams) { rc = LA_ERR_ARG; la_set_error("feat_create: parameter list length mismatch"); }
@@ -378,6 +405,13 @@ extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_ou
             const int pl = tap_lanes(HWo);
             hipLaunchKernelGGL(la_tap_fwd_kernel, dim3(la_cdiv(HWo, pl), N), dim3(256), 0, stream, cur, o.lin, feat_out, o.cout, HWo,
                                (long)h->F, o.feat_off, pl);
+        } else if (f_is_fc(o.kind)) {
+            // the activation in front is [N][C][res][res] contiguous: torch's flatten is a reinterpretation; the last FC writes the features
+            float* dst = k == h->nops - 1 ? feat_out : o.y;
+            if ((rc = la_fc_bias_act_f32(cur, o.w, o.bias, dst, N, o.cin, o.cout, o.kind == LA_FEAT_FC_RELU ? LA_ACT_RELU : LA_ACT_LINEAR, h->fcws,
+                                         h->fcws_bytes, stream)))
+                return rc;
+            cur = dst;
         } else {
             const long planes = (long)N * o.cout;
             hipLaunchKernelGGL(la_pool2_fwd_kernel, dim3(la_cdiv(planes * HWo, 256)), dim3(256), 0, stream, cur, o.y, o.res_in, planes,
@@ -393,6 +427,7 @@ extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_ou
 // gx [N][in_ch][in_res^2] = d(sum gfeat . feat)/dx for the last forward (x must still hold the forward's input)
 extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipStream_t stream) {
     LA_CHECK_ARG(h && gfeat && gx && h->lastN >= 1, "feat_backward: null pointer / no forward pass");
+    LA_CHECK_ARG(!h->detector, "feat_backward: a detector list (fc ops) is forward only");
     const int N = h->lastN;
     float* g = h->gA;       // gradient w.r.t. the activation that op k produced / tapped
     float* other = h->gB;

@@ -1,5 +1,5 @@
-"""Host-side mirror of the reference's quality metrics (metrics/) over the HIP C ABI -- everything downstream of the
-detector features.
+"""Host-side mirror of the reference's quality metrics (metrics/) over the HIP C ABI: the VGG16 detector features of images and
+everything downstream of detector features.
 
   FeatureStats                 metrics/metric_utils.py:79-155   (same fields, append / append_torch / get_all / get_mean_cov,
                                                                  save / load of the reference's pickle layout)
@@ -9,12 +9,20 @@ detector features.
   compute_kid_from_features    (not in the reference) Kernel Inception Distance, the community's kid50k_full recipe
   compute_dc_from_features     (not in the reference) density and coverage, Naeem et al., ICML 2020 (the `prdc` package)
   compute_prdc_from_features   precision, recall, density and coverage in one dict
+  compute_feature_stats_for_images        images -> FeatureStats through a `synthesis.DetectorEngine` (metric_utils.py:314-320)
+  compute_feature_stats_for_aug_dataset   metrics/metric_utils.py:264-328: the `img_aug/` pickles of the reference's drivers
+  compute_metrics_from_images             precision / recall / density / coverage / KID of two image sets
 
-The detectors themselves (Inception-v3 and VGG16 pickles hosted by NVIDIA, metric_utils.py:46-60) cannot be fetched offline:
-callers supply the features, e.g. from `synthesis.FeatureEngine` or from a detector they have on disk.
+The detectors (Inception-v3 and VGG16 pickles hosted by NVIDIA, metric_utils.py:46-60) cannot be fetched offline.  The VGG16 one has a
+local counterpart -- the TorchScript `vgg16.pt` the LPIPS criterion already needs -- and `synthesis.DetectorEngine.from_torchscript`
+runs its `return_features=True` branch on the HIP path, so precision / recall, density / coverage and KID start from images.  The
+Inception-v3 pickle has none: FID keeps taking features or moments that the caller supplies.
 torch only owns the device memory; the moments, distances, radii, membership tests and kernel sums are HIP kernels (la_metrics.hip).
 """
+import glob
+import os
 import pickle
+import uuid
 
 import numpy as np
 import scipy.linalg
@@ -310,3 +318,66 @@ def compute_prdc_from_features(real_features, gen_features, nhood_size=5, device
     precision, recall = compute_pr_from_features(real_features, gen_features, nhood_size=nhood_size, device=device)
     density, coverage = compute_dc_from_features(real_features, gen_features, nhood_size=nhood_size, device=device)
     return dict(precision=precision, recall=recall, density=density, coverage=coverage)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# images -> detector features -> FeatureStats (synthesis.DetectorEngine; no CPU fallback)
+def _batch_images(batch, mode):
+    if isinstance(batch, dict):
+        if mode not in ('A', 'B'):
+            raise ValueError("batches of output dicts need mode='A' or mode='B'")
+        batch = batch[mode]
+    if not torch.is_tensor(batch) or batch.ndim != 4:
+        raise ValueError('a batch must be a [N, 1|3, H, W] tensor, or a dict that holds one under its mode')
+    return batch
+
+
+def compute_feature_stats_for_images(batches, detector, mode=None, max_items=None, **stats_kwargs):
+    """FeatureStats of the detector features of `batches`: an iterable of [N, 1|3, H, W] tensors in the generator's [-1, 1] range, or
+    of the augmentation plugins' output dicts (then `mode` in {'A', 'B'} picks the modality).  Each batch is quantised to the uint8
+    grid, repeated to three channels and run through `detector` (metrics/metric_utils.py:314-319) on the device; `max_items` cuts
+    the last batch as FeatureStats does."""
+    stats = FeatureStats(max_items=max_items, device=detector.device, **stats_kwargs)
+    for batch in batches:
+        x = _batch_images(batch, mode).to(detector.device)
+        stats.append_torch(detector.features(x, quantize=True))
+        if stats.is_full():
+            break
+    return stats
+
+
+def compute_feature_stats_for_aug_dataset(datadir, mode, detector, max_items=None, cache_file=None, **stats_kwargs):
+    """metrics/metric_utils.py:264-328 for a local detector: the `img_aug/` pickles that the reference's drivers write
+    (backbone_latentaug.py: one dict of image batches per file) -> FeatureStats.  The pickles are read through the allow-list
+    loader of formats.py, never a plain unpickle.  `cache_file`: loaded if it exists, else written (atomically) in the
+    FeatureStats.save layout."""
+    if cache_file is not None and os.path.isfile(cache_file):
+        return FeatureStats.load(cache_file, device=detector.device)
+    from .formats import _restricted_load
+    files = sorted(f for f in glob.glob(os.path.join(datadir, 'img_aug', '*')) if os.path.isfile(f))
+    if not files:
+        raise FileNotFoundError(f"no augmented batches under {os.path.join(datadir, 'img_aug')}")
+
+    def batches():
+        for fname in files:
+            with open(fname, 'rb') as f:
+                yield _restricted_load(f)
+    stats = compute_feature_stats_for_images(batches(), detector, mode=mode, max_items=max_items, **stats_kwargs)
+    if cache_file is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(cache_file)), exist_ok=True)
+        tmp = cache_file + '.' + uuid.uuid4().hex
+        stats.save(tmp)
+        os.replace(tmp, cache_file)
+    return stats
+
+
+def compute_metrics_from_images(real_batches, gen_batches, detector, nhood_size=3, mode=None, max_items=None, kid_num_subsets=100,
+                                kid_max_subset_size=1000, kid_seed=0):
+    """{'precision', 'recall', 'density', 'coverage', 'kid'} of generated against real images, through `detector` and the functions
+    above (precision_recall.py:36-85 with nhood_size=3 is the reference's pr50k3)."""
+    real = compute_feature_stats_for_images(real_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
+    gen = compute_feature_stats_for_images(gen_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
+    out = compute_prdc_from_features(real, gen, nhood_size=nhood_size, device=detector.device)
+    out['kid'] = compute_kid_from_features(real, gen, num_subsets=kid_num_subsets, max_subset_size=kid_max_subset_size, seed=kid_seed,
+                                           device=detector.device)
+    return out

@@ -384,13 +384,16 @@ class DiscriminatorEngine:
         return g
 
 
-FEAT_CONV, FEAT_TAP, FEAT_MAXPOOL, FEAT_AVGPOOL = 0, 1, 2, 3
+FEAT_CONV, FEAT_TAP, FEAT_MAXPOOL, FEAT_AVGPOOL, FEAT_FC_RELU, FEAT_FC = 0, 1, 2, 3, 4, 5
+RESIZE_MODES = {'area': 0, 'bilinear': 1}
 
 
 class FeatureEngine:
     """LPIPS-style feature net on the HIP path: `vgg16(x, resize_images=False, return_lpips=True)` of
     util_latent_aug.py:395 and its backward.  `ops` is a list of ('conv', weight, bias) | ('tap', lin) | ('maxpool',) |
-    ('avgpool',) in execution order; see `vgg16_lpips_ops` for the VGG16 layout."""
+    ('avgpool',) in execution order; see `vgg16_lpips_ops` for the VGG16 layout.  ('fc', weight [O, K], bias [O], relu: bool) is a
+    fully connected layer on the flattened activation (K = C * res * res in torch's NCHW order); a list that ends in one is a detector
+    list (`DetectorEngine`): forward only, no taps, and its feature vector is the last fc's output."""
 
     def __init__(self, ops, device, in_res, max_batch, in_ch=3, precision='f32'):
         lib = _lib.load()
@@ -416,6 +419,13 @@ class FeatureEngine:
                 params.append(lin)
             elif op[0] in ('maxpool', 'avgpool'):
                 desc.append(_lib.FeatOp(FEAT_MAXPOOL if op[0] == 'maxpool' else FEAT_AVGPOOL, c, c))
+            elif op[0] == 'fc':
+                w = op[1].detach().to(self.device, torch.float32).contiguous()
+                b = op[2].detach().to(self.device, torch.float32).contiguous()
+                assert w.ndim == 2 and b.shape == (w.shape[0],)
+                desc.append(_lib.FeatOp(FEAT_FC_RELU if op[3] else FEAT_FC, w.shape[1], w.shape[0]))      # (the engine checks K)
+                c = w.shape[0]
+                params += [w, b]
             else:
                 raise ValueError(op[0])
         self._keep = params
@@ -425,12 +435,12 @@ class FeatureEngine:
         for op in ops:
             hsh.update(op[0].encode())
             for t in op[1:]:
-                hsh.update(t.detach().to('cpu', torch.float32).contiguous().numpy().tobytes())
+                hsh.update(t.detach().to('cpu', torch.float32).contiguous().numpy().tobytes() if torch.is_tensor(t) else repr(t).encode())
         self.weights_digest = hsh.hexdigest()[:10]
         self.in_ch, self.in_res, self.max_batch = in_ch, in_res, int(max_batch)
         arr = (_lib.FeatOp * len(desc))(*desc)
         nbytes = lib.la_feat_workspace_bytes(len(desc), arr, in_ch, in_res, self.max_batch)
-        assert nbytes > 0, 'invalid feature-net description'
+        assert nbytes > 0, 'invalid feature-net description: ' + (lib.la_last_error() or b'?').decode()
         self._workspace = torch.empty([nbytes], dtype=torch.uint8, device=self.device)
         pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
         h = C.c_void_p()
@@ -613,3 +623,187 @@ def vgg16_from_torchscript(src, map_location='cpu'):
                         ops.append(('maxpool',))
             out.append(ScriptedFeatureNet(ops, pre_scale, pre_shift, lin_is_sqrt, module))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Detector features: the `return_features=True` branch of the same scripted VGG16, which the reference's precision / recall calls on
+# uint8 images (metrics/precision_recall.py:36-85, metrics/metric_utils.py:264-328).
+def detector_prep(images, size, resize_mode='area', quantize=True, pre_scale=(1.0, 1.0, 1.0), pre_shift=(0.0, 0.0, 0.0)):
+    """[N, 1|3, H, W] float32 device images -> the detector's input [N, 3, size, size] in one launch (la_detector_prep_f32): optional
+    quantisation to the uint8 grid, bit for bit torch's `(x * 127.5 + 128).clamp(0, 255).to(torch.uint8)` of metric_utils.py:316; one
+    channel repeated three times (:314-315); resampling with F.interpolate's 'area' or 'bilinear' (align_corners=False) rule; then
+    the per-channel input affine v * pre_scale[k] + pre_shift[k]."""
+    _lib.require_gpu(images)
+    if images.ndim != 4 or images.shape[1] not in (1, 3):
+        raise ValueError(f'images must be [N, 1|3, H, W], got {tuple(images.shape)}')
+    if resize_mode not in RESIZE_MODES:
+        raise ValueError(f'resize_mode must be one of {sorted(RESIZE_MODES)}')
+    lib = _lib.load()
+    x = images.detach().to(torch.float32).contiguous()
+    N, Cc, H, W = x.shape
+    out = torch.empty([N, 3, size, size], dtype=torch.float32, device=x.device)
+    sc, sh = (C.c_float * 3)(*[float(v) for v in pre_scale]), (C.c_float * 3)(*[float(v) for v in pre_shift])
+    if N:
+        with torch.cuda.device(x.device):
+            _lib.check(lib.la_detector_prep_f32(_lib.ptr(x), _lib.ptr(out), N, Cc, H, W, size, 3 // Cc, RESIZE_MODES[resize_mode],
+                                                1 if quantize else 0, sc, sh, _lib.stream_ptr()), 'la_detector_prep_f32')
+    return out
+
+
+def fc_bias_act(x, weight, bias, relu=False):
+    """act(x @ weight.T + bias) on the HIP path (la_fc_bias_act_f32): float32, exact fp32 products, the same bits on every run."""
+    for t in (x, weight, bias):
+        _lib.require_gpu(t)
+    lib = _lib.load()
+    x, weight, bias = (t.detach().to(torch.float32).contiguous() for t in (x, weight, bias))
+    N, K = x.shape
+    O = weight.shape[0]
+    assert weight.shape == (O, K) and bias.shape == (O,)
+    y = torch.empty([N, O], dtype=torch.float32, device=x.device)
+    nbytes = lib.la_fc_workspace_bytes(N, K, O)
+    if nbytes == 0:
+        raise _lib.LatentAugHipError('la_fc_workspace_bytes refused the shape: ' + (lib.la_last_error() or b'?').decode())
+    ws = torch.empty([nbytes], dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.la_fc_bias_act_f32(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), N, K, O, 2 if relu else 1, _lib.ptr(ws),
+                                          nbytes, _lib.stream_ptr()), 'la_fc_bias_act_f32')
+    return y
+
+
+class ScriptedDetectorNet:
+    """One candidate reading of a scripted VGG16's `return_features=True` branch (`vgg16_detector_candidates`): the detector op list
+    (13 convolutions, 5 max-pools, `fc_depth` fully connected layers with ReLU), the input affine, the net's input size and the resize
+    rule."""
+
+    def __init__(self, ops, pre_scale, pre_shift, size, resize_mode, fc_depth, source):
+        self.ops, self.pre_scale, self.pre_shift, self.size = ops, pre_scale, pre_shift, size
+        self.resize_mode, self.fc_depth, self.source = resize_mode, fc_depth, source
+
+
+def vgg16_detector_candidates(src, map_location='cpu'):
+    """Parameter tensors of a TorchScript VGG16 -> candidate `ScriptedDetectorNet`s (host only).  The 13 convolutions and the input
+    layer are those `vgg16_from_torchscript` finds; the fully connected layers are the 2-D tensors with the [O] vector that follows
+    each (or `<name>.bias`), in state_dict order; the input size S follows from fc1's width, K1 = C5 * (S / 32)^2.  What the tensors
+    cannot tell -- the resize rule ('area' | 'bilinear') and whether `return_features=True` returns the activation after fc1 + ReLU
+    or after fc2 + ReLU -- is enumerated (together with the input-affine candidates of the LPIPS loader);
+    `DetectorEngine.from_torchscript` keeps the candidate that reproduces the module's own output."""
+    lp = vgg16_from_torchscript(src, map_location=map_location)
+    module = lp[0].source
+    items = _script_tensors(module)
+    fcs = []
+    for idx, (k, v) in enumerate(items):
+        if v.ndim != 2 or min(v.shape) < 2:
+            continue
+        bias = None
+        want = k[:-len('weight')] + 'bias' if k.endswith('weight') else None
+        for j, (kj, vj) in enumerate(items):
+            if vj.ndim == 1 and vj.shape[0] == v.shape[0] and ((want is not None and kj == want) or (want is None and j == idx + 1)):
+                bias = vj
+                break
+        if bias is None and idx + 1 < len(items) and items[idx + 1][1].ndim == 1 and items[idx + 1][1].shape[0] == v.shape[0]:
+            bias = items[idx + 1][1]
+        fcs.append((v, bias if bias is not None else torch.zeros([v.shape[0]])))
+    if len(fcs) < 2 or fcs[1][0].shape[1] != fcs[0][0].shape[0]:
+        raise _lib.LatentAugHipError(f'TorchScript detector: expected at least two chained fully connected layers, found '
+                                     f'{[tuple(w.shape) for w, _ in fcs]}: not a vgg16.pt layout')
+    convs = [op for op in lp[0].ops if op[0] == 'conv']
+    c5, k1 = convs[-1][1].shape[0], fcs[0][0].shape[1]
+    side = math.isqrt(k1 // c5) if k1 % c5 == 0 else 0
+    if side < 1 or side * side * c5 != k1:
+        raise _lib.LatentAugHipError(f'TorchScript detector: fc1 takes {k1} inputs, which is not {c5} x a square: not a vgg16.pt layout')
+    size = 32 * side
+    out, seen = [], set()
+    for cand in lp:
+        if (cand.pre_scale, cand.pre_shift) in seen:
+            continue
+        seen.add((cand.pre_scale, cand.pre_shift))
+        trunk = [op for op in cand.ops if op[0] != 'tap'] + [('maxpool',)]          # the LPIPS list stops before the fifth pool
+        for depth in (2, 1):
+            ops = trunk + [('fc', w, b, True) for w, b in fcs[:depth]]
+            for mode in ('area', 'bilinear'):
+                out.append(ScriptedDetectorNet(ops, cand.pre_scale, cand.pre_shift, size, mode, depth, module))
+    return out
+
+
+def detector_probe(size, n=2, seed=0):
+    """The probe batch of the load-time check: uint8-valued images with three different channels and a side that is no multiple of
+    the net's input size (so the resize rule shows)."""
+    g = torch.Generator().manual_seed(seed)
+    side = size + size // 2 + 3
+    return torch.randint(0, 256, [n, 3, side, side], generator=g).to(torch.float32)
+
+
+def run_scripted_detector(module, images_u8):
+    """`module(x, return_features=True)` as the reference calls it (uint8 images, metric_utils.py:316-318); on the host."""
+    with torch.no_grad():
+        try:
+            out = module(images_u8.to(torch.uint8), return_features=True)
+        except (RuntimeError, TypeError):
+            out = module(images_u8.to(torch.float32), return_features=True)
+    return out.reshape(images_u8.shape[0], -1).to(torch.float32)
+
+
+class DetectorEngine:
+    """Images -> detector features on the HIP path: `detector(x, return_features=True)` of metrics/metric_utils.py:318 with the
+    quantisation and channel repeat of :314-316 in front.  A thin class over a detector-list `FeatureEngine` (13 convolutions on the
+    contraction engine in `precision`, 5 max-pools, the fully connected layers in exact fp32) plus the image preparation kernel.
+    There is no CPU fallback."""
+
+    def __init__(self, ops, device, size, max_batch, resize_mode='area', pre_scale=(1.0, 1.0, 1.0), pre_shift=(0.0, 0.0, 0.0),
+                 precision='f32'):
+        if resize_mode not in RESIZE_MODES:
+            raise ValueError(f'resize_mode must be one of {sorted(RESIZE_MODES)}')
+        if not ops or ops[-1][0] != 'fc':
+            raise ValueError('a detector op list ends in an fc op')
+        self.engine = FeatureEngine(ops, device, in_res=size, max_batch=max_batch, in_ch=3, precision=precision)
+        self.device, self.max_batch = self.engine.device, self.engine.max_batch
+        self.S, self.resize_mode = int(size), resize_mode
+        self.pre_scale, self.pre_shift = tuple(float(v) for v in pre_scale), tuple(float(v) for v in pre_shift)
+        self.num_features = self.engine.num_features
+        self.weights_digest = self.engine.weights_digest
+        self.fc_depth = sum(1 for op in ops if op[0] == 'fc')
+
+    @classmethod
+    def from_torchscript(cls, src, device, max_batch, precision='f32', rtol=2e-3, probe_seed=0):
+        """Engine for a local TorchScript `vgg16.pt`, the file the LPIPS criterion already needs.  Every candidate of
+        `vgg16_detector_candidates` is run once, in exact fp32, on a probe batch and compared with the module's own
+        `module(x, return_features=True)` (the scripted module runs on the host for this check only); the first one within relative
+        L2 `rtol` is kept, otherwise loading fails with the candidates' errors -- a mapping is never trusted unverified."""
+        cands = vgg16_detector_candidates(src)
+        probe = detector_probe(cands[0].size, seed=probe_seed)
+        want = run_scripted_detector(cands[0].source, probe)
+        errs, engines = [], {}
+        for c in cands:
+            key = (c.pre_scale, c.pre_shift, c.fc_depth)
+            if key not in engines:          # (the two resize rules of one reading share the engine and its uploaded weights)
+                engines.clear()
+                engines[key] = cls(c.ops, device, c.size, max(max_batch, probe.shape[0]), 'area', c.pre_scale, c.pre_shift, 'f32')
+            det = engines[key]
+            det.resize_mode = c.resize_mode
+            if det.num_features != want.shape[1]:
+                errs.append((c.resize_mode, c.fc_depth, float('inf')))
+                continue
+            got = det.features(probe.to(det.device), quantize=False).cpu()
+            err = float((got - want).norm() / want.norm().clamp_min(1e-30))
+            errs.append((c.resize_mode, c.fc_depth, err))
+            if err <= rtol:
+                if precision != 'f32' or max_batch != det.max_batch:
+                    engines.clear()
+                    del det
+                    det = cls(c.ops, device, c.size, max_batch, c.resize_mode, c.pre_scale, c.pre_shift, precision)
+                return det
+        raise _lib.LatentAugHipError('TorchScript detector: no reading of its tensors (resize rule, fully connected depth, relative error: '
+                                     f"{errs}) reproduces the module's own return_features output; refusing to guess")
+
+    def prepare(self, images, quantize=True):
+        return detector_prep(images, self.S, self.resize_mode, quantize, self.pre_scale, self.pre_shift)
+
+    def features(self, images, quantize=True):
+        """[N, 1|3, H, W] device images in the generator's [-1, 1] range (quantize=True: rounded to the uint8 grid as the reference
+        does before the detector), or already on the 0..255 scale (quantize=False) -> [N, num_features] float32, in chunks of
+        `max_batch`."""
+        _lib.require_gpu(images)
+        out = torch.empty([images.shape[0], self.num_features], dtype=torch.float32, device=self.device)
+        for i in range(0, images.shape[0], self.max_batch):
+            out[i:i + self.max_batch] = self.engine.forward(self.prepare(images[i:i + self.max_batch].to(self.device), quantize))
+        return out
