@@ -61,6 +61,20 @@ void la_prof_close(int slot, hipStream_t stream);
 
 static inline int la_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Workspace carving: every buffer of a caller-supplied region starts on a 64-byte boundary.  A layout function is written once
+// and run twice -- with a null base to measure (take returns null, `off` ends as the bytes needed), then over the region.
+static inline size_t la_align64(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+struct LaCarver {
+    char* base = nullptr;
+    size_t off = 0;
+    size_t cap = 0;      // bytes behind `base` where the caller knows them (0: not given)
+    float* take(size_t nfloats) {
+        float* p = base ? (float*)(base + off) : nullptr;
+        off += la_align64(nfloats * sizeof(float));
+        return p;
+    }
+};
+
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float la_wave_sum(float v) {
 #pragma unroll
@@ -76,6 +90,42 @@ __device__ __forceinline__ float la_block_sum_256(float v, float* red) {
     if (lane == 0) red[wid] = v;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
+}
+
+// Block-wide maximum, same shape: wave shuffle, then 4 LDS floats.  Every thread of the workgroup must reach it (lanes with nothing
+// to contribute pass their neutral value); all threads get the result.
+__device__ __forceinline__ float la_block_max_256(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// output row of accumulator register r (0..15) of a 32x32 MFMA tile in the lane half lh (lane >> 5); the column is lane & 31
+__device__ __host__ constexpr int la_mfma32_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// One Adam update (torch.optim.Adam, no weight decay / amsgrad) of parameter p with moments m, v and gradient g:
+// step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t).  The expression shapes are fixed: results are compared bit for bit.
+__device__ __forceinline__ void la_adam_update(float& p, float& m, float& v, float g, float step_size, float bc2_sqrt, float b1, float b2,
+                                               float eps) {
+    const float mv = b1 * m + (1.f - b1) * g;
+    const float vv = b2 * v + (1.f - b2) * g * g;
+    m = mv; v = vv;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    p = p - step_size * (mv / denom);
+}
+
+// Step counter of a one-launch step tail whose threads have all read *ctr (the index of this step's bias corrections): every
+// workgroup draws a ticket AFTER the barrier, i.e. after its threads' reads; the one that draws the last ticket resets the ticket
+// and bumps the counter -- nobody is left to read the old value.  Every thread of the workgroup must reach it.
+__device__ __forceinline__ void la_step_ticket(int* ctr, int* ticket) {
+    __syncthreads();      // every thread of the workgroup has read *ctr
+    if (threadIdx.x == 0) {
+        if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) { *ticket = 0; *ctr += 1; }
+    }
 }
 
 // power-of-two operand scale of the fp16 split (la_conv_operand.hip): brings a tensor's max magnitude into [2^14, 2^15)
@@ -114,6 +164,33 @@ __device__ __forceinline__ void la_xs_lower(float* slot, float seen, float mult,
 // sub-slot of the calling workgroup inside a row (any spread will do; the multipliers keep neighbouring workgroups of every grid apart)
 // (returned as the float offset of the sub-slot inside the row)
 __device__ __forceinline__ int la_xs_sub(int salt = 0) { return (int)((blockIdx.x + 7u * blockIdx.y + 13u * blockIdx.z + (unsigned)salt) & (LA_XS_SUBS - 1)) * LA_XS_LINE; }
+// thread 0 of the calling workgroup lowers sub-slot la_xs_sub(salt) of sample b's row in `rows` [B][LA_XS_FAN] to the scale of wg_max
+__device__ __forceinline__ void la_xs_lower_wg(float* rows, long b, float mult, float wg_max, int salt = 0) {
+    if (threadIdx.x != 0) return;
+    float* row = rows + b * LA_XS_FAN + la_xs_sub(salt);
+    la_xs_lower(row, la_xs_peek(row), mult, wg_max);
+}
+// Lowering for 256-thread workgroups whose work items are consecutive planes, i.e. a handful of consecutive samples starting at b0:
+// thread (sample b, maximum omax; `live` false: nothing) -- the per-sample maxima of the workgroup are collected in LDS, then one
+// thread per sample lowers a sub-slot of that sample's row: one atomic per (workgroup, sample) instead of one per thread.  The LDS
+// maxima are bit patterns: non-negative floats order like unsigned ints, so atomicMax on the pattern is the float maximum.  The
+// table holds 64 samples; a thread whose sample lies further from b0 lowers its row directly (sub-slot spread by its thread id).
+// xs_mult: per-sample multipliers (null: 1); C planes per sample, P planes in all.  Every thread of the workgroup must reach it.
+__device__ __forceinline__ void la_xs_lower_by_sample(float* rows, const float* xs_mult, int b, int b0, int C, int P, bool live, float omax) {
+    __shared__ unsigned smx[64];
+    if (threadIdx.x < 64) smx[threadIdx.x] = 0u;
+    __syncthreads();
+    if (live && omax > 0.f) {
+        if (b - b0 < 64) atomicMax(&smx[b - b0], __float_as_uint(omax));
+        else { float* row = rows + (long)b * LA_XS_FAN + la_xs_sub(threadIdx.x); la_xs_lower(row, la_xs_peek(row), xs_mult ? xs_mult[b] : 1.f, omax); }
+    }
+    __syncthreads();
+    const int bt = b0 + (int)threadIdx.x;
+    if (threadIdx.x < 64 && smx[threadIdx.x] != 0u && bt * C < P) {
+        float* row = rows + (long)bt * LA_XS_FAN + la_xs_sub();
+        la_xs_lower(row, la_xs_peek(row), xs_mult ? xs_mult[bt] : 1.f, __uint_as_float(smx[threadIdx.x]));
+    }
+}
 // final per-sample scale: plain arrays [B] (fan <= 1: scales computed by a reduction launch or known a priori) or slot rows [B][LA_XS_FAN]
 __device__ __forceinline__ float la_xs_get(const float* p, int b, int fan) {
     if (fan <= 1) return p[b];

@@ -67,7 +67,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wm * (MT / WM_) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int m = m0 + wm * (MT / WM_) + i * 32 + la_mfma32_row(r, lh);
                     if (m < a.M) wsp[(long)m * G] = acc[i][j][r];
                 }
         }
@@ -463,7 +463,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
         for (int i = 0; i < TM; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ml = wm * (MT / WM_) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int ml = wm * (MT / WM_) + i * 32 + la_mfma32_row(r, lh);
                 const int m = m0 + ml;
                 const bool mok = m < a.M;
                 const float sc = (os_b && mok) ? os_b[m] : 1.f;
@@ -573,7 +573,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * (MT / WM_) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int m = m0 + wm * (MT / WM_) + i * 32 + la_mfma32_row(r, lh);
             if (m >= a.M) continue;
             float dmv = 1.f, bv = 0.f;
             if (fwd) {

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void la_conv_wgrad_mfma_kernel(WgArgs a) {
             if (n >= a.N) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int m = m0 + wm * 64 + i * 32 + la_mfma32_row(r, lh);
                 if (m < a.Ag) part[(long)m * a.N + n] = acc[i][j][r];
             }
         }

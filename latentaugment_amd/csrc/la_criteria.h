@@ -14,15 +14,11 @@ int la_l2_mean_from_bank(const float* Y, long m, long K, const float* X, int n, 
                          float* yy_ws, float* xx_ws, float scale, float* out, int accumulate, hipStream_t stream);
 int la_pix_grad(const float* img, const float* colsum, float* g, int B, int imgc, int R, int cc, int off, float coef2,
                 float mrows, hipStream_t stream);
-int la_latent_combine(const float* dws, const float* w, const float* colsumW, float* dw, int B, int num_ws, int wdim,
-                      float lat2, float mrows, hipStream_t stream);
 int la_broadcast_mix(const float* w_opt, const float* w0, float* w_aug, int B, int num_ws, int wdim, float alpha,
                      int soft, hipStream_t stream);
-// loop-engine Adam: bias corrections from a device table indexed by a device-side step counter (la_misc.hip)
-int la_adam_step_tab(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
-                     const float* tab, const int* ctr, hipStream_t stream);
-int la_step_advance(int* ctr, hipStream_t stream);
-// la_latent_combine + la_adam_step_tab + la_step_advance in one launch (bit-identical); ticket: a zeroed device int of the handle
+// Tail of a W-space loop step in one launch (la_misc.hip): dw = sum of dws over the ws slots + the latent criterion's gradient, the
+// Adam update with the bias corrections of step *ctr + 1 from the device table `tab` (la_adam_fill_table), and *ctr += 1;
+// ticket: a zeroed device int of the handle
 int la_step_tail(const float* dws, const float* colsumW, float* dw, float* p, float* m, float* v, int B, int num_ws, int wdim, float lat2,
                  float mrows, float lr, float beta1, float beta2, float eps, const float* tab, int* ctr, int* ticket, hipStream_t stream);
 void la_adam_fill_table(float* tab_host, int steps, float beta1, float beta2);

@@ -279,45 +279,6 @@ int la_pix_grad(const float* img, const float* colsum, float* g, int B, int imgc
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// latent-space gradient assembly for W-space optimisation (ws = w repeated num_ws times, util_latent_aug.py:493-494):
-//   dw[b][j] = sum_l dws[b][l][j]  +  lat2 * (num_ws * m * w[b][j] - sum_l colsumW[l][j])
-// lat2 = sign * 2 * w_latent / (m * n * num_ws * wdim); colsumW may be null (no latent criterion).
-__global__ void la_latent_combine_kernel(const float* __restrict__ dws, const float* __restrict__ w,
-                                         const float* __restrict__ colsumW, float* __restrict__ dw, int num_ws, int wdim,
-                                         float lat2, float mrows, long total) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const long b = i / wdim;
-    const int j = (int)(i - b * wdim);
-    float acc = 0.f, cs = 0.f;
-    int l = 0;
-    for (; l + 7 < num_ws; l += 8) {      // (eight slots' loads in flight, added in slot order)
-        float a[8], c[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            a[k] = dws ? dws[(b * num_ws + l + k) * wdim + j] : 0.f;
-            c[k] = colsumW ? colsumW[(long)(l + k) * wdim + j] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { if (dws) acc += a[k]; if (colsumW) cs += c[k]; }
-    }
-    for (; l < num_ws; ++l) {
-        if (dws) acc += dws[(b * num_ws + l) * wdim + j];
-        if (colsumW) cs += colsumW[(long)l * wdim + j];
-    }
-    if (colsumW) acc += lat2 * ((float)num_ws * mrows * w[i] - cs);
-    dw[i] = acc;
-}
-
-int la_latent_combine(const float* dws, const float* w, const float* colsumW, float* dw, int B, int num_ws, int wdim,
-                      float lat2, float mrows, hipStream_t stream) {
-    const long total = (long)B * wdim;
-    hipLaunchKernelGGL(la_latent_combine_kernel, dim3(la_cdiv(total, 256)), dim3(256), 0, stream, dws, w, colsumW, dw,
-                       num_ws, wdim, lat2, mrows, total);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
-}
-
 // w_aug[b][l][j] = alpha * w_opt[b][j] + (1 - alpha) * w0[b][j]   (hard_aug: alpha = 1)   util_latent_aug.py:438-454
 __global__ void la_broadcast_mix_kernel(const float* __restrict__ w_opt, const float* __restrict__ w0,
                                         float* __restrict__ w_aug, int num_ws, int wdim, float alpha, int soft,

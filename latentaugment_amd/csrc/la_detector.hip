@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void la_fc_mfma_kernel(FcArgs a) {
     for (int i = 0; i < NB; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const long n = n0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const long n = n0 + i * 32 + la_mfma32_row(r, lh);
             if (n >= a.N) continue;
             float v = acc[i][r];
             if (direct) { v += bias; if (a.act == LA_ACT_RELU) v = v > 0.f ? v : 0.f; }

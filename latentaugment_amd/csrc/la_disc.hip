@@ -55,13 +55,7 @@ struct la_disc {
 };
 
 static inline int dz_xhalf(int res) { return (res / 2 + 1 + 3) & ~3; }      // column-planar rows of a (res+1)-wide intermediate: odd columns start here
-static size_t alup(size_t v) { return (v + 63) & ~(size_t)63; }
-struct DCarver {
-    char* base; size_t off;
-    float* take(size_t nfloats) { float* p = base ? (float*)(base + off) : nullptr; off += alup(nfloats * 4); return p; }
-};
-
-static void dconv_layout(DCarver& c, DConv& L) {
+static void dconv_layout(LaCarver& c, DConv& L) {
     L.mb_ = (L.cin + 3) & ~3;
     const size_t kk = (size_t)L.k * L.k;
     L.wf = c.take((size_t)L.cin * L.cout * kk); L.wb = c.take((size_t)L.mb_ * L.cout * kk);
@@ -97,7 +91,7 @@ static int d_describe(la_disc* h, int R, int imgc, const int* channels, int maxB
 }
 
 static size_t d_layout(la_disc* h, void* ws) {
-    DCarver c{(char*)ws, 0};
+    LaCarver c{(char*)ws};
     const size_t mb = h->maxB;
     size_t gmax = 0, smax = 0, cw = 0, pmax = 0;
     for (int k = 0; k < h->nblocks; ++k) {

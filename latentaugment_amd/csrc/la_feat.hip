@@ -47,12 +47,6 @@ struct la_feat {
 
 static inline bool f_is_fc(int kind) { return kind == LA_FEAT_FC_RELU || kind == LA_FEAT_FC; }
 
-static size_t falign(size_t v) { return (v + 63) & ~(size_t)63; }
-struct FCarver {
-    char* base; size_t off;
-    float* take(size_t nfloats) { float* p = base ? (float*)(base + off) : nullptr; off += falign(nfloats * 4); return p; }
-};
-
 static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, int in_res, int maxN) {
     LA_CHECK_ARG(nops >= 1 && nops <= FEAT_MAX_OPS && ops, "feat: bad op list");
     LA_CHECK_ARG(in_ch >= 1 && in_res >= 2 && maxN >= 1, "feat: bad input shape");
@@ -92,7 +86,7 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
 }
 
 static size_t f_layout(la_feat* h, void* ws) {
-    FCarver c{(char*)ws, 0};
+    LaCarver c{(char*)ws};
     const size_t mn = h->maxN;
     size_t gmax = mn * h->in_ch * (size_t)h->in_res * h->in_res, cw = 0, pmax = 0;
     for (int k = 0; k < h->nops; ++k) {
@@ -332,19 +326,8 @@ __global__ __launch_bounds__(256) void la_tap_bwd_kernel(const float* __restrict
             omax = fmaxf(omax, fabsf(v));
         }
     }
-    if (xs_row) {      // (uniform) this workgroup's maximum lowers a sub-slot of sample n's row
-        __syncthreads();
-        red[0][threadIdx.x] = omax;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) red[0][threadIdx.x] = fmaxf(red[0][threadIdx.x], red[0][threadIdx.x + o]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            float* row = xs_row + n * LA_XS_FAN + la_xs_sub();
-            la_xs_lower(row, la_xs_peek(row), 1.f, red[0][0]);
-        }
-    }
+    // (uniform) this workgroup's maximum lowers a sub-slot of sample n's row
+    if (xs_row) la_xs_lower_wg(xs_row, n, 1.f, la_block_max_256(omax, red[0]));
 }
 
 // pixel lanes of a tap workgroup: the largest power of two <= min(64, HW)
@@ -534,9 +517,10 @@ __global__ void la_crop_repeat_bwd_kernel(const float* __restrict__ gxc, float* 
 }
 
 // scale / shift: one value per repeated channel ([rep], rep <= 4) -- e.g. the (x - mean_k) / std_k of an ImageNet-style input layer
-int la_crop_repeat_ex3(const float* img, float* xc, int B, int imgc, int R, int S, int y0, int x0, const int* pos_dev, int rep,
-                       const float* scale, const float* shift, hipStream_t stream) {
-    LA_CHECK_ARG(img && xc && y0 >= 0 && x0 >= 0 && y0 + S <= R && x0 + S <= R && rep >= 1 && rep <= 4 && scale && shift, "crop_repeat: bad arguments");
+int la_crop_repeat(const float* img, float* xc, int B, int imgc, int R, int S, int y0, int x0, const int* pos_dev, int rep,
+                   const float* scale, const float* shift, hipStream_t stream) {
+    LA_CHECK_ARG(rep >= 1 && rep <= 4, "crop_repeat: rep must be 1..4");
+    LA_CHECK_ARG(img && xc && y0 >= 0 && x0 >= 0 && y0 + S <= R && x0 + S <= R && scale && shift, "crop_repeat: bad arguments");
     LaPreAffine pre;
     for (int k = 0; k < 4; ++k) { pre.scale[k] = scale[k < rep ? k : rep - 1]; pre.shift[k] = shift[k < rep ? k : rep - 1]; }
     const long total = (long)B * imgc * rep * S * S;
@@ -545,20 +529,16 @@ int la_crop_repeat_ex3(const float* img, float* xc, int B, int imgc, int R, int 
     LA_CHECK_LAUNCH();
     return LA_OK;
 }
-int la_crop_repeat_ex(const float* img, float* xc, int B, int imgc, int R, int S, int y0, int x0, const int* pos_dev, int rep, float scale,
-                      float shift, hipStream_t stream) {
-    const float sc[4] = {scale, scale, scale, scale}, sh[4] = {shift, shift, shift, shift};
-    LA_CHECK_ARG(rep >= 1 && rep <= 4, "crop_repeat: rep must be 1..4");
-    return la_crop_repeat_ex3(img, xc, B, imgc, R, S, y0, x0, pos_dev, rep, sc, sh, stream);
-}
 extern "C" int la_crop_repeat_f32(const float* img, float* xc, int B, int imgc, int R, int S, int y0, int x0, int rep, float scale,
                                   float shift, hipStream_t stream) {
-    return la_crop_repeat_ex(img, xc, B, imgc, R, S, y0, x0, nullptr, rep, scale, shift, stream);
+    const float sc[4] = {scale, scale, scale, scale}, sh[4] = {shift, shift, shift, shift};
+    return la_crop_repeat(img, xc, B, imgc, R, S, y0, x0, nullptr, rep, sc, sh, stream);
 }
 
-int la_crop_repeat_grad_ex3(const float* gxc, float* g_img, int B, int imgc, int R, int S, int y0, int x0, const int* pos_dev, int rep,
-                            const float* scale, hipStream_t stream) {
-    LA_CHECK_ARG(gxc && g_img && y0 >= 0 && x0 >= 0 && y0 + S <= R && x0 + S <= R && rep >= 1 && rep <= 4 && scale, "crop_repeat_grad: bad arguments");
+int la_crop_repeat_grad(const float* gxc, float* g_img, int B, int imgc, int R, int S, int y0, int x0, const int* pos_dev, int rep,
+                        const float* scale, hipStream_t stream) {
+    LA_CHECK_ARG(rep >= 1 && rep <= 4, "crop_repeat_grad: rep must be 1..4");
+    LA_CHECK_ARG(gxc && g_img && y0 >= 0 && x0 >= 0 && y0 + S <= R && x0 + S <= R && scale, "crop_repeat_grad: bad arguments");
     LaPreAffine pre;
     for (int k = 0; k < 4; ++k) { pre.scale[k] = scale[k < rep ? k : rep - 1]; pre.shift[k] = 0.f; }
     const long total = (long)B * imgc * S * S;
@@ -567,13 +547,8 @@ int la_crop_repeat_grad_ex3(const float* gxc, float* g_img, int B, int imgc, int
     LA_CHECK_LAUNCH();
     return LA_OK;
 }
-int la_crop_repeat_grad_ex(const float* gxc, float* g_img, int B, int imgc, int R, int S, int y0, int x0, const int* pos_dev, int rep,
-                           float scale, hipStream_t stream) {
-    const float sc[4] = {scale, scale, scale, scale};
-    LA_CHECK_ARG(rep >= 1 && rep <= 4, "crop_repeat_grad: rep must be 1..4");
-    return la_crop_repeat_grad_ex3(gxc, g_img, B, imgc, R, S, y0, x0, pos_dev, rep, sc, stream);
-}
 extern "C" int la_crop_repeat_grad_f32(const float* gxc, float* g_img, int B, int imgc, int R, int S, int y0, int x0, int rep,
                                        float scale, hipStream_t stream) {
-    return la_crop_repeat_grad_ex(gxc, g_img, B, imgc, R, S, y0, x0, nullptr, rep, scale, stream);
+    const float sc[4] = {scale, scale, scale, scale};
+    return la_crop_repeat_grad(gxc, g_img, B, imgc, R, S, y0, x0, nullptr, rep, sc, stream);
 }

@@ -65,26 +65,34 @@ struct la_latent_opt {
 };
 #define LA_TEV 7      // step start | after synthesis | after latent | after pix | after disc | after lpips | step end
 
-static size_t al(size_t n) { return ((n * sizeof(float)) + 63) & ~(size_t)63; }
-
 static size_t carve(la_latent_opt* h, char* base) {
-    size_t off = 0;
-    auto take = [&](size_t n) { float* p = base ? (float*)(base + off) : nullptr; off += al(n); return p; };
+    LaCarver c{base};
     const size_t B = h->maxB, wd = h->wdim, cc2 = (size_t)h->cfg.crop * h->cfg.crop;
     const size_t wl = h->wplus ? (size_t)h->num_ws * wd : wd;      // floats of one sample's optimised latent
-    h->w_opt = take(B * wl); h->m = take(B * wl); h->v = take(B * wl); h->dw = take(B * wl);
-    h->dws = take(B * h->num_ws * wd);
-    h->g_img = take(B * h->imgc * (size_t)h->R * h->R);
-    h->colsumW = take((size_t)h->num_ws * wd);
-    h->colsumX = take((size_t)h->imgc * cc2);
+    h->w_opt = c.take(B * wl); h->m = c.take(B * wl); h->v = c.take(B * wl); h->dw = c.take(B * wl);
+    h->dws = c.take(B * h->num_ws * wd);
+    h->g_img = c.take(B * h->imgc * (size_t)h->R * h->R);
+    h->colsumW = c.take((size_t)h->num_ws * wd);
+    h->colsumX = c.take((size_t)h->imgc * cc2);
     const size_t mm = (size_t)(h->Mw > h->Mx ? h->Mw : h->Mx);
-    h->yx = take(LA_YX_FLOATS(mm ? mm : 1, B)); h->yy = take(LA_YY_FLOATS(mm ? mm : 1)); h->xx = take(LA_XX_FLOATS(B));
-    h->xc = take(B * h->imgc * cc2);
-    h->losses = take((size_t)(h->cfg.steps > 0 ? h->cfg.steps : 1) * 4);
-    h->adam_tab = take((size_t)(h->cfg.steps > 0 ? h->cfg.steps : 1) * 2);
-    h->step_ctr = reinterpret_cast<int*>(take(16));
+    h->yx = c.take(LA_YX_FLOATS(mm ? mm : 1, B)); h->yy = c.take(LA_YY_FLOATS(mm ? mm : 1)); h->xx = c.take(LA_XX_FLOATS(B));
+    h->xc = c.take(B * h->imgc * cc2);
+    h->losses = c.take((size_t)(h->cfg.steps > 0 ? h->cfg.steps : 1) * 4);
+    h->adam_tab = c.take((size_t)(h->cfg.steps > 0 ? h->cfg.steps : 1) * 2);
+    h->step_ctr = reinterpret_cast<int*>(c.take(16));
     h->crop_dev = h->step_ctr + 4;
-    return off;
+    return c.off;
+}
+
+// the perceptual criterion's buffers (la_latent_opt_set_lpips): from imgc, maxB, F, S, Mf of the handle
+static size_t carve_lpips(la_latent_opt* h, char* base) {
+    LaCarver c{base};
+    const size_t n = (size_t)h->imgc * h->maxB;
+    h->l_xc = c.take(n * 3 * h->S * h->S); h->l_gxc = c.take(n * 3 * h->S * h->S);
+    h->l_feat = c.take(n * h->F); h->l_gfeat = c.take(n * h->F);
+    h->l_colsum = c.take((size_t)h->imgc * h->F);
+    h->l_yx = c.take(LA_YX_FLOATS(h->Mf, h->maxB)); h->l_yy = c.take(LA_YY_FLOATS(h->Mf)); h->l_xx = c.take(LA_XX_FLOATS(h->maxB));
+    return c.off;
 }
 
 // latent_space: 0 W, 1 W+ (anything else: 0 bytes, and la_latent_opt_create_ex refuses it)
@@ -169,7 +177,6 @@ extern "C" int la_latent_opt_set_overlap(la_latent_opt* h, int enable) {
     // 0: criteria one after the other; 2 (the handle's default): fork / join captured as parallel branches of ONE step graph; 1: split
     // replay -- the perceptual branch as a graph of its own on the side stream beside the discriminator branch (round 5: measured equal)
     const int mode = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
-    if (h->overlap != mode) drop_graph(h);
     h->overlap = mode;
     drop_graph(h);
     return LA_OK;
@@ -195,7 +202,6 @@ extern "C" int la_latent_opt_set_col_window(la_latent_opt* h, int col_lo, int co
     return LA_OK;
 }
 
-// 1 (default): steps 2..N of the first batch and every step of later batches replay ONE captured step; 0: every launch eager
 extern "C" int la_latent_opt_set_trace(la_latent_opt* h, float* w_trace, float* img_trace) {
     LA_CHECK_ARG(h, "latent_opt_set_trace: null handle");
     h->trace_w = w_trace; h->trace_img = img_trace;
@@ -259,6 +265,7 @@ extern "C" int la_latent_opt_graph_state(const la_latent_opt* h) {
     return (h->graph_exec || h->seg_valid) ? 1 : (h->graph_refused ? -1 : 0);
 }
 
+// 1 (default): steps 2..N of the first batch and every step of later batches replay ONE captured step; 0: every launch eager
 extern "C" int la_latent_opt_set_graph(la_latent_opt* h, int enable) {
     LA_CHECK_ARG(h, "latent_opt_set_graph: null handle");
     h->graph_mode = enable ? 1 : 0;
@@ -278,13 +285,9 @@ extern "C" int la_latent_opt_set_disc(la_latent_opt* h, la_disc* d) {
 // LPIPS criterion: feature engine, real-feature banks [imgc][Mf][F] (modality-major), crop size S (crop_size_aug) and the
 // affine input preprocess x*scale + shift.  ws: la_latent_opt_lpips_workspace_bytes() of device memory.
 extern "C" size_t la_latent_opt_lpips_workspace_bytes(int img_channels, int F, int S, long Mf, int max_batch) {
-    const size_t n = (size_t)img_channels * max_batch;
-    size_t off = 0;
-    off += al(n * 3 * S * S) * 2;          // xc, gxc
-    off += al(n * F) * 2;                  // feat, gfeat
-    off += al((size_t)img_channels * F);   // colsum
-    off += al(LA_YX_FLOATS(Mf, max_batch)) + al(LA_YY_FLOATS(Mf)) + al(LA_XX_FLOATS(max_batch));
-    return off;
+    la_latent_opt h; memset(&h, 0, sizeof(h));
+    h.imgc = img_channels; h.F = F; h.S = S; h.Mf = Mf; h.maxB = max_batch;
+    return carve_lpips(&h, nullptr);
 }
 
 extern "C" int la_latent_opt_set_lpips(la_latent_opt* h, la_feat* f, const float* bankF, long Mf, int S, float pre_scale,
@@ -293,13 +296,7 @@ extern "C" int la_latent_opt_set_lpips(la_latent_opt* h, la_feat* f, const float
     const int F = la_feat_num_features(f);
     LA_CHECK_ARG(ws_bytes >= la_latent_opt_lpips_workspace_bytes(h->imgc, F, S, Mf, h->maxB), "latent_opt_set_lpips: workspace too small");
     h->f = f; h->bankF = bankF; h->Mf = Mf; h->F = F; h->S = S; for (int k = 0; k < 4; ++k) { h->pre_scale[k] = pre_scale; h->pre_shift[k] = pre_shift; }
-    char* base = (char*)ws; size_t off = 0;
-    auto take = [&](size_t n) { float* p = (float*)(base + off); off += al(n); return p; };
-    const size_t n = (size_t)h->imgc * h->maxB;
-    h->l_xc = take(n * 3 * S * S); h->l_gxc = take(n * 3 * S * S);
-    h->l_feat = take(n * F); h->l_gfeat = take(n * F);
-    h->l_colsum = take((size_t)h->imgc * F);
-    h->l_yx = take(LA_YX_FLOATS(Mf, h->maxB)); h->l_yy = take(LA_YY_FLOATS(Mf)); h->l_xx = take(LA_XX_FLOATS(h->maxB));
+    carve_lpips(h, (char*)ws);
     h->l_colsum_valid = 0;
     drop_graph(h);
     return LA_OK;
@@ -481,7 +478,7 @@ extern "C" int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const
                 const long FF = h->F;
                 if (segP) {
                     if (c.w_pix == 0.f && !use_disc) LA_HIP(hipMemsetAsync(h->g_img, 0, sizeof(float) * (size_t)B * h->imgc * h->R * h->R, st));
-                    if ((rc = la_crop_repeat_ex3(img, h->l_xc, B, h->imgc, h->R, h->S, h->crop_y, h->crop_x, h->crop_dev, 3, h->pre_scale, h->pre_shift, sl))) return rc;
+                    if ((rc = la_crop_repeat(img, h->l_xc, B, h->imgc, h->R, h->S, h->crop_y, h->crop_x, h->crop_dev, 3, h->pre_scale, h->pre_shift, sl))) return rc;
                     if ((rc = la_feat_forward(h->f, h->l_xc, N, h->l_feat, sl))) return rc;
                     if (L) {
                         for (int ch = 0; ch < h->imgc; ++ch)
@@ -498,7 +495,7 @@ extern "C" int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const
                     LA_HIP(hipEventRecord(h->ev_join, h->side_stream));
                     LA_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
                 }
-                if (segZ && (rc = la_crop_repeat_grad_ex3(h->l_gxc, h->g_img, B, h->imgc, h->R, h->S, h->crop_y, h->crop_x, h->crop_dev, 3, h->pre_scale, st)))
+                if (segZ && (rc = la_crop_repeat_grad(h->l_gxc, h->g_img, B, h->imgc, h->R, h->S, h->crop_y, h->crop_x, h->crop_dev, 3, h->pre_scale, st)))
                     return rc;
             }
             if (segZ) {

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void la_pr_tile_kernel(const _Float16* __restr
     float na[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const long m = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const long m = r0 + la_mfma32_row(r, lh);
         na[r] = rown[m < nr ? m : nr - 1];
     }
     float best[MODE == 0 ? 16 : 1][PR_KMAX];
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void la_pr_tile_kernel(const _Float16* __restr
                 } else if (MODE == 1) {
                     if (cok && d <= rad) member |= 1u << r;
                 } else {
-                    const long m = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const long m = r0 + la_mfma32_row(r, lh);
                     if (cok && m < nr) out_dist[m * nc + c] = d;
                 }
             }
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void la_pr_tile_kernel(const _Float16* __restr
                     best[MODE == 0 ? r : 0][PR_KMAX - 1] = __builtin_huge_valf();
                 }
             }
-            const long mrow = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const long mrow = r0 + la_mfma32_row(r, lh);
             if (l31 == 0 && mrow < nr) out_kth[mrow] = kth;
         }
     } else if (MODE == 1) {
@@ -138,16 +138,29 @@ __global__ __launch_bounds__(256) void la_pr_tile_kernel(const _Float16* __restr
         for (int r = 0; r < 16; ++r) {
             const unsigned long long any = __ballot((member >> r) & 1u);
             const unsigned half = (unsigned)(lh ? (any >> 32) : (any & 0xffffffffull));
-            const long mrow = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const long mrow = r0 + la_mfma32_row(r, lh);
             if (l31 == 0 && mrow < nr) out_member[mrow] = half ? 1 : 0;
         }
     }
 }
 
-static int pr_check(const void* rows, long nr, const void* cols, long nc, int D, const void* ws) {
+// squared norms of both feature sets into ws: [na] then [nb]
+static void sqnorms_f16(const void* a, long na, const void* b, long nb, int D, float* ws, hipStream_t stream) {
+    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(na, 4)), dim3(256), 0, stream, (const _Float16*)a, na, D, ws);
+    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nb, 4)), dim3(256), 0, stream, (const _Float16*)b, nb, D, ws + na);
+}
+
+// the three entries below: argument check, the norms of both sides, the tile launch of MODE (each entry passes the outputs it has)
+template <int MODE>
+static int pr_launch(const void* rows, long nr, const void* cols, long nc, int D, int kk, const float* radius, float* kth,
+                     unsigned char* member, float* dist, float* ws, hipStream_t stream) {
     LA_CHECK_ARG(rows && cols && ws && nr >= 1 && nc >= 1, "pr: bad args");
     LA_CHECK_ARG(D >= 16 && D % 16 == 0, "pr: the feature dimension must be a multiple of 16 (pad with zeros)");
     LA_CHECK_ARG((((size_t)rows | (size_t)cols) & 15) == 0, "pr: feature matrices must be 16-byte aligned");
+    sqnorms_f16(rows, nr, cols, nc, D, ws, stream);
+    hipLaunchKernelGGL(la_pr_tile_kernel<MODE>, dim3((unsigned)la_cdiv(nr, 128)), dim3(256), 0, stream, (const _Float16*)rows, (const float*)ws,
+                       nr, (const _Float16*)cols, (const float*)(ws + nr), nc, D, kk, radius, kth, member, dist);
+    LA_CHECK_LAUNCH();
     return LA_OK;
 }
 
@@ -156,49 +169,21 @@ extern "C" size_t la_pr_workspace_floats(long nr, long nc) { return (size_t)(nr 
 // kth[i] = (k+1)-th smallest Euclidean distance from row i to the columns (k = nhood_size; i's own zero distance counts)
 extern "C" int la_pr_kth_f16(const void* rows, long nr, const void* cols, long nc, int D, int nhood_size, float* kth, float* ws,
                              hipStream_t stream) {
-    int rc = pr_check(rows, nr, cols, nc, D, ws);
-    if (rc) return rc;
     LA_CHECK_ARG(kth && nhood_size >= 0 && nhood_size + 1 <= PR_KMAX && nhood_size + 1 <= nc, "pr_kth: nhood_size out of range");
-    float* rn = ws;
-    float* cn = ws + nr;
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nr, 4)), dim3(256), 0, stream, (const _Float16*)rows, nr, D, rn);
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nc, 4)), dim3(256), 0, stream, (const _Float16*)cols, nc, D, cn);
-    hipLaunchKernelGGL(la_pr_tile_kernel<0>, dim3((unsigned)la_cdiv(nr, 128)), dim3(256), 0, stream, (const _Float16*)rows, rn, nr,
-                       (const _Float16*)cols, cn, nc, D, nhood_size + 1, (const float*)nullptr, kth, (unsigned char*)nullptr,
-                       (float*)nullptr);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
+    return pr_launch<0>(rows, nr, cols, nc, D, nhood_size + 1, nullptr, kth, nullptr, nullptr, ws, stream);
 }
 
 // member[i] = 1 if dist(row i, col j) <= radius[j] for any j
 extern "C" int la_pr_member_f16(const void* rows, long nr, const void* cols, long nc, int D, const float* radius,
                                 unsigned char* member, float* ws, hipStream_t stream) {
-    int rc = pr_check(rows, nr, cols, nc, D, ws);
-    if (rc) return rc;
     LA_CHECK_ARG(radius && member, "pr_member: bad args");
-    float* rn = ws;
-    float* cn = ws + nr;
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nr, 4)), dim3(256), 0, stream, (const _Float16*)rows, nr, D, rn);
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nc, 4)), dim3(256), 0, stream, (const _Float16*)cols, nc, D, cn);
-    hipLaunchKernelGGL(la_pr_tile_kernel<1>, dim3((unsigned)la_cdiv(nr, 128)), dim3(256), 0, stream, (const _Float16*)rows, rn, nr,
-                       (const _Float16*)cols, cn, nc, D, 0, radius, (float*)nullptr, member, (float*)nullptr);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
+    return pr_launch<1>(rows, nr, cols, nc, D, 0, radius, nullptr, member, nullptr, ws, stream);
 }
 
 // dist[i][j] = Euclidean distance (the matrix torch.cdist returns), float32 [nr][nc]
 extern "C" int la_cdist_f16(const void* rows, long nr, const void* cols, long nc, int D, float* dist, float* ws, hipStream_t stream) {
-    int rc = pr_check(rows, nr, cols, nc, D, ws);
-    if (rc) return rc;
     LA_CHECK_ARG(dist, "cdist: bad args");
-    float* rn = ws;
-    float* cn = ws + nr;
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nr, 4)), dim3(256), 0, stream, (const _Float16*)rows, nr, D, rn);
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nc, 4)), dim3(256), 0, stream, (const _Float16*)cols, nc, D, cn);
-    hipLaunchKernelGGL(la_pr_tile_kernel<2>, dim3((unsigned)la_cdiv(nr, 128)), dim3(256), 0, stream, (const _Float16*)rows, rn, nr,
-                       (const _Float16*)cols, cn, nc, D, 0, (const float*)nullptr, (float*)nullptr, (unsigned char*)nullptr, dist);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
+    return pr_launch<2>(rows, nr, cols, nc, D, 0, nullptr, nullptr, nullptr, dist, ws, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -395,7 +380,7 @@ __global__ __launch_bounds__(256) void la_kid_tile_kernel(KidArgs a) {
             const long n = j0 + wn * 64 + j * 32 + l31;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long m = i0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const long m = i0 + wm * 64 + i * 32 + la_mfma32_row(r, lh);
                 if (m < ma && n < mb && !(diag && m == n)) {
                     const float v = tot[i][j][r] / fD + 1.f;
                     dsum += (double)(v * v * v);
@@ -526,7 +511,7 @@ __global__ __launch_bounds__(256) void la_dc_tile_kernel(const _Float16* __restr
     unsigned rowok = 0u;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const long m = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const long m = r0 + la_mfma32_row(r, lh);
         na[r] = rown[m < ng ? m : ng - 1];
         cnt[r] = 0;
         if (m < ng) rowok |= 1u << r;
@@ -623,7 +608,7 @@ __global__ __launch_bounds__(256) void la_dc_tile_kernel(const _Float16* __restr
         int s = cnt[r];
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);      // stays inside each 32-lane half
-        const long mrow = r0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const long mrow = r0 + la_mfma32_row(r, lh);
         if (l31 == 0 && mrow < ng && s) atomicAdd(count + mrow, s);
     }
 }
@@ -668,8 +653,7 @@ extern "C" int la_dc_count_f16(const void* gen, long ng, const void* real, long 
     float* rn = gn + ng;
     const long nmax = ng > nr ? ng : nr;
     hipLaunchKernelGGL(la_dc_init_kernel, dim3((unsigned)la_cdiv(nmax, 256)), dim3(256), 0, stream, count, ng, (unsigned*)nearest, nr);
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(ng, 4)), dim3(256), 0, stream, (const _Float16*)gen, ng, D, gn);
-    hipLaunchKernelGGL(la_rows_sqnorm_f16_kernel, dim3((unsigned)la_cdiv(nr, 4)), dim3(256), 0, stream, (const _Float16*)real, nr, D, rn);
+    sqnorms_f16(gen, ng, real, nr, D, gn, stream);
     hipLaunchKernelGGL(la_dc_tile_kernel, dim3((unsigned)rb, (unsigned)splits), dim3(256), 0, stream, (const _Float16*)gen, (const float*)gn,
                        ng, (const _Float16*)real, (const float*)rn, nr, D, chunk, radius, count, (unsigned*)nearest);
     LA_CHECK_LAUNCH();

@@ -86,50 +86,17 @@ __global__ void la_adam_kernel(float* __restrict__ p, const float* __restrict__ 
                                float bc2_sqrt, float gscale) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float gv = g[i] * gscale;
-    const float mv = b1 * m[i] + (1.f - b1) * gv;
-    const float vv = b2 * v[i] + (1.f - b2) * gv * gv;
-    m[i] = mv; v[i] = vv;
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    p[i] = p[i] - (lr / bc1) * (mv / denom);
+    la_adam_update(p[i], m[i], v[i], g[i] * gscale, lr / bc1, bc2_sqrt, b1, b2, eps);
 }
 
-// Loop-engine variant: the bias corrections of step t = *ctr + 1 come from a device table {1 - b1^t, sqrt(1 - b2^t)} (filled by
-// the host with the same powf as la_adam_step_f32), so that one captured launch serves every step; la_step_advance bumps the
-// counter at the end of a step.
-__global__ void la_adam_tab_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                   long n, float lr, float b1, float b2, float eps, const float2* __restrict__ tab,
-                                   const int* __restrict__ ctr) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float2 bc = tab[*ctr];
-    const float gv = g[i];
-    const float mv = b1 * m[i] + (1.f - b1) * gv;
-    const float vv = b2 * v[i] + (1.f - b2) * gv * gv;
-    m[i] = mv; v[i] = vv;
-    const float denom = sqrtf(vv) / bc.y + eps;
-    p[i] = p[i] - (lr / bc.x) * (mv / denom);
-}
-__global__ void la_step_advance_kernel(int* ctr) { if (threadIdx.x == 0 && blockIdx.x == 0) *ctr += 1; }
-
-int la_adam_step_tab(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
-                     const float* tab, const int* ctr, hipStream_t stream) {
-    if (n == 0) return LA_OK;
-    hipLaunchKernelGGL(la_adam_tab_kernel, dim3(la_cdiv(n, 256)), dim3(256), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps,
-                       reinterpret_cast<const float2*>(tab), ctr);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
-}
-int la_step_advance(int* ctr, hipStream_t stream) {
-    hipLaunchKernelGGL(la_step_advance_kernel, dim3(1), dim3(64), 0, stream, ctr);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
-}
-// Tail of an optimisation step in ONE launch (was three: la_latent_combine, la_adam_tab_kernel, la_step_advance -- each a 5 us link of
-// the step's serial chain): dw = sum over the ws slots of dws + the latent criterion's gradient (the arithmetic and its order are
-// la_latent_combine_kernel's), the Adam update with the bias corrections of step *ctr + 1 (la_adam_tab_kernel's), and the step
-// counter: every workgroup draws a ticket AFTER its threads have read *ctr; the one that draws the last ticket resets it and bumps
-// the counter -- nobody is left to read the old value.
+// Tail of an optimisation step in ONE launch (three separate ones were each a 5 us link of the step's serial chain).  Per element
+// (b, j) of the W-space latent (ws = w repeated num_ws times, util_latent_aug.py:493-494):
+//   dw[b][j] = sum_l dws[b][l][j]  +  lat2 * (num_ws * mrows * p[b][j] - sum_l colsumW[l][j])
+// both sums over the ws slots l in ascending order (eight loads in flight at a time, added in slot order), the latent criterion's
+// term added last; lat2 = sign * 2 * w_latent / (m * n * num_ws * wdim), mrows = rows of the latent bank; dws / colsumW may be null
+// (no image criterion / no latent criterion).  Then the Adam update (la_adam_update) with the bias corrections of step *ctr + 1 from
+// the device table tab[t - 1] = {1 - b1^t, sqrt(1 - b2^t)} (la_adam_fill_table: the same powf as la_adam_step_f32), so that one
+// captured launch serves every step, and the step counter (la_step_ticket).
 __global__ __launch_bounds__(256) void la_step_tail_kernel(const float* __restrict__ dws, const float* __restrict__ colsumW, float* __restrict__ dw,
                                                           float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, int num_ws,
                                                           int wdim, float lat2, float mrows, long total, float lr, float b1, float b2,
@@ -159,16 +126,11 @@ __global__ __launch_bounds__(256) void la_step_tail_kernel(const float* __restri
         const float pv = p[i];
         if (colsumW) acc += lat2 * ((float)num_ws * mrows * pv - cs);
         dw[i] = acc;
-        const float mv = b1 * m[i] + (1.f - b1) * acc;
-        const float vv = b2 * v[i] + (1.f - b2) * acc * acc;
-        m[i] = mv; v[i] = vv;
-        const float denom = sqrtf(vv) / bc.y + eps;
-        p[i] = pv - (lr / bc.x) * (mv / denom);
+        float pn = pv;
+        la_adam_update(pn, m[i], v[i], acc, lr / bc.x, bc.y, b1, b2, eps);
+        p[i] = pn;
     }
-    __syncthreads();      // every thread of the workgroup has read *ctr
-    if (threadIdx.x == 0) {
-        if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) { *ticket = 0; *ctr += 1; }
-    }
+    la_step_ticket(ctr, ticket);
 }
 
 int la_step_tail(const float* dws, const float* colsumW, float* dw, float* p, float* m, float* v, int B, int num_ws, int wdim, float lat2,

@@ -68,11 +68,6 @@ int la_torgb_forward(const float* x, const LaRgbFuse& r, int B, int C, int H, in
 // row_lo / row_hi (planes above 64x64; 0 / 0 = all): only these rows of rgb_pre / img are computed and written
 int la_seam_slabs(long HW);
 int la_seam_backward(const LaSeamArgs& a, int B, int imgc, hipStream_t);
-int la_style_backward_conv(float* ds_part, int ntiles, float* ddn_part, int nslabs, const float* d,
-                           int d_stride, const float* s, int s_stride, const float* wsq, int cin, int cout, int B,
-                           float* ds_out, int ds_stride, hipStream_t);
-int la_style_backward_rgb(const float* dweff_part, int nslabs, const float* wrgb, int C, int imgc, int B,
-                          float* ds_out, int ds_stride, hipStream_t);
 // Style-gradient finish of ALL layers of one backward pass in three launches (row sums of every partial buffer, conv layers,
 // ToRGB layers) instead of three small launches per layer: the per-layer partial buffers are kept until the end of the pass.
 #define LA_FIN_MAX_CONV 24

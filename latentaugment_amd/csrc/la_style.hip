@@ -516,18 +516,13 @@ __global__ __launch_bounds__(256) void la_seam_bwd_kernel(LaSeamArgs a) {
         gmax = fmaxf(gmax, fmaxf(fmaxf(fabsf(gz.x), fabsf(gz.y)), fmaxf(fabsf(gz.z), fabsf(gz.w))));
     }
     if (a.pmax_out || a.xs_out) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o, 64));
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = gmax;
-        __syncthreads();
+        const float m = la_block_max_256(gmax, red);
         if (threadIdx.x == 0) {
-            const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
             if (a.pmax_out) a.pmax_out[((long)b * a.C + c) * gridDim.x + slab] = m;
-            // the consumer's fp16 operand scale: this workgroup's maximum lowers a sub-slot of the sample's row (la_common.h)
+            // the consumer's fp16 operand scale: this workgroup's maximum lowers a sub-slot of the sample's row (la_common.h), against
+            // the early read of it above
             if (xs_row) la_xs_lower(xs_row, xs_seen, a.xs_mult, m);
         }
-        __syncthreads();
     }
     const float ddn_t = la_block_sum_256(ddn, red);
     if (threadIdx.x == 0 && a.ddn_part) a.ddn_part[((long)b * a.C + c) * gridDim.x + slab] = ddn_t;
@@ -562,88 +557,14 @@ int la_seam_backward(const LaSeamArgs& a, int B, int imgc, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// style-gradient finish for one conv layer:
+// Style-gradient finish of all layers of a backward pass (LaStyleFinish), three launches.  For a conv layer
 //   ds[b][i] = sum_tiles ds_part[b][i][.]  -  s[b][i] * sum_o (sum_slabs ddn_part[b][o][.]) * d[b][o]^2 * wsq[o][i]
-// pass 1 (wide): every partial row (one value per pixel tile / slab, contiguous) is summed by one wave with coalesced
-//   reads and a fixed shuffle tree (deterministic); the sum replaces element 0 of the row.
-// pass 2 (small): one thread per i (coalesced wsq reads over i), loop over o; q[b][o] staged in LDS.
-__global__ __launch_bounds__(256) void la_rows_sum_inplace_kernel(float* __restrict__ a0, long rows0, int n0,
-                                                                 float* __restrict__ a1, long rows1, int n1) {
-    const int lane = threadIdx.x & 63;
-    long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    float* row;
-    int n;
-    if (r < rows0) { row = a0 + r * n0; n = n0; }
-    else if (r - rows0 < rows1) { row = a1 + (r - rows0) * n1; n = n1; }
-    else return;
-    // The per-tile partials of a row (up to 8192 of them at 1024^2) are summed in float64: they are tiny next to the contraction
-    // that produced them, and against a smooth image gradient the sum is much smaller than its terms -- a float32 sum of the
-    // partials was the part of the style-gradient noise at 1024^2 that is NOT inherent in forming the data gradient first.
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-    int k = lane;
-    for (; k + 192 < n; k += 256) { v0 += (double)row[k]; v1 += (double)row[k + 64]; v2 += (double)row[k + 128]; v3 += (double)row[k + 192]; }
-    for (; k < n; k += 64) v0 += (double)row[k];
-    double v = (v0 + v1) + (v2 + v3);
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft, 64);
-    if (lane == 0) row[0] = (float)v;
-}
-
-__global__ __launch_bounds__(256) void la_style_bwd_conv_kernel(const float* __restrict__ ds_part, int ntiles,
-                                                               const float* __restrict__ ddn_part, int nslabs,
-                                                               const float* __restrict__ d, int d_stride,
-                                                               const float* __restrict__ s, int s_stride,
-                                                               const float* __restrict__ wsq, int cin, int cout,
-                                                               float* __restrict__ ds_out, int ds_stride) {
-    // block = 16 input channels x 16 output-channel parts (a wide grid of short loops: this kernel is pure latency);
-    // q[b][o] staged in LDS, the parts combined through LDS in a fixed order
-    extern __shared__ float q[];   // [cout] + [16][16]
-    float* comb = q + cout;
-    const int b = blockIdx.y;
-    for (int o = threadIdx.x; o < cout; o += blockDim.x) {
-        const float dv = d[(long)b * d_stride + o];
-        q[o] = ddn_part[((long)b * cout + o) * nslabs] * dv * dv;
-    }
-    __syncthreads();
-    const int il = threadIdx.x & 15, part = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + il;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (i < cin) {
-        const int per = (cout + 15) / 16;
-        const int o0 = part * per, o1 = o0 + per < cout ? o0 + per : cout;
-        int o = o0;
-        for (; o + 3 < o1; o += 4) {
-            a0 += q[o] * wsq[(long)o * cin + i];
-            a1 += q[o + 1] * wsq[(long)(o + 1) * cin + i];
-            a2 += q[o + 2] * wsq[(long)(o + 2) * cin + i];
-            a3 += q[o + 3] * wsq[(long)(o + 3) * cin + i];
-        }
-        for (; o < o1; ++o) a0 += q[o] * wsq[(long)o * cin + i];
-    }
-    comb[part * 16 + il] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (part == 0 && i < cin) {
-        float tot = 0.f;
-#pragma unroll
-        for (int p = 0; p < 16; ++p) tot += comb[p * 16 + il];
-        ds_out[(long)b * ds_stride + i] = ds_part[((long)b * cin + i) * ntiles] - s[(long)b * s_stride + i] * tot;
-    }
-}
-
-int la_style_backward_conv(float* ds_part, int ntiles, float* ddn_part, int nslabs, const float* d,
-                           int d_stride, const float* s, int s_stride, const float* wsq, int cin, int cout, int B,
-                           float* ds_out, int ds_stride, hipStream_t stream) {
-    const long rows0 = (long)B * cout, rows1 = (long)B * cin;
-    hipLaunchKernelGGL(la_rows_sum_inplace_kernel, dim3((unsigned)la_cdiv(rows0 + rows1, 4)), dim3(256), 0, stream, ddn_part, rows0,
-                       nslabs, ds_part, rows1, ntiles);
-    hipLaunchKernelGGL(la_style_bwd_conv_kernel, dim3(la_cdiv(cin, 16), B), dim3(256), (cout + 256) * sizeof(float), stream,
-                       ds_part, ntiles, ddn_part, nslabs, d, d_stride, s, s_stride, wsq, cin, cout, ds_out, ds_stride);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// One-pass finish for all layers (LaStyleFinish): same arithmetic and summation order as the per-layer kernels above.
+// and for a ToRGB layer
+//   ds[b][i] = sum_k wrgb[k][i] * sum_slabs dweff_part[b][k][i][.]
+// pass 1 (wide, la_rows_sum_all_kernel): every partial row of every layer (one value per pixel tile / slab, contiguous) is summed by
+//   one wave with coalesced reads and a fixed shuffle tree (deterministic); the sum replaces element 0 of the row.
+// pass 2 (small, one launch for the conv layers and one for the ToRGB layers): one thread per i (coalesced wsq reads over i), loop
+//   over o; q[b][o] = ddn[b][o] * d[b][o]^2 staged in LDS.
 struct LaRowSegs { int nseg; long row0[2 * LA_FIN_MAX_CONV + LA_FIN_MAX_RGB + 1]; float* ptr[2 * LA_FIN_MAX_CONV + LA_FIN_MAX_RGB]; int n[2 * LA_FIN_MAX_CONV + LA_FIN_MAX_RGB]; };
 
 __global__ __launch_bounds__(256) void la_rows_sum_all_kernel(LaRowSegs g) {
@@ -671,6 +592,8 @@ __global__ __launch_bounds__(256) void la_rows_sum_all_kernel(LaRowSegs g) {
 }
 
 __global__ __launch_bounds__(256) void la_style_bwd_conv_all_kernel(LaStyleFinish f) {
+    // block = 16 input channels x 16 output-channel parts of one layer (a wide grid of short loops: this kernel is pure latency);
+    // q[b][o] staged in LDS, the parts combined through LDS in a fixed order
     extern __shared__ float q[];   // [cout] + [16][16]
     int l = 0;
     while (l + 1 < f.nconv && (int)blockIdx.x >= f.conv[l + 1].blk0) ++l;
@@ -744,29 +667,6 @@ int la_style_backward_all(const LaStyleFinish& fin, int B, hipStream_t stream) {
         hipLaunchKernelGGL(la_rows_sum_all_kernel, dim3((unsigned)la_cdiv(g.row0[g.nseg], 4)), dim3(256), 0, stream, g);
     if (f.nconv) hipLaunchKernelGGL(la_style_bwd_conv_all_kernel, dim3(cblk, B), dim3(256), (max_cout + 256) * sizeof(float), stream, f);
     if (f.nrgb) hipLaunchKernelGGL(la_style_bwd_rgb_all_kernel, dim3(rblk, B), dim3(256), 0, stream, f);
-    LA_CHECK_LAUNCH();
-    return LA_OK;
-}
-
-// ToRGB style gradient: ds[b][i] = sum_k wrgb[k][i] * sum_slabs dweff_part[b][k][i][.]
-__global__ void la_style_bwd_rgb_kernel(const float* __restrict__ dweff_part, int nslabs, const float* __restrict__ wrgb,
-                                        int C, int imgc, float* __restrict__ ds_out, int ds_stride) {
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C) return;
-    float acc = 0.f;
-    for (int k = 0; k < imgc; ++k) {
-        float v = 0.f;
-        for (int t = 0; t < nslabs; ++t) v += dweff_part[(((long)b * imgc + k) * C + i) * nslabs + t];
-        acc += v * wrgb[k * C + i];
-    }
-    ds_out[(long)b * ds_stride + i] = acc;
-}
-
-int la_style_backward_rgb(const float* dweff_part, int nslabs, const float* wrgb, int C, int imgc, int B,
-                          float* ds_out, int ds_stride, hipStream_t stream) {
-    hipLaunchKernelGGL(la_style_bwd_rgb_kernel, dim3(la_cdiv(C, 256), B), dim3(256), 0, stream, dweff_part, nslabs,
-                       wrgb, C, imgc, ds_out, ds_stride);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }

@@ -82,22 +82,10 @@ static LaRgbFuse layer_rgb(const la_synth* h, const RgbLayer& T, const float* sk
     return LaRgbFuse{h->imgc, T.weight, h->s_all + T.s_off, h->S, T.bias, skip, T.rgb_pre, img, h->clamp};
 }
 
-static size_t align_up(size_t v) { return (v + 63) & ~(size_t)63; }
-
-struct Carver {
-    char* base; size_t off; size_t cap;
-    float* take(size_t nfloats) {
-        size_t bytes = align_up(nfloats * sizeof(float));
-        float* p = base ? (float*)(base + off) : nullptr;
-        off += bytes;
-        return p;
-    }
-};
-
 // column-planar intermediate of an up layer (la_modconv3x3_up2_fwd_ex): floats from the start of a row to its odd-column run
 static inline int zt_xhalf(int res) { return (res / 2 + 1 + 3) & ~3; }
 static int layout(la_synth* h, void* workspace, size_t cap, size_t* need) {
-    Carver c{(char*)workspace, 0, cap};
+    LaCarver c{(char*)workspace, 0, cap};
     const size_t mb = h->maxB;
     size_t gmax = 0, ztmax = 0, dsp = 0, ddn = 0, dwe = 0;
     size_t skf = 0;

@@ -124,18 +124,12 @@ __global__ __launch_bounds__(256) void la_fir4x4_s1_kernel(FirArgs a) {
         if (live) mx = la_fir4x4_plane<EPI>(a, f, xok, p, x, y0, ix0, iy0, HWin, HWout);
         if (a.pmax || a.xs_out) {      // one partial maximum per (plane, workgroup): plain store, reduced by the consumer (no atomics) ...
             __shared__ float wmax[4];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            __syncthreads();
-            if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
-            __syncthreads();
+            const float m = la_block_max_256(mx, wmax);
             if (threadIdx.x == 0) {
-                const float m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
                 if (a.pmax) a.pmax[(long)p * (gridDim.x * gridDim.y) + blockIdx.y * gridDim.x + blockIdx.x] = m;
                 if (a.xs_out) {      // ... or lowers a sub-slot of the sample's scale row for the consuming contraction (FirArgs::xs_out)
                     const int bs = p / a.C;
-                    float* row = a.xs_out + (long)bs * LA_XS_FAN + la_xs_sub(p);
-                    la_xs_lower(row, la_xs_peek(row), a.xs_mult ? a.xs_mult[bs] : 1.f, m);
+                    la_xs_lower_wg(a.xs_out, bs, a.xs_mult ? a.xs_mult[bs] : 1.f, m, p);
                 }
             }
         }
@@ -186,7 +180,6 @@ static int fir_fill(FirArgs& a, const float* in, float* out, int B, int C, int H
 // registers) 147 us; the same kernel on column-interleaved rows with three 16-byte loads per row 127 us.
 template <int EPI, int ROWS>
 __global__ __launch_bounds__(256) void la_fir4x4_s1p_kernel(FirArgs a, float4 fx, float4 fy) {
-    __shared__ unsigned smx[64];                   // xs_out: max |out| per sample of this workgroup (bit patterns: non-negative floats order like unsigned ints)
     // Work items = (plane, row strip, 4-column group) of the WANTED part of the output only (round 5): with a row / column window
     // (FirArgs::row_lo / col_lo) the grid holds the strips and column groups that contain a wanted row / column -- round 4 kept the
     // whole plane's items and let those outside return, which left the launch as long as the whole-frame one (123 us for 56 % of the
@@ -205,10 +198,6 @@ __global__ __launch_bounds__(256) void la_fir4x4_s1p_kernel(FirArgs a, float4 fx
     if (!live && !a.xs_out) return;
     const int b = (live ? p : a.P - 1) / a.C;
     float omax = 0.f;
-    if (a.xs_out) {
-        if (threadIdx.x < 64) smx[threadIdx.x] = 0u;
-        __syncthreads();
-    }
     if (live) {
         const int within = (int)(gid - (long)p * per_plane);
         const int strip = s_lo + within / gw, xg = g_lo + (within - (within / gw) * gw);
@@ -293,23 +282,10 @@ __global__ __launch_bounds__(256) void la_fir4x4_s1p_kernel(FirArgs a, float4 fx
             omax = fmaxf(omax, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
         }
     }
-    if (a.xs_out) {
-        // operand scale of `out` for its consumer (FirArgs::xs_out): per-sample maxima of the workgroup through LDS (the workgroup's 256
-        // work items are consecutive planes, i.e. a handful of consecutive samples), then one thread per sample lowers a sub-slot of
-        // that sample's row
-        const int b0 = (int)(((long)blockIdx.x * 256) / per_plane) / a.C;      // first sample of the workgroup
-        const int bi = b - b0;
-        if (live && omax > 0.f) {
-            if (bi < 64) atomicMax(&smx[bi], __float_as_uint(omax));
-            else { float* row = a.xs_out + (long)b * LA_XS_FAN + la_xs_sub(threadIdx.x); la_xs_lower(row, la_xs_peek(row), a.xs_mult ? a.xs_mult[b] : 1.f, omax); }
-        }
-        __syncthreads();
-        const int bt = b0 + (int)threadIdx.x;
-        if (threadIdx.x < 64 && smx[threadIdx.x] != 0u && bt * a.C < a.P) {
-            float* row = a.xs_out + (long)bt * LA_XS_FAN + la_xs_sub();
-            la_xs_lower(row, la_xs_peek(row), a.xs_mult ? a.xs_mult[bt] : 1.f, __uint_as_float(smx[threadIdx.x]));
-        }
-    }
+    // operand scale of `out` for its consumer (FirArgs::xs_out): the workgroup's 256 work items are consecutive planes, i.e. a handful
+    // of consecutive samples from b0 on -- one lowering per sample
+    if (a.xs_out)
+        la_xs_lower_by_sample(a.xs_out, a.xs_mult, b, (int)(((long)blockIdx.x * 256) / per_plane) / a.C, a.C, a.P, live, omax);
 }
 
 // f (4x4, effective correlation taps) == fy (x) fx ?  (rank one, as setup_filter's outer product is; tolerance 1e-6 relative)
@@ -331,17 +307,12 @@ int la_fir4x4_segments(int Hout, int Wout) { return la_cdiv(Wout, 64) * la_cdiv(
 // then columns, ascending) as the generic kernel above, without its per-output tap search; work item = 2 x 4 (up) / 1 x 2 (down)
 // outputs, flat over all planes.
 __global__ __launch_bounds__(256) void la_fir4x4_up2_kernel(FirArgs a) {      // up 2, pad0 2: out [2H][2W]
-    __shared__ unsigned smx[64];                                 // xs_out: max |out| per sample of this workgroup (as la_fir4x4_s1p_kernel)
     const int wq = a.Wout >> 2;                                  // 4-column groups per output row
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     const long per_plane = (long)a.Hin * wq;
     const int pp = (int)(gid / per_plane);
     const bool live = pp < a.P;
     if (!live && !a.xs_out) return;
-    if (a.xs_out) {
-        if (threadIdx.x < 64) smx[threadIdx.x] = 0u;
-        __syncthreads();
-    }
     const int p = live ? pp : a.P - 1;
     float omax = 0.f;
     if (live) {
@@ -387,20 +358,9 @@ __global__ __launch_bounds__(256) void la_fir4x4_up2_kernel(FirArgs a) {      //
         omax = fmaxf(omax, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
     }
     }
-    if (a.xs_out) {      // operand scale of `out` for its consumer: per-sample maxima of the workgroup through LDS, one lowering per sample
-        const int b = p / a.C, b0 = (int)(((long)blockIdx.x * 256) / per_plane) / a.C;
-        const int bi = b - b0;
-        if (live && omax > 0.f) {
-            if (bi < 64) atomicMax(&smx[bi], __float_as_uint(omax));
-            else { float* row = a.xs_out + (long)b * LA_XS_FAN + la_xs_sub(threadIdx.x); la_xs_lower(row, la_xs_peek(row), a.xs_mult ? a.xs_mult[b] : 1.f, omax); }
-        }
-        __syncthreads();
-        const int bt = b0 + (int)threadIdx.x;
-        if (threadIdx.x < 64 && smx[threadIdx.x] != 0u && bt * a.C < a.P) {
-            float* row = a.xs_out + (long)bt * LA_XS_FAN + la_xs_sub();
-            la_xs_lower(row, la_xs_peek(row), a.xs_mult ? a.xs_mult[bt] : 1.f, __uint_as_float(smx[threadIdx.x]));
-        }
-    }
+    // operand scale of `out` for its consumer: one lowering per sample of the workgroup (as la_fir4x4_s1p_kernel)
+    if (a.xs_out)
+        la_xs_lower_by_sample(a.xs_out, a.xs_mult, p / a.C, (int)(((long)blockIdx.x * 256) / per_plane) / a.C, a.C, a.P, live, omax);
 }
 
 __global__ __launch_bounds__(256) void la_fir4x4_down2_kernel(FirArgs a) {    // down 2, pad0 1: out [H/2][W/2]

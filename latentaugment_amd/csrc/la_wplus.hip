@@ -7,9 +7,10 @@
 
 // Tail of a W+ optimisation step in ONE launch, the W+ counterpart of la_step_tail_kernel (la_misc.hip): per element (b, l, j)
 //   g = dws[b][l][j] + lat2 * (Mw * p[b][l][j] - colsumW[l][j])
-// (no sum over the slots: each slot is a parameter of its own), the Adam update with the bias corrections of step *ctr + 1 from
-// the device table, and the same ticket scheme for the step counter.  Four elements per thread: w_dim % 4 == 0 and 16-byte
-// aligned buffers (checked by the caller).  dws / colsumW may be null (no image criterion / no latent criterion).
+// (no sum over the slots: each slot is a parameter of its own; the latent criterion's term is added to the slot's gradient), then
+// the Adam update (la_adam_update, component by component) with the bias corrections of step *ctr + 1 from the device table
+// tab[t - 1] = {1 - b1^t, sqrt(1 - b2^t)}, and the step counter (la_step_ticket).  Four elements per thread: w_dim % 4 == 0 and
+// 16-byte aligned buffers (checked by the caller).  dws / colsumW may be null (no image criterion / no latent criterion).
 __global__ __launch_bounds__(256) void la_wplus_step_tail_kernel(const float4* __restrict__ dws, const float4* __restrict__ colsumW,
                                                                 float4* __restrict__ dw, float4* __restrict__ p, float4* __restrict__ m,
                                                                 float4* __restrict__ v, long row4, float lat2, float mrows, long total4,
@@ -28,21 +29,15 @@ __global__ __launch_bounds__(256) void la_wplus_step_tail_kernel(const float4* _
             g.w += lat2 * (mrows * pv.w - cs.w);
         }
         dw[i] = g;
-        const float4 mo = m[i], vo = v[i];
-        float4 mv, vv, pn;
+        float4 mv = m[i], vv = v[i], pn = pv;
         const float step = lr / bc.x;
-#define LA_WP_ADAM(c)                                                   \
-        mv.c = b1 * mo.c + (1.f - b1) * g.c;                            \
-        vv.c = b2 * vo.c + (1.f - b2) * g.c * g.c;                      \
-        pn.c = pv.c - step * (mv.c / (sqrtf(vv.c) / bc.y + eps));
-        LA_WP_ADAM(x) LA_WP_ADAM(y) LA_WP_ADAM(z) LA_WP_ADAM(w)
-#undef LA_WP_ADAM
+        la_adam_update(pn.x, mv.x, vv.x, g.x, step, bc.y, b1, b2, eps);
+        la_adam_update(pn.y, mv.y, vv.y, g.y, step, bc.y, b1, b2, eps);
+        la_adam_update(pn.z, mv.z, vv.z, g.z, step, bc.y, b1, b2, eps);
+        la_adam_update(pn.w, mv.w, vv.w, g.w, step, bc.y, b1, b2, eps);
         m[i] = mv; v[i] = vv; p[i] = pn;
     }
-    __syncthreads();      // every thread of the workgroup has read *ctr
-    if (threadIdx.x == 0) {
-        if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) { *ticket = 0; *ctr += 1; }
-    }
+    la_step_ticket(ctr, ticket);
 }
 
 static bool al16(const void* p) { return ((size_t)p & 15) == 0; }

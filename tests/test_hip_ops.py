@@ -251,7 +251,7 @@ def _modconv_case(dev, B, cin, cout, res, up, noise_strength, seed, splitk=True,
         _lib.check(lib.la_modconv3x3_bwd_f32(_lib.ptr(gz), _lib.ptr(wb), _lib.ptr(wqb), prec, _lib.ptr(sd), cin, _lib.ptr(xd), cin * rin * rin,
                                              _lib.ptr(gx), _lib.ptr(dsp), _lib.ptr(skw), skn, B, cin, cout, res, st))
     close(gx, gxr, rtol=1e-4 * tol, atol=1e-5 * float(gxr.abs().max()) * tol)
-    # style gradient = modulation term (partials) + demodulation term (test-side, mirrors la_style_backward_conv)
+    # style gradient = modulation term (partials) + demodulation term (test-side, mirrors la_style_bwd_conv_all_kernel)
     zd = torch.where(y > 0, y / sq2, y / (0.2 * sq2)) - bd[None, :, None, None] - nd[None, None] * noise_strength
     ddn = (g1 * zd).sum(dim=[2, 3])
     ds = dsp.sum(dim=2) - sd * ((ddn * d * d) @ wsq)
