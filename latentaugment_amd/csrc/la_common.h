@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+
+#include <memory>
 
 // The public C ABI: every translation unit sees the prototypes, structs and LA_* constants it defines or calls from the one header
 // that callers get, so a definition that disagrees with it does not compile.  (la_stream_t there is hipStream_t.)
@@ -74,6 +77,16 @@ struct LaCarver {
         return p;
     }
 };
+
+// A host handle (plain data, malloc'ed: the destroy entries free() it), owned by its create entry until that releases it into *out
+struct LaFree { void operator()(void* p) const { free(p); } };
+template <class H> using LaHostHandle = std::unique_ptr<H, LaFree>;
+template <class H> static inline LaHostHandle<H> la_host_handle() { return LaHostHandle<H>((H*)malloc(sizeof(H))); }
+// the *_workspace_bytes entries: `measure` describes a scratch handle and lays it out on a null base (0: bad description)
+template <class H, class F> static inline size_t la_measure_workspace(F measure) {
+    const LaHostHandle<H> h = la_host_handle<H>();
+    return h ? measure(h.get()) : 0;
+}
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float la_wave_sum(float v) {

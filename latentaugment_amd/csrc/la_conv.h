@@ -169,6 +169,26 @@ static inline void la_conv_taps_3x3_corner(LaConvArgs& a) {
     a.ntaps = 9;
     for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3; a.tap_dx[t] = t % 3; a.tap_w[t] = t; }
 }
+// Launch geometries on top of a.C (la_conv_weights_select).  k x k conv (pad k / 2) at one resolution, or its backward-data contraction ...
+static inline void la_conv_geom_same(LaConvArgs& a, int res, int k, bool backward) {
+    a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
+    a.in_bstride = (long)a.C * res * res;
+    la_conv_taps_kxk(a, k, backward);
+}
+// ... and the stride-2 3x3 gather over a (res+1)^2 input onto a (res/2)^2 grid (D's down-sampling conv; backward-data of an up layer)
+static inline void la_conv_geom_down2(LaConvArgs& a, int res) {
+    a.Hin = a.Win = res + 1; a.Hout = a.Wout = a.Gy = a.Gx = res / 2;
+    a.in_sy = a.in_sx = 2;
+    a.in_bstride = (long)a.C * (res + 1) * (res + 1);
+    la_conv_taps_3x3_corner(a);
+}
+// the forward epilogue of a layer (demod and noise null: a plain bias / activation epilogue)
+static inline void la_conv_set_epi(LaConvArgs& a, const LaLayerEpi& e) {
+    a.epi = LA_EPI_FWD;
+    a.demod = e.demod; a.demod_stride = e.demod_stride;
+    a.noise = e.noise; a.noise_bstride = e.noise_bstride; a.noise_strength = e.noise_strength;
+    a.bias = e.bias; a.act = e.act; a.alpha = e.alpha; a.gain = e.gain; a.clamp = e.clamp;
+}
 // Output phase (py, px) of the transposed stride-2 3x3 conv over an hin^2 input: row Y = 2 * qy + py receives the taps ky with
 // (Y - ky) even.  Sets the launch-wide grid, offset (column phase px at out_ox = px * ox_step) and taps; merged: also appends them
 // as the next phase of a one-launch form (LaConvArgs::nphase).
@@ -195,14 +215,49 @@ long la_conv_bf16_pack_elems(int M, int C, int ktaps);   // elements per term
 int la_pack_conv_weights_bf16(const float* w, void* out, int cout, int cin, int ktaps, int transpose, int nterm,
                               hipStream_t stream, float scale = 1.f, int m_pad = 0);
 int la_conv_bf16_dispatch(const LaConvArgs& as, int MTsel, dim3 grid, bool split, hipStream_t stream);
+// bytes of one weight pack serving every split precision
+size_t la_conv_split_pack_bytes(int M, int C, int ktaps);
+// fp32 slabs wf [ktaps][cin][cout], wb [ktaps][cout][wb_ld] and wsq [cin][cout] = sum over taps of w^2 (each optional) of w * scale (la_style.hip)
+int la_pack_conv_weights(const float* w, float* wf, float* wb, float* wsq, int cout, int cin, int ktaps, hipStream_t,
+                         float scale = 1.f, int wb_ld = 0);   // wb_ld > cin: backward slab rows padded with zero columns
+
+// The weights of one conv layer as the contraction reads them, both directions, every precision.
+struct LaConvWeights {
+    int cin, cout, k;
+    int cin_pad;             // output channels of the backward contraction: cin padded to a multiple of 4 (the padded ones come out as zeros)
+    const float* w;          // the layer's parameter [cout][cin][k][k]
+    float *wf, *wb, *wsq;    // fp32 slabs, forward / backward; wsq: optional (demodulation)
+    void *wqf, *wqb;         // split packs, forward / backward
+};
+static inline void la_conv_weights_shape(LaConvWeights& L, int cin, int cout, int k) {
+    L.cin = cin; L.cout = cout; L.k = k; L.cin_pad = (cin + 3) & ~3;
+}
+static inline void la_conv_weights_layout(LaCarver& c, LaConvWeights& L, bool with_wsq = false) {
+    const size_t kk = (size_t)L.k * L.k;
+    L.wf = c.take((size_t)L.cin * L.cout * kk); L.wb = c.take((size_t)L.cin_pad * L.cout * kk);
+    L.wsq = with_wsq ? c.take((size_t)L.cin * L.cout) : nullptr;
+    L.wqf = c.take((la_conv_split_pack_bytes(L.cout, L.cin, (int)kk) + 3) / 4);
+    L.wqb = c.take((la_conv_split_pack_bytes(L.cin_pad, L.cout, (int)kk) + 3) / 4);
+}
+// packs L.w * gain (stream-ordered)
+static inline int la_conv_weights_pack(const LaConvWeights& L, float gain, hipStream_t stream) {
+    int rc = la_pack_conv_weights(L.w, L.wf, L.wb, L.wsq, L.cout, L.cin, L.k * L.k, stream, gain, L.cin_pad);
+    if (!rc) rc = la_pack_conv_weights_bf16(L.w, L.wqf, L.cout, L.cin, L.k * L.k, 0, 3, stream, gain);
+    if (!rc) rc = la_pack_conv_weights_bf16(L.w, L.wqb, L.cout, L.cin, L.k * L.k, 1, 3, stream, gain, L.cin_pad);
+    return rc;
+}
+// the weights and channel counts of a launch in one direction (backward: the transposed contraction, cout -> cin_pad)
+static inline void la_conv_weights_select(LaConvArgs& a, const LaConvWeights& L, bool backward) {
+    a.wgt = backward ? L.wb : L.wf; a.wgt_bf16 = backward ? L.wqb : L.wqf;
+    a.C = backward ? L.cout : L.cin; a.M = backward ? L.cin_pad : L.cout;
+    a.wgt_bf16_term_elems = la_conv_bf16_pack_elems(a.M, a.C, L.k * L.k);
+}
 
 // scratch floats that let every <= 32x32 launch of a (B, M) problem use split-K: slices * B * M * G, G <= 1024
 long la_conv_splitk_floats(int B, int M, int C, int Gy, int Gx, int precision);
 long la_conv_splitk_floats_phases(int B, int M, int C, int nphase, const int* Gy, const int* Gx, int precision);
 // bytes of the pre-split copy of an input [B][C][Hin][Win] (split paths; sized for the larger, 8 B/element format)
 size_t la_conv_presplit_bytes(int B, int C, int Hin, int Win);
-// bytes of one weight pack serving every split precision
-size_t la_conv_split_pack_bytes(int M, int C, int ktaps);
 // If a.precision needs a pre-split input and a.in_q is not set: split a.in (* a.in_scale) into the head of a.ws, point
 // a.in_q / a.acc_scale_x at it and advance a.ws / a.ws_bytes past it.  Callers that launch several phases over one input
 // call this once.  bf16: {hi | mid << 16, lo} (8 B / element);  fp16: per-sample power-of-two scale, {hi | lo << 16} (4 B).
@@ -221,3 +276,27 @@ bool la_conv_bf16_uses_halo(const LaConvArgs& a);     // fp32-input halo kernel 
 // number of pixel tiles per sample for a launch (the ds_part leading dimension)
 int la_conv_tiles_per_sample(int Gy, int Gx);
 int la_conv_launch(const LaConvArgs& a, hipStream_t stream);
+
+// Transposed stride-2 3x3 conv of an [B][C][hin][hin] input into a raw (2 hin + 1)-row intermediate: dense rows (pitch = xhalf = 0), or
+// COLUMN-PLANAR rows of `pitch` floats -- even output columns from 0, odd ones from xhalf on -- so that every output phase stores
+// contiguous runs.  The caller has set input, weights, operand scale, mask and windows.  16-bit precisions: the input is split once
+// and the four phases run in ONE launch -- above the split-K sizes each phase launch would end in a nearly empty round, at the
+// split-K sizes (<= 34x34 phase grids) four launches + four finish passes become one of each; fp32: a launch per phase.
+static inline int la_conv_up2_launch(LaConvArgs& a, int hin, int pitch, int xhalf, hipStream_t stream) {
+    const int res = 2 * hin;
+    a.Hin = a.Win = hin; a.Hout = a.Wout = res + 1;
+    a.out_sy = a.out_sx = 2; a.epi = LA_EPI_RAW;
+    if (pitch > 0) { a.out_pitch = pitch; a.out_plane = (long)pitch * (res + 1); }      // padded (2h+1)-wide rows
+    if (xhalf > 0) { a.out_sx = 1; a.Wout = pitch; }      // phase px writes the contiguous run from px * xhalf
+    const bool merged = a.precision != LA_PREC_F32;
+    int rc;
+    if (merged && (rc = la_conv_prepare_input(a, stream))) return rc;
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px) {
+            la_conv_up2_phase(a, hin, py, px, xhalf > 0 ? xhalf : 1, merged);
+            if (!merged && (rc = la_conv_launch(a, stream))) return rc;
+        }
+    if (!merged) return LA_OK;
+    a.out_oy = a.out_ox = 0; a.Gy = a.Gx = hin + 1; a.ntaps = 4;      // launch-wide fields = the largest phase (checks only)
+    return la_conv_launch(a, stream);
+}

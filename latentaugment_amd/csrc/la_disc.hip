@@ -18,12 +18,8 @@
 
 #define DMAX_BLOCKS 12
 
-struct DConv {
-    int cin, cout, k;
-    int mb_;                     // backward output channels, padded to a multiple of 4 (= cin for every layer but b4.conv)
-    const float *w, *bias;
-    float *wf, *wb;
-    void *wqf, *wqb;
+struct DConv : LaConvWeights {      // (cin_pad = cin for every layer but b4.conv)
+    const float* bias;
 };
 
 struct DBlock {
@@ -55,13 +51,6 @@ struct la_disc {
 };
 
 static inline int dz_xhalf(int res) { return (res / 2 + 1 + 3) & ~3; }      // column-planar rows of a (res+1)-wide intermediate: odd columns start here
-static void dconv_layout(LaCarver& c, DConv& L) {
-    L.mb_ = (L.cin + 3) & ~3;
-    const size_t kk = (size_t)L.k * L.k;
-    L.wf = c.take((size_t)L.cin * L.cout * kk); L.wb = c.take((size_t)L.mb_ * L.cout * kk);
-    L.wqf = c.take((la_conv_split_pack_bytes(L.cout, L.cin, (int)kk) + 3) / 4);
-    L.wqb = c.take((la_conv_split_pack_bytes(L.mb_, L.cout, (int)kk) + 3) / 4);
-}
 
 static int d_describe(la_disc* h, int R, int imgc, const int* channels, int maxB) {
     LA_CHECK_ARG(R >= 8 && (R & (R - 1)) == 0, "disc: resolution must be a power of two >= 8");
@@ -82,11 +71,11 @@ static int d_describe(la_disc* h, int R, int imgc, const int* channels, int maxB
         for (int r = 4; r < b.res; r <<= 1) ++idx;
         b.cin = channels[idx]; b.cout = channels[idx - 1];
         LA_CHECK_ARG(b.cin % 4 == 0 && b.cout % 4 == 0, "disc: channel counts must be multiples of 4");
-        b.conv0 = DConv{b.cin, b.cin, 3}; b.conv1 = DConv{b.cin, b.cout, 3}; b.skip = DConv{b.cin, b.cout, 1};
+        la_conv_weights_shape(b.conv0, b.cin, b.cin, 3); la_conv_weights_shape(b.conv1, b.cin, b.cout, 3); la_conv_weights_shape(b.skip, b.cin, b.cout, 1);
     }
     (void)nres;
     h->C4 = channels[0];
-    h->econv = DConv{h->C4 + 1, h->C4, 3};
+    la_conv_weights_shape(h->econv, h->C4 + 1, h->C4, 3);
     return LA_OK;
 }
 
@@ -99,7 +88,7 @@ static size_t d_layout(la_disc* h, void* ws) {
         const size_t hw = (size_t)b.res * b.res, hq = hw / 4;
         { const size_t p0 = mb * b.cin * la_conv_act_grad_segments((long)hw), p1 = mb * b.cout * la_conv_act_grad_segments((long)hq);
           if (p0 > pmax) pmax = p0; if (p1 > pmax) pmax = p1; }
-        dconv_layout(c, b.conv0); dconv_layout(c, b.conv1); dconv_layout(c, b.skip);
+        la_conv_weights_layout(c, b.conv0); la_conv_weights_layout(c, b.conv1); la_conv_weights_layout(c, b.skip);
         if (k == 0) { b.xin = c.take(mb * b.cin * hw); b.frgb_wt = c.take((size_t)h->imgc * b.cin); }
         b.y0 = c.take(mb * b.cin * hw);
         b.x1 = c.take(mb * b.cout * hq); b.ysk = c.take(mb * b.cout * hq); b.sum = c.take(mb * b.cout * hq);
@@ -115,7 +104,7 @@ static size_t d_layout(la_disc* h, void* ws) {
         w = la_modconv_workspace_bytes((int)mb, b.cin, b.cout, b.res / 2, 0); if (w > cw) cw = w;   // 1x1 at res/2
         w = la_modconv_workspace_bytes((int)mb, b.cout, b.cin, b.res / 2, 0); if (w > cw) cw = w;
     }
-    dconv_layout(c, h->econv);
+    la_conv_weights_layout(c, h->econv);
     { size_t w = la_modconv_workspace_bytes((int)mb, h->C4 + 1, h->C4 + 1, 4, 0); if (w > cw) cw = w; }
     h->mb = c.take(mb * (h->C4 + 1) * 16); h->yc = c.take(mb * h->C4 * 16); h->fc = c.take(mb * h->C4);
     h->xs_fwd = c.take(mb * LA_XS_FAN);
@@ -135,12 +124,7 @@ extern "C" int la_disc_num_params(int img_resolution) {
 }
 
 extern "C" size_t la_disc_workspace_bytes(int img_resolution, int img_channels, const int* channels, int max_batch) {
-    la_disc* h = (la_disc*)malloc(sizeof(la_disc));
-    if (!h) return 0;
-    size_t need = 0;
-    if (d_describe(h, img_resolution, img_channels, channels, max_batch) == LA_OK) need = d_layout(h, nullptr);
-    free(h);
-    return need;
+    return la_measure_workspace<la_disc>([&](la_disc* h) { return d_describe(h, img_resolution, img_channels, channels, max_batch) == LA_OK ? d_layout(h, nullptr) : 0; });
 }
 
 __global__ void la_transpose_scale_kernel(const float* __restrict__ w, float* __restrict__ wt, int M, int C, float scale) {
@@ -150,12 +134,8 @@ __global__ void la_transpose_scale_kernel(const float* __restrict__ w, float* __
     wt[(long)c * M + m] = w[i] * scale;
 }
 
-static int dconv_pack(DConv& L, hipStream_t stream) {
-    const float g = 1.0f / sqrtf((float)(L.cin * L.k * L.k));      // Conv2dLayer.weight_gain
-    int rc = la_pack_conv_weights(L.w, L.wf, L.wb, nullptr, L.cout, L.cin, L.k * L.k, stream, g, L.mb_);
-    if (!rc) rc = la_pack_conv_weights_bf16(L.w, L.wqf, L.cout, L.cin, L.k * L.k, 0, 3, stream, g);
-    if (!rc) rc = la_pack_conv_weights_bf16(L.w, L.wqb, L.cout, L.cin, L.k * L.k, 1, 3, stream, g, L.mb_);
-    return rc;
+static int dconv_pack(const DConv& L, hipStream_t stream) {
+    return la_conv_weights_pack(L, 1.0f / sqrtf((float)(L.cin * L.k * L.k)), stream);      // Conv2dLayer.weight_gain
 }
 
 // params (device tensors, names of legacy.py:271-288), resolution R first:
@@ -166,13 +146,14 @@ extern "C" int la_disc_create(int img_resolution, int img_channels, const int* c
                               const float* const* params, int nparams, const float* fir_host, int mbstd_group_size,
                               int max_batch, void* workspace, size_t workspace_bytes, hipStream_t stream, la_disc** out) {
     LA_CHECK_ARG(params && fir_host && workspace && out, "disc_create: null pointer");
-    la_disc* h = (la_disc*)malloc(sizeof(la_disc));
+    auto own = la_host_handle<la_disc>();
+    la_disc* h = own.get();
     LA_CHECK_ARG(h, "disc_create: out of host memory");
     int rc = d_describe(h, img_resolution, img_channels, channels, max_batch);
-    if (rc) { free(h); return rc; }
-    if (nparams != la_disc_num_params(img_resolution)) { free(h); la_set_error("disc_create: parameter list length mismatch"); return LA_ERR_ARG; }
-    for (int i = 0; i < nparams; ++i) if (!params[i]) { free(h); la_set_error("disc_create: null parameter tensor"); return LA_ERR_ARG; }
-    if (d_layout(h, workspace) > workspace_bytes) { free(h); la_set_error("disc_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    if (rc) return rc;
+    LA_CHECK_ARG(nparams == la_disc_num_params(img_resolution), "disc_create: parameter list length mismatch");
+    for (int i = 0; i < nparams; ++i) LA_CHECK_ARG(params[i], "disc_create: null parameter tensor");
+    if (d_layout(h, workspace) > workspace_bytes) { la_set_error("disc_create: workspace too small"); return LA_ERR_WORKSPACE; }
     h->clamp = conv_clamp; h->mbstd_group = mbstd_group_size > 0 ? mbstd_group_size : 4;
     memcpy(h->fir, fir_host, sizeof(float) * 16);
     int p = 0;
@@ -195,20 +176,20 @@ extern "C" int la_disc_create(int img_resolution, int img_channels, const int* c
         h->fc_w = params[p++]; h->fc_b = params[p++]; h->out_w = params[p++]; h->out_b = params[p++];
         rc = dconv_pack(h->econv, stream);
     }
-    if (rc) { free(h); return rc; }
+    if (rc) return rc;
     {   // bound 4 * clamp covers every forward input (see xs_fwd); the scale is the power of two that puts the bound in [2^14, 2^15)
         int e = 0;
         frexpf(4.f * (conv_clamp > 0.f ? conv_clamp : 1.f), &e);
         const int nb = max_batch < 256 ? max_batch : 256;
         float* hx = (float*)malloc(sizeof(float) * (size_t)nb * LA_XS_FAN);      // (slot rows: every sub-slot holds the constant)
-        if (!hx) { free(h); la_set_error("disc_create: out of host memory"); return LA_ERR_ARG; }
+        LA_CHECK_ARG(hx, "disc_create: out of host memory");
         for (size_t i = 0; i < (size_t)nb * LA_XS_FAN; ++i) hx[i] = ldexpf(1.f, 15 - e);
         const hipError_t ce = hipMemcpyAsync(h->xs_fwd, hx, sizeof(float) * (size_t)nb * LA_XS_FAN, hipMemcpyHostToDevice, stream);
         const hipError_t se = hipStreamSynchronize(stream);
         free(hx);
-        if (ce != hipSuccess || se != hipSuccess) { free(h); la_set_error("disc_create: copying the operand scales failed"); return LA_ERR_HIP; }
+        if (ce != hipSuccess || se != hipSuccess) { la_set_error("disc_create: copying the operand scales failed"); return LA_ERR_HIP; }
     }
-    *out = h;
+    *out = own.release();
     return LA_OK;
 }
 
@@ -459,33 +440,23 @@ __global__ void la_disc_loss_kernel(const float* __restrict__ logits, float* __r
     }
 }
 
-static void set_w(LaConvArgs& a, la_disc* h, const DConv& L, bool backward) {
-    a.wgt = backward ? L.wb : L.wf;
-    a.precision = h->precision; a.wgt_bf16 = backward ? L.wqb : L.wqf;
-    a.wgt_bf16_term_elems = la_conv_bf16_pack_elems(backward ? L.mb_ : L.cout, backward ? L.cout : L.cin, L.k * L.k);
-    a.ws = h->cws; a.ws_bytes = h->cws_bytes;
+// What every contraction of D starts from: the layer's weights of the direction, arithmetic, scratch, and the fp16 operand scale of
+// its input -- slot rows left by the producer of the input (xs_rows), else for a forward launch the constant a-priori scale: every
+// forward input of D is bounded by 4 * conv_clamp.  Backward without rows: the caller names plane maxima (in_pmax).
+static void start_args(LaConvArgs& a, const la_disc* h, const DConv& L, bool backward, int B, const float* xs_rows) {
+    la_conv_args_init(a);
+    la_conv_weights_select(a, L, backward);
+    a.precision = h->precision; a.ws = h->cws; a.ws_bytes = h->cws_bytes; a.B = B;
+    if (xs_rows) { a.acc_scale_x = xs_rows; a.acc_scale_fan = LA_XS_FAN; }
+    else if (!backward && h->precision == LA_PREC_F16X2 && h->clamp > 0.f && h->maxB <= 256) { a.acc_scale_x = h->xs_fwd; a.acc_scale_fan = LA_XS_FAN; }
 }
+// forward epilogue of a Conv2dLayer: bias, activation (lrelu slope 0.2), gain, clamp
+static LaLayerEpi d_epi(const DConv& L, int act, float gain, float clamp) { return LaLayerEpi{nullptr, 0, nullptr, 0, 0.f, L.bias, act, 0.2f, gain, clamp}; }
 
-// dense conv (k = 3 pad 1, or k = 1) at one resolution, forward (with bias/act epilogue) or backward-data (plain)
-static int conv_same(la_disc* h, const DConv& L, bool backward, const float* in, float* out, int B, int res, int act, float gain,
-                     float clamp, const float* addend, float* out2, hipStream_t stream, const float* in_pmax = nullptr, int in_nseg = 0,
-                     const float* xs_rows = nullptr, float in_gain = 1.f, float* xs_out = nullptr) {
-    LaConvArgs a; la_conv_args_init(a);
-    set_w(a, h, L, backward);
-    a.in = in; a.out = out; a.B = B; a.in_pmax = in_pmax; a.in_pmax_nseg = in_nseg;
-    if (xs_rows) { a.acc_scale_x = xs_rows; a.acc_scale_fan = LA_XS_FAN; a.in_pmax = nullptr; }      // slot rows left by the producer of `in`
-    a.in_gain = in_gain;
-    a.C = backward ? L.cout : L.cin; a.M = backward ? L.mb_ : L.cout;      // (padded channels of a backward come out as zeros)
-    a.in_bstride = (long)a.C * res * res;
-    a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
-    la_conv_taps_kxk(a, L.k, backward);
-    if (backward) { a.epi = LA_EPI_BWD; }
-    else {
-        a.epi = LA_EPI_FWD; a.bias = L.bias; a.act = act; a.alpha = 0.2f; a.gain = gain; a.clamp = clamp; a.addend = addend; a.out2 = out2;
-        a.fwd_xs_out = xs_out;
-        // (no slot rows given: the constant a-priori scale -- every forward input of D is bounded by 4 * conv_clamp)
-        if (!xs_rows && h->precision == LA_PREC_F16X2 && h->clamp > 0.f && h->maxB <= 256) { a.acc_scale_x = h->xs_fwd; a.acc_scale_fan = LA_XS_FAN; }
-    }
+// dense conv (k = 3 pad 1, or k = 1) at one resolution on started args: forward with the epilogue the caller set, or backward-data (plain)
+static int conv_same(LaConvArgs& a, const DConv& L, bool backward, int res, hipStream_t stream) {
+    la_conv_geom_same(a, res, L.k, backward);
+    if (backward) a.epi = LA_EPI_BWD;
     return la_conv_launch(a, stream);
 }
 
@@ -517,42 +488,40 @@ extern "C" int la_disc_forward(la_disc* h, const float* img, int B, hipStream_t 
         }
         // skip: FIR (pad 1,1,1,1) + decimate 2, then 1x1 conv, linear * sqrt(1/2)      (conv2d_resample.py:94-97)
         if ((rc = la_upfirdn2d_ex(b.xin, h->scrB, B, b.cin, res, res, h->fir, la_fir_down2(), stream))) return rc;
-        if ((rc = conv_same(h, b.skip, false, h->scrB, b.ysk, B, hq, LA_ACT_LINEAR, rs2, -1.f, nullptr, nullptr, stream, nullptr, 0, rows_x(k)))) return rc;
+        LaConvArgs a; start_args(a, h, b.skip, false, B, rows_x(k));
+        a.in = h->scrB; a.out = b.ysk; la_conv_set_epi(a, d_epi(b.skip, LA_ACT_LINEAR, rs2, -1.f));
+        if ((rc = conv_same(a, b.skip, false, hq, stream))) return rc;
         // conv0
-        if ((rc = conv_same(h, b.conv0, false, b.xin, b.y0, B, res, LA_ACT_LRELU, sq2, h->clamp, nullptr, nullptr, stream, nullptr, 0, rows_x(k), 1.f, rows_y(k)))) return rc;
+        start_args(a, h, b.conv0, false, B, rows_x(k));
+        a.in = b.xin; a.out = b.y0; la_conv_set_epi(a, d_epi(b.conv0, LA_ACT_LRELU, sq2, h->clamp)); a.fwd_xs_out = rows_y(k);
+        if ((rc = conv_same(a, b.conv0, false, res, stream))) return rc;
         // conv1: FIR pad (2,2,2,2) -> (res+1)^2, stride-2 conv, lrelu * sqrt2 * sqrt(1/2), clamp * sqrt(1/2); + skip  (:106-109)
         // fp16 x2 mode with the a-priori operand scale: the FIR writes its result ALREADY as the contraction's packed operand (scale,
         // fp16 split, channel interleave: la_fir4x4_adj_pack_kernel with the forward taps) -- one pass instead of the scalar FIR into a
         // (res+1)^2 fp32 scratch + the pre-split copy of that scratch
-        const size_t qbytes = (size_t)B * la_cdiv(b.cin, 32) * 32 * (res + 1) * (res + 1) * 4;
+        const size_t qbytes = la_fir4x4_adjoint_pack_bytes(B, b.cin, res, res);
         const bool fir_pack = slots && res % 4 == 0 && h->cws_bytes > qbytes + 1024;
         if (!fir_pack && (rc = la_upfirdn2d_ex(b.y0, h->scrA, B, b.cin, res, res, h->fir, la_fir_same_pad2(0, 1.f), stream))) return rc;
-        {
-            LaConvArgs a; la_conv_args_init(a);
-            set_w(a, h, b.conv1, false);
-            if (fir_pack) {
-                unsigned* q = reinterpret_cast<unsigned*>(h->cws);
-                if ((rc = la_fir4x4_adjoint_pack_f16(b.y0, q, rows_y(k), LA_XS_FAN, B, b.cin, res, res, h->fir, 1.f, stream, 1))) return rc;
-                const size_t used = (qbytes + 255) & ~(size_t)255;
-                a.in_q = q; a.ws = static_cast<char*>(h->cws) + used; a.ws_bytes = h->cws_bytes - used;
-            }
-            a.in = h->scrA; a.in_bstride = (long)b.cin * (res + 1) * (res + 1); a.out = b.x1;
-            a.B = B; a.C = b.cin; a.M = b.cout; a.Hin = a.Win = res + 1; a.Hout = a.Wout = a.Gy = a.Gx = hq;
-            a.in_sy = a.in_sx = 2;
-            la_conv_taps_3x3_corner(a);
-            a.epi = LA_EPI_FWD; a.bias = b.conv1.bias; a.act = LA_ACT_LRELU; a.alpha = 0.2f; a.gain = sq2 * rs2;
-            a.clamp = h->clamp >= 0.f ? h->clamp * rs2 : -1.f;
-            a.addend = b.ysk; a.out2 = b.sum;
-            a.fwd_xs_out = rows_x(k + 1);      // (the residual sum out2 is what the next block reads)
-            if (slots) { a.acc_scale_x = rows_y(k); a.acc_scale_fan = LA_XS_FAN; }
-            else if (h->precision == LA_PREC_F16X2 && h->clamp > 0.f && h->maxB <= 256) { a.acc_scale_x = h->xs_fwd; a.acc_scale_fan = LA_XS_FAN; }
-            if ((rc = la_conv_launch(a, stream))) return rc;
+        start_args(a, h, b.conv1, false, B, rows_y(k));
+        if (fir_pack) {
+            unsigned* q = reinterpret_cast<unsigned*>(h->cws);
+            if ((rc = la_fir4x4_adjoint_pack_f16(b.y0, q, rows_y(k), LA_XS_FAN, B, b.cin, res, res, h->fir, 1.f, stream, 1))) return rc;
+            const size_t used = (qbytes + 255) & ~(size_t)255;
+            a.in_q = q; a.ws = static_cast<char*>(h->cws) + used; a.ws_bytes = h->cws_bytes - used;
         }
+        a.in = h->scrA; a.out = b.x1;
+        la_conv_geom_down2(a, res);
+        la_conv_set_epi(a, d_epi(b.conv1, LA_ACT_LRELU, sq2 * rs2, h->clamp >= 0.f ? h->clamp * rs2 : -1.f));
+        a.addend = b.ysk; a.out2 = b.sum;
+        a.fwd_xs_out = rows_x(k + 1);      // (the residual sum out2 is what the next block reads)
+        if ((rc = la_conv_launch(a, stream))) return rc;
     }
     const DBlock& last = h->blk[h->nblocks - 1];
     hipLaunchKernelGGL(la_mbstd_fwd_kernel, dim3(B / G), dim3(256), 0, stream, last.sum, h->mb, B, G, h->C4, 16, rows_x(h->nblocks));
     LA_CHECK_LAUNCH();
-    if ((rc = conv_same(h, h->econv, false, h->mb, h->yc, B, 4, LA_ACT_LRELU, sq2, h->clamp, nullptr, nullptr, stream, nullptr, 0, rows_x(h->nblocks)))) return rc;
+    LaConvArgs a; start_args(a, h, h->econv, false, B, rows_x(h->nblocks));
+    a.in = h->mb; a.out = h->yc; la_conv_set_epi(a, d_epi(h->econv, LA_ACT_LRELU, sq2, h->clamp));
+    if ((rc = conv_same(a, h->econv, false, 4, stream))) return rc;
     if ((rc = la_fc_f32(h->yc, h->fc_w, h->fc_b, h->fc, B, h->C4 * 16, h->C4, 1.f, LA_ACT_LRELU, 0.2f, sq2, stream))) return rc;
     if ((rc = la_fc_f32(h->fc, h->out_w, h->out_b, h->logits, B, h->C4, 1, 1.f, LA_ACT_LINEAR, 0.f, 1.f, stream))) return rc;
     h->lastB = B;
@@ -592,9 +561,11 @@ extern "C" int la_disc_backward(la_disc* h, const float* dlogits, float* g_img, 
     LA_CHECK_LAUNCH();
     if ((rc = la_bias_act_grad_f32(h->g_flat, h->yc, h->g_flat, nullptr, (long)B * C4 * 16, 1, 1, LA_ACT_LRELU, 0.2f, sq2, h->clamp, stream))) return rc;
     // b4.conv backward-data: [B][C4][16] -> [B][C4+1][16]
-    if ((rc = conv_same(h, h->econv, true, h->g_flat, h->scrB, B, 4, 0, 0.f, 0.f, nullptr, nullptr, stream))) return rc;
+    LaConvArgs a; start_args(a, h, h->econv, true, B, nullptr);
+    a.in = h->g_flat; a.out = h->scrB;
+    if ((rc = conv_same(a, h->econv, true, 4, stream))) return rc;
     const DBlock& last = h->blk[h->nblocks - 1];
-    hipLaunchKernelGGL(la_mbstd_bwd_kernel, dim3(B / G), dim3(256), 0, stream, last.sum, h->scrB, h->gA, B, G, C4, 16, h->econv.mb_);
+    hipLaunchKernelGGL(la_mbstd_bwd_kernel, dim3(B / G), dim3(256), 0, stream, last.sum, h->scrB, h->gA, B, G, C4, 16, h->econv.cin_pad);
     LA_CHECK_LAUNCH();
     float* g_sum = h->gA;       // gradient w.r.t. the current block's output (sum)
     float* other = h->gB;
@@ -616,54 +587,37 @@ extern "C" int la_disc_backward(la_disc* h, const float* dlogits, float* g_img, 
         const int nsq = la_conv_act_grad_segments((long)hq * hq), nsf = la_conv_act_grad_segments((long)res * res);
         if (!gs && (rc = la_conv_act_grad_pmax(g_sum, b.x1, h->scrB, h->pm, B, b.cout, (long)hq * hq, LA_ACT_LRELU, 0.2f, sq2 * rs2,
                                                h->clamp >= 0.f ? h->clamp * rs2 : -1.f, stream))) return rc;
-        {
-            LaConvArgs a; la_conv_args_init(a);
-            set_w(a, h, b.conv1, true);
-            a.in = gs ? g_sum : h->scrB; a.in_bstride = (long)b.cout * hq * hq; a.out = h->scrA;
-            a.B = B; a.C = b.cout; a.M = b.cin; a.Hin = a.Win = hq; a.Hout = a.Wout = res + 1;
-            a.out_sy = a.out_sx = 2; a.epi = LA_EPI_RAW;
-            // fused tail: the intermediate in column-planar rows (even columns | odd columns: every phase stores contiguous runs), read by
-            // the planar vector FIR kernel (la_fir4x4_s1p_kernel) -- the scalar kernel on dense rows took 291 us at 8 x 128 x 256^2
-            const int zx = zx_of(res), zp = 2 * zx;
-            if (zx) { a.out_pitch = zp; a.out_plane = (long)zp * (res + 1); a.out_sx = 1; a.Wout = zp; }
-            if (gs) {
-                a.in_mask_y = b.x1; a.in_mask_act = LA_ACT_LRELU; a.in_mask_alpha = 0.2f; a.in_mask_gain = sq2 * rs2;
-                a.in_mask_clamp = h->clamp >= 0.f ? h->clamp * rs2 : -1.f;
-                a.acc_scale_x = rows_g(k); a.acc_scale_fan = LA_XS_FAN;
-            } else { a.in_pmax = h->pm; a.in_pmax_nseg = nsq; }
-            if (h->precision != LA_PREC_F32 && (rc = la_conv_prepare_input(a, stream))) return rc;   // split once for the four phases
-            const bool merged = h->precision != LA_PREC_F32;      // 16-bit kernels: the four phases in ONE launch (as the generator's up layers)
-            for (int py = 0; py < 2; ++py)
-                for (int px = 0; px < 2; ++px) {
-                    la_conv_up2_phase(a, hq, py, px, zx ? zx : 1, merged);
-                    if (!merged && (rc = la_conv_launch(a, stream))) return rc;
-                }
-            if (merged) {
-                a.out_oy = a.out_ox = 0; a.Gy = a.Gx = hq + 1; a.ntaps = 4;      // launch-wide fields = the largest phase (checks only)
-                if ((rc = la_conv_launch(a, stream))) return rc;
-            }
-        }
+        start_args(a, h, b.conv1, true, B, gs ? rows_g(k) : nullptr);
+        a.in = gs ? g_sum : h->scrB; a.in_bstride = (long)b.cout * hq * hq; a.out = h->scrA;
+        if (gs) {
+            a.in_mask_y = b.x1; a.in_mask_act = LA_ACT_LRELU; a.in_mask_alpha = 0.2f; a.in_mask_gain = sq2 * rs2;
+            a.in_mask_clamp = h->clamp >= 0.f ? h->clamp * rs2 : -1.f;
+        } else { a.in_pmax = h->pm; a.in_pmax_nseg = nsq; }
+        // fused tail: the intermediate in column-planar rows (even columns | odd columns: every phase stores contiguous runs), read by
+        // the planar vector FIR kernel (la_fir4x4_s1p_kernel) -- the scalar kernel on dense rows took 291 us at 8 x 128 x 256^2
+        if ((rc = la_conv_up2_launch(a, hq, 2 * zx_of(res), zx_of(res), stream))) return rc;
         if (fuse) {
             // FIR adjoint + act'(y0) + the slot rows of conv0's backward contraction in one kernel
             LaFirTail tail;
             tail.yref = b.y0; tail.act = LA_ACT_LRELU; tail.alpha = 0.2f; tail.gain = sq2; tail.clamp = h->clamp; tail.xs_out = rows_c0(k);
             if (zx_of(res)) { tail.in_pitch = 2 * zx_of(res); tail.in_plane = (long)tail.in_pitch * (res + 1); tail.in_xhalf = zx_of(res); }
             if ((rc = la_upfirdn2d_ex(h->scrA, other, B, b.cin, res + 1, res + 1, h->fir, la_fir_same_pad1(1, 1.f), stream, tail))) return rc;
-            if ((rc = conv_same(h, b.conv0, true, other, h->scrA, B, res, 0, 0.f, 0.f, nullptr, nullptr, stream, nullptr, 0, rows_c0(k)))) return rc;
         } else {
             if ((rc = la_upfirdn2d_ex(h->scrA, other, B, b.cin, res + 1, res + 1, h->fir, la_fir_same_pad1(1, 1.f), stream))) return rc;
             // ---- conv0: act' then backward-data
             if ((rc = la_conv_act_grad_pmax(other, b.y0, other, h->pm, B, b.cin, (long)res * res, LA_ACT_LRELU, 0.2f, sq2, h->clamp, stream))) return rc;
-            if ((rc = conv_same(h, b.conv0, true, other, h->scrA, B, res, 0, 0.f, 0.f, nullptr, nullptr, stream, h->pm, nsf))) return rc;   // scrA >= B*cin*res^2
         }
+        start_args(a, h, b.conv0, true, B, fuse ? rows_c0(k) : nullptr);
+        a.in = other; a.out = h->scrA;      // scrA >= B*cin*res^2
+        if (!fuse) { a.in_pmax = h->pm; a.in_pmax_nseg = nsf; }
+        if ((rc = conv_same(a, b.conv0, true, res, stream))) return rc;
         // ---- skip branch: * sqrt(1/2) -> 1x1 adjoint -> FIR-down adjoint (up 2, pad (2,1,2,1), flipped), added to the conv branch
-        if (gs) {
-            // (the pre-split copy of g_sum carries the factor; the contraction then overwrites the g_sum buffer: [B][cin][hq^2])
-            if ((rc = conv_same(h, b.skip, true, g_sum, g_sum, B, hq, 0, 0.f, 0.f, nullptr, nullptr, stream, nullptr, 0, rows_g(k), rs2))) return rc;
-        } else {
-            if ((rc = la_conv_act_grad_pmax(g_sum, b.ysk, h->scrB, h->pm, B, b.cout, (long)hq * hq, LA_ACT_LINEAR, 0.f, rs2, -1.f, stream))) return rc;
-            if ((rc = conv_same(h, b.skip, true, h->scrB, g_sum, B, hq, 0, 0.f, 0.f, nullptr, nullptr, stream, h->pm, nsq))) return rc;       // reuse g_sum buffer: [B][cin][hq^2]
-        }
+        if (!gs && (rc = la_conv_act_grad_pmax(g_sum, b.ysk, h->scrB, h->pm, B, b.cout, (long)hq * hq, LA_ACT_LINEAR, 0.f, rs2, -1.f, stream))) return rc;
+        start_args(a, h, b.skip, true, B, gs ? rows_g(k) : nullptr);
+        a.out = g_sum;      // (the contraction overwrites the g_sum buffer: [B][cin][hq^2])
+        if (gs) { a.in = g_sum; a.in_gain = rs2; }      // (the pre-split copy of g_sum carries the factor)
+        else { a.in = h->scrB; a.in_pmax = h->pm; a.in_pmax_nseg = nsq; }
+        if ((rc = conv_same(a, b.skip, true, hq, stream))) return rc;
         {
             LaFirTail tail;
             tail.addend = h->scrA; tail.xs_out = (fuse && k > 0) ? rows_g(k - 1) : nullptr;

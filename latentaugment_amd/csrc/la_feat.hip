@@ -23,8 +23,8 @@
 
 struct FOp {
     int kind, cin, cout, res_in, res_out;
-    const float *w, *bias, *lin;
-    float *wf, *wb; void *wqf, *wqb; int mb_;
+    const float *w, *bias, *lin;      // w: fc ops, used in place [cout][cin]
+    LaConvWeights cw;  // conv ops
     float* y;          // output activation [maxN][cout][res_out^2] (conv, pools, fc: res_out = 1); taps have none
     long feat_off;     // taps: offset of the slice inside the feature vector
 };
@@ -64,7 +64,8 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
                 LA_CHECK_ARG(ops[k].cin == c && ops[k].cout >= 4 && ops[k].cout % 4 == 0, "feat: conv channels mismatch / not a multiple of 4");
                 // (the backward pads the gradient of a conv's input to a multiple of 4 channels and copies the real ones out: only into gx)
                 LA_CHECK_ARG(c % 4 == 0 || k == 0, "feat: only the first conv may have cin % 4 != 0");
-                o.cout = ops[k].cout; o.res_out = r; c = o.cout; break;
+                o.cout = ops[k].cout; o.res_out = r; c = o.cout;
+                la_conv_weights_shape(o.cw, o.cin, o.cout, 3); break;
             case LA_FEAT_MAXPOOL2: case LA_FEAT_AVGPOOL2:
                 LA_CHECK_ARG(r % 2 == 0, "feat: pooling needs an even resolution");
                 o.cout = c; o.res_out = r / 2; r /= 2; break;
@@ -93,13 +94,11 @@ static size_t f_layout(la_feat* h, void* ws) {
         FOp& o = h->op[k];
         const size_t n_out = mn * o.cout * (size_t)o.res_out * o.res_out;
         if (o.kind == LA_FEAT_CONV_RELU) {
-            o.mb_ = (o.cin + 3) & ~3;
-            o.wf = c.take((size_t)o.cin * o.cout * 9); o.wb = c.take((size_t)o.mb_ * o.cout * 9);
-            o.wqf = c.take((la_conv_split_pack_bytes(o.cout, o.cin, 9) + 3) / 4);
-            o.wqb = c.take((la_conv_split_pack_bytes(o.mb_, o.cout, 9) + 3) / 4);
-            size_t w = la_modconv_workspace_bytes((int)mn, o.mb_ > o.cout ? o.mb_ : o.cout, o.mb_ > o.cout ? o.mb_ : o.cout, o.res_in, 0);
+            la_conv_weights_layout(c, o.cw);
+            const int cmax = o.cw.cin_pad > o.cout ? o.cw.cin_pad : o.cout;
+            size_t w = la_modconv_workspace_bytes((int)mn, cmax, cmax, o.res_in, 0);
             if (w > cw) cw = w;
-            const size_t gin = mn * o.mb_ * (size_t)o.res_in * o.res_in;
+            const size_t gin = mn * o.cw.cin_pad * (size_t)o.res_in * o.res_in;
             if (gin > gmax) gmax = gin;
             const size_t pmn = mn * o.cout * (size_t)la_conv_act_grad_segments((long)o.res_out * o.res_out);
             if (pmn > pmax) pmax = pmn;
@@ -133,32 +132,26 @@ static size_t f_layout(la_feat* h, void* ws) {
 }
 
 extern "C" size_t la_feat_workspace_bytes(int nops, const la_feat_op* ops, int in_ch, int in_res, int max_batch) {
-    la_feat* h = (la_feat*)malloc(sizeof(la_feat));
-    if (!h) return 0;
-    size_t need = 0;
-    if (f_describe(h, nops, ops, in_ch, in_res, max_batch) == LA_OK) need = f_layout(h, nullptr);
-    free(h);
-    return need;
+    return la_measure_workspace<la_feat>([&](la_feat* h) { return f_describe(h, nops, ops, in_ch, in_res, max_batch) == LA_OK ? f_layout(h, nullptr) : 0; });
 }
 
 // params: for each op in order: conv -> weight [cout][cin][3][3], bias [cout]; tap -> lin [C]; pools -> nothing
 extern "C" int la_feat_create(int nops, const la_feat_op* ops, const float* const* params, int nparams, int in_ch, int in_res,
                               int max_batch, void* workspace, size_t workspace_bytes, hipStream_t stream, la_feat** out) {
     LA_CHECK_ARG(params && workspace && out, "feat_create: null pointer");
-    la_feat* h = (la_feat*)malloc(sizeof(la_feat));
+    auto own = la_host_handle<la_feat>();
+    la_feat* h = own.get();
     LA_CHECK_ARG(h, "feat_create: out of host memory");
     int rc = f_describe(h, nops, ops, in_ch, in_res, max_batch);
-    if (rc) { free(h); return rc; }
-    if (f_layout(h, workspace) > workspace_bytes) { free(h); la_set_error("feat_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    if (rc) return rc;
+    if (f_layout(h, workspace) > workspace_bytes) { la_set_error("feat_create: workspace too small"); return LA_ERR_WORKSPACE; }
     int p = 0;
     for (int k = 0; k < nops && !rc; ++k) {
         FOp& o = h->op[k];
         if (o.kind == LA_FEAT_CONV_RELU) {
             if (p + 2 > nparams || !params[p] || !params[p + 1]) { rc = LA_ERR_ARG; la_set_error("feat_create: missing conv tensors"); break; }
-            o.w = params[p++]; o.bias = params[p++];
-            rc = la_pack_conv_weights(o.w, o.wf, o.wb, nullptr, o.cout, o.cin, 9, stream, 1.f, o.mb_);
-            if (!rc) rc = la_pack_conv_weights_bf16(o.w, o.wqf, o.cout, o.cin, 9, 0, 3, stream, 1.f);
-            if (!rc) rc = la_pack_conv_weights_bf16(o.w, o.wqb, o.cout, o.cin, 9, 1, 3, stream, 1.f, o.mb_);
+            o.cw.w = params[p++]; o.bias = params[p++];
+            rc = la_conv_weights_pack(o.cw, 1.f, stream);
         } else if (o.kind == LA_FEAT_TAP) {
             if (p + 1 > nparams || !params[p]) { rc = LA_ERR_ARG; la_set_error("feat_create: missing tap weights"); break; }
             o.lin = params[p++];
@@ -168,8 +161,8 @@ extern "C" int la_feat_create(int nops, const la_feat_op* ops, const float* cons
         }
     }
     if (!rc && p != nparams) { rc = LA_ERR_ARG; la_set_error("feat_create: parameter list length mismatch"); }
-    if (rc) { free(h); return rc; }
-    *out = h;
+    if (rc) return rc;
+    *out = own.release();
     return LA_OK;
 }
 
@@ -333,32 +326,24 @@ __global__ __launch_bounds__(256) void la_tap_bwd_kernel(const float* __restrict
 // pixel lanes of a tap workgroup: the largest power of two <= min(64, HW)
 static inline int tap_lanes(int HW) { int pl = 1; while (pl * 2 <= HW && pl < 64) pl *= 2; return pl; }
 
-// slot-row hand-over of the fp16 operand scales (f16x2 mode): xs_in = rows of this launch's input (null: absmax / plane-maxima passes),
-// xs_out = rows the epilogue lowers for the contraction that consumes the output (forward: the next conv's; backward: those of the conv
-// whose ReLU output `mask_y` is -- the epilogue then also applies that ReLU's mask to the outgoing gradient, LaConvArgs::seam)
-static int f_conv(la_feat* h, const FOp& o, bool backward, const float* in, float* out, int N, hipStream_t stream, const float* in_pmax = nullptr,
-                  int in_nseg = 0, const float* xs_in = nullptr, float* xs_out = nullptr, const float* mask_y = nullptr) {
-    LaConvArgs a; la_conv_args_init(a);
-    a.wgt = backward ? o.wb : o.wf;
-    a.precision = h->precision; a.wgt_bf16 = backward ? o.wqb : o.wqf;
-    a.wgt_bf16_term_elems = la_conv_bf16_pack_elems(backward ? o.mb_ : o.cout, backward ? o.cout : o.cin, 9);
-    a.ws = h->cws; a.ws_bytes = h->cws_bytes;
-    a.in = in; a.out = out; a.B = N; a.in_pmax = in_pmax; a.in_pmax_nseg = in_nseg;
-    a.C = backward ? o.cout : o.cin; a.M = backward ? o.mb_ : o.cout;
-    const int res = o.res_in;
-    a.in_bstride = (long)a.C * res * res;
-    a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
-    la_conv_taps_3x3(a, backward);
-    if (xs_in) { a.acc_scale_x = xs_in; a.acc_scale_fan = LA_XS_FAN; a.in_pmax = nullptr; }
-    if (backward) {
-        a.epi = LA_EPI_BWD;
-        if (mask_y) {      // activation backward of the layer below, fused (its saved output is the epilogue's xin)
-            a.xin = mask_y; a.xin_bstride = (long)a.M * res * res; a.tiles_per_sample = la_conv_tiles_per_sample(res, res);
-            a.seam.ddn_part = h->seam_scr; a.seam.act = LA_ACT_RELU; a.seam.alpha = 0.f; a.seam.gain = 1.f; a.seam.clamp = -1.f;
-            a.seam.xs_out = xs_out; a.seam.xs_mult = 1.f;
-        }
-    } else { a.epi = LA_EPI_FWD; a.bias = o.bias; a.act = LA_ACT_RELU; a.gain = 1.f; a.fwd_xs_out = xs_out; }
-    return la_conv_launch(a, stream);
+// What the launch of a conv op starts from: its weights of the direction, arithmetic, scratch, the 3x3 geometry at its resolution and
+// the bias + ReLU epilogue (backward: plain).  The callers name the tensors and the slot-row hand-over of the fp16 operand scales
+// (f16x2 mode): acc_scale_x = rows of the launch's input (none: absmax / plane-maxima passes), fwd_xs_out = rows the epilogue lowers
+// for the next conv.
+static void f_conv(LaConvArgs& a, const la_feat* h, const FOp& o, bool backward, int N) {
+    la_conv_args_init(a);
+    la_conv_weights_select(a, o.cw, backward);
+    a.precision = h->precision; a.ws = h->cws; a.ws_bytes = h->cws_bytes; a.B = N;
+    la_conv_geom_same(a, o.res_in, 3, backward);
+    if (backward) a.epi = LA_EPI_BWD;
+    else la_conv_set_epi(a, LaLayerEpi{nullptr, 0, nullptr, 0, 0.f, o.bias, LA_ACT_RELU, 0.f, 1.f, -1.f});
+}
+// Backward launch: the activation backward of the conv below, fused -- its saved ReLU output mask_y is the epilogue's xin, the
+// epilogue applies that ReLU's mask to the outgoing gradient and lowers the slot rows xs_out of that conv's contraction (LaConvArgs::seam)
+static void f_relu_seam(LaConvArgs& a, const la_feat* h, const float* mask_y, float* xs_out) {
+    a.xin = mask_y; a.xin_bstride = (long)a.M * a.Gy * a.Gx; a.tiles_per_sample = la_conv_tiles_per_sample(a.Gy, a.Gx);
+    a.seam.ddn_part = h->seam_scr; a.seam.act = LA_ACT_RELU; a.seam.alpha = 0.f; a.seam.gain = 1.f; a.seam.clamp = -1.f;
+    a.seam.xs_out = xs_out; a.seam.xs_mult = 1.f;
 }
 
 extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_out, hipStream_t stream) {
@@ -379,9 +364,11 @@ extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_ou
         if (o.kind == LA_FEAT_CONV_RELU) {
             int nxt = -1;
             for (int q = k + 1; q < h->nops; ++q) if (h->op[q].kind == LA_FEAT_CONV_RELU) { nxt = q; break; }
-            if ((rc = f_conv(h, o, false, cur, o.y, N, stream, nullptr, 0, (slots && !first_conv) ? rows(h->xs_f, k) : nullptr,
-                             (slots && nxt >= 0) ? rows(h->xs_f, nxt) : nullptr)))
-                return rc;
+            LaConvArgs a; f_conv(a, h, o, false, N);
+            a.in = cur; a.out = o.y;
+            if (slots && !first_conv) { a.acc_scale_x = rows(h->xs_f, k); a.acc_scale_fan = LA_XS_FAN; }
+            if (slots && nxt >= 0) a.fwd_xs_out = rows(h->xs_f, nxt);
+            if ((rc = la_conv_launch(a, stream))) return rc;
             first_conv = false;
             cur = o.y;
         } else if (o.kind == LA_FEAT_TAP) {
@@ -440,28 +427,27 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
             masked = fuse;
         } else if (o.kind == LA_FEAT_CONV_RELU) {
             LA_CHECK_ARG(have, "feat_backward: the op list must end with a tap");
-            float* dst = (k == 0 && o.mb_ == o.cin) ? gx : other;
+            float* dst = (k == 0 && o.cw.cin_pad == o.cin) ? gx : other;
             // the conv below, if it feeds this one directly: this contraction's epilogue masks its gradient and lowers its slot rows
-            const bool below = slots && k > 0 && h->op[k - 1].kind == LA_FEAT_CONV_RELU && o.mb_ == o.cin && dst != gx;
-            if (masked) {
-                if ((rc = f_conv(h, o, true, g, dst, N, stream, nullptr, 0, rows(h->xs_b, k), below ? rows(h->xs_b, k - 1) : nullptr,
-                                 below ? h->op[k - 1].y : nullptr)))
-                    return rc;
-            } else {
+            const bool below = slots && k > 0 && h->op[k - 1].kind == LA_FEAT_CONV_RELU && o.cw.cin_pad == o.cin && dst != gx;
+            LaConvArgs a; f_conv(a, h, o, true, N);
+            a.in = g; a.out = dst;
+            if (masked) { a.acc_scale_x = rows(h->xs_b, k); a.acc_scale_fan = LA_XS_FAN; }
+            else {
                 // ReLU mask of this layer on the incoming gradient, with the plane maxima the fp16 operand scale of its backward
                 // contraction needs (one sweep instead of a mask pass + an absmax pass): exact-fp32 / bf16 modes, op lists without
                 // a tap or a conv right behind this conv
                 if ((rc = la_conv_act_grad_pmax(g, o.y, g, h->pm, N, o.cout, HWo, LA_ACT_RELU, 0.f, 1.f, -1.f, stream))) return rc;
-                if ((rc = f_conv(h, o, true, g, dst, N, stream, h->pm, la_conv_act_grad_segments(HWo), nullptr, below ? rows(h->xs_b, k - 1) : nullptr,
-                                 below ? h->op[k - 1].y : nullptr)))
-                    return rc;
+                a.in_pmax = h->pm; a.in_pmax_nseg = la_conv_act_grad_segments(HWo);
             }
+            if (below) f_relu_seam(a, h, h->op[k - 1].y, rows(h->xs_b, k - 1));
+            if ((rc = la_conv_launch(a, stream))) return rc;
             masked = below;
             if (k == 0 && dst != gx) {
                 // padded backward channels (cin not a multiple of 4): copy the real ones out
                 const long HWi = (long)o.res_in * o.res_in;
                 // (one strided copy: a copy per sample was 16 launches of 5 us each in every step of preset E)
-                LA_HIP(hipMemcpy2DAsync(gx, sizeof(float) * o.cin * HWi, dst, sizeof(float) * o.mb_ * HWi, sizeof(float) * o.cin * HWi, (size_t)N,
+                LA_HIP(hipMemcpy2DAsync(gx, sizeof(float) * o.cin * HWi, dst, sizeof(float) * o.cw.cin_pad * HWi, sizeof(float) * o.cin * HWi, (size_t)N,
                                         hipMemcpyDeviceToDevice, stream));
             }
             float* t = g; g = other; other = t;

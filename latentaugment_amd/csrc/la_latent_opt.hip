@@ -129,21 +129,22 @@ extern "C" int la_latent_opt_create_ex(la_synth* g, int img_resolution, int img_
     LA_CHECK_ARG(cfg->crop >= 1 && cfg->crop_off >= 0 && cfg->crop + cfg->crop_off <= img_resolution,
                  "latent_opt_create: centre crop does not fit the image");
     LA_CHECK_ARG(cfg->criterion_mode == 0 || cfg->criterion_mode == 1, "latent_opt_create: criterion_mode must be 0 or 1");
-    la_latent_opt* h = (la_latent_opt*)malloc(sizeof(la_latent_opt));
+    auto own = la_host_handle<la_latent_opt>();
+    la_latent_opt* h = own.get();
     LA_CHECK_ARG(h, "latent_opt_create: out of host memory");
     memset(h, 0, sizeof(*h));
     h->g = g; h->cfg = *cfg; h->R = img_resolution; h->imgc = img_channels; h->wdim = w_dim;
     h->num_ws = la_synth_num_ws(img_resolution); h->maxB = max_batch; h->wplus = latent_space;
     h->bankW = bankW; h->Mw = cfg->w_latent != 0.f ? Mw : 0; h->bankX = bankXc; h->Mx = cfg->w_pix != 0.f ? Mx : 0;
     const size_t need = carve(h, (char*)workspace);
-    if (need > workspace_bytes) { free(h); la_set_error("latent_opt_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    if (need > workspace_bytes) { la_set_error("latent_opt_create: workspace too small"); return LA_ERR_WORKSPACE; }
     h->adam_tab_host = (float*)malloc(sizeof(float) * 2 * (size_t)(cfg->steps > 0 ? cfg->steps : 1));
-    if (!h->adam_tab_host) { free(h); la_set_error("latent_opt_create: out of host memory"); return LA_ERR_ARG; }
+    LA_CHECK_ARG(h->adam_tab_host, "latent_opt_create: out of host memory");
     la_adam_fill_table(h->adam_tab_host, cfg->steps, cfg->beta1, cfg->beta2);
     h->graph_mode = 1;
     h->overlap = 2;
     h->win_lo = h->win_hi = 0; h->wcol_lo = h->wcol_hi = 0;
-    *out = h;
+    *out = own.release();
     return LA_OK;
 }
 

@@ -24,12 +24,6 @@ static void start_args(LaConvArgs& a, const LaModconv& m, bool backward) {
     a.B = m.B; a.C = backward ? m.cout : m.cin; a.M = backward ? m.cin : m.cout;
     a.wgt_bf16_term_elems = la_conv_bf16_pack_elems(a.M, a.C, 9);
 }
-static void set_epi(LaConvArgs& a, const LaLayerEpi& e) {
-    a.epi = LA_EPI_FWD;
-    a.demod = e.demod; a.demod_stride = e.demod_stride;
-    a.noise = e.noise; a.noise_bstride = e.noise_bstride; a.noise_strength = e.noise_strength;
-    a.bias = e.bias; a.act = e.act; a.alpha = e.alpha; a.gain = e.gain; a.clamp = e.clamp;
-}
 static void set_bwd(LaConvArgs& a, const LaModconv& m, const float* xin, long xin_bstride, float* ds_part, int grid_res, const LaSeamFuse* seam) {
     a.epi = LA_EPI_BWD;
     a.out_scale = m.s; a.oscale_stride = m.s_stride;
@@ -44,8 +38,8 @@ bool la_modconv3x3_fwd_fuses_rgb(int precision, int B, int cin, int cout, int re
     if (off || precision == LA_PREC_F32 || (cout != 128 && cout != 64 && cout != 32)) return false;
     LaConvArgs a; la_conv_args_init(a);
     a.precision = precision;
-    a.B = B; a.C = cin; a.M = cout; a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
-    la_conv_taps_3x3(a, false);
+    a.B = B; a.C = cin; a.M = cout;
+    la_conv_geom_same(a, res, 3, false);
     return la_conv_bf16_uses_halo(a);
 }
 
@@ -66,11 +60,10 @@ int la_modconv3x3_fwd_ex(const float* x, long x_bstride, const LaModconv& m, con
         a.rgb = r;
     }
     if (m.precision == LA_PREC_F16X2 && o.xscale) { a.acc_scale_x = o.xscale; a.acc_scale_fan = LA_XS_FAN; }      // preset operand scale (slot rows of the caller): no absmax / plane-maxima pass
+    la_conv_geom_same(a, res, 3, false);
     a.in = x; a.in_bstride = x_bstride; a.out = y; a.in_pmax = o.in_pmax; a.in_pmax_nseg = o.in_nseg;
     a.in_scale = m.s; a.scale_stride = m.s_stride;
-    a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
-    la_conv_taps_3x3(a, false);
-    set_epi(a, epi);
+    la_conv_set_epi(a, epi);
     return la_conv_launch(a, stream);
 }
 
@@ -98,10 +91,6 @@ int la_modconv3x3_up2_fwd_ex(const float* x, long x_bstride, const LaModconv& m,
     LaConvArgs a; start_args(a, m, false);
     a.in = x; a.in_bstride = x_bstride; a.out = scratch;
     a.in_scale = m.s; a.scale_stride = m.s_stride;
-    a.Hin = a.Win = hin; a.Hout = a.Wout = res + 1;
-    a.out_sy = a.out_sx = 2; a.epi = LA_EPI_RAW;
-    if (scratch_pitch > 0) { a.out_pitch = scratch_pitch; a.out_plane = (long)scratch_pitch * (res + 1); }      // padded (2h+1)-wide rows
-    if (scratch_xhalf > 0) { a.out_sx = 1; a.Wout = scratch_pitch; }      // column-planar rows: phase px writes the contiguous run from px * xhalf
     if (m.precision == LA_PREC_F16X2 && o.xscale) { a.acc_scale_x = o.xscale; a.acc_scale_fan = LA_XS_FAN; }      // preset operand scale (slot rows of the caller): no absmax pass
     if (w.row_hi > 0) {
         // FIR output row y reads intermediate rows y - 1 .. y + 2; intermediate row Y = 2 q + py belongs to row q of phase py
@@ -111,27 +100,9 @@ int la_modconv3x3_up2_fwd_ex(const float* x, long x_bstride, const LaModconv& m,
         // the input rows those phase rows read: nothing else is copied into the pre-split operand, and the contraction reads the rest as zeros
         la_modconv3x3_up2_fwd_rows(res, w.row_lo, w.row_hi, &a.in_row_lo, &a.in_row_hi);
     }
-    if (m.precision != LA_PREC_F32) {
-        // split the (modulated) input once for the four phase launches
-        int rc = la_conv_prepare_input(a, stream);
-        if (rc) return rc;
-    }
-    // transposed stride-2 conv as 4 output phases (la_conv_up2_phase).  16-bit kernels: the four phases in ONE launch -- above the
-    // split-K sizes each phase launch would end in a nearly empty round, at the split-K sizes (<= 34x34 phase grids) four launches +
-    // four finish passes become one of each
-    const bool merged = m.precision != LA_PREC_F32;
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            la_conv_up2_phase(a, hin, py, px, scratch_xhalf > 0 ? scratch_xhalf : 1, merged);
-            if (merged) continue;
-            int rc = la_conv_launch(a, stream);
-            if (rc) return rc;
-        }
-    if (merged) {
-        a.out_oy = a.out_ox = 0; a.Gy = a.Gx = hin + 1; a.ntaps = 4;      // launch-wide fields = the largest phase (checks only)
-        int rc = la_conv_launch(a, stream);
-        if (rc) return rc;
-    }
+    // transposed stride-2 conv of the (modulated) input into the scratch
+    int rc = la_conv_up2_launch(a, hin, scratch_pitch, scratch_xhalf, stream);
+    if (rc) return rc;
     // FIR with pad (1,1,1,1) and gain up^2 = 4, then the layer epilogue
     LaFirTail t;
     t.pmax = o.y_pmax; t.xs_out = o.xs_out; t.xs_mult = o.xs_mult; t.win = w;
@@ -165,9 +136,8 @@ int la_modconv3x3_bwd_ex(const float* gz, const LaModconv& m, const float* xin, 
     LA_CHECK_ARG(gz && m.w && gx, "modconv_bwd: null pointer");
     LA_CHECK_ARG(!o.seam || (m.precision != LA_PREC_F32 && xin && o.seam->ddn_part), "modconv_bwd: the fused seam needs a 16-bit contraction and xin");
     LaConvArgs a; start_args(a, m, true);
-    a.in = gz; a.in_bstride = (long)m.cout * res * res; a.out = gx; a.in_pmax = o.in_pmax; a.in_pmax_nseg = o.in_nseg;
-    a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
-    la_conv_taps_3x3(a, true);
+    a.in = gz; a.out = gx; a.in_pmax = o.in_pmax; a.in_pmax_nseg = o.in_nseg;
+    la_conv_geom_same(a, res, 3, true);
     if (m.precision == LA_PREC_F16X2 && o.xscale) { a.acc_scale_x = o.xscale; a.acc_scale_fan = LA_XS_FAN; a.in_pmax = nullptr; }      // preset operand scale (slot rows)
     set_bwd(a, m, xin, xin_bstride, ds_part, res, o.seam);
     if (o.rows && m.precision != LA_PREC_F32) {
@@ -199,13 +169,9 @@ int la_modconv3x3_up2_bwd_ex(const float* gz, const LaModconv& m, const float* x
     const int hin = res / 2;
     LaConvArgs a; start_args(a, m, true);
     a.out = gx;
-    a.Hin = a.Win = res + 1; a.Hout = a.Wout = a.Gy = a.Gx = hin;
-    a.in_sy = a.in_sx = 2;
-    la_conv_taps_3x3_corner(a);
+    la_conv_geom_down2(a, res);
     set_bwd(a, m, xin, xin_bstride, ds_part, hin, seam);
-    a.in_bstride = (long)cout * (res + 1) * (res + 1);
-    const size_t qbytes = (size_t)B * la_cdiv(cout, 32) * 32 * (res + 1) * (res + 1) * 4;
-    const size_t fused_need = 512 + ((qbytes + 255) & ~(size_t)255);
+    const size_t fused_need = 512 + ((la_fir4x4_adjoint_pack_bytes(B, cout, res, res) + 255) & ~(size_t)255);
     if (m.precision == LA_PREC_F16X2 && (o.xscale || (o.in_pmax && o.in_nseg >= 1)) && res % 4 == 0 && ws && ws_bytes > fused_need && (((size_t)ws | (size_t)gz) & 15) == 0) {
         // fp16 mode with the plane maxima of gz at hand (left by the seam kernel): ONE pass turns gz into the contraction's
         // operand -- FIR adjoint (pad 2, flipped taps, gain 4; upfirdn2d.py:255-266) + operand scale + fp16 split + channel

@@ -49,8 +49,6 @@ struct LaSeamArgs {
                              // the incoming gradient is zero outside them (la_synth.hip: row windows); the slabs share the window
 };
 
-int la_pack_conv_weights(const float* w, float* wf, float* wb, float* wsq, int cout, int cin, int ktaps, hipStream_t,
-                         float scale = 1.f, int wb_ld = 0);   // wb_ld > cin: backward slab rows padded with zero columns
 int la_affine_forward(const LaStyleTable& t, const float* ws, long ws_bstride, long ws_lstride, int B, int wdim,
                       float* s_all, hipStream_t);
 // xs[l][b] = power-of-two fp16 operand scale of conv layer l's forward contraction from the bound  bound[l] * max_i |s[b][i]|

@@ -15,12 +15,10 @@
 
 #define MAX_BLOCKS 12
 
-struct ConvLayer {
-    int cin, cout, res, up, widx;
-    const float *affine_w, *affine_b, *weight, *bias, *noise_const;
+struct ConvLayer : LaConvWeights {      // (channel counts are multiples of 4: cin_pad = cin; wsq feeds the demodulation)
+    int res, up, widx;
+    const float *affine_w, *affine_b, *bias, *noise_const;
     float noise_strength;
-    float *wf, *wb, *wsq;   // packed (fp32)
-    void *wqf, *wqb;        // packed split-bf16 (3 terms), forward / backward
     float* y;               // saved output [maxB][cout][res*res]
     float *dsp, *ddnp;      // style-gradient partials of this layer (kept until the one-pass finish at the end of a backward pass)
     int s_off, d_off, style_idx;
@@ -91,10 +89,7 @@ static int layout(la_synth* h, void* workspace, size_t cap, size_t* need) {
     size_t skf = 0;
     for (int k = 0; k < h->nconv; ++k) {
         ConvLayer& L = h->conv[k];
-        const size_t wn = (size_t)L.cin * L.cout;
-        L.wf = c.take(9 * wn); L.wb = c.take(9 * wn); L.wsq = c.take(wn);
-        L.wqf = c.take((la_modconv_bf16_pack_bytes(L.cin, L.cout, 0, 3) + 3) / 4);
-        L.wqb = c.take((la_modconv_bf16_pack_bytes(L.cin, L.cout, 1, 3) + 3) / 4);
+        la_conv_weights_layout(c, L, true);
         const size_t hw = (size_t)L.res * L.res;
         L.y = c.take(mb * L.cout * hw);
         if (mb * L.cout * hw > gmax) gmax = mb * L.cout * hw;
@@ -188,10 +183,10 @@ static int describe(la_synth* h, int R, int imgc, int wdim, const int* channels,
         h->channels[k] = co;
         if (k > 0) {
             ConvLayer& L = h->conv[nconv++];
-            L.cin = channels[k - 1]; L.cout = co; L.res = res; L.up = 1; L.widx = widx++;
+            la_conv_weights_shape(L, channels[k - 1], co, 3); L.res = res; L.up = 1; L.widx = widx++;
         }
         ConvLayer& L1 = h->conv[nconv++];
-        L1.cin = co; L1.cout = co; L1.res = res; L1.up = 0; L1.widx = widx++;
+        la_conv_weights_shape(L1, co, co, 3); L1.res = res; L1.up = 0; L1.widx = widx++;
         RgbLayer& T = h->rgb[k];
         T.cin = co; T.res = res; T.widx = widx;   // shares its w with the next block's conv0
     }
@@ -232,12 +227,11 @@ extern "C" int la_synth_num_params(int img_resolution) {
 
 extern "C" size_t la_synth_workspace_bytes(int img_resolution, int img_channels, int w_dim, const int* channels,
                                            int max_batch) {
-    la_synth* h = (la_synth*)malloc(sizeof(la_synth));
-    if (!h) return 0;
-    size_t need = 0;
-    if (describe(h, img_resolution, img_channels, w_dim, channels, max_batch) == LA_OK) layout(h, nullptr, 0, &need);
-    free(h);
-    return need;
+    return la_measure_workspace<la_synth>([&](la_synth* h) {
+        size_t need = 0;
+        if (describe(h, img_resolution, img_channels, w_dim, channels, max_batch) == LA_OK) layout(h, nullptr, 0, &need);
+        return need;
+    });
 }
 
 extern "C" int la_synth_create(int img_resolution, int img_channels, int w_dim, const int* channels, float conv_clamp,
@@ -246,23 +240,21 @@ extern "C" int la_synth_create(int img_resolution, int img_channels, int w_dim, 
                                size_t workspace_bytes, hipStream_t stream, la_synth** out) {
     LA_CHECK_ARG(params && noise_strength && fir_host && workspace && out, "synth_create: null pointer");
     LA_CHECK_ARG(fir_h == 4 && fir_w == 4, "synth_create: resample filter must be 4x4 (setup_filter([1,3,3,1]))");
-    la_synth* h = (la_synth*)malloc(sizeof(la_synth));
+    auto own = la_host_handle<la_synth>();
+    la_synth* h = own.get();
     LA_CHECK_ARG(h, "synth_create: out of host memory");
     int rc = describe(h, img_resolution, img_channels, w_dim, channels, max_batch);
-    if (rc) { free(h); return rc; }
-    if (nparams != la_synth_num_params(img_resolution) || nlayers != h->nconv) {
-        free(h); la_set_error("synth_create: parameter list length mismatch"); return LA_ERR_ARG;
-    }
-    for (int i = 0; i < nparams; ++i)
-        if (!params[i]) { free(h); la_set_error("synth_create: null parameter tensor"); return LA_ERR_ARG; }
+    if (rc) return rc;
+    LA_CHECK_ARG(nparams == la_synth_num_params(img_resolution) && nlayers == h->nconv, "synth_create: parameter list length mismatch");
+    for (int i = 0; i < nparams; ++i) LA_CHECK_ARG(params[i], "synth_create: null parameter tensor");
     size_t need = 0;
     layout(h, workspace, workspace_bytes, &need);
-    if (need > workspace_bytes) { free(h); la_set_error("synth_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    if (need > workspace_bytes) { la_set_error("synth_create: workspace too small"); return LA_ERR_WORKSPACE; }
     h->clamp = conv_clamp;
     h->win_lo = h->win_hi = 0; h->wcol_lo = h->wcol_hi = 0; h->fw_c0 = h->fw_c1 = 0;
     // every buffer starts as zeros: a forward pass restricted to a row window (la_synth_set_row_window) leaves the other rows of its saved
     // activations as they were, and the backward pass multiplies them with gradients that are exactly zero there -- they must be finite
-    if (hipMemsetAsync(workspace, 0, need, stream) != hipSuccess) { free(h); la_set_error("synth_create: clearing the workspace failed"); return LA_ERR_HIP; }
+    if (hipMemsetAsync(workspace, 0, need, stream) != hipSuccess) { la_set_error("synth_create: clearing the workspace failed"); return LA_ERR_HIP; }
     memcpy(h->fir, fir_host, sizeof(float) * 16);
     int p = 0, ci = 0;
     for (int k = 0; k < h->nblocks; ++k) {
@@ -270,15 +262,12 @@ extern "C" int la_synth_create(int img_resolution, int img_channels, int w_dim, 
         const int nl = (k == 0) ? 1 : 2;
         for (int q = 0; q < nl; ++q) {
             ConvLayer& L = h->conv[ci];
-            L.affine_w = params[p++]; L.affine_b = params[p++]; L.weight = params[p++]; L.bias = params[p++];
+            L.affine_w = params[p++]; L.affine_b = params[p++]; L.w = params[p++]; L.bias = params[p++];
             L.noise_const = params[p++];
             L.noise_strength = noise_strength[ci];
             h->st.aw[L.style_idx] = L.affine_w; h->st.ab[L.style_idx] = L.affine_b;
             h->dt.wsq[ci] = L.wsq;
-            rc = la_pack_conv_weights(L.weight, L.wf, L.wb, L.wsq, L.cout, L.cin, 9, stream);
-            if (!rc) rc = la_pack_conv_weights_bf16_f32(L.weight, L.wqf, L.cout, L.cin, 9, 0, 3, stream);
-            if (!rc) rc = la_pack_conv_weights_bf16_f32(L.weight, L.wqb, L.cout, L.cin, 9, 1, 3, stream);
-            if (rc) { free(h); return rc; }
+            if ((rc = la_conv_weights_pack(L, 1.f, stream))) return rc;
             ++ci;
         }
         RgbLayer& T = h->rgb[k];
@@ -286,7 +275,7 @@ extern "C" int la_synth_create(int img_resolution, int img_channels, int w_dim, 
         h->st.aw[T.style_idx] = T.affine_w; h->st.ab[T.style_idx] = T.affine_b;
     }
     h->lastB = 0;
-    *out = h;
+    *out = own.release();
     return LA_OK;
 }
 

@@ -73,6 +73,7 @@ int la_upfirdn2d_modconv_epilogue(const float* in, float* out, int B, int C, int
 int la_fir4x4_adjoint_pack_f16(const float* in, unsigned* q, const float* xscale, int xs_fan, int B, int C, int H, int W, const float* f_host,
                                float gain, hipStream_t stream, int flip_taps = 0, const LaWindow& in_win = LaWindow{},
                                const LaWindow& out_win = LaWindow{});
+static inline size_t la_fir4x4_adjoint_pack_bytes(int B, int C, int H, int W) { return (size_t)B * la_cdiv(C, 32) * 32 * (H + 1) * (W + 1) * 4; }      // bytes of q
 
 // The image-gradient pyramid of a synthesis backward pass in one launch: outs[l] [planes][R0 >> (l+1)]^2 = adjoint of upsample2d applied l + 1
 // times to g_top [planes][R0]^2 (per level exactly la_upfirdn2d_ex(.., la_fir_down2_adjoint())); R0 <= 256: the kernel keeps two levels in LDS,

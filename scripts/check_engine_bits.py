@@ -1,0 +1,98 @@
+"""Dev tool: are the outputs of the four engines byte-equal on two builds of the library?
+    python scripts/check_engine_bits.py tmp_libs/base/liblatentaug_hip.so latentaugment_amd/liblatentaug_hip.so
+Each library runs the same calls in a fresh process of its own (`--dump LIB OUT.npz`, the library path replacing _lib.LIB_PATH before
+anything loads it, as scripts/check_op_bits.py does); this process only compares the bytes and prints one line.  The cases are the
+smallest that reach every host branch of the engines' launch set-up (la_synth.hip / la_modconv.hip, la_disc.hip, la_feat.hip), each in
+f32, bf16x3 and f16x2:
+  generator      64^2, channel cap 64, B = 3, const noise: split-K grids, merged up-2 phases, the fused ToRGB at 64^2 x 64 channels;
+                 image, then d/d(ws) of a seeded image gradient; once more with the row window (13, 52) (gradient zero outside it)
+  discriminator  128^2, channel cap 32, B = 4: the packed FIR operand, blocks whose gradient arrives with slot rows, the masked FromRGB
+                 backward above 64^2; logits and image gradient.  And 16^2, B = 8, MinibatchStd group 4
+  feature net    conv, conv, tap, maxpool, conv, tap on a 3-channel 12^2 input, N = 3: the padded first-conv gradient copy, both sources
+                 of the ReLU mask; features and input gradient
+  detector       conv, maxpool, conv, fc + ReLU, fc: features
+Inputs: seeded CPU generators."""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MODES = ('f32', 'bf16x3', 'f16x2')
+
+
+def dump(lib_path, out_path):
+    sys.path.insert(0, ROOT)
+    import torch
+    from latentaugment_amd import _lib
+    _lib.LIB_PATH = os.path.abspath(lib_path)
+    from latentaugment_amd import synthesis, synthetic
+    lib = _lib.load()
+    assert _lib.LOADED_PATH == os.path.realpath(lib_path)
+    dev = torch.device('cuda', 0)
+    gen = torch.Generator().manual_seed(0)
+    res = {}
+
+    def draw(*shape):
+        return torch.randn(shape, generator=gen).to(dev)
+
+    def keep(key, t):
+        res[key] = t.detach().contiguous().cpu().view(torch.uint8).numpy().ravel()
+
+    g_sd, meta = synthetic.make_generator_state_dict(64, 2, channel_max=64, w_dim=64, noise_strength=0.1)
+    ws, g_img = draw(3, meta['num_ws'], 64), draw(3, 2, 64, 64)
+    g_win = torch.zeros_like(g_img)
+    g_win[:, :, 13:52] = g_img[:, :, 13:52]
+    d128 = synthetic.make_discriminator_state_dict(128, 2, channel_max=32)
+    d16 = synthetic.make_discriminator_state_dict(16, 2, channel_max=32)
+    x128, dl4, x16, dl8 = draw(4, 2, 128, 128), draw(4, 1), draw(8, 2, 16, 16), draw(8, 1)
+
+    def conv(cin, cout):
+        return ('conv', draw(cout, cin, 3, 3) * (2.0 / (9 * cin)) ** 0.5, draw(cout) * 0.1)
+
+    f_ops = [conv(3, 8), conv(8, 8), ('tap', draw(8).abs()), ('maxpool',), conv(8, 16), ('tap', draw(16).abs())]
+    d_ops = [conv(3, 8), ('maxpool',), conv(8, 8), ('fc', draw(12, 8 * 4 * 4) * 0.1, draw(12) * 0.1, True), ('fc', draw(5, 12), draw(5), False)]
+    xf, xd = draw(3, 3, 12, 12), draw(3, 3, 8, 8)
+
+    for mode in MODES:
+        G = synthesis.SynthesisEngine.from_generator(g_sd, dev, max_batch=3, conv_clamp=256.0, precision=mode)
+        keep(f'gen/{mode}/img', G.forward(ws, noise_mode='const'))
+        keep(f'gen/{mode}/dws', G.backward(g_img))
+        _lib.check(lib.la_synth_set_row_window(G.handle, 13, 52), 'la_synth_set_row_window')
+        img = G.forward(ws, noise_mode='const', out=torch.zeros_like(g_img))
+        keep(f'gen/{mode}/window/img', img[:, :, 13:52])      # (the rows outside are not written)
+        keep(f'gen/{mode}/window/dws', G.backward(g_win))
+        for name, sd, x, dl, group in (('disc128', d128, x128, dl4, 4), ('disc16', d16, x16, dl8, 4)):
+            D = synthesis.DiscriminatorEngine(sd, dev, max_batch=x.shape[0], precision=mode, mbstd_group_size=group)
+            keep(f'{name}/{mode}/logits', D.forward(x))
+            keep(f'{name}/{mode}/gx', D.backward(dl))
+        F = synthesis.FeatureEngine(f_ops, dev, in_res=12, max_batch=3, precision=mode)
+        f = F.forward(xf)
+        keep(f'feat/{mode}/f', f)
+        keep(f'feat/{mode}/gx', F.backward(torch.randn(f.shape, generator=torch.Generator().manual_seed(1)).to(dev)))
+        keep(f'detector/{mode}/f', synthesis.FeatureEngine(d_ops, dev, in_res=8, max_batch=3, precision=mode).forward(xd))
+    torch.cuda.synchronize()
+    np.savez(out_path, **res)
+
+
+def main():
+    if sys.argv[1] == '--dump':
+        return dump(sys.argv[2], sys.argv[3])
+    outs = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for i, lib in enumerate(sys.argv[1:3]):
+            out = os.path.join(tmp, f'engine_bits_{i}.npz')
+            subprocess.run([sys.executable, os.path.abspath(__file__), '--dump', lib, out], check=True, timeout=300)
+            outs.append(dict(np.load(out)))
+    a, b = outs
+    assert sorted(a) == sorted(b)
+    differ = [k for k in a if not np.array_equal(a[k], b[k])]
+    print(f'engine_bits: {len(a)} outputs, {sum(a[k].size for k in a)} bytes, {len(differ)} differ' +
+          ''.join(f'\n  {k}' for k in differ[:20]))
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == '__main__':
+    main()
