@@ -364,6 +364,13 @@ int la_synth_set_row_window(la_synth* h, int row_lo, int row_hi);
  * whole 32-column tiles; every other kernel computes whole rows. */
 int la_synth_set_col_window(la_synth* h, int col_lo, int col_hi);
 int la_synth_get_precision(const la_synth* h);
+/* Host only, no launch.  The backward pass of a windowed forward pass follows the CONE of the image window: window[0..1] = the rows of
+ * the gradient of conv output conv_index (engine layer order) that can be non-zero for image rows [row_lo, row_hi) -- the forward windows
+ * without their tile rounding; the launch that writes them rounds them outward to its own 4-row tiles -- and window[2..3] = the tile
+ * columns that launch writes for image columns [col_lo, col_hi) (top block's up-sampling layer only).  0, 0 on an axis = all of it. */
+int la_synth_plan_bwd_window(int img_resolution, int row_lo, int row_hi, int col_lo, int col_hi, int conv_index, int* window);
+/* the rows the last la_synth_forward of a handle recorded for its backward pass */
+int la_synth_bwd_rows(const la_synth* h, int conv_index, int* row_lo, int* row_hi);
 /* ws element (b,l,j) = ws[b*ws_bstride + l*ws_lstride + j] (ws_lstride = 0: W space, one w per sample).
  * noise_mode 0 'none', 1 'const', 2 explicit unit-variance tensors noises[layer] [B][res][res] ('random' drawn by the caller).
  * img_out NULL: the image stays in the engine (la_synth_image). */

@@ -65,7 +65,57 @@ struct la_synth {
     int wcol_lo, wcol_hi;      // ... and its column window (la_synth_set_col_window; top block only)
     int fw_c0, fw_c1;          // column window (32-column tiles) of the top block's conv1 output in the LAST forward pass (0 / 0 = all)
     int fw_lo[2 * MAX_BLOCKS], fw_hi[2 * MAX_BLOCKS];      // row windows of the conv outputs in the LAST forward pass (0 / 0 = whole plane)
+    int bw_lo[2 * MAX_BLOCKS], bw_hi[2 * MAX_BLOCKS];      // ... and the rows in which the gradient of those outputs can be non-zero (plan_row_windows; 0 / 0 = whole plane)
 };
+
+// Row windows of a pass for the image row window [win_lo, win_hi) (la_synth_set_row_window), top block downwards until a window is the whole
+// plane.
+//   wlo / whi  what the FORWARD pass computes of every conv output: conv1 in 4-row tiles around what the image / the block above need, conv0
+//              (FIR output) one row more on either side, the block below what conv0's transposed conv reads (la_modconv3x3_up2_fwd_rows)
+//              and what the image up-sampling reads.  Everything a consumer reads must be exact, so the tile rounding of one level is part
+//              of the next level's need.
+//   ilo / ihi  image rows a block has to deliver
+//   blo / bhi  where the GRADIENT of a conv output can be non-zero: the same recursion WITHOUT the tile rounding (a row that was computed
+//              only because a tile had to be whole feeds nothing that is read, its gradient is an exact zero) -- need of conv1, conv0 one
+//              row more, the block below what those conv0 rows read united with its image rows.  Inside wlo / whi by construction; set
+//              for exactly the layers that have a forward window.  The backward launches round them to their own tiles, once.
+struct SynthRowPlan { int wlo[2 * MAX_BLOCKS], whi[2 * MAX_BLOCKS], ilo[MAX_BLOCKS], ihi[MAX_BLOCKS], blo[2 * MAX_BLOCKS], bhi[2 * MAX_BLOCKS]; };
+static void plan_row_windows(int nblocks, int nconv, int win_lo, int win_hi, SynthRowPlan& p) {
+    memset(&p, 0, sizeof(p));
+    if (win_hi <= 0) return;
+    int img_lo = win_lo, img_hi = win_hi, up_lo = 0, up_hi = 0;      // needs of block k: image rows, rows read by block k + 1
+    int gup_lo = 0, gup_hi = 0;                                       // (gradient cone: rows read by the NEEDED conv0 rows of block k + 1)
+    for (int k = nblocks - 1, c1 = nconv - 1; k >= 1; --k, c1 -= 2) {
+        const int res = 4 << k;
+        if (res < 64) break;
+        int lo = img_lo, hi = img_hi, glo = img_lo, ghi = img_hi;
+        if (up_hi > 0) { lo = up_lo < lo ? up_lo : lo; hi = up_hi > hi ? up_hi : hi; }
+        if (gup_hi > 0) { glo = gup_lo < glo ? gup_lo : glo; ghi = gup_hi > ghi ? gup_hi : ghi; }
+        la_span_tiles(lo, hi, 4, res);
+        if (lo <= 0 && hi >= res) break;                      // everything is needed from here down
+        p.wlo[c1] = lo; p.whi[c1] = hi;
+        p.blo[c1] = glo; p.bhi[c1] = ghi;
+        p.ilo[k] = img_lo; p.ihi[k] = img_hi;
+        int l0 = lo, h0 = hi;
+        la_span_grow(l0, h0, 1, 1, res);
+        p.wlo[c1 - 1] = l0; p.whi[c1 - 1] = h0;
+        la_modconv3x3_up2_fwd_rows(res, l0, h0, &up_lo, &up_hi);
+        la_span_grow(glo, ghi, 1, 1, res);
+        p.blo[c1 - 1] = glo; p.bhi[c1 - 1] = ghi;
+        la_modconv3x3_up2_fwd_rows(res, glo, ghi, &gup_lo, &gup_hi);
+        img_lo = (img_lo - 2) >> 1; if (img_lo < 0) img_lo = 0;
+        img_hi = (img_hi >> 1) + 1; if (img_hi > res / 2) img_hi = res / 2;
+    }
+}
+// Column window (32-column tiles) of the top block's conv1 for the image column window [wcol_lo, wcol_hi): needs a tile column to spare on
+// both sides (the gradient of conv1's input reaches one column beyond the image window: it must stay inside the tiles).  0 / 0: all columns.
+static void plan_col_window(int R, int wcol_lo, int wcol_hi, int& c1lo, int& c1hi) {
+    c1lo = c1hi = 0;
+    if (wcol_hi <= 0 || R < 64) return;
+    int lo = wcol_lo, hi = wcol_hi;
+    la_span_tiles(lo, hi, 32, R);
+    if (wcol_lo - 1 >= lo && wcol_hi + 1 <= hi && (lo > 0 || hi < R)) { c1lo = lo; c1hi = hi; }
+}
 
 // a layer's epilogue (SynthesisLayer.forward: lrelu, gain sqrt(2), conv_clamp) with the noise the last forward pass used ...
 static LaLayerEpi layer_epi(const la_synth* h, const ConvLayer& L) {
@@ -316,6 +366,30 @@ extern "C" int la_synth_set_col_window(la_synth* h, int col_lo, int col_hi) {
     return LA_OK;
 }
 
+// Host only, no launch: the window of the gradient of conv output `conv_index` (0 .. 2 log2(R) - 2, the engine's layer order) that a backward pass
+// computes for the image window rows [row_lo, row_hi) x columns [col_lo, col_hi) (0, 0 = all) of a 16-bit engine at img_resolution --
+// window[0..1]: the rows in which that gradient can be non-zero (the cone of the image window; the launch that writes them rounds
+// them outward to its 4-row tiles, once), window[2..3]: the tile columns the launch writes; 0, 0 on an axis = all of it.
+extern "C" int la_synth_plan_bwd_window(int img_resolution, int row_lo, int row_hi, int col_lo, int col_hi, int conv_index, int* window) {
+    const int R = img_resolution;
+    LA_CHECK_ARG(R >= 4 && (R & (R - 1)) == 0 && R <= 4096 && window, "synth_plan_bwd_window: resolution must be a power of two >= 4");
+    LA_CHECK_ARG(row_lo >= 0 && (row_hi == 0 ? row_lo == 0 : (row_hi > row_lo && row_hi <= R)), "synth_plan_bwd_window: bad row window");
+    LA_CHECK_ARG(col_lo >= 0 && (col_hi == 0 ? col_lo == 0 : (col_hi > col_lo && col_hi <= R)), "synth_plan_bwd_window: bad column window");
+    const int nblocks = la_synth_num_ws(R) / 2, nconv = 2 * nblocks - 1;
+    LA_CHECK_ARG(conv_index >= 0 && conv_index < nconv, "synth_plan_bwd_window: no such conv layer");
+    SynthRowPlan plan;
+    plan_row_windows(nblocks, nconv, row_lo, row_hi, plan);
+    window[0] = plan.blo[conv_index]; window[1] = plan.bhi[conv_index]; window[2] = window[3] = 0;
+    if (conv_index == nconv - 2 && plan.whi[nconv - 1] > 0) plan_col_window(R, col_lo, col_hi, window[2], window[3]);
+    return LA_OK;
+}
+// ... and what the LAST forward pass of a handle recorded for its backward pass (rows only)
+extern "C" int la_synth_bwd_rows(const la_synth* h, int conv_index, int* row_lo, int* row_hi) {
+    LA_CHECK_ARG(h && row_lo && row_hi && conv_index >= 0 && conv_index < h->nconv, "synth_bwd_rows: no such conv layer");
+    *row_lo = h->bw_lo[conv_index]; *row_hi = h->bw_hi[conv_index];
+    return LA_OK;
+}
+
 #ifdef LA_DEV
 // development build: the transposed-conv intermediate of the LAST up-sampling layer that ran (column-planar rows; scripts/exp_overlap_*.py)
 extern "C" const float* la_synth_dev_zt(const la_synth* h) { return h ? h->zT : nullptr; }
@@ -345,45 +419,16 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
     if (f16 && (rc = la_xscale_from_bounds(h->dt, h->s_all, h->S, h->cst, h->channels[0] * 16, h->xs_fwd, h->xs_mult, B, stream, h->xs_bwd))) return rc;
     auto fwd_row = [&](int conv_index) { return (f16 && conv_index < h->nconv) ? h->xs_fwd + (long)conv_index * B * LA_XS_FAN : nullptr; };
     auto fwd_mult = [&](int conv_index) { return (f16 && conv_index < h->nconv) ? h->xs_mult + (long)conv_index * B : nullptr; };
-    // row windows of the conv outputs for an image row window (la_synth_set_row_window), top block downwards until a window is the
-    // whole plane: conv1 in 4-row tiles around what the image / the block above need, conv0 (FIR output) one row more on either side,
-    // the block below what conv0's transposed conv reads (la_modconv3x3_up2_fwd_rows) and what the image up-sampling reads
-    int wlo[2 * MAX_BLOCKS], whi[2 * MAX_BLOCKS], ilo[MAX_BLOCKS], ihi[MAX_BLOCKS];      // (ilo / ihi: image rows a block has to deliver)
-    for (int i = 0; i < h->nconv; ++i) wlo[i] = whi[i] = 0;
-    for (int i = 0; i < MAX_BLOCKS; ++i) ilo[i] = ihi[i] = 0;
-    if (h->win_hi > 0 && h->precision != LA_PREC_F32 && !zt_dense) {
-        int img_lo = h->win_lo, img_hi = h->win_hi, up_lo = 0, up_hi = 0;      // needs of block k: image rows, rows read by block k + 1
-        for (int k = h->nblocks - 1, c1 = h->nconv - 1; k >= 1; --k, c1 -= 2) {
-            const int res = 4 << k;
-            if (res < 64) break;
-            int lo = img_lo, hi = img_hi;
-            if (up_hi > 0) { lo = up_lo < lo ? up_lo : lo; hi = up_hi > hi ? up_hi : hi; }
-            la_span_tiles(lo, hi, 4, res);
-            if (lo <= 0 && hi >= res) break;                      // everything is needed from here down
-            wlo[c1] = lo; whi[c1] = hi;
-            ilo[k] = img_lo; ihi[k] = img_hi;
-            int l0 = lo, h0 = hi;
-            la_span_grow(l0, h0, 1, 1, res);
-            wlo[c1 - 1] = l0; whi[c1 - 1] = h0;
-            la_modconv3x3_up2_fwd_rows(res, l0, h0, &up_lo, &up_hi);
-            img_lo = (img_lo - 2) >> 1; if (img_lo < 0) img_lo = 0;
-            img_hi = (img_hi >> 1) + 1; if (img_hi > res / 2) img_hi = res / 2;
-        }
-    }
-    for (int i = 0; i < h->nconv; ++i) { h->fw_lo[i] = wlo[i]; h->fw_hi[i] = whi[i]; }
-    // column window: the top block's conv1 in whole 32-column tiles, the FIR in front of it one column more on either side.  Needs a tile
-    // column to spare on both sides (the gradient of conv1's input reaches one column beyond the image window: it must stay inside the tiles)
+    // row windows of the pass (plan_row_windows), 16-bit kernels with the column-planar scratch only
+    SynthRowPlan plan;
+    plan_row_windows(h->nblocks, h->nconv, (h->precision != LA_PREC_F32 && !zt_dense) ? h->win_lo : 0, (h->precision != LA_PREC_F32 && !zt_dense) ? h->win_hi : 0, plan);
+    const int *wlo = plan.wlo, *whi = plan.whi, *ilo = plan.ilo, *ihi = plan.ihi;
+    for (int i = 0; i < h->nconv; ++i) { h->fw_lo[i] = wlo[i]; h->fw_hi[i] = whi[i]; h->bw_lo[i] = plan.blo[i]; h->bw_hi[i] = plan.bhi[i]; }
+    // column window: the top block's conv1 in whole 32-column tiles, the FIR in front of it one column more on either side
     int c1lo = 0, c1hi = 0, c0lo = 0, c0hi = 0;
-    h->fw_c0 = h->fw_c1 = 0;
-    if (h->wcol_hi > 0 && whi[h->nconv - 1] > 0 && h->R >= 64) {
-        c1lo = h->wcol_lo; c1hi = h->wcol_hi;
-        la_span_tiles(c1lo, c1hi, 32, h->R);
-        if (h->wcol_lo - 1 >= c1lo && h->wcol_hi + 1 <= c1hi && (c1lo > 0 || c1hi < h->R)) {
-            c0lo = c1lo; c0hi = c1hi;
-            la_span_grow(c0lo, c0hi, 1, 1, h->R);
-            h->fw_c0 = c1lo; h->fw_c1 = c1hi;
-        } else c1lo = c1hi = 0;
-    }
+    if (whi[h->nconv - 1] > 0) plan_col_window(h->R, h->wcol_lo, h->wcol_hi, c1lo, c1hi);
+    h->fw_c0 = c1lo; h->fw_c1 = c1hi;
+    if (c1hi > 0) { c0lo = c1lo; c0hi = c1hi; la_span_grow(c0lo, c0hi, 1, 1, h->R); }
     int ci = 0;
     const float* x = h->cst;
     long x_bstride = 0;
@@ -469,27 +514,32 @@ extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hi
     auto xs_slot = [&](int conv_index) { return xs_hand ? h->xs_bwd + (long)conv_index * B * LA_XS_FAN : nullptr; };
     bool seam2_done = false;      // this block's conv1 seam was already applied by the epilogue of the up layer's backward above it
     bool pyramid_done = false;    // the image-gradient levels below the current block exist already (la_image_grad_pyramid)
-    // Row windows (la_synth_set_row_window): the gradient of a conv output is non-zero only inside the rows its forward window covers (the
-    // window IS the cone of the image window), so the backward pass of a windowed forward pass reads, computes and writes those rows only:
-    // a producer writes its window, its consumer reads everything outside it as zeros (LaBwdRows) -- the ping-pong buffers G0 / G1 hold
-    // older contents there.  Default path only (fused seams, slot rows); needs an image gradient that is zero outside the image window.
+    // Row windows (la_synth_set_row_window): the gradient of a conv output is non-zero only inside the cone of the image window (bw_lo /
+    // bw_hi: the forward windows without their tile rounding, plan_row_windows), so the backward pass of a windowed forward pass reads,
+    // computes and writes those rows only, each launch in its own tiles: a producer writes the tiles around its window, its consumer reads
+    // everything outside them as zeros (LaBwdRows) -- the ping-pong buffers G0 / G1 hold older contents there.  Default path only (fused
+    // seams, slot rows); needs an image gradient that is zero outside the image window.
     const bool bw = xs_hand && !no_fuse && !no_fuse2 && h->precision != LA_PREC_F32;
+    auto cone_tiles = [&](int conv_index, int res, int& lo, int& hi) {      // the 4-row tiles around the gradient rows of a conv output
+        lo = h->bw_lo[conv_index]; hi = h->bw_hi[conv_index];
+        la_span_tiles(lo, hi, 4, res);
+    };
     for (int k = h->nblocks - 1; k >= 0; --k) {
         const int res = 4 << k;
         const long HW = (long)res * res;
-        // W1 = window of this block's conv1 output (= valid rows of the gradient G0 that reaches it), R1 = the 4-row tiles around the
-        // window of conv0's output (what conv1's backward contraction writes into G1), Wb = window of the block below's conv1 output
-        const bool win = bw && k > 0 && h->fw_hi[ci] > 0;
+        // rw1: conv1's backward contraction reads the tiles around the gradient rows of conv1's output (what the seam kernel or the block
+        // above wrote into G0) and writes those of conv0's output into G1; rw0: the up-sampling layer's backward reads these and writes
+        // the tiles around the gradient rows of the block below's conv1 output
+        const bool win = bw && k > 0 && h->bw_hi[ci] > 0;
         LaBwdRows rw1 = {}, rw0 = {};
         if (win && k == h->nblocks - 1 && h->fw_c1 > 0) {      // top block: conv1's backward contraction writes the window's tile columns, the FIR adjoint reads the others as zeros
             rw1.out.col_lo = rw0.in.col_lo = h->fw_c0; rw1.out.col_hi = rw0.in.col_hi = h->fw_c1;
         }
         if (win) {
-            rw1.in.row_lo = h->fw_lo[ci]; rw1.in.row_hi = h->fw_hi[ci];
-            rw1.out.row_lo = h->fw_lo[ci - 1]; rw1.out.row_hi = h->fw_hi[ci - 1];
-            la_span_tiles(rw1.out.row_lo, rw1.out.row_hi, 4, res);
+            cone_tiles(ci, res, rw1.in.row_lo, rw1.in.row_hi);
+            cone_tiles(ci - 1, res, rw1.out.row_lo, rw1.out.row_hi);
             rw0.in.row_lo = rw1.out.row_lo; rw0.in.row_hi = rw1.out.row_hi;
-            if (ci - 2 >= 0 && h->fw_hi[ci - 2] > 0) { rw0.out.row_lo = h->fw_lo[ci - 2]; rw0.out.row_hi = h->fw_hi[ci - 2]; }
+            if (ci - 2 >= 0 && h->bw_hi[ci - 2] > 0) cone_tiles(ci - 2, res / 2, rw0.out.row_lo, rw0.out.row_hi);
         }
         RgbLayer& T = h->rgb[k];
         ConvLayer& L1 = h->conv[ci];

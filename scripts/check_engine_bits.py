@@ -28,6 +28,11 @@ def dump(lib_path, out_path):
     import torch
     from latentaugment_amd import _lib
     _lib.LIB_PATH = os.path.abspath(lib_path)
+    import ctypes
+    probe = ctypes.CDLL(_lib.LIB_PATH)
+    for k in list(_lib.SIGNATURES):      # (entries the other build lacks are dropped from the binding table, as scripts/bench_with_lib.py does)
+        if not hasattr(probe, k):
+            del _lib.SIGNATURES[k]
     from latentaugment_amd import synthesis, synthetic
     lib = _lib.load()
     assert _lib.LOADED_PATH == os.path.realpath(lib_path)

@@ -9,6 +9,7 @@ declare -A BASE=(
   [halo_splitk_small_grids.patch]=884a882 [image_chain_side_stream.patch]=4efbee0 [splitk_direct_fp32_loader.patch]=a6f3349
   [disc_skip_branch_side_stream.patch]=f51b360 [halo_persistent_small_tiles.patch]=198c70d
   [epilogue_wide_stores.patch]=bd209d2 [epilogue_straightline_and_stagger.patch]=f8bfd28
+  [halo_factor_ring.patch]=ba8b4aa
 )
 rc=0
 for p in scripts/exp/*.patch; do
