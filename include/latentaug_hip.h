@@ -643,6 +643,39 @@ int la_dc_count_f16(const void* gen, long ng, const void* real, long nr, int D, 
                     void* ws, size_t ws_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Paired image metrics (no reference counterpart): what describes a PAIR of images.  Images are float32 [N][C][H][W]; pair p is
+ * (x[ix[p]], y[iy[p]]), ix / iy int32 device arrays of length P (NULL: p itself; the caller vouches for the range of the indices).
+ *
+ * la_pair_metrics_f32, per plane (p, c):
+ *   err [P][C][2]        sum d^2 and sum |d| over the H W pixels, d = x - y formed in float32, accumulated in float64 in a fixed order.
+ *   ssim, cs [P][C][levels]   means over the 'valid' extent (h - win + 1) x (w - win + 1) of a level of
+ *                          cs   = (2 s_xy + c2) / (s_xx + s_yy + c2)
+ *                          ssim = (2 mu_x mu_y + c1) / (mu_x^2 + mu_y^2 + c1) * cs
+ *                        with mu_x = g * x, s_xx = g * (x x) - mu_x^2 (likewise s_yy, s_xy) and g the separable window taps_host[win]
+ *                        (win odd, 1 .. 11).  The next level is the 2 x 2 mean with stride 2 of both images: H and W must be multiples
+ *                        of 2^(levels-1), the last level at least win x win, 1 <= levels <= 5.
+ *   ms [P][C]            prod_{l < levels-1} max(cs_l, 0)^w_l * max(ssim_{levels-1}, 0)^w_{levels-1}, w = weights_host[levels] (>= 0),
+ *                        from the float64 means; a negative factor gives exactly 0.  levels = 1 with w = {1} is SSIM clamped at 0.
+ * One fused launch per level (a workgroup owns a 32 x 32 block: both images with their halo in LDS, row pass, column pass, the two
+ * quotients, one float64 partial pair per tile; the same launch writes the next level's images and, on level 0, the error partials),
+ * one launch that adds the tile partials per plane in tile order, one that combines the levels.  No float atomics: two runs give the
+ * same bits.  workspace: la_pair_metrics_workspace_bytes bytes, 8-byte aligned (partials and the pyramid; 0: the shape is refused).
+ * A refused shape is LA_ERR_ARG and a short workspace LA_ERR_WORKSPACE, both before any launch.
+ *
+ * la_joint_hist_f32: hist[p][bin(a_i)][bin(b_i)] += 1 (uint32) over the npix values of plane p of a (at a + p * a_plane_stride floats)
+ * and of b, bin(v) = min(bins - 1, max(0, (int)floorf((v - lo) * scale))) in float32, 1 <= bins <= 64; the caller passes
+ * scale = float32(bins / (hi - lo)).  The entry zeroes hist on `stream`.  Workgroups count in LDS and add their non-zero bins with
+ * integer atomics: order-independent, two runs give the same counts.  The plane strides let two channels of one [N][2][H][W] tensor be
+ * read in place.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t la_pair_metrics_workspace_bytes(long P, int C, int H, int W, int win, int levels);
+int la_pair_metrics_f32(const float* x, const float* y, const int* ix, const int* iy, long P, int C, int H, int W,
+                        const float* taps_host, int win, int levels, const float* weights_host, float c1, float c2, double* err,
+                        float* ssim, float* cs, float* ms, void* workspace, size_t workspace_bytes, la_stream_t stream);
+int la_joint_hist_f32(const float* a, long a_plane_stride, const float* b, long b_plane_stride, long planes, long npix, int bins,
+                      float lo, float scale, unsigned* hist, la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in profiler for the contraction launches (HIP events on the launch stream).  No reference counterpart: the
  * reference's only timing hook is wall-clock stats_time (augments/latent_aug.py:276).
  * la_prof_end: summed device ms, launch count, algorithmic FLOPs (2*MACs) and algorithmic bytes (input + output +

@@ -12,6 +12,10 @@ everything downstream of detector features.
   compute_feature_stats_for_images        images -> FeatureStats through a `synthesis.DetectorEngine` (metric_utils.py:314-320)
   compute_feature_stats_for_aug_dataset   metrics/metric_utils.py:264-328: the `img_aug/` pickles of the reference's drivers
   compute_metrics_from_images             precision / recall / density / coverage / KID of two image sets
+  compute_pair_metrics                    (not in the reference) MSE / MAE / PSNR / SSIM / MS-SSIM of image PAIRS (la_pair_metrics_f32)
+  compute_pair_metrics_for_aug_dataset    the same for `img/img_{i}` against `img_aug/img_aug_{i}` of a run directory of the drivers
+  compute_msssim_diversity                MS-SSIM over random pairs of one image set (the usual collapse check)
+  compute_modality_mi, compute_pair_mi    mutual information of two planes from their joint histogram (la_joint_hist_f32)
 
 The detectors (Inception-v3 and VGG16 pickles hosted by NVIDIA, metric_utils.py:46-60) cannot be fetched offline.  The VGG16 one has a
 local counterpart -- the TorchScript `vgg16.pt` the LPIPS criterion already needs -- and `synthesis.DetectorEngine.from_torchscript`
@@ -381,3 +385,248 @@ def compute_metrics_from_images(real_batches, gen_batches, detector, nhood_size=
     out['kid'] = compute_kid_from_features(real, gen, num_subsets=kid_num_subsets, max_subset_size=kid_max_subset_size, seed=kid_seed,
                                            device=detector.device)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# paired image metrics (la_pairmetrics.hip; no reference counterpart, no CPU fallback)
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)          # Wang, Simoncelli, Bovik 2003
+_PAIR_WORKSPACE_BYTES = 256 << 20                                   # pairs are chunked so that one call's workspace stays below this
+
+
+def gaussian_window(win_size=11, win_sigma=1.5):
+    """The `win_size` taps g[k] = exp(-(k - win_size // 2)^2 / (2 sigma^2)) normalised to sum 1, float64."""
+    if int(win_size) != win_size or not 1 <= win_size <= 11 or win_size % 2 == 0:
+        raise ValueError(f'win_size must be odd and lie in 1 .. 11 (got {win_size})')
+    if not win_sigma > 0:
+        raise ValueError(f'win_sigma must be positive (got {win_sigma})')
+    k = np.arange(int(win_size), dtype=np.float64) - int(win_size) // 2
+    g = np.exp(-(k * k) / (2.0 * float(win_sigma) ** 2))
+    return g / g.sum()
+
+
+def msssim_weights(levels, weights=None):
+    """float32 level weights of MS-SSIM: the caller's, or the first `levels` of MS_SSIM_WEIGHTS (divided by their sum when levels < 5)."""
+    if int(levels) != levels or not 1 <= levels <= 5:
+        raise ValueError(f'levels must lie in 1 .. 5 (got {levels})')
+    if weights is None:
+        w = np.asarray(MS_SSIM_WEIGHTS[:levels], dtype=np.float64)
+        if levels < 5:
+            w = w / w.sum()
+    else:
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (levels,) or not (w >= 0).all():
+            raise ValueError(f'weights: {levels} non-negative numbers, one per level')
+    return w.astype(np.float32)
+
+
+def _device_images(t, name):
+    if not torch.is_tensor(t):
+        raise _lib.LatentAugHipError(f'{name}: latentaugment_amd needs a ROCm device tensor (no CPU fallback); got {type(t).__name__}')
+    _lib.require_gpu(t)
+    if t.dtype != torch.float32:
+        raise _lib.LatentAugHipError(f'{name}: the paired metrics take float32 images; got {t.dtype}')
+    if t.ndim != 4 or min(t.shape) < 1:
+        raise ValueError(f'{name}: images must be a non-empty [N, C, H, W] tensor; got {tuple(t.shape)}')
+    return t.detach().contiguous()
+
+
+def _pair_indices(pairs, nx, ny):
+    ix, iy = (np.ascontiguousarray(i, dtype=np.int32) for i in pairs)
+    if ix.ndim != 1 or ix.shape != iy.shape or ix.size < 1:
+        raise ValueError('pairs: (ix [P], iy [P]) with P >= 1')
+    if ix.min() < 0 or ix.max() >= nx or iy.min() < 0 or iy.max() >= ny:
+        raise ValueError('pairs: an image number outside its batch')
+    return ix, iy
+
+
+def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigma=1.5, levels=5, weights=None):
+    """Per pair of images: MSE, MAE, PSNR, SSIM and MS-SSIM.  x, y: float32 device tensors [N, C, H, W] in a range of width
+    `data_range` (2 for the generator's [-1, 1]).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy); the kernel
+    gathers, the images are not copied.  A Gaussian window of `win_size` taps (odd, 1 .. 11) and `win_sigma`, 'valid' extent;
+    `levels` pyramid levels (1 .. 5) by 2 x 2 means, so H and W must be multiples of 2^(levels-1) and the last level at least the
+    window; levels=1 is plain SSIM.  MS-SSIM is prod_{l<levels-1} max(cs_l, 0)^w_l * max(ssim_last, 0)^w_last with `msssim_weights`.
+    Returns float64 CPU tensors: 'mse', 'mae', 'psnr', 'ssim', 'ms_ssim' [P] -- the mean over channels, psnr = 10 log10(L^2 / mse) of
+    that mean (inf at 0) -- their '*_per_channel' forms [P, C], and 'ssim_levels', 'cs_levels' [P, C, levels].
+    Two calls give the same bits (la_pair_metrics_f32).  There is no CPU fallback."""
+    x, y = _device_images(x, 'x'), _device_images(y, 'y')
+    if x.device != y.device or x.shape[1:] != y.shape[1:]:
+        raise ValueError(f'x and y must be on one device and agree in [C, H, W]: {tuple(x.shape)} on {x.device}, {tuple(y.shape)} on {y.device}')
+    if not data_range > 0:
+        raise ValueError('data_range must be positive')
+    taps = gaussian_window(win_size, win_sigma).astype(np.float32)
+    w = msssim_weights(levels, weights)
+    win, levels = int(win_size), int(levels)
+    C, H, W = (int(s) for s in x.shape[1:])
+    dev = x.device
+    if pairs is None:
+        if x.shape[0] != y.shape[0]:
+            raise ValueError('without pairs, x and y must hold the same number of images')
+        P, ixd, iyd = int(x.shape[0]), None, None
+    else:
+        ix, iy = _pair_indices(pairs, x.shape[0], y.shape[0])
+        P, ixd, iyd = int(ix.size), torch.from_numpy(ix).to(dev), torch.from_numpy(iy).to(dev)
+    lib = _lib.load()
+    per_pair = lib.la_pair_metrics_workspace_bytes(1, C, H, W, win, levels)
+    if per_pair == 0:
+        raise ValueError(f'pair metrics: [{C}, {H}, {W}] images with win_size {win} and {levels} levels are refused: H and W must be '
+                         'multiples of 2^(levels-1) and the last level at least win_size x win_size')
+    chunk = max(1, min(P, _PAIR_WORKSPACE_BYTES // per_pair))
+    ws_bytes = lib.la_pair_metrics_workspace_bytes(chunk, C, H, W, win, levels)
+    ws = torch.empty([ws_bytes // 8], dtype=torch.float64, device=dev)
+    err = torch.empty([P, C, 2], dtype=torch.float64, device=dev)
+    ssim = torch.empty([P, C, levels], dtype=torch.float32, device=dev)
+    cs = torch.empty([P, C, levels], dtype=torch.float32, device=dev)
+    ms = torch.empty([P, C], dtype=torch.float32, device=dev)
+    c1, c2 = (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
+    with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
+        for p0 in range(0, P, chunk):
+            n = min(chunk, P - p0)
+            xa, ya = (x, y) if pairs is not None else (x[p0:], y[p0:])
+            _lib.check(lib.la_pair_metrics_f32(
+                _lib.ptr(xa), _lib.ptr(ya), _lib.ptr(ixd[p0:]) if pairs is not None else None,
+                _lib.ptr(iyd[p0:]) if pairs is not None else None, n, C, H, W, taps.ctypes.data, win, levels, w.ctypes.data, c1, c2,
+                _lib.ptr(err[p0:]), _lib.ptr(ssim[p0:]), _lib.ptr(cs[p0:]), _lib.ptr(ms[p0:]), _lib.ptr(ws), ws_bytes,
+                _lib.stream_ptr()), 'pair_metrics')
+    err = err.cpu()
+    out = {'mse_per_channel': err[..., 0] / (H * W), 'mae_per_channel': err[..., 1] / (H * W),
+           'ssim_per_channel': ssim[..., 0].cpu().double(), 'ms_ssim_per_channel': ms.cpu().double(),
+           'ssim_levels': ssim.cpu().double(), 'cs_levels': cs.cpu().double()}
+    for k in ('mse', 'mae', 'ssim', 'ms_ssim'):
+        out[k] = out[k + '_per_channel'].mean(dim=1)
+    for k in ('psnr', 'psnr_per_channel'):
+        out[k] = 10.0 * torch.log10(float(data_range) ** 2 / out[k.replace('psnr', 'mse')])          # x / 0 = inf in float64 tensors
+    return out
+
+
+def _aug_pair_files(datadir):
+    i, files = 0, []
+    while os.path.isfile(os.path.join(datadir, 'img', f'img_{i}')) and os.path.isfile(os.path.join(datadir, 'img_aug', f'img_aug_{i}')):
+        files.append((os.path.join(datadir, 'img', f'img_{i}'), os.path.join(datadir, 'img_aug', f'img_aug_{i}')))
+        i += 1
+    return files
+
+
+def compute_pair_metrics_for_aug_dataset(datadir, device='cuda:0', **kw):
+    """compute_pair_metrics of every source image against its augmented version in a run directory of the reference's drivers
+    (backbone_latentaug.py:112-118): `img/img_{i}` and `img_aug/img_aug_{i}`, i = 0, 1, .., each a pickled dict of image batches whose
+    'A' and 'B' entries ([n, 1, H, W]) become the two channels.  The pickles are read through the allow-list loader of formats.py,
+    never a plain unpickle.  Returns the per-sample tensors of compute_pair_metrics over all files, a float '<key>_mean' for each of
+    'mse', 'mae', 'psnr', 'ssim', 'ms_ssim', and 'num_items'."""
+    from .formats import _restricted_load
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); got device ' + str(dev))
+    files = _aug_pair_files(datadir)
+    if not files:
+        raise FileNotFoundError(f"no img/img_0 with img_aug/img_aug_0 under {datadir}")
+
+    def two_channels(fname):
+        with open(fname, 'rb') as f:
+            d = _restricted_load(f)
+        planes = [torch.as_tensor(d[m]).to(torch.float32) for m in ('A', 'B')]
+        if any(p.ndim != 4 or p.shape[1] != 1 for p in planes):
+            raise ValueError(f"{fname}: 'A' and 'B' must be [n, 1, H, W] batches")
+        return torch.cat(planes, dim=1).to(dev)
+    parts = [compute_pair_metrics(two_channels(src), two_channels(aug), **kw) for src, aug in files]
+    out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
+    out['num_items'] = int(out['mse'].shape[0])
+    for k in ('mse', 'mae', 'psnr', 'ssim', 'ms_ssim'):
+        out[k + '_mean'] = float(out[k].mean())
+    return out
+
+
+def msssim_diversity_pairs(num_images, num_pairs=1000, seed=0):
+    """(ix, iy) int32: `num_pairs` distinct unordered pairs i < j of `num_images` images.  When the set has no more than `num_pairs`
+    pairs: all of them, in lexicographic order.  Otherwise numpy.random.RandomState(seed) draws batches of `num_pairs` candidates
+    `randint(0, num_images, [num_pairs, 2])`; a candidate with i == j or equal (as an unordered pair) to an earlier one is dropped,
+    and the first `num_pairs` survivors are kept in the order drawn."""
+    n = int(num_images)
+    if n < 2 or num_pairs < 1:
+        raise ValueError('MS-SSIM diversity needs at least 2 images and 1 pair')
+    total = n * (n - 1) // 2
+    if total <= num_pairs:
+        i, j = np.triu_indices(n, k=1)
+        return i.astype(np.int32), j.astype(np.int32)
+    rs = np.random.RandomState(seed)
+    seen, keep = set(), []
+    while len(keep) < num_pairs:
+        for a, b in rs.randint(0, n, [num_pairs, 2]):
+            key = (min(a, b), max(a, b))
+            if a != b and key not in seen and len(keep) < num_pairs:
+                seen.add(key)
+                keep.append(key)
+    keep = np.asarray(keep, dtype=np.int32)
+    return np.ascontiguousarray(keep[:, 0]), np.ascontiguousarray(keep[:, 1])
+
+
+def compute_msssim_diversity(images, num_pairs=1000, seed=0, **kw):
+    """Mean MS-SSIM over `msssim_diversity_pairs(N, num_pairs, seed)` of one image set [N, C, H, W] (float32, on the device): near 1
+    means that the samples resemble one another (mode collapse).  The kernel gathers the pairs; the images are never copied.
+    Returns {'mean': float, 'ms_ssim': float64 [P], 'ix', 'iy'}; **kw goes to compute_pair_metrics."""
+    images = _device_images(images, 'images')
+    ix, iy = msssim_diversity_pairs(images.shape[0], num_pairs, seed)
+    ms = compute_pair_metrics(images, images, pairs=(ix, iy), **kw)['ms_ssim']
+    return dict(mean=float(ms.mean()), ms_ssim=ms, ix=ix, iy=iy)
+
+
+def mi_from_counts(counts):
+    """(mi, nmi) float64 [...] from joint-histogram counts [..., bins, bins], natural logarithms: MI = sum p_ab log(p_ab / (p_a p_b)),
+    NMI = (H_a + H_b) / H_ab; where H_ab = 0 (all of a plane in one bin) NMI = 2, the value for identical images, and MI = 0."""
+    c = np.asarray(counts).astype(np.float64)
+    n = c.sum(axis=(-2, -1), keepdims=True)
+    if not (n > 0).all():
+        raise ValueError('mi_from_counts: an empty histogram')
+    pab = c / n
+    pa, pb = pab.sum(axis=-1, keepdims=True), pab.sum(axis=-2, keepdims=True)
+
+    def entropy(p, axes):
+        return -np.sum(p * np.log(np.where(p > 0, p, 1.0)), axis=axes)
+    ha, hb, hab = entropy(pa, (-2, -1)), entropy(pb, (-2, -1)), entropy(pab, (-2, -1))
+    ratio = np.where(pab > 0, pab, 1.0) / np.where(pab > 0, pa * pb, 1.0)
+    mi = np.sum(pab * np.log(ratio), axis=(-2, -1))
+    one_bin = c.max(axis=(-2, -1)) == n[..., 0, 0]
+    nmi = np.where(one_bin, 2.0, (ha + hb) / np.where(one_bin, 1.0, hab))
+    return np.where(one_bin, 0.0, mi), nmi
+
+
+def _joint_hist(a, a_stride, b, b_stride, planes, npix, bins, value_range, dev):
+    lo, hi = float(value_range[0]), float(value_range[1])
+    if int(bins) != bins or not 1 <= bins <= 64:
+        raise ValueError(f'bins must lie in 1 .. 64 (got {bins})')
+    if not hi > lo:
+        raise ValueError('value_range must be (lo, hi) with hi > lo')
+    lib = _lib.load()
+    hist = torch.empty([planes, int(bins), int(bins)], dtype=torch.int32, device=dev)          # uint32 counts
+    with torch.cuda.device(dev):
+        _lib.check(lib.la_joint_hist_f32(a, a_stride, b, b_stride, planes, npix, int(bins), float(np.float32(lo)),
+                                         float(np.float32(bins / (hi - lo))), _lib.ptr(hist), _lib.stream_ptr()), 'joint_hist')
+    counts = hist.cpu().numpy().view(np.uint32).astype(np.int64)
+    mi, nmi = mi_from_counts(counts)
+    return dict(mi=mi, nmi=nmi, counts=counts)
+
+
+def compute_modality_mi(images, channels=(0, 1), bins=64, value_range=(-1.0, 1.0)):
+    """Mutual information of two channels (the generator's CT and MRI) of every sample of `images` [N, C, H, W] (float32, on the
+    device), read in place.  The joint histogram has `bins` x `bins` cells (1 .. 64) over `value_range`, values outside it counted in
+    the edge bins (la_joint_hist_f32: float32 bin rule, integer counts, the same on every run).
+    Returns {'mi', 'nmi': float64 [N], 'counts': int64 [N, bins, bins]} (mi_from_counts)."""
+    images = _device_images(images, 'images')
+    N, C, H, W = (int(s) for s in images.shape)
+    ca, cb = (int(c) for c in channels)
+    if not (0 <= ca < C and 0 <= cb < C):
+        raise ValueError(f'channels {channels} outside the {C} channels of the images')
+    base = images.data_ptr()
+    return _joint_hist(base + 4 * ca * H * W, C * H * W, base + 4 * cb * H * W, C * H * W, N, H * W, bins, value_range, images.device)
+
+
+def compute_pair_mi(x, y, channel=0, bins=64, value_range=(-1.0, 1.0)):
+    """compute_modality_mi between plane `channel` of x[i] and the same plane of y[i] (two batches of one shape)."""
+    x, y = _device_images(x, 'x'), _device_images(y, 'y')
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError(f'x and y must agree in shape and device: {tuple(x.shape)}, {tuple(y.shape)}')
+    N, C, H, W = (int(s) for s in x.shape)
+    c = int(channel)
+    if not 0 <= c < C:
+        raise ValueError(f'channel {channel} outside the {C} channels of the images')
+    return _joint_hist(x.data_ptr() + 4 * c * H * W, C * H * W, y.data_ptr() + 4 * c * H * W, C * H * W, N, H * W, bins, value_range,
+                       x.device)
