@@ -438,6 +438,14 @@ const float* la_disc_logits(const la_disc* h);
  * ends in an FC op is a detector list: forward only (la_feat_backward refuses it), its feature vector is the last FC's output,
  * it holds no tap (a list with both is refused), and only FC ops may follow the first FC.  Its convolutions run in the engine's
  * precision mode; the FC ops are always exact fp32 (la_fc_bias_act_f32).
+ * Pair distance (tap lists only): la_feat_pair_distance runs the trunk once on xy [2P][in_ch][in_res^2] and writes, per tap,
+ * the LPIPS distance of rows p and p + P -- dist [P][ntaps] float64, dist[p][t] = mean over pixels of
+ * sum_c lin[c] (fx rx - fy ry)^2 with the tap's r = rsqrt(sum_c f^2 + 1e-10) -- without writing a feature vector.  lin enters
+ * as it is (no sqrt), so its sign does not matter here.  ws: la_feat_pair_workspace_bytes(h, P) bytes (0: detector list or
+ * 2P > max_batch, which la_feat_pair_distance refuses with LA_ERR_ARG before any launch).  No atomics: two runs give the same
+ * bits; no host sync, no allocation.  It overwrites the activations of an earlier la_feat_forward (la_feat_backward then refuses
+ * until the next forward).  la_feat_num_taps: taps of the list = columns of dist.  la_crop_repeat_affine_f32: la_crop_repeat_f32
+ * with one scale / shift per repeated channel (host arrays of `rep` floats), e.g. the (x - mean_k) / std_k of an input layer.
  * ------------------------------------------------------------------------------------------------------------- */
 #define LA_FEAT_CONV_RELU 0
 #define LA_FEAT_TAP 1
@@ -455,8 +463,13 @@ int la_feat_num_features(const la_feat* h);
 int la_feat_set_precision(la_feat* h, int precision);
 int la_feat_forward(la_feat* h, const float* x, int N, float* feat_out, la_stream_t stream);
 int la_feat_backward(la_feat* h, const float* gfeat, float* gx, la_stream_t stream);
+int la_feat_num_taps(const la_feat* h);
+size_t la_feat_pair_workspace_bytes(const la_feat* h, int P);
+int la_feat_pair_distance(la_feat* h, const float* xy, int P, double* dist, void* ws, size_t ws_bytes, la_stream_t stream);
 int la_crop_repeat_f32(const float* img, float* xc, int B, int imgc, int R, int S, int y0, int x0, int rep, float scale,
                        float shift, la_stream_t stream);
+int la_crop_repeat_affine_f32(const float* img, float* xc, int B, int imgc, int R, int S, int y0, int x0, int rep,
+                              const float* scale, const float* shift, la_stream_t stream);
 int la_crop_repeat_grad_f32(const float* gxc, float* g_img, int B, int imgc, int R, int S, int y0, int x0, int rep,
                             float scale, la_stream_t stream);
 

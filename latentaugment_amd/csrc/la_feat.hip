@@ -470,6 +470,192 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// LPIPS distance of image pairs: rows p and p + P of one 2P batch, one launch per tap and no feature vector in memory.
+//       part[p][tap][tile] = sum over the tile's pixels and all channels of lin[c] * (fx * rx - fy * ry)^2,   r = rsqrt(sum_c f^2 + 1e-10)
+// Thread layout of la_tap_fwd_kernel (PL pixel lanes x 256 / PL channel groups; pass 1 sums each thread's channels in the same order,
+// so r is the tap's).  Pass 2 takes DIFFERENCES of the normalised values -- the images of a pair are close, the expanded form
+// |x|^2 + |y|^2 - 2 x.y cancels -- with contraction off: a fused fx * rx - (fy * ry) would round one product and not the other, and
+// d(x, x) = 0, d(x, y) = d(y, x) would no longer hold bit for bit.  lin enters as it is (no sqrt: a negative weight is legal here).
+// KEEP > 0: a thread's ceil(C / groups) <= KEEP channels of both images stay in registers between the passes; KEEP = 0 reads them again.
+// One float64 partial per workgroup, combined in a fixed order: no atomics, two runs give the same bits.
+template <int KEEP>
+__global__ __launch_bounds__(256) void la_tap_pair_dist_kernel(const float* __restrict__ f, const float* __restrict__ lin, double* __restrict__ part,
+                                                                int C, int HW, int P, int PL, long part_stride, long part_off) {
+    __shared__ float red[2][256];
+    __shared__ double dred[256];
+    const int pl = threadIdx.x % PL, cg = threadIdx.x / PL, CG = 256 / PL;
+    const int p = blockIdx.x * PL + pl;
+    const long n = blockIdx.y;
+    const bool ok = p < HW;
+    const float* fx = f + n * C * HW + p;
+    const float* fy = f + (n + P) * C * HW + p;
+    float vx[KEEP ? KEEP : 1], vy[KEEP ? KEEP : 1];
+    float sx = 0.f, sy = 0.f;
+    if (ok) {
+        if constexpr (KEEP > 0) {
+#pragma unroll
+            for (int k = 0; k < KEEP; ++k) {
+                const int c = cg + k * CG;
+                vx[k] = c < C ? fx[(long)c * HW] : 0.f;
+                vy[k] = c < C ? fy[(long)c * HW] : 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k < KEEP; ++k) { sx += vx[k] * vx[k]; sy += vy[k] * vy[k]; }
+        } else {
+            int c = cg;
+            for (; c + 7 * CG < C; c += 8 * CG) {      // (eight channels' loads of each image in flight: see la_tap_fwd_kernel)
+                float a[8], b[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { a[k] = fx[(long)(c + k * CG) * HW]; b[k] = fy[(long)(c + k * CG) * HW]; }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { sx += a[k] * a[k]; sy += b[k] * b[k]; }
+            }
+            for (; c < C; c += CG) { const float a = fx[(long)c * HW], b = fy[(long)c * HW]; sx += a * a; sy += b * b; }
+        }
+    }
+    red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy;
+    __syncthreads();
+    float tx = 0.f, ty = 0.f;
+    for (int g = 0; g < CG; ++g) { tx += red[0][g * PL + pl]; ty += red[1][g * PL + pl]; }
+    const float rx = rsqrtf(tx + 1e-10f), ry = rsqrtf(ty + 1e-10f);
+    double acc = 0.0;
+    if (ok) {
+#pragma clang fp contract(off)
+        if constexpr (KEEP > 0) {
+#pragma unroll
+            for (int k = 0; k < KEEP; ++k) {
+                const int c = cg + k * CG;
+                const float w = c < C ? lin[c] : 0.f;
+                const float ax = vx[k] * rx, ay = vy[k] * ry;
+                const float d = ax - ay;
+                acc += (double)(w * (d * d));
+            }
+        } else {
+            int c = cg;
+            for (; c + 7 * CG < C; c += 8 * CG) {
+                float a[8], b[8], w[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { a[k] = fx[(long)(c + k * CG) * HW]; b[k] = fy[(long)(c + k * CG) * HW]; w[k] = lin[c + k * CG]; }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float ax = a[k] * rx, ay = b[k] * ry;
+                    const float d = ax - ay;
+                    acc += (double)(w[k] * (d * d));
+                }
+            }
+            for (; c < C; c += CG) {
+                const float ax = fx[(long)c * HW] * rx, ay = fy[(long)c * HW] * ry;
+                const float d = ax - ay;
+                acc += (double)(lin[c] * (d * d));
+            }
+        }
+    }
+    dred[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) dred[threadIdx.x] += dred[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[n * part_stride + part_off + blockIdx.x] = dred[0];
+}
+
+// dist[p][tap] = (sum of the tap's tiles, in order) / HW.  One 64-thread workgroup per (tap, pair): thread i adds tiles i, i + 64, ..
+struct LaPairTaps { int n, tiles_max; int tiles[FEAT_MAX_OPS], hw[FEAT_MAX_OPS]; };
+__global__ __launch_bounds__(64) void la_pair_dist_finish_kernel(const double* __restrict__ part, double* __restrict__ dist, LaPairTaps t) {
+    __shared__ double red[64];
+    const int tap = blockIdx.x;
+    const long p = blockIdx.y;
+    const double* src = part + (p * t.n + tap) * t.tiles_max;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < t.tiles[tap]; i += 64) s += src[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int g = 0; g < 64; ++g) tot += red[g];
+        dist[p * t.n + tap] = tot / (double)t.hw[tap];
+    }
+}
+
+// channels of BOTH images a thread of the pair kernel keeps in registers: 32 or 64 each where its share of the tap fits, else none
+static inline int pair_keep(int C, int HW) {
+    const int per = la_cdiv(C, 256 / tap_lanes(HW));
+    return per <= 32 ? 32 : per <= 64 ? 64 : 0;
+}
+
+static void pair_taps(const la_feat* h, LaPairTaps& t) {
+    t.n = 0; t.tiles_max = 1;
+    for (int k = 0; k < h->nops; ++k)
+        if (h->op[k].kind == LA_FEAT_TAP) {
+            const int HW = h->op[k].res_out * h->op[k].res_out;
+            t.hw[t.n] = HW; t.tiles[t.n] = la_cdiv(HW, tap_lanes(HW));
+            if (t.tiles[t.n] > t.tiles_max) t.tiles_max = t.tiles[t.n];
+            ++t.n;
+        }
+}
+
+extern "C" int la_feat_num_taps(const la_feat* h) {
+    if (!h || h->detector) return 0;
+    LaPairTaps t; pair_taps(h, t);
+    return t.n;
+}
+
+// the float64 partials [P][ntaps][tiles of the largest tap]; 0: no handle, a detector list, or 2P outside 2 .. max_batch
+extern "C" size_t la_feat_pair_workspace_bytes(const la_feat* h, int P) {
+    if (!h || h->detector || P < 1 || 2L * P > h->maxN) return 0;
+    LaPairTaps t; pair_taps(h, t);
+    return la_align64(sizeof(double) * (size_t)P * t.n * t.tiles_max);
+}
+
+// dist [P][ntaps] (float64) = per tap, the LPIPS distance of rows p and p + P of xy [2P][in_ch][in_res^2]: the trunk of la_feat_forward
+// once on the 2P rows (its loop, repeated here because that entry stays as it is), the pair kernel where it launches the tap.  No host
+// sync, no allocation.  The activations of an earlier la_feat_forward are overwritten: la_feat_backward refuses until the next forward.
+extern "C" int la_feat_pair_distance(la_feat* h, const float* xy, int P, double* dist, void* ws, size_t ws_bytes, hipStream_t stream) {
+    LA_CHECK_ARG(h && xy && dist && ws, "feat_pair_distance: null pointer");
+    LA_CHECK_ARG(!h->detector, "feat_pair_distance: a detector list (fc ops) has no taps");
+    LA_CHECK_ARG(P >= 1 && 2L * P <= h->maxN, "feat_pair_distance: 2 * pairs exceeds max_batch");
+    if (ws_bytes < la_feat_pair_workspace_bytes(h, P)) { la_set_error("feat_pair_distance: workspace too small"); return LA_ERR_WORKSPACE; }
+    LaPairTaps t; pair_taps(h, t);
+    const int N = 2 * P;
+    const float* cur = xy;
+    int rc, tap = 0;
+    h->lastN = 0;
+    const bool slots = h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS");
+    if (slots) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_f), (int)LA_XS_INIT, (size_t)h->nops * h->maxN * LA_XS_FAN, stream));
+    auto rows = [&](float* base, int op) { return base + (size_t)op * h->maxN * LA_XS_FAN; };
+    bool first_conv = true;
+    for (int k = 0; k < h->nops; ++k) {
+        FOp& o = h->op[k];
+        const int HWo = o.res_out * o.res_out;
+        if (o.kind == LA_FEAT_CONV_RELU) {
+            int nxt = -1;
+            for (int q = k + 1; q < h->nops; ++q) if (h->op[q].kind == LA_FEAT_CONV_RELU) { nxt = q; break; }
+            LaConvArgs a; f_conv(a, h, o, false, N);
+            a.in = cur; a.out = o.y;
+            if (slots && !first_conv) { a.acc_scale_x = rows(h->xs_f, k); a.acc_scale_fan = LA_XS_FAN; }
+            if (slots && nxt >= 0) a.fwd_xs_out = rows(h->xs_f, nxt);
+            if ((rc = la_conv_launch(a, stream))) return rc;
+            first_conv = false;
+            cur = o.y;
+        } else if (o.kind == LA_FEAT_TAP) {
+            const int pl = tap_lanes(HWo), keep = pair_keep(o.cout, HWo);
+            auto kern = keep == 32 ? la_tap_pair_dist_kernel<32> : keep == 64 ? la_tap_pair_dist_kernel<64> : la_tap_pair_dist_kernel<0>;
+            hipLaunchKernelGGL(kern, dim3(t.tiles[tap], P), dim3(256), 0, stream, cur, o.lin, (double*)ws, o.cout, HWo, P, pl,
+                               (long)t.n * t.tiles_max, (long)tap * t.tiles_max);
+            ++tap;
+        } else {
+            const long planes = (long)N * o.cout;
+            hipLaunchKernelGGL(la_pool2_fwd_kernel, dim3(la_cdiv(planes * HWo, 256)), dim3(256), 0, stream, cur, o.y, o.res_in, planes,
+                               o.kind == LA_FEAT_MAXPOOL2);
+            cur = o.y;
+        }
+    }
+    hipLaunchKernelGGL(la_pair_dist_finish_kernel, dim3(t.n, P), dim3(64), 0, stream, (const double*)ws, dist, t);
+    LA_CHECK_LAUNCH();
+    return LA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // criterion glue: crop (+ repeat to 3 channels, affine preprocess) and its adjoint
 //   xc[(c*B + b)][k][y][x] = img[b][c][y0+y][x0+x] * scale + shift      k = 0..rep-1
 // (pos != null: the window position {y0, x0} is read from device memory, so that a captured launch follows the position the
@@ -519,6 +705,11 @@ extern "C" int la_crop_repeat_f32(const float* img, float* xc, int B, int imgc, 
                                   float shift, hipStream_t stream) {
     const float sc[4] = {scale, scale, scale, scale}, sh[4] = {shift, shift, shift, shift};
     return la_crop_repeat(img, xc, B, imgc, R, S, y0, x0, nullptr, rep, sc, sh, stream);
+}
+
+extern "C" int la_crop_repeat_affine_f32(const float* img, float* xc, int B, int imgc, int R, int S, int y0, int x0, int rep,
+                                         const float* scale, const float* shift, hipStream_t stream) {
+    return la_crop_repeat(img, xc, B, imgc, R, S, y0, x0, nullptr, rep, scale, shift, stream);
 }
 
 int la_crop_repeat_grad(const float* gxc, float* g_img, int B, int imgc, int R, int S, int y0, int x0, const int* pos_dev, int rep,

@@ -213,6 +213,7 @@ class LatentAug:
             raise _lib.LatentAugHipError(f'opt.latent_space = {space!r}: expected one of {sorted(LATENT_SPACES)}')
         self.wplus = self.latent_space == 'w+'
         self._script_path = None
+        self._reference_net_paths = None
         if self.w_lpips > 0 and feature_net is None:
             # the reference's default perceptual net (`lpips_script`): NVIDIA's TorchScript vgg16.pt, fetched from a URL by load_vgg()
             # (:35-43).  There is no network here: a LOCAL copy is accepted at opt.lpips_script_path or <model_dir>/vgg16.pt.
@@ -220,11 +221,25 @@ class LatentAug:
             if getattr(opt, 'lpips_script', 'lpips_script') == 'lpips_script' and getattr(opt, 'model_dir', None):
                 cands.append(os.path.join(opt.model_dir, 'vgg16.pt'))
             self._script_path = next((c for c in cands if c and os.path.isfile(c)), None)
-            if self._script_path is None:
+            # the reference's other perceptual branch (`lpips_script != 'lpips_script'`: augments/criteria/lpips/lpips.py::LPIPS('vgg'),
+            # util_latent_aug.py:129-131, which downloads torchvision's VGG16 and the LPIPS lin weights): LOCAL state dicts at
+            # opt.lpips_vgg_path / opt.lpips_lin_path, or <model_dir>/vgg16.pth and <model_dir>/lpips_vgg.pth
+            if not getattr(opt, 'lpips_script_path', None) and getattr(opt, 'lpips_script', 'lpips_script') != 'lpips_script':
+                pair = []
+                for attr, name in (('lpips_vgg_path', 'vgg16.pth'), ('lpips_lin_path', 'lpips_vgg.pth')):
+                    cands = [getattr(opt, attr, None)]
+                    if getattr(opt, 'model_dir', None):
+                        cands.append(os.path.join(opt.model_dir, name))
+                    pair.append(next((c for c in cands if c and os.path.isfile(c)), None))
+                if all(pair):
+                    self._reference_net_paths = tuple(pair)
+            if self._script_path is None and self._reference_net_paths is None:
                 raise NotImplementedError(
                     'w_lpips > 0 needs `feature_net=` (op list for synthesis.FeatureEngine, e.g. vgg16_lpips_ops(...)) or a local copy '
                     "of NVIDIA's TorchScript vgg16.pt at opt.lpips_script_path / <model_dir>/vgg16.pt (the reference downloads it, "
-                    "util_latent_aug.py:36; there is no network here), and banks['fea'] or the interim image zip to build them from")
+                    "util_latent_aug.py:36; there is no network here), or -- with opt.lpips_script != 'lpips_script' -- local state dicts of "
+                    "torchvision's VGG16 and the LPIPS lin layers at opt.lpips_vgg_path / opt.lpips_lin_path (<model_dir>/vgg16.pth, "
+                    "<model_dir>/lpips_vgg.pth), and banks['fea'] or the interim image zip to build them from")
         if generator is None:
             # load_stylegan (reference :466-484): <model_dir>/<dataset>/training-runs/<dataset_name>/<modalities>/<exp>/<pkl>
             from . import formats
@@ -376,6 +391,16 @@ class LatentAug:
             if feature_net is not None:
                 self.feat = FeatureEngine(feature_net, self.device, in_res=self.crop_size, max_batch=imgc * max_local,
                                           precision=self.precision)
+            elif self._reference_net_paths is not None:
+                # LPIPS('vgg') of the reference: three taps, z-score input.  The tap vector makes squared L2 against a bank row the
+                # reference's d(x, y_m), so sum / (n * M) per modality is its forward_tr (lpips.py:60-68) -- exactly at n = 1, the only
+                # batch its broadcast (fx - fy) admits -- through the loop code of the TorchScript branch, unchanged.
+                from .synthesis import lpips_reference_net
+                print(f'Loading VGG16 / LPIPS lin weights from: {self._reference_net_paths}')
+                self.feat = FeatureEngine.from_net(lpips_reference_net(*self._reference_net_paths), self.device, in_res=self.crop_size,
+                                                   max_batch=imgc * max_local, precision=self.precision)
+                if not hasattr(opt, 'lpips_preproc'):
+                    opt.lpips_preproc = (self.feat.pre_scale, self.feat.pre_shift)
             else:
                 print(f'Loading VGG16 from: {self._script_path}')
                 self.feat = FeatureEngine.from_torchscript(self._script_path, self.device, in_res=self.crop_size,
@@ -436,9 +461,12 @@ class LatentAug:
                 def fmt(v):
                     return f'{v[0]:g}' if v[0] == v[1] == v[2] else '_'.join(f'{t:g}' for t in v)
                 tag += f"-{'raw' if raw else 'unit'}-s{fmt(scale)}-b{fmt(shift)}-w{self.feat.weights_digest}"
-            st = formats.compute_stats(ds, 'features_jit', os.path.join(root, 'cache_dir'), cache_tag=tag,
+            # (the reference's LPIPS('vgg') branch caches under the 'features' manifold, util_latent_aug.py:184: its per-layer list is
+            #  this engine's one tap vector, kept as [M, F, 1, 1])
+            manifold = 'features' if self._reference_net_paths is not None else 'features_jit'
+            st = formats.compute_stats(ds, manifold, os.path.join(root, 'cache_dir'), cache_tag=tag,
                                        step=opt.step_img, feature_fn=feature_fn)
-            out.append(st.get_all_torch())
+            out.append(st.get_all_torch().flatten(1))
         return out
 
     def __del__(self):

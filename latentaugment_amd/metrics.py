@@ -23,6 +23,7 @@ runs its `return_features=True` branch on the HIP path, so precision / recall, d
 Inception-v3 pickle has none: FID keeps taking features or moments that the caller supplies.
 torch only owns the device memory; the moments, distances, radii, membership tests and kernel sums are HIP kernels (la_metrics.hip).
 """
+import ctypes as C
 import glob
 import os
 import pickle
@@ -439,7 +440,68 @@ def _pair_indices(pairs, nx, ny):
     return ix, iy
 
 
-def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigma=1.5, levels=5, weights=None):
+def compute_lpips(x, y, net, pairs=None):
+    """LPIPS distance per pair of images, modality by modality, the way the perceptual criterion feeds its net
+    (util_latent_aug.py:387-409): every channel of x[p] and of y[p] is repeated to three channels, given the net's input affine
+    (`net.pre_scale`, `net.pre_shift`) and sent through `net`, a synthesis.FeatureEngine of three input channels; the distance comes
+    from one fused launch per tap (FeatureEngine.pair_distance_rows), no feature vector is written.  x, y: float32 device tensors
+    [N, C, R, R] with R == net.in_res (whole frames, not crops), values in the range the net expects ([-1, 1] for
+    lpips_reference_net).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy), gathered chunk by chunk with
+    index_select.  Returns float64 CPU tensors: 'lpips' [P] (mean over channels), 'lpips_per_channel' [P, C] (sum over taps),
+    'lpips_layers' [P, C, ntaps].  Two calls give the same bits.  There is no CPU fallback."""
+    x, y = _device_images(x, 'x'), _device_images(y, 'y')
+    if x.device != y.device or x.shape[1:] != y.shape[1:]:
+        raise ValueError(f'x and y must be on one device and agree in [C, H, W]: {tuple(x.shape)} on {x.device}, {tuple(y.shape)} on {y.device}')
+    if not hasattr(net, 'pair_distance_rows'):
+        raise _lib.LatentAugHipError(f'compute_lpips: net must be a synthesis.FeatureEngine; got {type(net).__name__}')
+    per_call = net.pair_rows()          # (refuses a detector engine)
+    C_, H, W = (int(s) for s in x.shape[1:])
+    if net.in_ch != 3 or H != net.in_res or W != net.in_res:
+        raise ValueError(f'compute_lpips: the net takes [3, {net.in_res}, {net.in_res}] inputs (in_ch {net.in_ch}); the images are [{C_}, {H}, {W}]')
+    if x.device != net.device:
+        raise ValueError(f'compute_lpips: images on {x.device}, net on {net.device}')
+    dev, R = x.device, H
+    if pairs is None:
+        if x.shape[0] != y.shape[0]:
+            raise ValueError('without pairs, x and y must hold the same number of images')
+        P, ixd, iyd = int(x.shape[0]), None, None
+    else:
+        ix, iy = _pair_indices(pairs, x.shape[0], y.shape[0])
+        P, ixd, iyd = int(ix.size), torch.from_numpy(ix).to(dev).long(), torch.from_numpy(iy).to(dev).long()
+    chunk = per_call // C_
+    if chunk < 1:
+        raise _lib.LatentAugHipError(f'compute_lpips: one pair of {C_}-channel images is {2 * C_} rows; the net has max_batch = {net.max_batch}')
+    lib = _lib.load()
+    sc, sh = (C.c_float * 3)(*net.pre_scale), (C.c_float * 3)(*net.pre_shift)
+    out = torch.empty([P, C_, net.num_taps], dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        for p0 in range(0, P, chunk):
+            n = min(chunk, P - p0)
+            xa = x[p0:p0 + n] if pairs is None else x.index_select(0, ixd[p0:p0 + n])
+            ya = y[p0:p0 + n] if pairs is None else y.index_select(0, iyd[p0:p0 + n])
+            xy = torch.empty([2 * C_ * n, 3, R, R], dtype=torch.float32, device=dev)          # rows c * n + b, x then y
+            for half, src in enumerate((xa, ya)):
+                _lib.check(lib.la_crop_repeat_affine_f32(_lib.ptr(src), _lib.ptr(xy[half * C_ * n:]), n, C_, R, R, 0, 0, 3, sc, sh,
+                                                         _lib.stream_ptr()), 'la_crop_repeat')
+            d = torch.empty([C_ * n, net.num_taps], dtype=torch.float64, device=dev)
+            net.pair_distance_rows(xy, C_ * n, d)
+            out[p0:p0 + n] = d.reshape(C_, n, net.num_taps).permute(1, 0, 2)
+    layers = out.cpu()
+    per_channel = layers.sum(dim=2)
+    return {'lpips': per_channel.mean(dim=1), 'lpips_per_channel': per_channel, 'lpips_layers': layers}
+
+
+def compute_lpips_diversity(images, net, num_pairs=1000, seed=0):
+    """Mean LPIPS distance over `msssim_diversity_pairs(N, num_pairs, seed)` of one image set [N, C, R, R] (float32, on the device):
+    near 0 means that the samples resemble one another.  The trunk is recomputed for both images of every pair (about 0.1 ms per
+    256^2 image: cheaper than keeping the activations of every image).  Returns {'mean': float, 'lpips': float64 [P], 'ix', 'iy'}."""
+    images = _device_images(images, 'images')
+    ix, iy = msssim_diversity_pairs(images.shape[0], num_pairs, seed)
+    d = compute_lpips(images, images, net, pairs=(ix, iy))['lpips']
+    return dict(mean=float(d.mean()), lpips=d, ix=ix, iy=iy)
+
+
+def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigma=1.5, levels=5, weights=None, lpips_net=None):
     """Per pair of images: MSE, MAE, PSNR, SSIM and MS-SSIM.  x, y: float32 device tensors [N, C, H, W] in a range of width
     `data_range` (2 for the generator's [-1, 1]).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy); the kernel
     gathers, the images are not copied.  A Gaussian window of `win_size` taps (odd, 1 .. 11) and `win_sigma`, 'valid' extent;
@@ -447,7 +509,9 @@ def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigm
     window; levels=1 is plain SSIM.  MS-SSIM is prod_{l<levels-1} max(cs_l, 0)^w_l * max(ssim_last, 0)^w_last with `msssim_weights`.
     Returns float64 CPU tensors: 'mse', 'mae', 'psnr', 'ssim', 'ms_ssim' [P] -- the mean over channels, psnr = 10 log10(L^2 / mse) of
     that mean (inf at 0) -- their '*_per_channel' forms [P, C], and 'ssim_levels', 'cs_levels' [P, C, levels].
-    Two calls give the same bits (la_pair_metrics_f32).  There is no CPU fallback."""
+    Two calls give the same bits (la_pair_metrics_f32).  There is no CPU fallback.
+    lpips_net (a synthesis.FeatureEngine, e.g. of lpips_reference_net, with in_res == H == W): adds the keys of compute_lpips for the
+    same pairs; without it the result is what it was."""
     x, y = _device_images(x, 'x'), _device_images(y, 'y')
     if x.device != y.device or x.shape[1:] != y.shape[1:]:
         raise ValueError(f'x and y must be on one device and agree in [C, H, W]: {tuple(x.shape)} on {x.device}, {tuple(y.shape)} on {y.device}')
@@ -495,6 +559,8 @@ def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigm
         out[k] = out[k + '_per_channel'].mean(dim=1)
     for k in ('psnr', 'psnr_per_channel'):
         out[k] = 10.0 * torch.log10(float(data_range) ** 2 / out[k.replace('psnr', 'mse')])          # x / 0 = inf in float64 tensors
+    if lpips_net is not None:
+        out.update(compute_lpips(x, y, lpips_net, pairs=pairs))
     return out
 
 
@@ -511,7 +577,8 @@ def compute_pair_metrics_for_aug_dataset(datadir, device='cuda:0', **kw):
     (backbone_latentaug.py:112-118): `img/img_{i}` and `img_aug/img_aug_{i}`, i = 0, 1, .., each a pickled dict of image batches whose
     'A' and 'B' entries ([n, 1, H, W]) become the two channels.  The pickles are read through the allow-list loader of formats.py,
     never a plain unpickle.  Returns the per-sample tensors of compute_pair_metrics over all files, a float '<key>_mean' for each of
-    'mse', 'mae', 'psnr', 'ssim', 'ms_ssim', and 'num_items'."""
+    'mse', 'mae', 'psnr', 'ssim', 'ms_ssim', and 'num_items'.  With `lpips_net=` (see compute_pair_metrics) the LPIPS keys and
+    'lpips_mean' are added."""
     from .formats import _restricted_load
     dev = torch.device(device)
     if dev.type != 'cuda':
@@ -530,7 +597,7 @@ def compute_pair_metrics_for_aug_dataset(datadir, device='cuda:0', **kw):
     parts = [compute_pair_metrics(two_channels(src), two_channels(aug), **kw) for src, aug in files]
     out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
     out['num_items'] = int(out['mse'].shape[0])
-    for k in ('mse', 'mae', 'psnr', 'ssim', 'ms_ssim'):
+    for k in ('mse', 'mae', 'psnr', 'ssim', 'ms_ssim') + (('lpips',) if 'lpips' in out else ()):
         out[k + '_mean'] = float(out[k].mean())
     return out
 

@@ -7,6 +7,7 @@ network pickle -- copies the tensors to the device once and hands their pointers
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -449,7 +450,19 @@ class FeatureEngine:
                                           _lib.ptr(self._workspace), nbytes, _lib.stream_ptr(), C.byref(h)), 'la_feat_create')
         self._h = h
         self.num_features = lib.la_feat_num_features(h)
+        self.num_taps = lib.la_feat_num_taps(h)      # columns of pair_distance (0: a detector list)
         _lib.check(lib.la_feat_set_precision(h, PRECISIONS[precision]), 'la_feat_set_precision')
+        # the net's own input layer, x_k * pre_scale[k] + pre_shift[k] on the three repeated channels: applied by whoever feeds the
+        # engine (the criterion's crop + repeat, metrics.compute_lpips); from_torchscript / from_net set it
+        self.pre_scale, self.pre_shift = (1.0, 1.0, 1.0), (0.0, 0.0, 0.0)
+
+    @classmethod
+    def from_net(cls, net, device, in_res, max_batch, precision='f32'):
+        """Engine for a described net (`lpips_reference_net`, a candidate of `vgg16_from_torchscript`): its op list, with its input
+        affine kept as `engine.pre_scale` / `engine.pre_shift`."""
+        eng = cls(net.ops, device, in_res, max_batch, precision=precision)
+        eng.pre_scale, eng.pre_shift = tuple(float(v) for v in net.pre_scale), tuple(float(v) for v in net.pre_shift)
+        return eng
 
     @classmethod
     def from_torchscript(cls, src, device, in_res, max_batch, precision='f32', probe_seed=0, rtol=2e-3):
@@ -514,21 +527,99 @@ class FeatureEngine:
             _lib.check(self._lib.la_feat_backward(self._h, _lib.ptr(gfeat), _lib.ptr(gx), _lib.stream_ptr()), 'la_feat_backward')
         return gx
 
+    def pair_rows(self):
+        """Pairs one la_feat_pair_distance call takes: both images of a pair are rows of one batch, so max_batch // 2."""
+        if self.num_taps < 1:
+            raise _lib.LatentAugHipError('pair_distance: a detector list (fc ops) has no taps')
+        if self.max_batch < 2:
+            raise _lib.LatentAugHipError('pair_distance: both images of a pair go through one batch; the engine needs max_batch >= 2')
+        return self.max_batch // 2
 
-def vgg16_lpips_ops(state_dict, lins):
+    def pair_distance_rows(self, xy, P, dist):
+        """la_feat_pair_distance on a prepared batch: xy [2P, in_ch, in_res, in_res] float32 (rows p and p + P are a pair, 2P <=
+        max_batch) -> dist [P, num_taps] float64, both on the device and contiguous."""
+        nbytes = self._lib.la_feat_pair_workspace_bytes(self._h, P)
+        if nbytes == 0:
+            raise _lib.LatentAugHipError(f'pair_distance: {P} pairs refused (detector list, or 2 * pairs > max_batch = {self.max_batch})')
+        ws = getattr(self, '_pair_ws', None)
+        if ws is None or ws.numel() * 8 < nbytes:
+            ws = self._pair_ws = torch.empty([nbytes // 8], dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.la_feat_pair_distance(self._h, _lib.ptr(xy), P, _lib.ptr(dist), _lib.ptr(ws), ws.numel() * 8,
+                                                       _lib.stream_ptr()), 'la_feat_pair_distance')
+
+    def pair_distance(self, x, y):
+        """LPIPS distance of x[p] and y[p] per tap: float64 [P, num_taps] on the device, dist[p, t] = mean over the tap's pixels of
+        sum_c lin_c (fx rx - fy ry)^2 -- what squared L2 of forward(x)[p] - forward(y)[p] gives tap by tap, from one fused launch per tap
+        and without the feature vectors (la_feat_pair_distance).  x, y: [P, in_ch, in_res, in_res] as forward() takes them; chunks of
+        max_batch // 2 pairs.  Two calls give the same bits.  A later backward() needs a new forward() first."""
+        _lib.require_gpu(x)
+        _lib.require_gpu(y)
+        chunk = self.pair_rows()
+        want = (self.in_ch, self.in_res, self.in_res)
+        if x.ndim != 4 or x.shape != y.shape or tuple(x.shape[1:]) != want or x.shape[0] < 1:
+            raise ValueError(f'pair_distance: x and y must both be [P, {want[0]}, {want[1]}, {want[2]}]; got {tuple(x.shape)}, {tuple(y.shape)}')
+        x, y = x.contiguous().float(), y.contiguous().float()
+        P = x.shape[0]
+        dist = torch.empty([P, self.num_taps], dtype=torch.float64, device=self.device)
+        for p0 in range(0, P, chunk):
+            n = min(chunk, P - p0)
+            self.pair_distance_rows(torch.cat([x[p0:p0 + n], y[p0:p0 + n]]), n, dist[p0:p0 + n])
+        return dist
+
+
+def vgg16_lpips_ops(state_dict, lins, taps=(0, 1, 2, 3, 4)):
     """Op list of the LPIPS VGG16 from torchvision-style names (`features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.weight/bias`,
-    cf. augments/criteria/lpips/networks.py:87-97) and the five per-channel lin weights; taps after relu1_2, 2_2, 3_3, 4_3, 5_3."""
+    cf. augments/criteria/lpips/networks.py:87-97) and per-channel lin weights.  `taps` selects among the five places relu1_2, 2_2,
+    3_3, 4_3, 5_3 (0 .. 4, ascending); `lins` holds one weight vector per selected tap, in that order.  The default is all five;
+    taps=(2, 3, 4) with three lins is the reference's `target_layers = [16, 23, 30]` (networks.py:94).  The list ends at its last tap."""
     conv_ids = [0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28]
     tap_after = {2: 0, 7: 1, 14: 2, 21: 3, 28: 4}
     pool_after = {2, 7, 14, 21}
+    taps = [int(t) for t in taps]
+    if not taps or taps != sorted(set(taps)) or taps[0] < 0 or taps[-1] > 4:
+        raise ValueError(f'taps: ascending, distinct places out of 0 .. 4 (got {taps})')
+    if len(lins) != len(taps):
+        raise ValueError(f'{len(taps)} taps need {len(taps)} lin weight vectors (got {len(lins)})')
     ops = []
     for i in conv_ids:
         ops.append(('conv', state_dict[f'features.{i}.weight'], state_dict[f'features.{i}.bias']))
-        if i in tap_after:
-            ops.append(('tap', lins[tap_after[i]]))
+        if tap_after.get(i) in taps:
+            ops.append(('tap', lins[taps.index(tap_after[i])]))
+            if tap_after[i] == taps[-1]:
+                break
         if i in pool_after:
             ops.append(('maxpool',))
     return ops
+
+
+LPIPS_ZSCORE_MEAN, LPIPS_ZSCORE_STD = (-.030, -.088, -.188), (.458, .448, .450)      # networks.py:40-43, images in [-1, 1]
+
+
+def lpips_reference_net(vgg_state_dict, lin_state_dict):
+    """The reference's non-TorchScript perceptual net, `augments/criteria/lpips/lpips.py::LPIPS('vgg')`, as a described net for
+    `FeatureEngine.from_net`: VGG16 tapped after relu3_3 / 4_3 / 5_3 (networks.py:94), the z-score (x - mean_k) / std_k as input affine
+    (networks.py:40-50), and the LAST three `lin{k}.model.1.weight` tensors of the LPIPS weight file (what utils.py:32-52 keeps of
+    its five).  Each argument is a state dict or the path of one, read with torch.load(weights_only=True).  A negative lin weight
+    is refused: the criterion's tap emits sqrt(lin)."""
+    import re
+
+    def read(src, what):
+        if isinstance(src, dict):
+            return src
+        if not os.path.isfile(src):
+            raise FileNotFoundError(f'{what}: no such file: {src}')
+        return torch.load(src, map_location='cpu', weights_only=True)
+    vgg, lin = read(vgg_state_dict, 'VGG16 weights'), read(lin_state_dict, 'LPIPS lin weights')
+    found = sorted((int(m.group(1)), v) for k, v in lin.items() for m in [re.fullmatch(r'lin(\d+)\.model\.1\.weight', k)] if m)
+    if len(found) < 3:
+        raise _lib.LatentAugHipError(f'LPIPS lin weights: found {len(found)} `lin<k>.model.1.weight` tensors, need at least 3')
+    lins = [v.detach().to('cpu', torch.float32).reshape(-1) for _, v in found[-3:]]
+    if any(float(v.min()) < 0.0 for v in lins):
+        raise _lib.LatentAugHipError('LPIPS lin weights: a negative channel weight (the criterion takes its square root); refusing')
+    ops = vgg16_lpips_ops(vgg, lins, taps=(2, 3, 4))
+    return ScriptedFeatureNet(ops, tuple(1.0 / s for s in LPIPS_ZSCORE_STD),
+                              tuple(-m / s for m, s in zip(LPIPS_ZSCORE_MEAN, LPIPS_ZSCORE_STD)), False, None)
 
 
 # ------------------------------------------------------------------------------------------------------------

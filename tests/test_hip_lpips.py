@@ -1,0 +1,368 @@
+"""The LPIPS distance on the GPU: la_tap_pair_dist_kernel alone, la_feat_pair_distance against the reference's own LPIPS class
+(tests/golden/lpips.npz), exactness properties, agreement with the feature-vector route, the public functions of metrics.py and the
+LPIPS('vgg') branch of the plugin.
+
+Bound (the project's rule from test_hip_conv2d_op.py, nothing tuned): error <= 4 x the float32 yardstick's own error + 2e-6 x the
+largest float64 magnitude (lpips_cases.check).  Yardstick: the reference's float32 result for the goldens, the float32 restatement of
+tests/lpips_cases.py otherwise; anchor: the reference's float64 result / the float64 restatement (pinned to the reference to 1e-12 by
+test_lpips_cases_cpu.py)."""
+import os
+import pickle
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lpips_cases as lc  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def dev():
+    if not torch.cuda.is_available():
+        pytest.fail('GPU tests need a ROCm device')
+    return torch.device('cuda', 0)
+
+
+@pytest.fixture(scope='module')
+def gl(golden_dir):
+    return np.load(os.path.join(golden_dir, 'lpips.npz'))
+
+
+def _net(gl, tag):
+    """The fixture's net as a described net: lpips_reference_net for the three taps, the same affine around the five-tap list."""
+    from latentaugment_amd.synthesis import ScriptedFeatureNet, lpips_reference_net, vgg16_lpips_ops
+    vgg, lin = lc.golden_state_dicts(gl, tag)
+    net = lpips_reference_net(vgg, lin)
+    if tag == 't5':
+        net = ScriptedFeatureNet(vgg16_lpips_ops(vgg, [torch.tensor(gl[f'lin{k}']) for k in range(5)]), net.pre_scale, net.pre_shift, False, None)
+    return net
+
+
+_ENGINES = {}
+
+
+def _engine(gl, dev, tag, precision='f32', max_batch=8, in_res=32):
+    from latentaugment_amd.synthesis import FeatureEngine
+    key = (tag, precision, max_batch, in_res)
+    if key not in _ENGINES:
+        _ENGINES[key] = FeatureEngine.from_net(_net(gl, tag), dev, in_res=in_res, max_batch=max_batch, precision=precision)
+    return _ENGINES[key]
+
+
+def _gray3(a, dtype=torch.float32):
+    return torch.tensor(a).to(dtype).repeat(1, 3, 1, 1)
+
+
+def _fed(eng, a, dev):
+    """[n, 1, R, R] fixture images as the engine's input: repeated to three channels with the net's affine (plumbing, in torch)."""
+    return lc.affine(_gray3(a), eng.pre_scale, eng.pre_shift).to(dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 1. the kernel alone: tap-only op lists
+
+def _tap_engine(dev, lins, C, R, max_batch):
+    from latentaugment_amd.synthesis import FeatureEngine
+    return FeatureEngine(lins, dev, in_res=R, max_batch=max_batch, in_ch=C)
+
+
+@pytest.mark.parametrize('P', lc.KERNEL_PAIRS)
+@pytest.mark.parametrize('C,R', lc.KERNEL_CASES)
+def test_kernel_alone(dev, C, R, P):
+    x, y, lin = lc.kernel_inputs(C, R, P)
+    ops = [('tap', lin)]
+    eng = _tap_engine(dev, ops, C, R, 2 * P)
+    assert eng.num_taps == 1
+    got = eng.pair_distance(x.float().to(dev), y.float().to(dev))
+    assert got.dtype == torch.float64 and got.shape == (P, 1)
+    ref64 = lc.pair_distance(ops, x, y, 'engine')
+    yard = lc.pair_distance(lc.cast_ops(ops, torch.float32), x.float(), y.float(), 'engine')
+    lc.check(f'tap C={C} R={R} P={P}', got.cpu(), ref64, yard)
+
+
+def test_kernel_alone_several_taps_and_pools(dev):
+    """Three taps of different tile counts in one list (the partials of a tap sit behind those of the taps before it)."""
+    C, R, P = 5, 12, 3
+    x, y, lin = lc.kernel_inputs(C, R, P)
+    lin2, lin3 = lin.flip(0), (lin * 0.5 + 0.1)
+    ops = [('tap', lin), ('maxpool',), ('tap', lin2), ('avgpool',), ('tap', lin3)]
+    eng = _tap_engine(dev, ops, C, R, 2 * P)
+    assert eng.num_taps == 3
+    got = eng.pair_distance(x.float().to(dev), y.float().to(dev)).cpu()
+    ref64 = lc.pair_distance(ops, x, y, 'engine')
+    yard = lc.pair_distance(lc.cast_ops(ops, torch.float32), x.float(), y.float(), 'engine')
+    lc.check('three taps', got, ref64, yard)
+
+
+def test_close_pair_keeps_its_digits(dev):
+    """An augmented image is close to its source.  The kernel subtracts the NORMALISED values: each carries a few float32 roundings
+    (the product f * r, r's own rsqrt: <= 3 ulp, 1.8e-7 relative), so for values that differ by a relative 1e-3 the difference is good
+    to 2 * 1.8e-7 / 1e-3 = 3.6e-4 and its square to 7.2e-4 -- every term, hence the sum: bound 1e-3 relative.  (The expanded form
+    |x|^2 + |y|^2 - 2 x.y would leave 1e-7 of terms that are 1e6 times the result.)"""
+    C, R = 64, 8
+    g = torch.Generator().manual_seed(5)
+    x = (torch.rand([1, C, R, R], generator=g, dtype=torch.float64) + 0.5).float().double()
+    y = (x * (1 + 1e-3 * (torch.rand([1, C, R, R], generator=g, dtype=torch.float64) + 0.5))).float().double()
+    lin = torch.rand([C], generator=g, dtype=torch.float64).float().double()
+    ops = [('tap', lin)]
+    got = _tap_engine(dev, ops, C, R, 2).pair_distance(x.float().to(dev), y.float().to(dev)).cpu()
+    ref64 = lc.pair_distance(ops, x, y, 'engine')
+    rel = float(((got - ref64).abs() / ref64).max())
+    print(f'close pair: d = {float(ref64):.3e}, relative error {rel:.2e}')
+    assert 0 < float(ref64) < 1e-5 and rel <= 1e-3
+
+
+def test_lin_enters_as_it_is(dev):
+    """No square root: negating every weight negates the distance, bit for bit."""
+    C, R, P = 33, 10, 2
+    x, y, lin = lc.kernel_inputs(C, R, P)
+    xd, yd = x.float().to(dev), y.float().to(dev)
+    a = _tap_engine(dev, [('tap', lin)], C, R, 2 * P).pair_distance(xd, yd)
+    b = _tap_engine(dev, [('tap', -lin)], C, R, 2 * P).pair_distance(xd, yd)
+    assert torch.equal(a, -b) and bool((a > 0).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 2. goldens: the reference's own class
+
+@pytest.mark.parametrize('precision', ['f32', 'f16x2'])
+@pytest.mark.parametrize('tag', ['t3', 't5'])
+def test_golden_pairs(dev, gl, tag, precision):
+    from latentaugment_amd import metrics
+    eng = _engine(gl, dev, tag, precision)
+    assert eng.num_taps == len(lc.TAPS[tag])
+    out = metrics.compute_lpips(torch.tensor(gl['x']).to(dev), torch.tensor(gl['y']).to(dev), eng)
+    assert out['lpips_layers'].shape == (3, 1, eng.num_taps) and out['lpips_layers'].dtype == torch.float64 and out['lpips'].device.type == 'cpu'
+    lc.check(f'{tag} {precision} per layer', out['lpips_layers'][:, 0], gl[f'{tag}_layers64'], gl[f'{tag}_layers32'])
+    lc.check(f'{tag} {precision} per pair', out['lpips'], gl[f'{tag}_pair64'], gl[f'{tag}_pair32'])
+    assert torch.equal(out['lpips_per_channel'][:, 0], out['lpips']) and torch.equal(out['lpips_per_channel'], out['lpips_layers'].sum(2))
+    # the engine's own entry on prepared inputs
+    d = eng.pair_distance(_fed(eng, gl['x'], dev), _fed(eng, gl['y'], dev)).cpu()
+    lc.check(f'{tag} {precision} pair_distance', d, gl[f'{tag}_layers64'], gl[f'{tag}_layers32'])
+
+
+@pytest.mark.parametrize('precision', ['f32', 'f16x2'])
+@pytest.mark.parametrize('tag', ['t3', 't5'])
+def test_golden_criterion_side(dev, gl, tag, precision):
+    """forward_tr and its gradient from what the criterion uses: the tap vectors, the pairwise L2 and FeatureEngine.backward."""
+    from latentaugment_amd import ops as la_ops
+    eng = _engine(gl, dev, tag, precision)
+    fb = eng.forward(_fed(eng, gl['bank'], dev))
+    f = eng.forward(_fed(eng, gl['x1'], dev))
+    M = fb.shape[0]
+    tr = la_ops.l2_loss_vectorized(f, fb, compute_mean=False).double().sum() / M
+    lc.check(f'{tag} {precision} forward_tr', tr.cpu().reshape(1), gl[f'{tag}_tr64'].reshape(1), gl[f'{tag}_tr32'].reshape(1))
+    gfeat = 2.0 * (f - fb.mean(0, keepdim=True))          # d/df of sum_m |f - b_m|^2 / M
+    gx = eng.backward(gfeat) * torch.tensor(eng.pre_scale, device=dev).reshape(1, 3, 1, 1)
+    lc.check(f'{tag} {precision} forward_tr gradient', gx.cpu(), gl[f'{tag}_tr_grad64'], gl[f'{tag}_tr_grad32'])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 3. exactness, 4. agreement with the feature-vector route
+
+@pytest.mark.parametrize('precision', ['f32', 'f16x2'])
+def test_exactness(dev, gl, precision):
+    eng = _engine(gl, dev, 't5', precision)
+    x, y = _fed(eng, gl['x'], dev), _fed(eng, gl['y'], dev)
+    dxy = eng.pair_distance(x, y)
+    assert torch.equal(eng.pair_distance(x, x), torch.zeros_like(dxy))
+    assert torch.equal(eng.pair_distance(y, x), dxy)
+    assert torch.equal(eng.pair_distance(x, y), dxy)
+    assert bool((dxy >= 0).all()) and bool((dxy > 0).any())
+    # the kernel alone, every register form
+    for C, R in ((33, 10), (132, 8), (260, 8)):
+        a, b, lin = lc.kernel_inputs(C, R, 3)
+        a, b = a.float().to(dev), b.float().to(dev)
+        te = _tap_engine(dev, [('tap', lin)], C, R, 6)
+        d = te.pair_distance(a, b)
+        assert torch.equal(te.pair_distance(a, a), torch.zeros_like(d)) and torch.equal(te.pair_distance(b, a), d)
+        assert torch.equal(te.pair_distance(a, b), d) and bool((d >= 0).all())
+
+
+@pytest.mark.parametrize('precision', ['f32', 'f16x2'])
+@pytest.mark.parametrize('tag', ['t3', 't5'])
+def test_agrees_with_the_feature_vector_route(dev, gl, tag, precision):
+    eng = _engine(gl, dev, tag, precision)
+    x, y = _fed(eng, gl['x'], dev), _fed(eng, gl['y'], dev)
+    route = (eng.forward(x).double() - eng.forward(y).double()).square().sum(1).cpu().numpy()
+    fused = eng.pair_distance(x, y).sum(1).cpu().numpy()
+    b = lc.bound(gl[f'{tag}_pair64'], gl[f'{tag}_pair32'])
+    print(f'{tag} {precision}: fused {fused}  route {route}  |diff| {np.abs(fused - route).max():.3e}  bound {b:.3e}')
+    assert np.abs(fused - route).max() <= b
+    # a forward after a pair call is intact, and backward refuses in between
+    from latentaugment_amd import _lib
+    f1 = eng.forward(x)
+    eng.pair_distance(x, y)
+    with pytest.raises(_lib.LatentAugHipError):
+        eng.backward(torch.zeros_like(f1))
+    assert torch.equal(eng.forward(x), f1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 5. public functions
+
+class _Pub:
+    """Six two-channel 32 x 32 images and the restated taps of every (image, channel) row, computed once."""
+
+    def __init__(self, gl):
+        g = torch.Generator().manual_seed(77)
+        self.img = torch.rand([6, 2, 32, 32], generator=g) * 2 - 1
+        self.img[1] = self.img[0] + 0.02 * (self.img[1] - self.img[0])
+        net = _net(gl, 't3')
+        rows = self.img.reshape(12, 1, 32, 32).repeat(1, 3, 1, 1)
+        self.t64 = lc.tapped(lc.cast_ops(net.ops, torch.float64), lc.affine(rows.double(), net.pre_scale, net.pre_shift), 'engine')
+        self.t32 = lc.tapped(lc.cast_ops(net.ops, torch.float32), lc.affine(rows, net.pre_scale, net.pre_shift), 'engine')
+
+    def layers(self, ix, iy):
+        """([P, C, ntaps] float64 anchor, float32 yardstick) of the pairs (img[ix[p]], img[iy[p]])."""
+        ix, iy = np.asarray(ix), np.asarray(iy)
+        return tuple(torch.stack([lc.distance_of_rows(t, 2 * ix + c, 2 * iy + c) for c in range(2)], dim=1) for t in (self.t64, self.t32))
+
+
+@pytest.fixture(scope='module')
+def pub(gl):
+    return _Pub(gl)
+
+
+def test_compute_pair_metrics_with_lpips(dev, gl, pub):
+    from latentaugment_amd import metrics
+    eng = _engine(gl, dev, 't3')
+    x, y = pub.img[:3].to(dev), pub.img[3:].to(dev)
+    base = metrics.compute_pair_metrics(x, y, levels=2)
+    with_ = metrics.compute_pair_metrics(x, y, levels=2, lpips_net=eng)
+    assert set(with_) == set(base) | {'lpips', 'lpips_per_channel', 'lpips_layers'}
+    for k in base:
+        assert base[k].dtype == with_[k].dtype and np.array_equal(base[k].numpy(), with_[k].numpy(), equal_nan=True), k
+    ref64, yard = pub.layers([0, 1, 2], [3, 4, 5])
+    lc.check('pair metrics lpips_layers', with_['lpips_layers'], ref64, yard)
+    lc.check('pair metrics lpips', with_['lpips'], ref64.sum(2).mean(1), yard.sum(2).mean(1))
+    # gathered pairs
+    ix, iy = np.array([0, 5, 2, 0], np.int32), np.array([1, 0, 2, 4], np.int32)
+    got = metrics.compute_pair_metrics(pub.img.to(dev), pub.img.to(dev), pairs=(ix, iy), levels=2, lpips_net=eng)
+    ref64, yard = pub.layers(ix, iy)
+    lc.check('gathered lpips_layers', got['lpips_layers'], ref64, yard)
+    assert float(got['lpips'][2]) == 0.0
+
+
+def test_chunking(dev, gl, pub):
+    """P = 5 on an engine of max_batch = 4: pair_distance in chunks of 2 pairs, compute_lpips (two channels) one pair at a time."""
+    from latentaugment_amd import metrics
+    eng = _engine(gl, dev, 't3', max_batch=4)
+    ix, iy = [0, 1, 2, 3, 4], [1, 2, 3, 4, 5]
+    ref64, yard = pub.layers(ix, iy)
+    got = metrics.compute_lpips(pub.img[:5].to(dev), pub.img[1:].to(dev), eng)
+    lc.check('chunked compute_lpips', got['lpips_layers'], ref64, yard)
+    rows = lc.affine(pub.img[:, :1].repeat(1, 3, 1, 1), eng.pre_scale, eng.pre_shift).to(dev)
+    d = eng.pair_distance(rows[:5], rows[1:]).cpu()
+    lc.check('chunked pair_distance', d, ref64[:, 0], yard[:, 0])
+    big = _engine(gl, dev, 't3', max_batch=8)
+    lc.check('one chunk', big.pair_distance(rows[:4], rows[1:5]).cpu(), ref64[:4, 0], yard[:4, 0])
+
+
+def test_lpips_diversity(dev, gl, pub):
+    from latentaugment_amd import metrics
+    eng = _engine(gl, dev, 't3')
+    out = metrics.compute_lpips_diversity(pub.img.to(dev), eng, num_pairs=7, seed=3)
+    ix, iy = metrics.msssim_diversity_pairs(6, 7, 3)
+    assert len(ix) == 7 and (out['ix'] == ix).all() and (out['iy'] == iy).all()
+    ref64, yard = pub.layers(ix, iy)
+    lc.check('diversity', out['lpips'], ref64.sum(2).mean(1), yard.sum(2).mean(1))
+    assert out['mean'] == float(out['lpips'].mean())
+    everything = metrics.compute_lpips_diversity(pub.img.to(dev), eng, num_pairs=1000)
+    assert everything['lpips'].shape == (15,)
+
+
+def test_aug_dataset_with_lpips(dev, gl, pub, tmp_path):
+    from latentaugment_amd import metrics
+    eng = _engine(gl, dev, 't3')
+    run = tmp_path / 'run'
+    os.makedirs(run / 'img')
+    os.makedirs(run / 'img_aug')
+    for i, (a, b) in enumerate(((0, 2), (2, 3))):
+        src, aug = pub.img[a:b].numpy(), pub.img[a + 3:b + 3].numpy()
+        with open(run / 'img' / f'img_{i}', 'wb') as f:
+            pickle.dump({'A': src[:, :1].copy(), 'B': src[:, 1:].copy()}, f)
+        with open(run / 'img_aug' / f'img_aug_{i}', 'wb') as f:
+            pickle.dump({'A': aug[:, :1].copy(), 'B': aug[:, 1:].copy()}, f)
+    out = metrics.compute_pair_metrics_for_aug_dataset(str(run), levels=2, lpips_net=eng)
+    ref64, yard = pub.layers([0, 1, 2], [3, 4, 5])
+    assert out['num_items'] == 3
+    lc.check('aug dataset lpips_layers', out['lpips_layers'], ref64, yard)
+    assert out['lpips_mean'] == float(out['lpips'].mean())
+    plain = metrics.compute_pair_metrics_for_aug_dataset(str(run), levels=2)
+    assert 'lpips_mean' not in plain and 'lpips' not in plain and plain['mse_mean'] == out['mse_mean']
+
+
+def test_misuse_leaves_the_device_usable(dev, gl, pub):
+    from latentaugment_amd import _lib, metrics
+    from latentaugment_amd.synthesis import FeatureEngine
+    eng = _engine(gl, dev, 't3')
+    x, y = pub.img[:2].to(dev), pub.img[2:4].to(dev)
+    with pytest.raises(ValueError, match='32'):
+        metrics.compute_lpips(x[:, :, :16, :16].contiguous(), y[:, :, :16, :16].contiguous(), eng)
+    with pytest.raises(_lib.LatentAugHipError, match='no CPU fallback'):
+        metrics.compute_lpips(x.cpu(), y, eng)
+    with pytest.raises(_lib.LatentAugHipError):
+        eng.pair_distance(torch.zeros([1, 3, 32, 32]), torch.zeros([1, 3, 32, 32]))
+    with pytest.raises(ValueError):
+        eng.pair_distance(torch.zeros([1, 3, 16, 16], device=dev), torch.zeros([1, 3, 16, 16], device=dev))
+    with pytest.raises(ValueError):
+        metrics.compute_lpips(x, y[:1], eng)
+    g = torch.Generator().manual_seed(1)
+    det = FeatureEngine([('fc', torch.randn([5, 3 * 32 * 32], generator=g) * 0.01, torch.zeros([5]), False)], dev, in_res=32, max_batch=4)
+    assert det.num_taps == 0
+    with pytest.raises(_lib.LatentAugHipError, match='detector'):
+        metrics.compute_lpips(x, y, det)
+    with pytest.raises(_lib.LatentAugHipError, match='detector'):
+        det.pair_distance(torch.zeros([1, 3, 32, 32], device=dev), torch.zeros([1, 3, 32, 32], device=dev))
+    # the C entry itself: refused with LA_ERR_ARG before any launch
+    lib = _lib.load()
+    buf = torch.zeros([64], dtype=torch.float64, device=dev)
+    assert lib.la_feat_pair_workspace_bytes(det.handle, 1) == 0
+    assert lib.la_feat_pair_distance(det.handle, _lib.ptr(buf), 1, _lib.ptr(buf), _lib.ptr(buf), 512, _lib.stream_ptr()) == -1
+    assert lib.la_feat_pair_distance(eng.handle, _lib.ptr(buf), 5, _lib.ptr(buf), _lib.ptr(buf), 512, _lib.stream_ptr()) == -1
+    torch.cuda.synchronize()
+    ref64, yard = pub.layers([0, 1], [2, 3])
+    lc.check('after misuse', metrics.compute_lpips(x, y, eng)['lpips_layers'], ref64, yard)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 6. the plugin's LPIPS('vgg') branch
+
+def test_plugin_reference_branch(dev, gl, golden_dir, tmp_path):
+    """opt.lpips_script = 'lpips' with the two weight files on disk: the step-0 LPIPS loss of the toy loop (batch 1) is the reference's
+    calc_loss_lpips_tr -- forward_tr of each modality's crop against its bank, times w_lpips, averaged over the modalities -- as the
+    fixture recorded it from the reference's class on this repository's CPU oracle of the same generator."""
+    from latentaugment_amd.latent_aug import LatentAug
+    from latentaugment_amd.synthesis import FeatureEngine, lpips_reference_net
+    from oracle import sg2_networks as nets
+    ll = np.load(os.path.join(golden_dir, 'latent_loop.npz'))
+    G = nets.make_generator(img_resolution=int(ll['res']), img_channels=2, channel_base=int(ll['cbase']), channel_max=int(ll['cmax']),
+                            seed=0, noise_strength=0.1, w_dim=int(ll['wdim']), mapping_layers=2)
+    vgg, lin = lc.golden_state_dicts(gl, 't3')
+    torch.save(vgg, tmp_path / 'vgg16.pth')
+    torch.save(lin, tmp_path / 'lpips_vgg.pth')
+    # banks: the engine's tap vectors of real crops (here the fixture's 16 x 16 bank images), one bank per modality
+    bank_eng = FeatureEngine.from_net(lpips_reference_net(vgg, lin), dev, in_res=16, max_batch=8)
+    fea = [bank_eng.forward(_fed(bank_eng, gl['plug_bank'][m], dev)).cpu() for m in range(2)]
+    w_lpips = 3.0
+    opt = types.SimpleNamespace(img_resolution=32, batch_size=1, modalities_aug='A,B', opt_num_epochs=2, opt_lr=0.01, truncation_psi=1.0,
+                                w_pix=0.0, w_lpips=w_lpips, w_latent=0.0, w_disc=0.0, crop_size_aug=16, preprocess_aug='center_random_crop',
+                                soft_aug=False, alpha=1.0, verbose_log=False, criterion_mode='gemm', final_noise_mode='const', precision='f32',
+                                lpips_script='lpips', lpips_vgg_path=str(tmp_path / 'vgg16.pth'), lpips_lin_path=str(tmp_path / 'lpips_vgg.pth'))
+    la = LatentAug('train', opt, str(tmp_path), [0], generator=G, banks={'fea': fea})
+    assert la.feat.num_taps == 3 and la.feat.pre_scale == bank_eng.pre_scale
+    w0 = torch.tensor(ll['w0'])[:1]
+    img, w_aug, losses = la.run_local(w0.to(dev), want_losses=True, crop_pos=tuple(int(v) for v in gl['plug_pos']))
+    got = losses.cpu().numpy()[0, 3]
+    lc.check('plugin step-0 lpips loss', np.array([got]), np.array([gl['plug_tr64'].mean() * w_lpips]), np.array([gl['plug_tr32'].mean() * w_lpips]))
+    # through <model_dir> instead of the two options
+    opt2 = types.SimpleNamespace(**{k: v for k, v in vars(opt).items() if k not in ('lpips_vgg_path', 'lpips_lin_path', 'lpips_preproc')},
+                                 model_dir=str(tmp_path))
+    la2 = LatentAug('train', opt2, str(tmp_path), [0], generator=G, banks={'fea': fea})
+    assert la2.feat.weights_digest == la.feat.weights_digest
