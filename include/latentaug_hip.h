@@ -689,6 +689,27 @@ int la_joint_hist_f32(const float* a, long a_plane_stride, const float* b, long 
                       float lo, float scale, unsigned* hist, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Points on latent paths (no reference counterpart): the inputs of perceptual path length (Karras et al. 2019 / 2020).
+ *
+ * la_path_points_f32: a, b float32 [N][D] and t float32 [N] on the device, dt_host double [T] on the host, 1 <= T <= 64.
+ *   out [T][N][reps][D] = the point of path p, from a[p] to b[p], at parameter s = (double)t[p] + dt_host[k], written reps times
+ *   (reps = num_ws broadcasts a W point to the layers; reps = 1 for Z, or for W+ rows with D = num_ws * w_dim).
+ *   mode 0, lerp:   a + (b - a) * s.
+ *   mode 1, slerp of the published PPL: with a' = a / |a|, b' = b / |b|, d = <a', b'>, c = (b' - d a') / |b' - d a'|, omega = acos(d):
+ *                   normalise(a' cos(s omega) + c sin(s omega)).  omega is evaluated as atan2(|b' - d a'|, d), the same angle without
+ *                   acos's loss of digits next to d = +-1 (a rounded d above 1 would make acos NaN), so a == b gives a'.
+ *                   Where |b' - d a'| == 0 (identical or opposite directions) every point is a'; the published form gives NaN there.
+ *                   Nearly opposite rows have no stable geodesic: c is then rounding noise.  A zero row has no direction and
+ *                   gives NaN, as the published form does.
+ *   s outside [0, 1] extrapolates (t + eps next to 1).  Every operation is in double, in the order written and unfused, and the result is
+ *   rounded once to float32: t + dt is never formed in float32, and the lerp equals its float64 restatement bit for bit.
+ *   One workgroup per path; the norms and the dot product are block reductions in a fixed order, no atomics: two runs give the same bits.
+ *   Null pointers, N, D, reps < 1, T outside 1 .. 64 and an unknown mode are LA_ERR_ARG before any launch; a failed launch is LA_ERR_HIP.
+ * ------------------------------------------------------------------------------------------------------------- */
+int la_path_points_f32(const float* a, const float* b, const float* t, const double* dt_host, int T, int N, int D, int reps, int mode,
+                       float* out, la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in profiler for the contraction launches (HIP events on the launch stream).  No reference counterpart: the
  * reference's only timing hook is wall-clock stats_time (augments/latent_aug.py:276).
  * la_prof_end: summed device ms, launch count, algorithmic FLOPs (2*MACs) and algorithmic bytes (input + output +

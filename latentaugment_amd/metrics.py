@@ -16,6 +16,9 @@ everything downstream of detector features.
   compute_pair_metrics_for_aug_dataset    the same for `img/img_{i}` against `img_aug/img_aug_{i}` of a run directory of the drivers
   compute_msssim_diversity                MS-SSIM over random pairs of one image set (the usual collapse check)
   compute_modality_mi, compute_pair_mi    mutual information of two planes from their joint histogram (la_joint_hist_f32)
+  compute_ppl, ppl_from_distances         (not in the reference) perceptual path length of the generator, Karras et al. 2019 / 2020
+  compute_path_length                     perceptual length of the straight segment between two latents (la_path_points_f32)
+  compute_path_length_for_aug_dataset     the same for `latent/w_{i}` against `latent_aug/w_aug_{i}` of a run directory of the drivers
 
 The detectors (Inception-v3 and VGG16 pickles hosted by NVIDIA, metric_utils.py:46-60) cannot be fetched offline.  The VGG16 one has a
 local counterpart -- the TorchScript `vgg16.pt` the LPIPS criterion already needs -- and `synthesis.DetectorEngine.from_torchscript`
@@ -697,3 +700,212 @@ def compute_pair_mi(x, y, channel=0, bins=64, value_range=(-1.0, 1.0)):
         raise ValueError(f'channel {channel} outside the {C} channels of the images')
     return _joint_hist(x.data_ptr() + 4 * c * H * W, C * H * W, y.data_ptr() + 4 * c * H * W, C * H * W, N, H * W, bins, value_range,
                        x.device)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# perceptual path length (la_pathpoints.hip; Karras et al. 2019 / 2020; no reference counterpart, no CPU fallback)
+def ppl_from_distances(d):
+    """The published PPL filter over per-sample distances d [N] (any real array or tensor, NaN-free): the mean of the d with
+    lo <= d <= hi, lo = the 1st percentile by the 'lower' rule (sorted[floor(0.01 (N - 1))]) and hi = the 99th by the 'higher' rule
+    (sorted[ceil(0.99 (N - 1))]).  Runs on the host in float64; returns a float."""
+    d = np.asarray(d, dtype=np.float64)
+    if d.ndim != 1 or d.size < 1:
+        raise ValueError(f'ppl_from_distances: a non-empty [N] array of distances; got shape {d.shape}')
+    s = np.sort(d)
+    lo = s[int(np.floor(0.01 * (d.size - 1)))]
+    hi = s[int(np.ceil(0.99 * (d.size - 1)))]
+    return float(d[(d >= lo) & (d <= hi)].mean())
+
+
+def _path_points(a, b, t, dt, reps, mode):
+    """la_path_points_f32: a, b [N, D], t [N] float32 on one device, dt a sequence of T floats -> [T, N, reps, D] float32."""
+    N, D = (int(s) for s in a.shape)
+    dt = np.ascontiguousarray(dt, dtype=np.float64)
+    out = torch.empty([dt.size, N, int(reps), D], dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.load().la_path_points_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(t), dt.ctypes.data, int(dt.size), N, D, int(reps),
+                                                  int(mode), _lib.ptr(out), _lib.stream_ptr()), 'path_points')
+    return out
+
+
+def _path_engines(synth, net, what):
+    """The checks the path metrics share; returns the pairs one call of the net takes."""
+    if not hasattr(synth, 'num_ws') or not hasattr(synth, 'max_batch'):
+        raise _lib.LatentAugHipError(f'{what}: synth must be a synthesis.SynthesisEngine; got {type(synth).__name__}')
+    if not hasattr(net, 'pair_distance_rows'):
+        raise _lib.LatentAugHipError(f'{what}: net must be a synthesis.FeatureEngine; got {type(net).__name__}')
+    per_call = net.pair_rows()          # (refuses a detector engine)
+    if net.in_ch != 3:
+        raise ValueError(f'{what}: the net must take three input channels (in_ch {net.in_ch})')
+    if synth.device != net.device:
+        raise ValueError(f'{what}: generator on {synth.device}, net on {net.device}')
+    R = synth.img_resolution
+    if R % net.in_res != 0:
+        raise ValueError(f'{what}: the image resolution {R} must be the net\'s in_res {net.in_res} or an integer multiple of it')
+    if synth.max_batch < 2:
+        raise _lib.LatentAugHipError(f'{what}: both ends of a step go through one batch; the generator has max_batch = {synth.max_batch}')
+    return per_call
+
+
+def _lpips_rows(img, net):
+    """[M, C, R, R] images -> the net's input [M * C, 3, in_res, in_res] (row m * C + c): every channel on its own, reduced by area when
+    R is a multiple of in_res (la_detector_prep_f32, no quantisation), repeated to three and given the net's input affine."""
+    M, C_, R = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
+    lib = _lib.load()
+    sc, sh = (C.c_float * 3)(*net.pre_scale), (C.c_float * 3)(*net.pre_shift)
+    rows = torch.empty([M * C_, 3, net.in_res, net.in_res], dtype=torch.float32, device=img.device)
+    if R == net.in_res:
+        _lib.check(lib.la_crop_repeat_affine_f32(_lib.ptr(img), _lib.ptr(rows), M * C_, 1, R, R, 0, 0, 3, sc, sh, _lib.stream_ptr()),
+                   'la_crop_repeat')
+    else:
+        _lib.check(lib.la_detector_prep_f32(_lib.ptr(img), _lib.ptr(rows), M * C_, 1, R, R, net.in_res, 3, 0, 0, sc, sh,
+                                            _lib.stream_ptr()), 'la_detector_prep_f32')
+    return rows
+
+
+def compute_ppl(mapping, synth, net, num_samples, epsilon=1e-4, space='w', sampling='full', truncation_psi=1.0, seed=0, batch=None):
+    """Perceptual path length of a generator (Karras et al. 2019 / 2020): per sample, the LPIPS distance of the images at two latent
+    points `epsilon` apart on the path between two random latents, divided by epsilon^2.  `mapping` is a synthesis.MappingEngine, `synth`
+    a SynthesisEngine, `net` a FeatureEngine of three input channels whose in_res is the image resolution or divides it (then the images
+    are reduced by area first).  z0, z1 = the halves of randn([2 N, z_dim]), then t = rand([N]) ('full') or 0 ('end'), from one CPU
+    torch.Generator(seed): the draws do not depend on the chunking.  space='w': both z are mapped (truncation_psi applies) and the
+    points are the lerp at t and t + epsilon, broadcast to num_ws; space='z': the points are the slerp at t and t + epsilon, then
+    mapped (la_path_points_f32 forms t + epsilon in double).  Chunks of n <= min(synth.max_batch // 2, batch) samples: both points of
+    a chunk are one synthesis batch (noise_mode='const'), every image channel goes through the net as compute_lpips feeds it.
+    Returns float64 CPU tensors: 'dist' [N] (mean over channels), 'dist_per_channel' [N, C] (sum over taps / epsilon^2), 'ppl' (0-dim,
+    ppl_from_distances of 'dist') and 'ppl_per_channel' [C].  Two calls give the same bits.  There is no CPU fallback."""
+    if space not in ('w', 'z') or sampling not in ('full', 'end'):
+        raise ValueError(f"compute_ppl: space 'w' | 'z' and sampling 'full' | 'end' (got {space!r}, {sampling!r})")
+    if int(num_samples) != num_samples or num_samples < 1 or not epsilon > 0:
+        raise ValueError('compute_ppl: num_samples must be a positive integer and epsilon positive')
+    if not hasattr(mapping, 'z_dim') or not hasattr(mapping, 'forward'):
+        raise _lib.LatentAugHipError(f'compute_ppl: mapping must be a synthesis.MappingEngine; got {type(mapping).__name__}')
+    per_call = _path_engines(synth, net, 'compute_ppl')
+    if mapping.device != synth.device or mapping.w_dim != synth.w_dim:
+        raise ValueError(f'compute_ppl: mapping (w_dim {mapping.w_dim}, {mapping.device}) and generator (w_dim {synth.w_dim}, '
+                         f'{synth.device}) do not belong together')
+    if batch is not None and (int(batch) != batch or batch < 1):
+        raise ValueError('compute_ppl: batch must be a positive integer')
+    N, C_, dev = int(num_samples), synth.img_channels, synth.device
+    chunk = min(synth.max_batch // 2, max(1, per_call // C_), N if batch is None else int(batch))
+    g = torch.Generator().manual_seed(int(seed))
+    z = torch.randn([2 * N, mapping.z_dim], generator=g)
+    t = torch.rand([N], generator=g) if sampling == 'full' else torch.zeros([N])
+    z0, z1, t = z[:N].to(dev), z[N:].to(dev), t.to(dev)
+    eps = float(epsilon)
+    out = torch.empty([N, C_, net.num_taps], dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        for p0 in range(0, N, chunk):
+            n = min(chunk, N - p0)
+            if space == 'w':
+                w = mapping.forward(torch.cat([z0[p0:p0 + n], z1[p0:p0 + n]]), 1, truncation_psi).reshape(2 * n, synth.w_dim)
+                ws = _path_points(w[:n], w[n:], t[p0:p0 + n], [0.0, eps], synth.num_ws, 0)
+            else:
+                zz = _path_points(z0[p0:p0 + n].contiguous(), z1[p0:p0 + n].contiguous(), t[p0:p0 + n], [0.0, eps], 1, 1)
+                ws = mapping.forward(zz.reshape(2 * n, mapping.z_dim), synth.num_ws, truncation_psi)
+            img = synth.forward(ws.reshape(2 * n, synth.num_ws, synth.w_dim), noise_mode='const')          # rows p and p + n: a pair
+            rows, P = _lpips_rows(img, net), n * C_
+            if P <= per_call:
+                d = torch.empty([P, net.num_taps], dtype=torch.float64, device=dev)
+                net.pair_distance_rows(rows, P, d)
+            else:          # (a net whose batch is smaller than one sample's channels)
+                d = net.pair_distance(rows[:P], rows[P:])
+            out[p0:p0 + n] = d.reshape(n, C_, net.num_taps)
+    per_channel = out.cpu().sum(dim=2) / (eps * eps)
+    dist = per_channel.mean(dim=1)
+    return {'dist': dist, 'dist_per_channel': per_channel,
+            'ppl': torch.tensor(ppl_from_distances(dist.numpy()), dtype=torch.float64),
+            'ppl_per_channel': torch.tensor([ppl_from_distances(per_channel[:, c].numpy()) for c in range(C_)], dtype=torch.float64)}
+
+
+def compute_path_length(synth, net, w0, w1, segments=8):
+    """Perceptual length of the straight segments from w0[p] to w1[p] (e.g. an inverted latent and its augmented version): the
+    segment is cut into `segments` equal steps (1 .. 63), every one of the segments + 1 points is synthesised once (noise_mode='const')
+    and consecutive images are compared with `net` as compute_lpips compares them.  sqrt(LPIPS) is the metric whose steps add up; the
+    chord is the same between the two ends.  w0, w1: float32 device tensors [N, w_dim], [N, 1, w_dim] (W) or [N, num_ws, w_dim] (W+,
+    the lerp then runs over the num_ws * w_dim values of a row).  `synth`, `net`: as compute_ppl takes them.
+    Returns float64 CPU tensors: 'length' [N] (sum over the steps of sqrt of the mean over channels of LPIPS), 'chord' [N], 'ratio' [N]
+    = length / chord, 1 where the chord is 0 (w0 == w1: a path that does not move is as straight as it can be), and 'segment_lpips'
+    [N, segments] (mean over channels).  With segments=1 length is chord bit for bit.  Two calls give the same bits."""
+    for name, w in (('w0', w0), ('w1', w1)):
+        if not torch.is_tensor(w):
+            raise _lib.LatentAugHipError(f'{name}: latentaugment_amd needs a ROCm device tensor (no CPU fallback); got {type(w).__name__}')
+        _lib.require_gpu(w)
+    _path_engines(synth, net, 'compute_path_length')
+    if int(segments) != segments or not 1 <= segments <= 63:
+        raise ValueError(f'compute_path_length: segments must lie in 1 .. 63 (got {segments})')
+    S = int(segments)
+    if w0.shape != w1.shape or w0.device != w1.device or w0.device != synth.device:
+        raise ValueError(f'w0 and w1 must agree in shape and sit on the generator\'s device: {tuple(w0.shape)} on {w0.device}, '
+                         f'{tuple(w1.shape)} on {w1.device}')
+    if w0.ndim == 2:
+        w0, w1 = w0[:, None], w1[:, None]
+    if w0.ndim != 3 or w0.shape[0] < 1 or w0.shape[1] not in (1, synth.num_ws) or w0.shape[2] != synth.w_dim:
+        raise ValueError(f'w0, w1: [N, {synth.w_dim}], [N, 1, {synth.w_dim}] or [N, {synth.num_ws}, {synth.w_dim}]; got {tuple(w0.shape)}')
+    N, L = int(w0.shape[0]), int(w0.shape[1])
+    C_, dev, T = synth.img_channels, synth.device, S + 1
+    npairs = S if S == 1 else S + 1          # the steps, then the chord (with one step the chord IS the step)
+    chunk = max(1, min(N, 256 // T))          # paths per round: at most 256 images at a time
+    a = w0.detach().to(torch.float32).reshape(N, L * synth.w_dim).contiguous()
+    b = w1.detach().to(torch.float32).reshape(N, L * synth.w_dim).contiguous()
+    t = torch.zeros([N], dtype=torch.float32, device=dev)
+    dt = [k / S for k in range(T)]
+    R = synth.img_resolution
+    out = torch.empty([N, npairs, C_, net.num_taps], dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        for p0 in range(0, N, chunk):
+            n = min(chunk, N - p0)
+            ws = _path_points(a[p0:p0 + n], b[p0:p0 + n], t[p0:p0 + n], dt, 1, 0).reshape(T * n, L, synth.w_dim)      # row k * n + p
+            img = torch.empty([T * n, C_, R, R], dtype=torch.float32, device=dev)
+            for r0 in range(0, T * n, synth.max_batch):
+                synth.forward(ws[r0:r0 + synth.max_batch], noise_mode='const', out=img[r0:r0 + synth.max_batch])
+            rows = _lpips_rows(img, net)          # row (k * n + p) * C + c
+            first = torch.arange(S * n * C_, device=dev)
+            ia = first if S == 1 else torch.cat([first, first[:n * C_]])
+            ib = first + n * C_ if S == 1 else torch.cat([first + n * C_, first[:n * C_] + S * n * C_])
+            d = net.pair_distance(rows.index_select(0, ia), rows.index_select(0, ib))
+            out[p0:p0 + n] = d.reshape(npairs, n, C_, net.num_taps).permute(1, 0, 2, 3)
+    lp = out.cpu().sum(dim=3).mean(dim=2)          # [N, npairs]
+    seg, chord = lp[:, :S], lp[:, npairs - 1].sqrt()
+    length = seg.sqrt().sum(dim=1)
+    ratio = torch.where(chord > 0, length / torch.where(chord > 0, chord, torch.ones_like(chord)), torch.ones_like(chord))
+    return {'length': length, 'chord': chord, 'ratio': ratio, 'segment_lpips': seg.contiguous()}
+
+
+def compute_path_length_for_aug_dataset(datadir, synth, net, segments=8):
+    """compute_path_length from every inverted latent to its augmented version in a run directory of the reference's drivers
+    (backbone_latentaug.py:112-118): `latent/w_{i}` and `latent_aug/w_aug_{i}`, i = 0, 1, .., each a pickled batch of latents
+    ([n, w_dim] as the drivers squeeze them -- [w_dim] for a batch of one --, [n, 1, w_dim] or [n, num_ws, w_dim]; a W file against a W+
+    file is broadcast).  The pickles are read through the
+    allow-list loader of formats.py, never a plain unpickle.  Returns the per-sample tensors of compute_path_length over all files, a
+    float '<key>_mean' for 'length', 'chord' and 'ratio', and 'num_items'."""
+    from .formats import _restricted_load
+    _path_engines(synth, net, 'compute_path_length_for_aug_dataset')
+    files, i = [], 0
+    while os.path.isfile(os.path.join(datadir, 'latent', f'w_{i}')) and os.path.isfile(os.path.join(datadir, 'latent_aug', f'w_aug_{i}')):
+        files.append((os.path.join(datadir, 'latent', f'w_{i}'), os.path.join(datadir, 'latent_aug', f'w_aug_{i}')))
+        i += 1
+    if not files:
+        raise FileNotFoundError(f"no latent/w_0 with latent_aug/w_aug_0 under {datadir}")
+
+    def latents(fname):
+        with open(fname, 'rb') as f:
+            w = torch.as_tensor(_restricted_load(f)).to(torch.float32)
+        if w.ndim == 1:          # the drivers squeeze what they dump: a batch of one is [w_dim]
+            w = w[None]
+        if w.ndim == 2:
+            w = w[:, None]
+        if w.ndim != 3 or w.shape[1] not in (1, synth.num_ws) or w.shape[2] != synth.w_dim:
+            raise ValueError(f'{fname}: latents must be [n, {synth.w_dim}], [n, 1, {synth.w_dim}] or [n, {synth.num_ws}, {synth.w_dim}]')
+        return w
+    parts = []
+    for src, aug in files:
+        w0, w1 = latents(src), latents(aug)
+        if w0.shape[1] != w1.shape[1]:
+            w0, w1 = (w.expand(-1, synth.num_ws, -1) for w in (w0, w1))
+        parts.append(compute_path_length(synth, net, w0.contiguous().to(synth.device), w1.contiguous().to(synth.device), segments=segments))
+    out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
+    out['num_items'] = int(out['length'].shape[0])
+    for k in ('length', 'chord', 'ratio'):
+        out[k + '_mean'] = float(out[k].mean())
+    return out
