@@ -565,10 +565,16 @@ int la_latent_opt_set_trace(la_latent_opt* h, float* w_trace, float* img_trace);
  * the tensor `loss.backward()` leaves in w_opt.grad (:275) before Adam consumes it (W+ handle: [steps][B][num_ws][w_dim]).  While set
  * the loop launches eagerly. */
 int la_latent_opt_set_grad_trace(la_latent_opt* h, float* dw_trace);
-/* 1 (default): with both the discriminator and the perceptual criterion active, the two run side by side inside a step -- the
- * discriminator branch on the launch stream, crop + feature net forward / backward on a stream of the handle's own, forked after the
- * synthesis forward and joined before the crop gradient is added to the image gradient (two parallel branches of the captured step).
- * 0: one after the other.  Bit-identical results either way (same launches, same accumulation order).  Drops a captured step. */
+/* How a step places its discriminator branch and its perceptual branch (crop + feature net forward / backward) when both criteria are
+ * active; `enable` is a mode, values outside 0 .. 2 are clamped.
+ *   0: one after the other on the launch stream.
+ *   1: split replay -- the step is captured as four graphs and the perceptual one is replayed on a stream of the handle's own beside
+ *      the discriminator's on the launch stream.  The branches overlap only while the step is replayed: launched steps (the first of a
+ *      batch size, a run with loss scalars or traces, graph mode off) run them one after the other.
+ *   2 (the handle's default): fork / join inside the step -- the perceptual branch on the handle's own stream, forked after the synthesis
+ *      forward and joined before its crop gradient is added to the image gradient; launched that way, and captured as two parallel
+ *      branches of one graph.  A run that asks for loss scalars keeps both branches on the launch stream.
+ * Bit-identical results in every mode (same launches, same accumulation order).  Drops the captured graphs. */
 int la_latent_opt_set_overlap(la_latent_opt* h, int enable);
 /* Image rows [row_lo, row_hi) that the loop's image criteria read (0, 0 = not known, the default).  The reference synthesises a whole
  * frame in every epoch and hands the pixel criterion its centre crop and the perceptual criterion a window inside it

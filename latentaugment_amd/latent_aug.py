@@ -357,11 +357,8 @@ class LatentAug:
         # launch mode of the step loop: one captured step replayed (default) or every launch eager (`opt.hip_graph = False`)
         self.hip_graph = bool(getattr(opt, 'hip_graph', True))
         _lib.check(lib.la_latent_opt_set_graph(h, int(self.hip_graph)), 'la_latent_opt_set_graph')
-        # independent image criteria (discriminator, perceptual) side by side inside a step (default) or one after the other
-        # (`opt.overlap_criteria = False`): bit-identical results, la_latent_opt_set_overlap
-        # `opt.overlap_criteria`: True / 2 (default) = fork / join inside the captured step (two parallel branches of one graph), 1 = split
-        # replay (round-5 experiment: the perceptual branch as a graph of its own on a side stream; measured equal: 145.5 against 145.1 ms
-        # at preset E, 158.6 one after the other), False / 0 = one after the other
+        # `opt.overlap_criteria`, discriminator and perceptual criterion of a step: False / 0 one after the other, 1 split replay, True / 2
+        # (default) fork / join inside the step; bit-identical results (la_latent_opt_set_overlap in include/latentaug_hip.h)
         oc = getattr(opt, 'overlap_criteria', True)
         self.overlap_criteria = int(oc) if not isinstance(oc, bool) else (2 if oc else 0)
         _lib.check(lib.la_latent_opt_set_overlap(h, self.overlap_criteria), 'la_latent_opt_set_overlap')
@@ -496,6 +493,34 @@ class LatentAug:
         """Rows of one sample's optimised latent: 1 in W space, num_ws in W+."""
         return self.num_ws if self.wplus else 1
 
+    def _crop_pos(self, crop_pos=None):
+        """The given crop position, else the one forward() drew for this batch, else a fresh draw."""
+        cp = getattr(self, 'crop_params', None)
+        return crop_pos if crop_pos is not None else cp['crop_pos'] if cp else get_params(self.res, self.crop_size, self.preprocess)['crop_pos']
+
+    def _empty_pair(self, b):
+        """Uninitialised (img [b,C,R,R], w_aug [b,num_ws,w_dim]) on the current stream."""
+        return (torch.empty([b, self.engine.img_channels, self.res, self.res], device=self.device, dtype=torch.float32),
+                torch.empty([b, self.num_ws, self.w_dim], device=self.device, dtype=torch.float32))
+
+    def _shard_noises(self, noises, B, lo, hi, seed):
+        """Final-synthesis noise of samples lo:hi of a batch of B: the caller's rows, else rows of the batch's seeded draw, else None."""
+        if noises is not None:
+            return [t[lo:hi].contiguous() if t is not None else None for t in noises]
+        return self.engine.make_noises(B, batch_seed=seed, rows=(lo, hi)) if self._cfg.final_noise_mode == 2 else None
+
+    def _gather_pair(self, img, w_aug, per, B, ev=None):
+        """This rank's rows -> the full batch: image and latent packed into a single buffer, ONE collective per batch (ev: its shard_timers events).
+        The widths are explicit: a rank with an empty shard packs 0 rows, and reshape(0, -1) is refused."""
+        n_img = self.engine.img_channels * self.res * self.res
+        flat = torch.cat([img.reshape(img.shape[0], n_img), w_aug.reshape(w_aug.shape[0], self.num_ws * self.w_dim)], dim=1)
+        if ev is not None:
+            ev[1].record()
+        full = gather_shards(flat, per, B, self.group)
+        if ev is not None:
+            ev[2].record()
+        return full[:, :n_img].reshape(B, self.engine.img_channels, self.res, self.res), full[:, n_img:].reshape(B, self.num_ws, self.w_dim)
+
     def run_local(self, w, final_noises=None, want_losses=False, crop_pos=None, trace=None, out=None):
         """w [b,1,w_dim] on this device (W+: [b,num_ws,w_dim]) -> (img [b,C,R,R], w_aug [b,num_ws,w_dim], losses or None).
         out (optional): (img, w_aug) tensors to fill instead of allocating them on the current stream.
@@ -503,22 +528,16 @@ class LatentAug:
         [steps,b,num_ws,w_dim]) and 'img' [steps,b,C,R,R]; trace['want'] (default ('w', 'img')) selects them, and may name 'grad'
         (dL/dw, the shape of 'w')."""
         if self.feat is not None:
-            if crop_pos is None:
-                crop_pos = getattr(self, 'crop_params', None)
-                crop_pos = crop_pos['crop_pos'] if crop_pos else get_params(self.res, self.crop_size, self.preprocess)['crop_pos']
-            ax, ay = self.crop_window(crop_pos)
+            ax, ay = self.crop_window(self._crop_pos(crop_pos))
             _lib.check(self._lib.la_latent_opt_set_crop_pos(self._h, ax, ay), 'la_latent_opt_set_crop_pos')
         w = w.to(device=self.device, dtype=torch.float32).contiguous()
         b = w.shape[0]
         assert w.ndim == 3 and w.shape[1:] == (self.latent_rows, self.w_dim), \
             f'latent_space {self.latent_space!r} takes w [b, {self.latent_rows}, {self.w_dim}], got {tuple(w.shape)}'
+        img, w_aug = out if out is not None else self._empty_pair(b)
         if out is not None:
-            img, w_aug = out
             assert img.shape == (b, self.engine.img_channels, self.res, self.res) and w_aug.shape == (b, self.num_ws, self.w_dim)
             assert img.is_contiguous() and w_aug.is_contiguous() and img.dtype == w_aug.dtype == torch.float32
-        else:
-            img = torch.empty([b, self.engine.img_channels, self.res, self.res], device=self.device, dtype=torch.float32)
-            w_aug = torch.empty([b, self.num_ws, self.w_dim], device=self.device, dtype=torch.float32)
         losses = torch.zeros([max(self.num_epochs, 1), 4], device=self.device) if want_losses else None
         fn = None
         if self._cfg.final_noise_mode == 2:
@@ -598,16 +617,14 @@ class LatentAug:
         w = w.to(device=self.device, dtype=torch.float32).contiguous()
         b = w.shape[0]
         assert b == self._max_local and b % 2 == 0, 'stream lanes take the full (even) local batch'
-        if crop_pos is None and self.feat is not None:
-            crop_pos = getattr(self, 'crop_params', None)
-            crop_pos = crop_pos['crop_pos'] if crop_pos else get_params(self.res, self.crop_size, self.preprocess)['crop_pos']
+        if self.feat is not None:
+            crop_pos = self._crop_pos(crop_pos)
         if self._cfg.final_noise_mode == 2 and final_noises is None:
             final_noises = self.engine.make_noises(b)      # ONE draw for the batch, as the single loop makes it; a lane keeps its rows
         parts, outs, fns = [], [], []
         for k in (0, 1):
             parts.append(w[k::2].contiguous())
-            outs.append((torch.empty([b // 2, self.engine.img_channels, self.res, self.res], device=self.device, dtype=torch.float32),
-                         torch.empty([b // 2, self.num_ws, self.w_dim], device=self.device, dtype=torch.float32)))
+            outs.append(self._empty_pair(b // 2))
             fns.append([t[k::2].contiguous() if t is not None else None for t in final_noises] if final_noises is not None else None)
         main = torch.cuda.current_stream(self.device)
         side = self._lane_stream if concurrent else main
@@ -618,8 +635,7 @@ class LatentAug:
             self._lanes[1].run_local(parts[1], fns[1], crop_pos=crop_pos, out=outs[1])
         if concurrent:
             main.wait_stream(side)
-        img = torch.empty([b, self.engine.img_channels, self.res, self.res], device=self.device, dtype=torch.float32)
-        w_aug = torch.empty([b, self.num_ws, self.w_dim], device=self.device, dtype=torch.float32)
+        img, w_aug = self._empty_pair(b)
         for k in (0, 1):
             img[k::2] = outs[k][0]
             w_aug[k::2] = outs[k][1]
@@ -645,10 +661,7 @@ class LatentAug:
             self.build_lanes()
         if self._cfg.final_noise_mode == 2 and final_noises is None:
             final_noises = self.engine.make_noises(w.shape[0])      # one draw for both runs
-        crop_pos = None
-        if self.feat is not None:
-            cp = getattr(self, 'crop_params', None)
-            crop_pos = cp['crop_pos'] if cp else get_params(self.res, self.crop_size, self.preprocess)['crop_pos']
+        crop_pos = self._crop_pos() if self.feat is not None else None
         ref_img, ref_w, _ = self.run_lanes(w, final_noises, crop_pos=crop_pos, concurrent=False)
         img, w_aug, _ = self.run_lanes(w, final_noises, crop_pos=crop_pos, concurrent=True)
         if torch.equal(img, ref_img) and torch.equal(w_aug, ref_w):
@@ -733,16 +746,12 @@ class LatentAug:
             self._last_controls = (cx, cy, noise_seed)
             self.crop_params = {'crop_pos': (cx, cy)}
             timers = getattr(self, 'shard_timers', None)      # bench.py: [(start, loop done, gather done)] HIP events per forward
-            if timers is not None:
-                ev = tuple(torch.cuda.Event(enable_timing=True) for _ in range(3))
+            ev = tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) if timers is not None else None
+            if ev is not None:
                 ev[0].record()
+                timers.append(ev)      # ([1] and [2] are recorded around the collective, _gather_pair)
             if hi > lo:
-                if final_noises is not None:
-                    fn = [t[lo:hi].contiguous() if t is not None else None for t in final_noises]
-                elif self._cfg.final_noise_mode == 2:
-                    fn = self.engine.make_noises(B, batch_seed=noise_seed, rows=(lo, hi))
-                else:
-                    fn = None
+                fn = self._shard_noises(final_noises, B, lo, hi, noise_seed)
                 if self._verbose_flag and rank == 0:
                     # first-batch log of the reference (:278-300): rank 0 reports its own shard, as replica 0 of a DataParallel run would
                     img, w_aug = self._run_verbose(w[lo:hi], fn, fname[lo:hi] if fname is not None else None)
@@ -750,20 +759,8 @@ class LatentAug:
                     img, w_aug, _ = self.run_batch(w[lo:hi], fn)
                 self._verbose_flag = False
             else:
-                img = torch.empty([0, self.engine.img_channels, self.res, self.res], device=self.device)
-                w_aug = torch.empty([0, self.num_ws, self.w_dim], device=self.device)
-            # one collective per batch: image and latent packed into a single buffer
-            flat = torch.cat([img.reshape(img.shape[0], -1), w_aug.reshape(w_aug.shape[0], -1)], dim=1)
-            if timers is not None:
-                ev[1].record()
-            full = gather_shards(flat, per, B, self.group)
-            if timers is not None:
-                ev[2].record()
-                timers.append(ev)
-            n_img = self.engine.img_channels * self.res * self.res
-            img = full[:, :n_img].reshape(B, self.engine.img_channels, self.res, self.res)
-            w_aug = full[:, n_img:].reshape(B, self.num_ws, self.w_dim)
-            return img, w_aug
+                img, w_aug = self._empty_pair(0)
+            return self._gather_pair(img, w_aug, per, B, ev)
         if self._verbose_flag:
             img, w_aug = self._run_verbose(w, final_noises, fname)
             self._verbose_flag = False
@@ -836,22 +833,12 @@ class LatentAug:
             gloo = dist.get_backend(self.group) == 'gloo'
             zb = z.detach().to('cpu' if gloo else self.device, torch.float32).contiguous()
             dist.broadcast(zb, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
-            n_img = self.engine.img_channels * self.res * self.res
             if hi > lo:
                 ws = self.mapping.forward(zb[lo:hi].to(self.device), self.num_ws, self.truncation_psi)
-                if noises is not None:
-                    fn = [t[lo:hi].contiguous() if t is not None else None for t in noises]
-                elif self.final_noise_mode == 'random':
-                    fn = self.engine.make_noises(B, batch_seed=noise_seed, rows=(lo, hi))
-                else:
-                    fn = None
-                img = self.engine.forward(ws, noise_mode=self.final_noise_mode, noises=fn)
-                flat = torch.cat([img.reshape(hi - lo, -1), ws.reshape(hi - lo, -1)], dim=1)
+                img = self.engine.forward(ws, noise_mode=self.final_noise_mode, noises=self._shard_noises(noises, B, lo, hi, noise_seed))
             else:
-                flat = torch.empty([0, n_img + self.num_ws * self.w_dim], device=self.device)
-            full = gather_shards(flat, per, B, self.group)
-            return (full[:, :n_img].reshape(B, self.engine.img_channels, self.res, self.res),
-                    full[:, n_img:].reshape(B, self.num_ws, self.w_dim))
+                img, ws = self._empty_pair(0)
+            return self._gather_pair(img, ws, per, B)
         ws = self.mapping.forward(z.to(self.device), self.num_ws, self.truncation_psi)
         img = self.engine.forward(ws, noise_mode=self.final_noise_mode, noises=noises)
         return img, ws

@@ -11,11 +11,20 @@ f32, bf16x3 and f16x2:
   feature net    conv, conv, tap, maxpool, conv, tap on a 3-channel 12^2 input, N = 3: the padded first-conv gradient copy, both sources
                  of the ReLU mask; features and input gradient
   detector       conv, maxpool, conv, fc + ReLU, fc: features
+  loop           LatentAug above them (la_latent_opt.hip): every branch of its schedule decision.  The 64^2 generator, a 64^2 discriminator
+                 (channel cap 32), the feature net at crop_size_aug 12, banks W [16], X [8], fea [8]; 3 steps, const noise, f16x2; one loop per
+                 handle (stream_lanes 1, so that a handle re-captures) except in c.  img and w_aug of every batch of
+                   a  w_latent + w_pix, batches of 4, 4, 2, 4 (windowed steps; re-capture on a new batch size), captured and eager
+                   b  all four criteria, overlap_criteria 0 / 1 / 2 x captured / eager, batches of 4, 4, 2, crop at (0, 0), (3, 1), (3, 1)
+                   c  all four criteria, batch 8 on two stream lanes (split replay in each lane; the first-batch self-check), two batches
+                   d  W+ with w_latent + w_pix + w_lpips, batch 2, two batches
+                   e  all four criteria, batch 1 with loss scalars, per-criterion timers and the w / img / grad traces: those too
 Inputs: seeded CPU generators."""
 import os
 import subprocess
 import sys
 import tempfile
+import types
 
 import numpy as np
 
@@ -78,8 +87,54 @@ def dump(lib_path, out_path):
         keep(f'feat/{mode}/f', f)
         keep(f'feat/{mode}/gx', F.backward(torch.randn(f.shape, generator=torch.Generator().manual_seed(1)).to(dev)))
         keep(f'detector/{mode}/f', synthesis.FeatureEngine(d_ops, dev, in_res=8, max_batch=3, precision=mode).forward(xd))
+    loop_cases(dev, lib, g_sd, meta, f_ops, draw, keep)
     torch.cuda.synchronize()
     np.savez(out_path, **res)
+
+
+def loop_cases(dev, lib, g_sd, meta, f_ops, draw, keep):
+    import ctypes
+    import torch
+    from latentaugment_amd import _lib, synthesis, synthetic
+    from latentaugment_amd.latent_aug import LatentAug
+    d64 = synthetic.make_discriminator_state_dict(64, 2, channel_max=32)
+    F = synthesis.FeatureEngine(f_ops, dev, in_res=12, max_batch=2, precision='f16x2').num_features
+    banks = {'W': draw(16, meta['num_ws'], 64), 'X': draw(8, 2, 64, 64).clamp(-1, 1), 'fea': [draw(8, F) * (1.0 / F) ** 0.5 for _ in range(2)]}
+    w, wp = draw(8, 1, 64), draw(2, meta['num_ws'], 64)
+    all4 = dict(w_latent=0.3, w_pix=1.0, w_disc=0.5, w_lpips=2.0)
+
+    def make(batch, **kw):
+        opt = types.SimpleNamespace(img_resolution=64, batch_size=batch, modalities_aug='A,B', opt_num_epochs=3, opt_lr=0.01, truncation_psi=1.0,
+                                    w_pix=0.0, w_lpips=0.0, w_latent=0.0, w_disc=0.0, crop_size_aug=12, preprocess_aug='center_random_crop',
+                                    soft_aug=False, alpha=1.0, verbose_log=False, criterion_mode='gemm', final_noise_mode='const',
+                                    precision='f16x2', stream_lanes=1)
+        opt.__dict__.update(kw)
+        return LatentAug('train', opt, None, [0], generator=g_sd, discriminator=d64 if opt.w_disc > 0 else None, banks=dict(banks),
+                         feature_net=f_ops if opt.w_lpips > 0 else None)
+
+    def batches(key, la, runs):
+        for i, (wb, pos) in enumerate(runs):
+            la.crop_params = {'crop_pos': pos}      # (what forward() draws once per batch)
+            img, w_aug, _ = la.run_batch(wb)
+            keep(f'loop/{key}/batch{i}/img', img)
+            keep(f'loop/{key}/batch{i}/w_aug', w_aug)
+
+    for graph in (True, False):
+        batches(f'a/graph{int(graph)}', make(4, w_latent=0.3, w_pix=1.0, hip_graph=graph), [(w[:4], (0, 0)), (w[4:], (0, 0)), (w[:2], (0, 0)), (w[:4], (0, 0))])
+        for overlap in (0, 1, 2):
+            batches(f'b/overlap{overlap}/graph{int(graph)}', make(4, hip_graph=graph, overlap_criteria=overlap, **all4),
+                    [(w[:4], (0, 0)), (w[4:], (3, 1)), (w[:2], (3, 1))])
+    la = make(8, stream_lanes=2, **all4)
+    batches('c', la, [(w, (3, 1)), (w.flip(0), (3, 1))])
+    assert la.lanes_active and la.lanes_selfcheck == 'bit-identical', la.lanes_selfcheck
+    batches('d', make(2, latent_space='w+', w_latent=0.3, w_pix=1.0, w_lpips=2.0), [(wp, (3, 1)), (wp.flip(0), (3, 1))])
+    la, trace = make(1, **all4), {'want': ('w', 'img', 'grad')}
+    _lib.check(lib.la_latent_opt_set_time_trace(la._h, 1), 'la_latent_opt_set_time_trace')
+    img, w_aug, losses = la.run_local(w[:1], want_losses=True, crop_pos=(3, 1), trace=trace)
+    torch.cuda.synchronize()
+    _lib.check(lib.la_latent_opt_get_times(la._h, (ctypes.c_float * 15)()), 'la_latent_opt_get_times')
+    for name, t in (('img', img), ('w_aug', w_aug), ('losses', losses), ('trace_w', trace['w']), ('trace_img', trace['img']), ('trace_grad', trace['grad'])):
+        keep(f'loop/e/{name}', t)
 
 
 def main():

@@ -321,6 +321,28 @@ def test_curve_png_writer(tmp_path):
     write_curve_png(str(path), [])
 
 
+def test_gather_pair_packs_an_empty_shard(monkeypatch):
+    """LatentAug._gather_pair on a rank whose shard is empty (B = 5 on 4 ranks: the last rank has no rows): 0 rows are packed at the full
+    width, so the rank reaches the collective like the others, and the unpacked pair has the batch's shapes.  With rows, pack / unpack
+    return image and latent unchanged."""
+    import types
+    from latentaugment_amd import latent_aug
+    from latentaugment_amd.latent_aug import LatentAug
+    me = types.SimpleNamespace(engine=types.SimpleNamespace(img_channels=2), res=4, num_ws=3, w_dim=5, group=None)
+    seen = []
+
+    def fake_gather(local, per, batch, group=None):      # the other ranks' rows: zeros
+        seen.append(tuple(local.shape))
+        return torch.cat([local, torch.zeros([batch - local.shape[0], local.shape[1]])])
+
+    monkeypatch.setattr(latent_aug, 'gather_shards', fake_gather)
+    img, w_aug = LatentAug._gather_pair(me, torch.empty([0, 2, 4, 4]), torch.empty([0, 3, 5]), 2, 5)
+    assert seen == [(0, 2 * 4 * 4 + 3 * 5)] and img.shape == (5, 2, 4, 4) and w_aug.shape == (5, 3, 5)
+    a, b = torch.randn([2, 2, 4, 4]), torch.randn([2, 3, 5])
+    img, w_aug = LatentAug._gather_pair(me, a, b, 2, 5)
+    assert torch.equal(img[:2], a) and torch.equal(w_aug[:2], b) and not img[2:].any() and not w_aug[2:].any()
+
+
 def test_stream_lane_rule():
     """LatentAug.lanes_eligible (host logic, no GPU): two lanes take the FULL, even local batch of >= 4; with the discriminator a multiple
     of 8 (MinibatchStd groups sample n with n + b/4, n + 2b/4, n + 3b/4: the even / odd halves keep them only then); 'auto' not with the
