@@ -160,11 +160,16 @@ class SynthesisBlock(nn.Module):
 
 class SynthesisNetwork(nn.Module):
     def __init__(self, w_dim, img_resolution, img_channels, channel_base=32768, channel_max=512,
-                 conv_clamp=256, resample_filter=(1, 3, 3, 1)):
+                 conv_clamp=256, resample_filter=(1, 3, 3, 1), channels=None):
+        """channels: optional explicit table {resolution: channels} for 4, 8, ..., img_resolution (test shapes the
+        channel_base / channel_max rule cannot produce); None: the rule."""
         super().__init__()
         self.w_dim, self.img_resolution, self.img_channels = w_dim, img_resolution, img_channels
         self.block_resolutions = [2 ** i for i in range(2, int(math.log2(img_resolution)) + 1)]
         ch = channels_dict(img_resolution, channel_base, channel_max)
+        if channels is not None:
+            assert sorted(channels) == sorted(ch), 'the channel table needs one entry per resolution 4..img_resolution'
+            ch = {int(r): int(c) for r, c in channels.items()}
         self.channels = ch
         self.num_ws = 0
         for res in self.block_resolutions:
@@ -203,12 +208,12 @@ class Generator(nn.Module):
     .z_dim/.w_dim/.num_ws  (util_latent_aug.py:119-121,203,227,460,488)."""
 
     def __init__(self, z_dim=512, w_dim=512, img_resolution=256, img_channels=2, channel_base=32768,
-                 channel_max=512, conv_clamp=256, mapping_layers=8):
+                 channel_max=512, conv_clamp=256, mapping_layers=8, channels=None):
         super().__init__()
         self.z_dim, self.w_dim, self.c_dim = z_dim, w_dim, 0
         self.img_resolution, self.img_channels = img_resolution, img_channels
         self.synthesis = SynthesisNetwork(w_dim, img_resolution, img_channels, channel_base, channel_max,
-                                          conv_clamp)
+                                          conv_clamp, channels=channels)
         self.num_ws = self.synthesis.num_ws
         self.mapping = MappingNetwork(z_dim, w_dim, self.num_ws, num_layers=mapping_layers)
 
@@ -324,7 +329,7 @@ class Discriminator(nn.Module):
 
 
 def make_generator(img_resolution=256, img_channels=2, channel_base=32768, channel_max=512, seed=0,
-                   noise_strength=0.0, conv_clamp=256, w_dim=512, mapping_layers=8):
+                   noise_strength=0.0, conv_clamp=256, w_dim=512, mapping_layers=8, channels=None):
     """Random-init G exactly as BASELINE.md "Synthetic inputs": SG2 default init under manual_seed(seed)."""
     g = torch.Generator().manual_seed(seed)
     state = torch.random.get_rng_state()
@@ -332,7 +337,7 @@ def make_generator(img_resolution=256, img_channels=2, channel_base=32768, chann
     try:
         G = Generator(z_dim=w_dim, w_dim=w_dim, img_resolution=img_resolution, img_channels=img_channels,
                       channel_base=channel_base, channel_max=channel_max, conv_clamp=conv_clamp,
-                      mapping_layers=mapping_layers)
+                      mapping_layers=mapping_layers, channels=channels)
     finally:
         torch.random.set_rng_state(state)
     del g
