@@ -268,6 +268,32 @@ size_t la_modconv_workspace_bytes(int B, int cin, int cout, int res, int up);
 size_t la_modconv_bf16_pack_bytes(int cin, int cout, int transpose, int nterm);
 int la_pack_conv_weights_bf16_f32(const float* w, void* out, int cout, int cin, int ktaps, int transpose, int nterm,
                                   la_stream_t stream);
+/* Host only, no launch, usable without a GPU.  The kernel form that ONE contraction launch of these calls takes: C = contraction depth,
+ * M = rows (a multiple of 4), geom = the launch geometry at output resolution res, have_in_q != 0 = the launch input was split up
+ * front (the merged up-sampling launch), ws_bytes = what the caller hands to the launch.  The library decides with the same function
+ * when it launches.  info[LA_CONV_PLAN_NINFO]: profiler class (the index of la_prof_end_classes), row tile, LA_CONV_MFMA_*, K slices
+ * (1 = direct), a pre-split copy of the input is read (0 / 1), merged phases (0 / 1), operand-preparation brackets of the launch
+ * (0 / 1), the grid x / y / z of the contraction launch, and the workspace bytes taken in front of the split-K partials.  A launch that
+ * would be refused is refused here with the same code and message. */
+#define LA_CONV_GEOM_SAME_FWD 0   /* 3x3 conv at res^2 ... */
+#define LA_CONV_GEOM_SAME_BWD 1   /* ... and its backward-data contraction */
+#define LA_CONV_GEOM_DOWN2 2      /* stride-2 3x3 gather over (res+1)^2 onto (res/2)^2: backward of the up-sampling layer */
+#define LA_CONV_GEOM_UP2_PHASE 3  /* + 2 * py + px: one output phase of the transposed stride-2 conv of a (res/2)^2 input ... */
+#define LA_CONV_GEOM_UP2_MERGED 7 /* ... and the four phases in one launch */
+#define LA_CONV_MFMA_F32_32X32X2 0
+#define LA_CONV_MFMA_32X32 1      /* the 16-bit formats' 32x32 forms */
+#define LA_CONV_MFMA_16X16X32 2
+#define LA_CONV_PLAN_CLS 0
+#define LA_CONV_PLAN_MT 1
+#define LA_CONV_PLAN_MFMA 2
+#define LA_CONV_PLAN_KSPLIT 3
+#define LA_CONV_PLAN_PRESPLIT 4
+#define LA_CONV_PLAN_MERGED 5
+#define LA_CONV_PLAN_PREP 6
+#define LA_CONV_PLAN_GRID 7       /* .. 9 */
+#define LA_CONV_PLAN_WS_HEAD 10
+#define LA_CONV_PLAN_NINFO 11
+int la_conv_plan_query(int precision, int B, int C, int M, int geom, int res, int have_in_q, size_t ws_bytes, long* info);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Criteria and optimiser

@@ -163,12 +163,6 @@ static inline void la_conv_taps_kxk(LaConvArgs& a, int k, bool backward) {
         a.tap_dy[t] = backward ? -dy : dy; a.tap_dx[t] = backward ? -dx : dx; a.tap_w[t] = t;
     }
 }
-static inline void la_conv_taps_3x3(LaConvArgs& a, bool backward) { la_conv_taps_kxk(a, 3, backward); }
-// 3 x 3 taps from the corner (offsets 0 .. 2): the stride-2 gathers over a (2h+1)^2 input
-static inline void la_conv_taps_3x3_corner(LaConvArgs& a) {
-    a.ntaps = 9;
-    for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3; a.tap_dx[t] = t % 3; a.tap_w[t] = t; }
-}
 // Launch geometries on top of a.C (la_conv_weights_select).  k x k conv (pad k / 2) at one resolution, or its backward-data contraction ...
 static inline void la_conv_geom_same(LaConvArgs& a, int res, int k, bool backward) {
     a.Hin = a.Win = a.Hout = a.Wout = a.Gy = a.Gx = res;
@@ -180,7 +174,8 @@ static inline void la_conv_geom_down2(LaConvArgs& a, int res) {
     a.Hin = a.Win = res + 1; a.Hout = a.Wout = a.Gy = a.Gx = res / 2;
     a.in_sy = a.in_sx = 2;
     a.in_bstride = (long)a.C * (res + 1) * (res + 1);
-    la_conv_taps_3x3_corner(a);
+    a.ntaps = 9;      // 3 x 3 taps from the corner (offsets 0 .. 2)
+    for (int t = 0; t < 9; ++t) { a.tap_dy[t] = t / 3; a.tap_dx[t] = t % 3; a.tap_w[t] = t; }
 }
 // the forward epilogue of a layer (demod and noise null: a plain bias / activation epilogue)
 static inline void la_conv_set_epi(LaConvArgs& a, const LaLayerEpi& e) {
@@ -204,19 +199,46 @@ static inline void la_conv_up2_phase(LaConvArgs& a, int hin, int py, int px, int
     P.Gy = a.Gy; P.Gx = a.Gx; P.out_oy = py; P.out_ox = a.out_ox; P.ntaps = nt;
     for (int t = 0; t < nt; ++t) { P.tap_dy[t] = a.tap_dy[t]; P.tap_dx[t] = a.tap_dx[t]; P.tap_w[t] = a.tap_w[t]; }
 }
+// ... the raw (2 hin + 1)-row intermediate those phases write: dense rows (pitch = xhalf = 0) or column-planar ones (la_conv_up2_launch) ...
+static inline void la_conv_geom_up2(LaConvArgs& a, int hin, int pitch, int xhalf) {
+    const int res = 2 * hin;
+    a.Hin = a.Win = hin; a.Hout = a.Wout = res + 1;
+    a.out_sy = a.out_sx = 2; a.epi = LA_EPI_RAW;
+    if (pitch > 0) { a.out_pitch = pitch; a.out_plane = (long)pitch * (res + 1); }      // padded (2h+1)-wide rows
+    if (xhalf > 0) { a.out_sx = 1; a.Wout = pitch; }      // phase px writes the contiguous run from px * xhalf
+}
+// ... and the four phases as one launch
+static inline void la_conv_up2_merged(LaConvArgs& a, int hin, int ox_step) {
+    for (int k = 0; k < 4; ++k) la_conv_up2_phase(a, hin, k >> 1, k & 1, ox_step, true);
+    a.out_oy = a.out_ox = 0; a.Gy = a.Gx = hin + 1; a.ntaps = 4;      // launch-wide fields = the largest phase (checks only)
+}
 
-// ---- 16-bit split path, three units: la_conv_operand.hip (weight packs, operand scales, pre-split copy, kernel selection),
-// la_conv_flat.hip (la_conv_bf16_kernel) and la_conv_halo.hip (la_conv_bf16_halo_kernel)
-// the launches of the two kernels for as.precision (la_conv_bf16_dispatch picks one)
-int la_conv_flat_launch(const LaConvArgs& as, int MTsel, dim3 grid, bool split, hipStream_t stream);
-int la_conv_halo_launch(const LaConvArgs& as, int MTsel, dim3 grid, hipStream_t stream);
+// The kernel form of one launch, decided once by la_conv_plan (host only: no HIP call) and read by everything that prepares, launches or
+// accounts for it.  Not a kernel parameter.
+enum { LA_FORM_F32 = 0, LA_FORM_F32_SPLIT, LA_FORM_FLAT, LA_FORM_FLAT_SPLIT, LA_FORM_HALO };
+enum { LA_PREP_NONE = 0, LA_PREP_SCALE, LA_PREP_PRESPLIT };      // operand preparation: nothing, the fp16 scale pass only, a pre-split copy
+struct LaConvPlan {
+    int form, cls;           // LA_FORM_*, profiler class (LA_PC_CONV_*)
+    int mt, mtiles, mfma, ksplit;      // row tile (128 / 64 / 32), row tiles, LA_CONV_MFMA_*, K slices (1: direct)
+    dim3 grid;               // of the contraction launch; a windowed 16-bit launch holds the window's tiles only
+    int prep; bool scale_pass;      // LA_PREP_*; with the per-sample fp16 operand scale computed into the workspace header
+    size_t q_off, ws_head;   // byte offset of the pre-split copy in the workspace; bytes taken from its head, in front of the split-K partials
+    int tile0[LA_CONV_MAX_PHASES]; long ws_off[LA_CONV_MAX_PHASES];      // split-K form, per phase: LaConvArgs::Phase::tile0 / ws_off
+};
+// LA_OK and the plan, or the refusal (error code + la_set_error text) of a launch with these arguments
+int la_conv_plan(const LaConvArgs& a, LaConvPlan& p);
+
+// ---- 16-bit split path, three units: la_conv_operand.hip (weight packs, operand scales, pre-split copy), la_conv_flat.hip
+// (la_conv_bf16_kernel) and la_conv_halo.hip (la_conv_bf16_halo_kernel): the launches of the two kernels in the form p (LA_FORM_FLAT* / LA_FORM_HALO)
+int la_conv_flat_launch(const LaConvArgs& as, const LaConvPlan& p, hipStream_t stream);
+int la_conv_halo_launch(const LaConvArgs& as, const LaConvPlan& p, hipStream_t stream);
 
 long la_conv_bf16_pack_elems(int M, int C, int ktaps);   // elements per term
 int la_pack_conv_weights_bf16(const float* w, void* out, int cout, int cin, int ktaps, int transpose, int nterm,
                               hipStream_t stream, float scale = 1.f, int m_pad = 0);
-int la_conv_bf16_dispatch(const LaConvArgs& as, int MTsel, dim3 grid, bool split, hipStream_t stream);
-// bytes of one weight pack serving every split precision
+// bytes of one weight pack serving every split precision: [3 bf16 terms][2 fp16 terms][pad to 16 B][wscale float] (term offsets: la_conv_device.h)
 size_t la_conv_split_pack_bytes(int M, int C, int ktaps);
+static inline size_t la_conv_pack_wscale_offset(long term_elems) { return ((size_t)5 * term_elems * 2 + 15) & ~(size_t)15; }
 // fp32 slabs wf [ktaps][cin][cout], wb [ktaps][cout][wb_ld] and wsq [cin][cout] = sum over taps of w^2 (each optional) of w * scale (la_style.hip)
 int la_pack_conv_weights(const float* w, float* wf, float* wb, float* wsq, int cout, int cin, int ktaps, hipStream_t,
                          float scale = 1.f, int wb_ld = 0);   // wb_ld > cin: backward slab rows padded with zero columns
@@ -254,14 +276,19 @@ static inline void la_conv_weights_select(LaConvArgs& a, const LaConvWeights& L,
 }
 
 // scratch floats that let every <= 32x32 launch of a (B, M) problem use split-K: slices * B * M * G, G <= 1024
-long la_conv_splitk_floats(int B, int M, int C, int Gy, int Gx, int precision);
 long la_conv_splitk_floats_phases(int B, int M, int C, int nphase, const int* Gy, const int* Gx, int precision);
+static inline long la_conv_splitk_floats(int B, int M, int C, int Gy, int Gx, int precision) { return la_conv_splitk_floats_phases(B, M, C, 1, &Gy, &Gx, precision); }
 // bytes of the pre-split copy of an input [B][C][Hin][Win] (split paths; sized for the larger, 8 B/element format)
 size_t la_conv_presplit_bytes(int B, int C, int Hin, int Win);
-// If a.precision needs a pre-split input and a.in_q is not set: split a.in (* a.in_scale) into the head of a.ws, point
-// a.in_q / a.acc_scale_x at it and advance a.ws / a.ws_bytes past it.  Callers that launch several phases over one input
-// call this once.  bf16: {hi | mid << 16, lo} (8 B / element);  fp16: per-sample power-of-two scale, {hi | lo << 16} (4 B).
-int la_conv_prepare_input(LaConvArgs& a, hipStream_t stream);
+size_t la_conv_presplit_hdr_bytes(int B, int C);      // ... and of its header alone (fp16 operand scales and their segment maxima)
+// Operand preparation as the plan says (p.prep): split a.in (* a.in_scale) into the head of a.ws and / or compute the fp16 operand scale there,
+// point a.in_q / a.acc_scale_x at them and advance a.ws / a.ws_bytes past p.ws_head.  bf16: {hi | mid << 16, lo} (8 B / element);  fp16:
+// per-sample power-of-two scale, {hi | lo << 16} (4 B).  Without a plan: that of a launch of `a` as it stands -- callers that launch several
+// phases over one input call this once, up front; the launch that then arrives with in_q set plans no preparation.
+int la_conv_prepare_input(LaConvArgs& a, const LaConvPlan& p, hipStream_t stream);
+static inline int la_conv_prepare_input(LaConvArgs& a, hipStream_t stream) {
+    LaConvPlan p; const int rc = la_conv_plan(a, p); return rc ? rc : la_conv_prepare_input(a, p, stream);
+}
 // Activation backward fused with the plane maxima of its result (pass 1 of the fp16 operand scale of the consuming contraction):
 // dx [B][C][HW] = dy * act'(yref) (dx may alias dy), pm [B][C][la_conv_act_grad_segments(HW)] -> LaConvArgs::in_pmax / in_pmax_nseg.
 // Replaces la_bias_act_grad_f32 (bias_act.py:170, grad = 1) where the result feeds a contraction.
@@ -271,7 +298,6 @@ int la_conv_act_grad_pmax(const float* dy, const float* yref, float* dx, float* 
 int la_conv_xscale_from_pmax(const float* pmax, int nseg, const float* scale, int scale_stride, float mult, float* xscale, int B, int C,
                              hipStream_t stream);
 int la_absmax_bits(const float* w, long n, unsigned* amax_bits, hipStream_t stream);      // max |w| as a float bit pattern (zero it first)
-bool la_conv_bf16_uses_halo(const LaConvArgs& a);     // fp32-input halo kernel (no pre-split copy needed)
 
 // number of pixel tiles per sample for a launch (the ds_part leading dimension)
 int la_conv_tiles_per_sample(int Gy, int Gx);
@@ -283,20 +309,18 @@ int la_conv_launch(const LaConvArgs& a, hipStream_t stream);
 // and the four phases run in ONE launch -- above the split-K sizes each phase launch would end in a nearly empty round, at the
 // split-K sizes (<= 34x34 phase grids) four launches + four finish passes become one of each; fp32: a launch per phase.
 static inline int la_conv_up2_launch(LaConvArgs& a, int hin, int pitch, int xhalf, hipStream_t stream) {
-    const int res = 2 * hin;
-    a.Hin = a.Win = hin; a.Hout = a.Wout = res + 1;
-    a.out_sy = a.out_sx = 2; a.epi = LA_EPI_RAW;
-    if (pitch > 0) { a.out_pitch = pitch; a.out_plane = (long)pitch * (res + 1); }      // padded (2h+1)-wide rows
-    if (xhalf > 0) { a.out_sx = 1; a.Wout = pitch; }      // phase px writes the contiguous run from px * xhalf
-    const bool merged = a.precision != LA_PREC_F32;
+    la_conv_geom_up2(a, hin, pitch, xhalf);
+    const int ox_step = xhalf > 0 ? xhalf : 1;
     int rc;
-    if (merged && (rc = la_conv_prepare_input(a, stream))) return rc;
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            la_conv_up2_phase(a, hin, py, px, xhalf > 0 ? xhalf : 1, merged);
-            if (!merged && (rc = la_conv_launch(a, stream))) return rc;
-        }
-    if (!merged) return LA_OK;
-    a.out_oy = a.out_ox = 0; a.Gy = a.Gx = hin + 1; a.ntaps = 4;      // launch-wide fields = the largest phase (checks only)
-    return la_conv_launch(a, stream);
+    if (a.precision != LA_PREC_F32) {
+        la_conv_up2_phase(a, hin, 0, 0, ox_step, false);      // (the preparation is planned on the largest phase)
+        if ((rc = la_conv_prepare_input(a, stream))) return rc;
+        la_conv_up2_merged(a, hin, ox_step);
+        return la_conv_launch(a, stream);
+    }
+    for (int k = 0; k < 4; ++k) {
+        la_conv_up2_phase(a, hin, k >> 1, k & 1, ox_step, false);
+        if ((rc = la_conv_launch(a, stream))) return rc;
+    }
+    return LA_OK;
 }

@@ -16,6 +16,10 @@
 int la_conv_tiles_per_sample(int Gy, int Gx) { return la_cdiv((long)Gy * Gx, NT); }
 
 #define SPLITK_MAX_G 1156     // up to 34x34 grids (covers the 33x33 phases of the 32 -> 64 up-sampling layer)
+// K chunks and row tile of a launch, for la_conv_plan and the workspace sizes alike; 32-row tiles only exist for the halo kernel (the
+// 32-channel layers of the 1024^2 generators)
+static inline int conv_nck(int C, bool bf) { return la_cdiv(C, bf ? KCB : KC); }
+static inline int conv_mt(int M, bool halo) { return M >= 128 ? 128 : (M <= 32 && halo ? 32 : 64); }
 // K slices of a split-K launch over `tiles` (flattened-pixel tiles x row tiles) workgroups, each walking nck chunks x `taps`
 // (chunk, tap) steps.  The 16-bit kernels keep 2 workgroups per CU = 512 resident slots.  Cost model in microseconds, fitted to
 // the kernel trace of the config-f generator (profiles/): a step costs ~1.7 us of a resident slot, a workgroup ~10 us of
@@ -51,9 +55,9 @@ static int choose_ksplit(bool bf, long tiles, int nck, float taps, double out_by
 // would not be split
 long la_conv_splitk_floats_phases(int B, int M, int C, int nphase, const int* Gy, const int* Gx, int precision) {
     const bool bf = precision != LA_PREC_F32;
-    const int nck = la_cdiv(C, bf ? 32 : KC);
+    const int nck = conv_nck(C, bf);
     if (nck < 2 || nphase < 1 || (nphase > 1 && !bf)) return 0;
-    const int mtiles = la_cdiv(M, M >= 128 ? 128 : 64);
+    const int mtiles = la_cdiv(M, conv_mt(M, false));      // (a launch that splits is no halo launch)
     long tiles = 0, Gsum = 0;
     for (int p = 0; p < nphase; ++p) {
         const long G = (long)Gy[p] * Gx[p];
@@ -67,9 +71,6 @@ long la_conv_splitk_floats_phases(int B, int M, int C, int nphase, const int* Gy
     const int ks1 = choose_ksplit(bf, tiles * mtiles, nck, 1.f, 4.0 * B * M * (double)Gsum);
     if (ks1 > ks) ks = ks1;
     return ks >= 2 ? (long)ks * B * M * Gsum : 0;
-}
-long la_conv_splitk_floats(int B, int M, int C, int Gy, int Gx, int precision) {
-    return la_conv_splitk_floats_phases(B, M, C, 1, &Gy, &Gx, precision);
 }
 
 // SPLIT = false: one workgroup owns a (sample, 128-pixel tile, MT-channel tile) and runs the whole K loop, epilogue fused.
@@ -387,149 +388,196 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
     }
 }
 
+// can this launch use the halo kernel?  dense stride-1 3x3 taps within +-1, grid = whole 4x32 tiles, above the split-K sizes
+static bool la_conv_bf16_uses_halo(const LaConvArgs& a) {
+    if (a.precision == LA_PREC_F32 || a.in_q) return false;
+    if (a.in_mask_y || (a.in_gain != 0.f && a.in_gain != 1.f)) return false;      // (an input mask is applied by the pre-split copy)
+    if (a.in_sy != 1 || a.in_sx != 1 || a.out_sy != 1 || a.out_sx != 1 || a.out_oy != 0 || a.out_ox != 0) return false;
+    if ((a.Gx & 31) != 0 || (a.Gy & 3) != 0 || a.Gy != a.Hout || a.Gx != a.Wout || a.ntaps != 9) return false;
+    // Grids up to 34x34 stay on the split-K path (SPLITK_MAX_G).  Round 3 measured the 32x32 layers (512 -> 512, K = 4608) on
+    // this kernel: 114 us against 135 us for slices + finish pass + pre-split copy in isolation, no difference inside a batch -- and
+    // the first-step gradient of the 1024^2 loop 12x further from float64 (rms 4.4e-6 against 3.7e-7 of max |g| 0.4; the reference's
+    // float32: 1.5e-6): K slices summed afterwards are a blocked summation, one accumulator walking all 4608 terms is not.  Dev knob
+    // LA_KNOB_HALO_MING: grids of at least that many points run here.
+    if ((long)a.Gy * a.Gx < (la_dev_knob(LA_KNOB_HALO_MING) ? la_dev_knob(LA_KNOB_HALO_MING) : SPLITK_MAX_G + 1)) return false;
+    if ((long)a.C * a.Hin * a.Win >= (1l << 28) || a.C > 4096) return false;   // 32-bit byte offsets inside one sample, below the
+                                                                             // out-of-range sentinel of the pixel-stationary loader
+    for (int t = 0; t < a.ntaps; ++t)
+        if (a.tap_dy[t] < -1 || a.tap_dy[t] > 1 || a.tap_dx[t] < -1 || a.tap_dx[t] > 1) return false;
+    return true;
+}
 
-int la_conv_launch(const LaConvArgs& a, hipStream_t stream) {
+// The one place that decides which kernel a launch runs, in which form and on what grid (LaConvPlan, la_conv.h); the dev-build knobs
+// that bend the decision are read here (and in the predicate above) only.
+int la_conv_plan(const LaConvArgs& a, LaConvPlan& p) {
     LA_CHECK_ARG(a.in && a.wgt && a.out, "conv: null pointer");
     LA_CHECK_ARG(a.B > 0 && a.C > 0 && a.M > 0 && a.Gy > 0 && a.Gx > 0, "conv: empty shape");
     LA_CHECK_ARG(a.M % 4 == 0, "conv: M must be a multiple of 4");
     LA_CHECK_ARG(a.ntaps >= 1 && a.ntaps <= LA_CONV_MAX_TAPS, "conv: bad tap count");
     LA_CHECK_ARG(a.in_sy >= 1 && a.in_sx >= 1 && a.out_sy >= 1 && a.out_sx >= 1, "conv: bad strides");
     // last grid point must land inside the output
-    LA_CHECK_ARG((a.Gy - 1) * a.out_sy + a.out_oy < a.Hout && (a.Gx - 1) * a.out_sx + a.out_ox < a.Wout &&
-                     a.out_oy >= 0 && a.out_ox >= 0,
+    LA_CHECK_ARG((a.Gy - 1) * a.out_sy + a.out_oy < a.Hout && (a.Gx - 1) * a.out_sx + a.out_ox < a.Wout && a.out_oy >= 0 && a.out_ox >= 0,
                  "conv: output grid exceeds output tensor");
     LA_CHECK_ARG((long)a.Hout * a.Wout < (1L << 31) && (long)a.Hin * a.Win < (1L << 31), "conv: plane too large");
     if (a.epi == LA_EPI_BWD && a.ds_part) {
         LA_CHECK_ARG(a.tiles_per_sample == la_conv_tiles_per_sample(a.Gy, a.Gx), "conv: tiles_per_sample mismatch");
         LA_CHECK_ARG(a.out_sy == 1 && a.out_sx == 1 && a.out_oy == 0 && a.out_ox == 0, "conv: bwd epilogue needs dense output");
     }
-    int tiles = la_conv_tiles_per_sample(a.Gy, a.Gx);
-    const int nphase = a.nphase;
+    const int nphase = a.nphase, np = nphase > 0 ? nphase : 1;
     LA_CHECK_ARG(nphase >= 0 && nphase <= LA_CONV_MAX_PHASES, "conv: bad phase count");
-    if (nphase > 0) {
-        LA_CHECK_ARG(a.precision != LA_PREC_F32 && a.epi == LA_EPI_RAW && a.in_q, "conv: merged phases need a pre-split 16-bit launch without epilogue");
-        tiles = 0;
-        for (int p = 0; p < nphase; ++p) {
-            const LaConvArgs::Phase& P = a.ph[p];
-            LA_CHECK_ARG(P.Gy > 0 && P.Gx > 0 && P.ntaps >= 1 && P.ntaps <= LA_CONV_PHASE_TAPS, "conv: bad phase");
-            LA_CHECK_ARG((P.Gy - 1) * a.out_sy + P.out_oy < a.Hout && (P.Gx - 1) * a.out_sx + P.out_ox < a.Wout && P.out_oy >= 0 && P.out_ox >= 0,
-                         "conv: phase grid exceeds output tensor");
-            const int t = la_conv_tiles_per_sample(P.Gy, P.Gx);
-            if (t > tiles) tiles = t;
-        }
+    if (nphase > 0) LA_CHECK_ARG(a.precision != LA_PREC_F32 && a.epi == LA_EPI_RAW && a.in_q, "conv: merged phases need a pre-split 16-bit launch without epilogue");
+    for (int q = 0; q < nphase; ++q) {
+        const LaConvArgs::Phase& P = a.ph[q];
+        LA_CHECK_ARG(P.Gy > 0 && P.Gx > 0 && P.ntaps >= 1 && P.ntaps <= LA_CONV_PHASE_TAPS, "conv: bad phase");
+        LA_CHECK_ARG((P.Gy - 1) * a.out_sy + P.out_oy < a.Hout && (P.Gx - 1) * a.out_sx + P.out_ox < a.Wout && P.out_oy >= 0 && P.out_ox >= 0,
+                     "conv: phase grid exceeds output tensor");
     }
-    // split-K for the small-resolution layers (see kernel comment)
-    LaConvArgs as = a;
-    as.ksplit = 1;
-    const long G = (long)a.Gy * a.Gx;
     const bool bf = a.precision != LA_PREC_F32;
     LA_CHECK_ARG(!bf || (a.wgt_bf16 && a.wgt_bf16_term_elems > 0), "conv: split-bf16 precision needs packed bf16 weights");
-    const int nck = la_cdiv(a.C, bf ? 32 : KC);
-    // 32-row tiles only exist for the halo kernel (the 32-channel layers of the 1024^2 generators)
-    int MTsel = a.M >= 128 ? 128 : ((a.M <= 32 && bf && !a.in_q && la_conv_bf16_uses_halo(a)) ? 32 : 64);
-    {   // dev knob (kernel experiments only): LA_FORCE_MT=64 runs the >= 128-row layers on 64-row tiles
-        static const int force_mt = []() { const char* e = la_dev_env("LA_FORCE_MT"); return e ? atoi(e) : 0; }();
-        if (force_mt == 64 && MTsel == 128) MTsel = 64;
-    }
-    const int mtiles = la_cdiv(a.M, MTsel);
-    // scratch: pre-split input first (split precisions only), split-K partials after it
-    if (bf) { int rc = la_conv_prepare_input(as, stream); if (rc) return rc; }
-    // launch profiler: algorithmic work of this launch = 2*MACs; bytes = input read once + output written once (+ weights once)
-    int pslot = -1, pcls = LA_PC_CONV_F32;
-    double pflops = 0, pbytes = 0;
-    if (la_prof_enabled()) {
-        double gt = (double)a.Gy * a.Gx * a.ntaps, gout = (double)a.Gy * a.Gx, ntw = a.ntaps;
-        if (nphase > 0) {
-            gt = gout = ntw = 0.0;
-            for (int p = 0; p < nphase; ++p) { gt += (double)a.ph[p].Gy * a.ph[p].Gx * a.ph[p].ntaps; gout += (double)a.ph[p].Gy * a.ph[p].Gx; ntw += a.ph[p].ntaps; }
+    const bool halo = la_conv_bf16_uses_halo(a);      // (never a merged launch: those arrive pre-split)
+    p = LaConvPlan{}; p.ksplit = 1;
+    // dev knob (kernel experiments only): LA_FORCE_MT=64 runs the >= 128-row layers on 64-row tiles
+    static const int force_mt = []() { const char* e = la_dev_env("LA_FORCE_MT"); return e ? atoi(e) : 0; }();
+    p.mt = (force_mt == 64 && a.M >= 128) ? 64 : conv_mt(a.M, halo);
+    p.mtiles = la_cdiv(a.M, p.mt);
+    // Operand preparation, from the head of the workspace.  Halo launches read the fp32 input directly (modulation, scaling and the split
+    // happen on the way into LDS) and only need the fp16 scale; every other 16-bit launch gets a pre-split copy, [header | copy].
+    if (bf && !a.in_q) {
+        const size_t hb = la_conv_presplit_hdr_bytes(a.B, a.C), qb = la_conv_presplit_bytes(a.B, a.C, a.Hin, a.Win);
+        p.scale_pass = a.precision == LA_PREC_F16X2 && !a.acc_scale_x;      // (a preset scale: e.g. from the clamp bound of the producer)
+        p.prep = !halo ? LA_PREP_PRESPLIT : (p.scale_pass ? LA_PREP_SCALE : LA_PREP_NONE);
+        if (p.prep != LA_PREP_NONE) {
+            LA_CHECK_ARG(a.ws && a.ws_bytes >= (halo ? hb : qb), "conv: split precisions need a workspace (la_modconv_workspace_bytes)");
+            LA_CHECK_ARG(((size_t)a.ws & 15) == 0, "conv: workspace must be 16-byte aligned");
+            LA_CHECK_ARG(a.B <= 64, "conv: split precisions support at most 64 samples per launch");
         }
-        if (a.row_hi > 0 && a.Gy > 0) {      // row window: only the wanted rows are work (tiles hold 4 rows / 128 flattened pixels: counted as wanted)
-            int lo = a.row_lo > 0 ? a.row_lo : 0, hi = a.row_hi < a.Gy ? a.row_hi : a.Gy;
-            lo &= ~3; hi = (hi + 3) & ~3; if (hi > a.Gy) hi = a.Gy;
-            double f = hi > lo ? (double)(hi - lo) / a.Gy : 0.0;
-            if (a.col_hi > 0 && a.Gx > 0 && la_conv_bf16_uses_halo(a)) f *= (double)((((a.col_hi < a.Gx ? a.col_hi : a.Gx) + 31) & ~31) - (a.col_lo & ~31)) / a.Gx;
-            gt *= f; gout *= f;
-        }
-        pflops = 2.0 * a.B * gt * a.M * (double)a.C;
-        pbytes = 4.0 * ((double)a.B * a.C * a.Hin * a.Win * (a.in_bstride ? 1.0 : 1.0 / a.B) + (double)a.B * a.M * gout + ntw * a.C * a.M);
+        if (p.prep == LA_PREP_PRESPLIT) {
+            LA_CHECK_ARG(qb < 0x7ff00000u, "conv: pre-split operand too large for 32-bit buffer offsets");
+            LA_CHECK_ARG((!a.in_mask_y && (a.in_gain == 0.f || a.in_gain == 1.f)) || !p.scale_pass, "conv: an input mask needs a preset operand scale");
+            p.q_off = (a.precision == LA_PREC_F16X2 && !p.scale_pass) ? 0 : hb;
+            const size_t off = (qb + 255) & ~(size_t)255; p.ws_head = a.ws_bytes > off ? off : a.ws_bytes;
+        } else if (p.prep == LA_PREP_SCALE) p.ws_head = hb;
     }
-    if (as.seam.xs_out) as.seam.pmax = nullptr;      // every kernel form lowers the consumer's slot row itself: no plane maxima
-    as.splitk_ws = nullptr;
-    long splitk_floats = 0;
-    if (as.ws && as.ws_bytes >= sizeof(float)) {
-        as.splitk_ws = reinterpret_cast<float*>(as.ws);
-        splitk_floats = (long)(as.ws_bytes / sizeof(float));
+    // Split-K for the small-resolution layers (see kernel comment), where the rest of the workspace holds the slice partials.  Merged
+    // phases: blockIdx.x walks the phases' flattened-pixel tiles back to back.  (The halo kernel claims what it can run directly.)
+    const long splitk_floats = a.ws ? (long)((a.ws_bytes - p.ws_head) / sizeof(float)) : 0;
+    const int nck = conv_nck(a.C, bf);
+    auto grid_of = [&](int q, int& Gy, int& Gx) { Gy = nphase > 0 ? a.ph[q].Gy : a.Gy; Gx = nphase > 0 ? a.ph[q].Gx : a.Gx; return nphase > 0 ? a.ph[q].ntaps : a.ntaps; };
+    bool small = !halo;
+    long Gsum = 0, tiles_flat = 0; int tiles = 0, Gy, Gx;
+    for (int q = 0; q < np; ++q) {
+        grid_of(q, Gy, Gx);
+        const long Gq = (long)Gy * Gx;
+        small = small && Gq <= SPLITK_MAX_G; Gsum += Gq;
+        p.tile0[q] = (int)tiles_flat; tiles_flat += la_cdiv((long)a.B * Gq, NT);
+        if (la_conv_tiles_per_sample(Gy, Gx) > tiles) tiles = la_conv_tiles_per_sample(Gy, Gx);
     }
-    bool small = G <= SPLITK_MAX_G && !(bf && la_conv_bf16_uses_halo(as));      // (the halo kernel claims what it can run directly)
-    long Gsum = G, Gmax = G, tiles_flat = la_cdiv((long)a.B * G, NT);
-    if (nphase > 0) {
-        Gsum = 0; Gmax = 0; tiles_flat = 0;
-        for (int p = 0; p < nphase; ++p) {
-            const long Gp = (long)a.ph[p].Gy * a.ph[p].Gx;
-            small = small && Gp <= SPLITK_MAX_G;
-            Gsum += Gp; if (Gp > Gmax) Gmax = Gp;
-            as.ph[p].tile0 = (int)tiles_flat;
-            tiles_flat += la_cdiv((long)a.B * Gp, NT);
-        }
-        small = small && bf;       // (merged phases exist for the 16-bit kernels only)
-    }
-    if (as.splitk_ws && small && nck >= 2) {
-        const int ntiles_flat = (int)tiles_flat;
-        float taps = (float)a.ntaps;
-        if (nphase > 0) { taps = 0.f; for (int p = 0; p < nphase; ++p) taps += (float)a.ph[p].ntaps * ((float)a.ph[p].Gy * a.ph[p].Gx / (float)Gsum); }
-        int ks = choose_ksplit(bf, (long)ntiles_flat * mtiles, nck, taps, 4.0 * a.B * a.M * (double)Gsum);
+    if (splitk_floats >= 1 && small && nck >= 2) {
+        float taps = 0.f;      // per step of the K loop, weighted by the phases' share of the pixels
+        for (int q = 0; q < np; ++q) { const int nt = grid_of(q, Gy, Gx); taps += (float)nt * ((float)Gy * Gx / (float)Gsum); }
+        int ks = choose_ksplit(bf, tiles_flat * p.mtiles, nck, taps, 4.0 * a.B * a.M * (double)Gsum);
         if (la_dev_knob(LA_KNOB_KSPLIT) > 0 && la_dev_knob(LA_KNOB_KSPLIT) <= nck) { const int per = la_cdiv(nck, la_dev_knob(LA_KNOB_KSPLIT)); ks = la_cdiv(nck, per); }
-        {
-            if ((long)ks * a.B * a.M * Gsum <= splitk_floats && ks >= 2) {
-                as.ksplit = ks;
-                long off = 0;
-                for (int p = 0; p < nphase; ++p) { as.ph[p].ws_off = off; off += (long)ks * a.B * a.M * a.ph[p].Gy * a.ph[p].Gx; }
-                dim3 grid(ntiles_flat, mtiles, ks);
-                pslot = la_prof_open(bf ? LA_PC_CONV_SPLITK : LA_PC_CONV_F32, pflops, pbytes, stream);
-                if (bf) { int rc = la_conv_bf16_dispatch(as, MTsel, grid, true, stream); if (rc) return rc; }
-                else if (MTsel == 128) hipLaunchKernelGGL((la_conv_igemm_kernel<128, true>), grid, dim3(256), 0, stream, as);
-                else hipLaunchKernelGGL((la_conv_igemm_kernel<64, true>), grid, dim3(256), 0, stream, as);
-                const unsigned nz = nphase > 0 ? nphase : 1;
-                // one wave per (b, m) plane, four planes per workgroup, at every split-K size (<= 34x34): a whole workgroup per plane
-                // (the <1> form) measured 21 against 13 us on the 8 x 512 x 32^2 launches
-                hipLaunchKernelGGL(la_conv_splitk_finish_kernel<4>, dim3(la_cdiv(a.M, 4), a.B, nz), dim3(256), 0, stream, as);
-                // (the consumer's operand scale, LaConvArgs::seam.xs_out: the finish workgroups lower the sample's slot row themselves)
-            }
-        }
+        if (ks >= 2 && (long)ks * a.B * a.M * Gsum <= splitk_floats) p.ksplit = ks;
     }
-    if (as.ksplit == 1) {
+    if (p.ksplit > 1) {
+        long off = 0;
+        for (int q = 0; q < np; ++q) { grid_of(q, Gy, Gx); p.ws_off[q] = off; off += (long)p.ksplit * a.B * a.M * Gy * Gx; }
+        p.form = bf ? LA_FORM_FLAT_SPLIT : LA_FORM_F32_SPLIT; p.cls = bf ? LA_PC_CONV_SPLITK : LA_PC_CONV_F32;
+        p.grid = dim3((unsigned)tiles_flat, p.mtiles, p.ksplit);
+    } else {
         // a windowed 16-bit launch holds the window's tiles only (rounded up to a multiple of 8: one run of tiles per XCD); the kernels
         // derive the same counts from row_lo / row_hi / col_lo / col_hi
         if (bf && a.row_hi > 0) {
             int nt = 0;
-            if (la_conv_bf16_uses_halo(as)) {
-                const int tpr = a.Gx >> 5, r0 = a.row_lo >> 2, r1 = ((a.row_hi < a.Gy ? a.row_hi : a.Gy) + 3) >> 2;
-                int cw = tpr;
-                if (a.col_hi > 0) cw = (((a.col_hi < a.Gx ? a.col_hi : a.Gx) + 31) >> 5) - (a.col_lo >> 5);
+            if (halo) {
+                const int r0 = a.row_lo >> 2, r1 = ((a.row_hi < a.Gy ? a.row_hi : a.Gy) + 3) >> 2;
+                const int cw = a.col_hi > 0 ? (((a.col_hi < a.Gx ? a.col_hi : a.Gx) + 31) >> 5) - (a.col_lo >> 5) : a.Gx >> 5;
                 nt = (r1 - r0) * cw;
             } else {
-                for (int p = 0; p < (nphase > 0 ? nphase : 1); ++p) {
-                    const int Gy = nphase > 0 ? a.ph[p].Gy : a.Gy, Gx = nphase > 0 ? a.ph[p].Gx : a.Gx;
-                    const int tall = la_cdiv(Gy * Gx, NT), t0 = (a.row_lo * Gx) / NT;
-                    int t1 = la_cdiv((a.row_hi < Gy ? a.row_hi : Gy) * Gx, NT);
-                    if (t1 > tall) t1 = tall;
+                for (int q = 0; q < np; ++q) {
+                    grid_of(q, Gy, Gx);
+                    const int t0 = (a.row_lo * Gx) / NT, t1 = la_cdiv((a.row_hi < Gy ? a.row_hi : Gy) * Gx, NT);
                     if (t1 - t0 > nt) nt = t1 - t0;
                 }
             }
-            const int n8 = (nt + 7) & ~7;
-            if (nt > 0 && n8 < tiles) tiles = n8;
+            if (nt > 0 && ((nt + 7) & ~7) < tiles) tiles = (nt + 7) & ~7;
         }
-#ifdef LA_DEV
-        as.dbg_stamp = la_dev_knob(LA_KNOB_HALO_STAMP);
-#endif
-        dim3 grid(tiles, mtiles, a.B * (nphase > 0 ? nphase : 1));
-        if (bf) pcls = la_conv_bf16_uses_halo(as) ? LA_PC_CONV_HALO : LA_PC_CONV_FLAT;
-        pslot = la_prof_open(pcls, pflops, pbytes, stream);
-        if (bf) { int rc = la_conv_bf16_dispatch(as, MTsel, grid, false, stream); if (rc) return rc; }
-        else if (MTsel == 128) hipLaunchKernelGGL((la_conv_igemm_kernel<128, false>), grid, dim3(256), 0, stream, as);
-        else hipLaunchKernelGGL((la_conv_igemm_kernel<64, false>), grid, dim3(256), 0, stream, as);
+        p.form = !bf ? LA_FORM_F32 : (halo ? LA_FORM_HALO : LA_FORM_FLAT); p.cls = !bf ? LA_PC_CONV_F32 : (halo ? LA_PC_CONV_HALO : LA_PC_CONV_FLAT);
+        p.grid = dim3(tiles, p.mtiles, a.B * np);
     }
+    // the MFMA form of that kernel: fp16 x2 has three-wave 16x16x32 forms on 128-row tiles (la_conv_flat.hip; la_conv_halo.hip: with more
+    // than one chunk), every other 16-bit launch runs 32x32 MFMAs
+    p.mfma = !bf ? LA_CONV_MFMA_F32_32X32X2 : (a.precision == LA_PREC_F16X2 && p.mt == 128 && (!halo || a.C > KCB) ? LA_CONV_MFMA_16X16X32 : LA_CONV_MFMA_32X32);
+    return LA_OK;
+}
+
+// launch profiler: algorithmic work of a launch = 2*MACs; bytes = input read once + output written once (+ weights once)
+static void conv_prof_work(const LaConvArgs& a, const LaConvPlan& p, double& flops, double& bytes) {
+    double gt = (double)a.Gy * a.Gx * a.ntaps, gout = (double)a.Gy * a.Gx, ntw = a.ntaps;
+    if (a.nphase > 0) gt = gout = ntw = 0.0;
+    for (int q = 0; q < a.nphase; ++q) { gt += (double)a.ph[q].Gy * a.ph[q].Gx * a.ph[q].ntaps; gout += (double)a.ph[q].Gy * a.ph[q].Gx; ntw += a.ph[q].ntaps; }
+    if (a.row_hi > 0 && a.Gy > 0) {      // row window: only the wanted rows are work (tiles hold 4 rows / 128 flattened pixels: counted as wanted)
+        int lo = a.row_lo > 0 ? a.row_lo : 0, hi = a.row_hi < a.Gy ? a.row_hi : a.Gy;
+        lo &= ~3; hi = (hi + 3) & ~3; if (hi > a.Gy) hi = a.Gy;
+        double f = hi > lo ? (double)(hi - lo) / a.Gy : 0.0;
+        if (a.col_hi > 0 && a.Gx > 0 && p.form == LA_FORM_HALO) f *= (double)((((a.col_hi < a.Gx ? a.col_hi : a.Gx) + 31) & ~31) - (a.col_lo & ~31)) / a.Gx;
+        gt *= f; gout *= f;
+    }
+    flops = 2.0 * a.B * gt * a.M * (double)a.C;
+    bytes = 4.0 * ((double)a.B * a.C * a.Hin * a.Win * (a.in_bstride ? 1.0 : 1.0 / a.B) + (double)a.B * a.M * gout + ntw * a.C * a.M);
+}
+
+// plan, operand preparation as planned, the kernel-parameter fields the plan determines, one launch by the plan's form (+ the finish pass)
+int la_conv_launch(const LaConvArgs& a, hipStream_t stream) {
+    LaConvPlan p;
+    int rc = la_conv_plan(a, p); if (rc) return rc;
+    LaConvArgs as = a;
+    if ((rc = la_conv_prepare_input(as, p, stream))) return rc;      // scratch: operand first, split-K partials after it
+    as.ksplit = p.ksplit;
+    as.splitk_ws = (as.ws && as.ws_bytes >= sizeof(float)) ? reinterpret_cast<float*>(as.ws) : nullptr;
+    for (int q = 0; q < a.nphase; ++q) { as.ph[q].tile0 = p.tile0[q]; as.ph[q].ws_off = p.ws_off[q]; }
+    if (a.precision == LA_PREC_F16X2)      // the fp16 weight scale lives behind the terms of the pack
+        as.acc_scale_w = reinterpret_cast<const float*>(static_cast<const char*>(a.wgt_bf16) + la_conv_pack_wscale_offset(a.wgt_bf16_term_elems));
+    if (as.seam.xs_out) as.seam.pmax = nullptr;      // every kernel form lowers the consumer's slot row itself: no plane maxima
+#ifdef LA_DEV
+    if (p.ksplit == 1) as.dbg_stamp = la_dev_knob(LA_KNOB_HALO_STAMP);
+#endif
+    double pflops = 0, pbytes = 0; if (la_prof_enabled()) conv_prof_work(a, p, pflops, pbytes);
+    const int pslot = la_prof_open(p.cls, pflops, pbytes, stream);
+    if (p.ksplit > 1) {
+        if (p.form == LA_FORM_FLAT_SPLIT) rc = la_conv_flat_launch(as, p, stream);
+        else if (p.mt == 128) hipLaunchKernelGGL((la_conv_igemm_kernel<128, true>), p.grid, dim3(256), 0, stream, as);
+        else hipLaunchKernelGGL((la_conv_igemm_kernel<64, true>), p.grid, dim3(256), 0, stream, as);
+        // the finish pass (it also lowers the consumer's operand scale, LaConvArgs::seam.xs_out): one wave per (b, m) plane, four planes per workgroup,
+        // at every split-K size (<= 34x34): a whole workgroup per plane (the <1> form) measured 21 against 13 us on the 8 x 512 x 32^2 launches
+        if (!rc) hipLaunchKernelGGL(la_conv_splitk_finish_kernel<4>, dim3(la_cdiv(a.M, 4), a.B, a.nphase > 0 ? a.nphase : 1), dim3(256), 0, stream, as);
+    } else if (p.form == LA_FORM_HALO) rc = la_conv_halo_launch(as, p, stream);
+    else if (p.form == LA_FORM_FLAT) rc = la_conv_flat_launch(as, p, stream);
+    else if (p.mt == 128) hipLaunchKernelGGL((la_conv_igemm_kernel<128, false>), p.grid, dim3(256), 0, stream, as);
+    else hipLaunchKernelGGL((la_conv_igemm_kernel<64, false>), p.grid, dim3(256), 0, stream, as);
+    if (rc) return rc;
     LA_CHECK_LAUNCH();
     la_prof_close(pslot, stream);
+    return LA_OK;
+}
+
+// Host-only query of the plan (include/latentaug_hip.h): an LaConvArgs of that geometry from the builders of la_conv.h, through la_conv_plan
+extern "C" int la_conv_plan_query(int precision, int B, int C, int M, int geom, int res, int have_in_q, size_t ws_bytes, long* info) {
+    LA_CHECK_ARG(info && precision >= LA_PREC_F32 && precision <= LA_PREC_F16X2 && geom >= 0 && geom <= LA_CONV_GEOM_UP2_MERGED && res >= 1 &&
+                     (geom < LA_CONV_GEOM_DOWN2 || res % 2 == 0), "conv_plan_query: bad arguments (the stride-2 geometries need an even resolution)");
+    alignas(16) static float never_read[4]; LaConvArgs a; la_conv_args_init(a);
+    a.in = a.wgt = never_read; a.out = never_read; a.wgt_bf16 = never_read; a.wgt_bf16_term_elems = la_conv_bf16_pack_elems(M, C, 9);
+    a.precision = precision; a.B = B; a.C = C; a.M = M;
+    a.ws = ws_bytes ? never_read : nullptr; a.ws_bytes = ws_bytes; a.in_q = have_in_q ? never_read : nullptr;
+    if (geom >= LA_CONV_GEOM_UP2_PHASE) la_conv_geom_up2(a, res / 2, 0, 0);
+    if (geom <= LA_CONV_GEOM_SAME_BWD) la_conv_geom_same(a, res, 3, geom == LA_CONV_GEOM_SAME_BWD);
+    else if (geom == LA_CONV_GEOM_DOWN2) la_conv_geom_down2(a, res);
+    else if (geom == LA_CONV_GEOM_UP2_MERGED) la_conv_up2_merged(a, res / 2, 1);
+    else la_conv_up2_phase(a, res / 2, (geom - LA_CONV_GEOM_UP2_PHASE) >> 1, (geom - LA_CONV_GEOM_UP2_PHASE) & 1, 1, false);
+    LaConvPlan p;
+    const int rc = la_conv_plan(a, p); if (rc) return rc;
+    const long out[LA_CONV_PLAN_NINFO] = {p.cls, p.mt, p.mfma, p.ksplit, precision != LA_PREC_F32 && (have_in_q || p.prep == LA_PREP_PRESPLIT), a.nphase > 0, p.prep != LA_PREP_NONE,
+                                          (long)p.grid.x, (long)p.grid.y, (long)p.grid.z, (long)p.ws_head};
+    memcpy(info, out, sizeof(out));
     return LA_OK;
 }

@@ -481,31 +481,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
 }
 
 template <int FMT>
-static int launch_flat(const LaConvArgs& as, int MTsel, dim3 grid, bool split, hipStream_t stream) {
+static int launch_flat(const LaConvArgs& as, const LaConvPlan& p, hipStream_t stream) {
     constexpr int NTERM = FMT == FMT_BF16X3 ? 3 : 2;
     const size_t lds = (size_t)2 * NTERM * NT * BPITCH;      // two pixel buffers (>= the epilogue's 4 * MT floats)
-    if (MTsel == 128) {
-        if constexpr (FMT == FMT_F16X2) {
-            // the three-wave 16x16x32 forms: split-K slices on two pixel buffers (the accumulator hand-over needs 36 KB of LDS), direct
-            // launches on three
+    const bool split = p.form == LA_FORM_FLAT_SPLIT;
+    if constexpr (FMT == FMT_F16X2) {
+        if (p.mfma == LA_CONV_MFMA_16X16X32) {
+            // the three-wave 16x16x32 forms (128-row tiles): split-K slices on two pixel buffers (the accumulator hand-over needs 36 KB of
+            // LDS), direct launches on three
             const size_t lds_mf = lds > (size_t)4 * 64 * 36 * 4 ? lds : (size_t)4 * 64 * 36 * 4;
-            if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, 3, FLAT_MF_16>), grid, dim3(256), lds_mf, stream, as);
-            else
-                hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, 3, FLAT_MF_16_3BUF>), grid, dim3(256), (size_t)3 * NTERM * NT * BPITCH,
-                                   stream, as);
-        } else {
-            if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, 2>), grid, dim3(256), lds, stream, as);
-            else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, 2>), grid, dim3(256), lds, stream, as);
+            if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, 3, FLAT_MF_16>), p.grid, dim3(256), lds_mf, stream, as);
+            else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, 3, FLAT_MF_16_3BUF>), p.grid, dim3(256), (size_t)3 * NTERM * NT * BPITCH, stream, as);
+            return LA_OK;
         }
-    } else {
-        if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<64, true, FMT, 2>), grid, dim3(256), lds, stream, as);
-        else hipLaunchKernelGGL((la_conv_bf16_kernel<64, false, FMT, 2>), grid, dim3(256), lds, stream, as);
+    } else if (p.mt == 128) {
+        if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<128, true, FMT, 2>), p.grid, dim3(256), lds, stream, as);
+        else hipLaunchKernelGGL((la_conv_bf16_kernel<128, false, FMT, 2>), p.grid, dim3(256), lds, stream, as);
+        return LA_OK;
     }
+    if (split) hipLaunchKernelGGL((la_conv_bf16_kernel<64, true, FMT, 2>), p.grid, dim3(256), lds, stream, as);
+    else hipLaunchKernelGGL((la_conv_bf16_kernel<64, false, FMT, 2>), p.grid, dim3(256), lds, stream, as);
     return LA_OK;
 }
 
-int la_conv_flat_launch(const LaConvArgs& as, int MTsel, dim3 grid, bool split, hipStream_t stream) {
-    if (as.precision == LA_PREC_BF16X3) return launch_flat<FMT_BF16X3>(as, MTsel, grid, split, stream);
-    if (as.precision == LA_PREC_F16X2) return launch_flat<FMT_F16X2>(as, MTsel, grid, split, stream);
-    return launch_flat<FMT_BF16X2>(as, MTsel, grid, split, stream);
+int la_conv_flat_launch(const LaConvArgs& as, const LaConvPlan& p, hipStream_t stream) {
+    if (as.precision == LA_PREC_BF16X3) return launch_flat<FMT_BF16X3>(as, p, stream);
+    if (as.precision == LA_PREC_F16X2) return launch_flat<FMT_F16X2>(as, p, stream);
+    return launch_flat<FMT_BF16X2>(as, p, stream);
 }

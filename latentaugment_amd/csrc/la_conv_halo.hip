@@ -567,30 +567,30 @@ static int launch_halo(const LaConvArgs& as, dim3 grid, size_t lds, hipStream_t 
 }
 
 template <int FMT>
-static int select_halo(const LaConvArgs& as, int MTsel, dim3 grid, hipStream_t stream) {
+static int select_halo(const LaConvArgs& as, const LaConvPlan& p, hipStream_t stream) {
     constexpr int NTERM = FMT == FMT_BF16X3 ? 3 : 2;
     // two halo buffers (>= the epilogue's 4 * MT floats) + the per-channel factor table
     size_t lds = (size_t)(as.C > KCB ? 2 : 1) * NTERM * HALO_PX * HPITCH + (size_t)la_cdiv(as.C, KCB) * KCB * sizeof(float);
-    const size_t epi = (size_t)160 * MTsel + (size_t)2048 * (MTsel / 32);      // what the epilogue addresses (row tables + fused-ToRGB partials)
+    const size_t epi = (size_t)160 * p.mt + (size_t)2048 * (p.mt / 32);      // what the epilogue addresses (row tables + fused-ToRGB partials)
     if (lds < epi) lds = epi;
     if constexpr (FMT == FMT_F16X2) {
         // the pixel-stationary loader; on 128-row tiles with more than one chunk its 16x16x32 form.  Dev knob LA_KNOB_HALO_LDSPAD:
         // extra KB of dynamic LDS per workgroup of that form -- fewer workgroups per CU, for scripts/halo_wave_timeline.py
-        if (MTsel == 128 && as.C > KCB)
-            return launch_halo<128, FMT, 3, HALO_MF_F16_16>(as, grid, lds + (size_t)la_dev_knob(LA_KNOB_HALO_LDSPAD) * 1024, stream);
-        if (MTsel == 128) return launch_halo<128, FMT, 3, HALO_MF_F16_32>(as, grid, lds, stream);
-        if (MTsel == 64) return launch_halo<64, FMT, 2, HALO_MF_F16_32>(as, grid, lds, stream);
-        return launch_halo<32, FMT, 2, HALO_MF_F16_32>(as, grid, lds, stream);
+        if (p.mfma == LA_CONV_MFMA_16X16X32)
+            return launch_halo<128, FMT, 3, HALO_MF_F16_16>(as, p.grid, lds + (size_t)la_dev_knob(LA_KNOB_HALO_LDSPAD) * 1024, stream);
+        if (p.mt == 128) return launch_halo<128, FMT, 3, HALO_MF_F16_32>(as, p.grid, lds, stream);
+        if (p.mt == 64) return launch_halo<64, FMT, 2, HALO_MF_F16_32>(as, p.grid, lds, stream);
+        return launch_halo<32, FMT, 2, HALO_MF_F16_32>(as, p.grid, lds, stream);
     } else {
         // three waves per SIMD on 128-row tiles for the two-term format (the three-term one does not fit them)
-        if (MTsel == 128) return launch_halo<128, FMT, NTERM == 2 ? 3 : 2, HALO_MF_BF16>(as, grid, lds, stream);
-        if (MTsel == 64) return launch_halo<64, FMT, 2, HALO_MF_BF16>(as, grid, lds, stream);
-        return launch_halo<32, FMT, 2, HALO_MF_BF16>(as, grid, lds, stream);
+        if (p.mt == 128) return launch_halo<128, FMT, NTERM == 2 ? 3 : 2, HALO_MF_BF16>(as, p.grid, lds, stream);
+        if (p.mt == 64) return launch_halo<64, FMT, 2, HALO_MF_BF16>(as, p.grid, lds, stream);
+        return launch_halo<32, FMT, 2, HALO_MF_BF16>(as, p.grid, lds, stream);
     }
 }
 
-int la_conv_halo_launch(const LaConvArgs& as, int MTsel, dim3 grid, hipStream_t stream) {
-    if (as.precision == LA_PREC_BF16X3) return select_halo<FMT_BF16X3>(as, MTsel, grid, stream);
-    if (as.precision == LA_PREC_F16X2) return select_halo<FMT_F16X2>(as, MTsel, grid, stream);
-    return select_halo<FMT_BF16X2>(as, MTsel, grid, stream);
+int la_conv_halo_launch(const LaConvArgs& as, const LaConvPlan& p, hipStream_t stream) {
+    if (as.precision == LA_PREC_BF16X3) return select_halo<FMT_BF16X3>(as, p, stream);
+    if (as.precision == LA_PREC_F16X2) return select_halo<FMT_F16X2>(as, p, stream);
+    return select_halo<FMT_BF16X2>(as, p, stream);
 }

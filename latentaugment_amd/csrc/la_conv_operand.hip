@@ -18,8 +18,8 @@
 // (pack_slab_offset) that the waves read straight from global memory.  Pixels: the halo kernel reads the fp32 input and
 // splits on the way into LDS; the flat kernel (whose gather re-reads every element once per tap) reads a pre-split copy
 // made once per launch input (la_presplit_*: 8 bytes per element {h | m<<16, l} bf16, 4 bytes {h | l<<16} fp16).
-// This unit: operand preparation (weight packs, fp16 operand scales, the pre-split copy) and the choice between the two kernels
-// (la_conv_halo.hip, la_conv_flat.hip).
+// This unit: operand preparation (weight packs, fp16 operand scales, the pre-split copy); which of the two kernels (la_conv_halo.hip,
+// la_conv_flat.hip) a launch runs is la_conv_plan's decision (la_conv.hip).
 #include "la_conv_device.h"
 
 #define PRESPLIT_HDR 512       // head of the workspace: [0,256) xscale[b] floats; the segment maxima follow the header
@@ -58,12 +58,8 @@ __global__ void la_pack_bf16_kernel(const float* __restrict__ w, __bf16* __restr
     }
 }
 
-// max |w| of a tensor into *amax_bits as a float bit pattern (the caller zeroes it first)
-int la_absmax_bits(const float* w, long n, unsigned* amax_bits, hipStream_t stream);
 long la_conv_bf16_pack_elems(int M, int C, int ktaps) { return (long)ktaps * la_cdiv(C, KCB) * pack_mp(M) * KCB; }
 
-// pack layout: [3 bf16 terms][2 fp16 terms][pad to 16 B][wscale float] (term offsets: la_conv_device.h)
-static inline size_t pack_wscale_offset(long term_elems) { return ((size_t)5 * term_elems * 2 + 15) & ~(size_t)15; }
 size_t la_conv_split_pack_bytes(int M, int C, int ktaps) {
     return (size_t)5 * la_conv_bf16_pack_elems(M, C, ktaps) * 2 + 256;
 }
@@ -126,7 +122,7 @@ int la_pack_conv_weights_bf16(const float* w, void* out, int cout, int cin, int 
     hipLaunchKernelGGL(la_pack_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, w, (__bf16*)out, cout, cin, ktaps,
                        transpose, 3, scale, m_pad);
     char* base = static_cast<char*>(out);
-    float* wscale = reinterpret_cast<float*>(base + pack_wscale_offset(n));
+    float* wscale = reinterpret_cast<float*>(base + la_conv_pack_wscale_offset(n));
     unsigned* amax = reinterpret_cast<unsigned*>(wscale) + 1;
     LA_HIP(hipMemsetAsync(amax, 0, sizeof(unsigned), stream));
     const long nw = (long)cout * cin * ktaps;
@@ -356,107 +352,52 @@ __global__ __launch_bounds__(256) void la_presplit_t_kernel(const float* __restr
     }
 }
 
-static inline size_t presplit_hdr_bytes(int B, int C) { return (PRESPLIT_HDR + (size_t)B * C * PM_NS * 4 + 255) & ~(size_t)255; }
+size_t la_conv_presplit_hdr_bytes(int B, int C) { return (PRESPLIT_HDR + (size_t)B * C * PM_NS * 4 + 255) & ~(size_t)255; }
 size_t la_conv_presplit_bytes(int B, int C, int Hin, int Win) {      // channel-interleaved copy, C padded to whole chunks, 8 B / element
-    return (size_t)B * la_cdiv(C, KCB) * KCB * Hin * Win * 8 + 16 + presplit_hdr_bytes(B, C);
+    return (size_t)B * la_cdiv(C, KCB) * KCB * Hin * Win * 8 + 16 + la_conv_presplit_hdr_bytes(B, C);
 }
 
-// fp16 path: per-sample operand scale (segment maxima -> xscale[b]) in the header of the workspace; advances a.ws past it
-static int prepare_scale(LaConvArgs& a, hipStream_t stream) {
-    if (a.precision != LA_PREC_F16X2 || a.acc_scale_x) return LA_OK;      // (a preset scale: e.g. from the clamp bound of the producer)
+// Operand preparation of a split-precision launch as la_conv_plan laid it out (it has checked the workspace): the fp16 per-sample
+// operand scale (segment maxima -> xscale[b]) in the header, the pre-split copy at p.q_off
+int la_conv_prepare_input(LaConvArgs& a, const LaConvPlan& p, hipStream_t stream) {
+    if (p.prep == LA_PREP_NONE) return LA_OK;      // (nothing is launched, nothing is bracketed)
     const long HW = (long)a.Hin * a.Win;
-    const size_t hb = presplit_hdr_bytes(a.B, a.C);
-    LA_CHECK_ARG(a.ws && a.ws_bytes >= hb, "conv: split precisions need a workspace (la_modconv_workspace_bytes)");
-    LA_CHECK_ARG(((size_t)a.ws & 15) == 0, "conv: workspace must be 16-byte aligned");
-    LA_CHECK_ARG(a.B <= 64, "conv: split precisions support at most 64 samples per launch");
-    char* base = static_cast<char*>(a.ws);
-    float* xscale = reinterpret_cast<float*>(base);
-    float* pm = reinterpret_cast<float*>(base + PRESPLIT_HDR);       // segment maxima [B][C][ns]
-    int ns = (int)(HW / 8192);
-    ns = ns < 1 ? 1 : (ns > PM_NS ? PM_NS : ns);
-    if (a.in_pmax) {      // the producer of `in` already reduced every plane: max over the sample of |style| * plane max
-        hipLaunchKernelGGL(la_xscale_pmax_kernel, dim3(a.B), dim3(1024), 0, stream, a.in_pmax, a.in_pmax_nseg > 0 ? a.in_pmax_nseg : 1, a.in_scale,
-                           a.scale_stride, xscale, a.C, 1.f);
-    } else {
-        hipLaunchKernelGGL(la_plane_absmax_kernel, dim3(ns, a.C, a.B), dim3(256), 0, stream, a.in, a.in_bstride, a.in_scale,
-                           a.scale_stride, pm, a.C, HW, ns);
-        hipLaunchKernelGGL(la_xscale_kernel, dim3(a.B), dim3(256), 0, stream, pm, xscale, a.C * ns);
-    }
-    LA_CHECK_LAUNCH();
-    a.acc_scale_x = xscale; a.acc_scale_fan = 1;
-    a.ws = base + hb;
-    a.ws_bytes -= hb;
-    return LA_OK;
-}
-
-// can this launch use the halo kernel?  dense stride-1 3x3 taps within +-1, grid = whole 4x32 tiles, above the split-K sizes
-bool la_conv_bf16_uses_halo(const LaConvArgs& a) {
-    if (a.precision == LA_PREC_F32 || a.in_q) return false;
-    if (a.in_mask_y || (a.in_gain != 0.f && a.in_gain != 1.f)) return false;      // (an input mask is applied by the pre-split copy)
-    if (a.in_sy != 1 || a.in_sx != 1 || a.out_sy != 1 || a.out_sx != 1 || a.out_oy != 0 || a.out_ox != 0) return false;
-    if ((a.Gx & 31) != 0 || (a.Gy & 3) != 0 || a.Gy != a.Hout || a.Gx != a.Wout || a.ntaps != 9) return false;
-    // Grids up to 34x34 stay on the split-K path (la_conv.hip SPLITK_MAX_G).  Round 3 measured the 32x32 layers (512 -> 512, K = 4608) on
-    // this kernel: 114 us against 135 us for slices + finish pass + pre-split copy in isolation, no difference inside a batch -- and
-    // the first-step gradient of the 1024^2 loop 12x further from float64 (rms 4.4e-6 against 3.7e-7 of max |g| 0.4; the reference's
-    // float32: 1.5e-6): K slices summed afterwards are a blocked summation, one accumulator walking all 4608 terms is not.  Dev knob
-    // LA_KNOB_HALO_MING: grids of at least that many points run here.
-    if ((long)a.Gy * a.Gx < (la_dev_knob(LA_KNOB_HALO_MING) ? la_dev_knob(LA_KNOB_HALO_MING) : 1157)) return false;
-    if ((long)a.C * a.Hin * a.Win >= (1l << 28) || a.C > 4096) return false;   // 32-bit byte offsets inside one sample, below the
-                                                                             // out-of-range sentinel of the pixel-stationary loader
-    for (int t = 0; t < a.ntaps; ++t)
-        if (a.tap_dy[t] < -1 || a.tap_dy[t] > 1 || a.tap_dx[t] < -1 || a.tap_dx[t] > 1) return false;
-    return true;
-}
-
-// Operand preparation of a split-precision launch.  Halo launches read the fp32 input directly (modulation, scaling and
-// the split happen on the way into LDS) and only need the fp16 scale; every other launch gets a pre-split copy.
-int la_conv_prepare_input(LaConvArgs& a, hipStream_t stream) {
-    if (a.precision == LA_PREC_F32 || a.in_q) return LA_OK;
-    const long HW = (long)a.Hin * a.Win;
+    const bool copy = p.prep == LA_PREP_PRESPLIT;
     // launch profiler: operand preparation = its own class (read the fp32 input once; the pre-split copy is written once)
     struct Bracket { int slot; hipStream_t st; ~Bracket() { la_prof_close(slot, st); } };
-    if (la_conv_bf16_uses_halo(a)) {
-        if (a.precision != LA_PREC_F16X2 || a.acc_scale_x) return LA_OK;      // (scale known: nothing is launched, nothing is bracketed)
-        Bracket br{la_prof_open(LA_PC_PRESPLIT, 0.0, a.in_pmax ? 0.0 : 4.0 * a.B * (double)a.C * HW * (a.in_bstride ? 1.0 : 1.0 / a.B), stream), stream};
-        return prepare_scale(a, stream);
-    }
-    Bracket br{la_prof_open(LA_PC_PRESPLIT, 0.0, 4.0 * a.B * (double)a.C * HW * ((a.in_bstride ? 1.0 : 1.0 / a.B) + 1.0), stream), stream};
-    const size_t qb = la_conv_presplit_bytes(a.B, a.C, a.Hin, a.Win);
-    LA_CHECK_ARG(a.ws && a.ws_bytes >= qb, "conv: split precisions need a workspace (la_modconv_workspace_bytes)");
-    LA_CHECK_ARG(((size_t)a.ws & 15) == 0, "conv: workspace must be 16-byte aligned");
-    LA_CHECK_ARG(a.B <= 64, "conv: split precisions support at most 64 samples per launch");
-    LA_CHECK_ARG(qb < 0x7ff00000u, "conv: pre-split operand too large for 32-bit buffer offsets");
+    const double elems = 4.0 * a.B * (double)a.C * HW, in_reads = a.in_bstride ? 1.0 : 1.0 / a.B;
+    Bracket br{la_prof_open(LA_PC_PRESPLIT, 0.0, copy ? elems * (in_reads + 1.0) : (a.in_pmax ? 0.0 : elems * in_reads), stream), stream};
     char* base = static_cast<char*>(a.ws);
-    const size_t ws_bytes = a.ws_bytes;
-    const dim3 pgrid((unsigned)la_cdiv(HW, 64), (unsigned)la_cdiv(a.C, KCB), (unsigned)a.B);
-    const LaInMask mk{a.in_mask_y, a.in_mask_act, a.in_mask_alpha, a.in_mask_gain, a.in_mask_clamp, a.in_gain != 0.f ? a.in_gain : 1.f,
-                      a.in_row_hi > 0 ? (long)a.in_row_lo * a.Win : 0, a.in_row_hi > 0 ? (long)a.in_row_hi * a.Win : 0};
-    LA_CHECK_ARG((!a.in_mask_y && mk.in_gain == 1.f) || a.acc_scale_x || a.precision != LA_PREC_F16X2, "conv: an input mask needs a preset operand scale");
-    if (a.precision == LA_PREC_F16X2) {
-        int rc = prepare_scale(a, stream);
-        if (rc) return rc;
-        void* q = a.ws;
-        hipLaunchKernelGGL(la_presplit_t_kernel<true>, pgrid, dim3(256), 0, stream, a.in, a.in_bstride, a.in_scale, a.scale_stride,
-                           a.acc_scale_x, a.acc_scale_fan, (unsigned*)q, a.C, HW, mk);
-        a.in_q = q;
-    } else {
-        void* q = base + presplit_hdr_bytes(a.B, a.C);
-        hipLaunchKernelGGL(la_presplit_t_kernel<false>, pgrid, dim3(256), 0, stream, a.in, a.in_bstride, a.in_scale, a.scale_stride,
-                           (const float*)nullptr, 0, (unsigned*)q, a.C, HW, mk);
+    if (p.scale_pass) {
+        float* xscale = reinterpret_cast<float*>(base);
+        float* pm = reinterpret_cast<float*>(base + PRESPLIT_HDR);       // segment maxima [B][C][ns]
+        const int ns = la_conv_act_grad_segments(HW);
+        if (a.in_pmax)      // the producer of `in` already reduced every plane: max over the sample of |style| * plane max
+            hipLaunchKernelGGL(la_xscale_pmax_kernel, dim3(a.B), dim3(1024), 0, stream, a.in_pmax, a.in_pmax_nseg > 0 ? a.in_pmax_nseg : 1, a.in_scale,
+                               a.scale_stride, xscale, a.C, 1.f);
+        else {
+            hipLaunchKernelGGL(la_plane_absmax_kernel, dim3(ns, a.C, a.B), dim3(256), 0, stream, a.in, a.in_bstride, a.in_scale,
+                               a.scale_stride, pm, a.C, HW, ns);
+            hipLaunchKernelGGL(la_xscale_kernel, dim3(a.B), dim3(256), 0, stream, pm, xscale, a.C * ns);
+        }
+        LA_CHECK_LAUNCH();
+        a.acc_scale_x = xscale; a.acc_scale_fan = 1;
+    }
+    if (copy) {
+        const dim3 pgrid((unsigned)la_cdiv(HW, 64), (unsigned)la_cdiv(a.C, KCB), (unsigned)a.B);
+        const LaInMask mk{a.in_mask_y, a.in_mask_act, a.in_mask_alpha, a.in_mask_gain, a.in_mask_clamp, a.in_gain != 0.f ? a.in_gain : 1.f,
+                          a.in_row_hi > 0 ? (long)a.in_row_lo * a.Win : 0, a.in_row_hi > 0 ? (long)a.in_row_hi * a.Win : 0};
+        unsigned* q = reinterpret_cast<unsigned*>(base + p.q_off);
+        if (a.precision == LA_PREC_F16X2)
+            hipLaunchKernelGGL(la_presplit_t_kernel<true>, pgrid, dim3(256), 0, stream, a.in, a.in_bstride, a.in_scale, a.scale_stride,
+                               a.acc_scale_x, a.acc_scale_fan, q, a.C, HW, mk);
+        else
+            hipLaunchKernelGGL(la_presplit_t_kernel<false>, pgrid, dim3(256), 0, stream, a.in, a.in_bstride, a.in_scale, a.scale_stride,
+                               (const float*)nullptr, 0, q, a.C, HW, mk);
+        LA_CHECK_LAUNCH();
         a.in_q = q;
     }
-    LA_CHECK_LAUNCH();
-    const size_t off = (qb + 255) & ~(size_t)255;
-    a.ws = ws_bytes > off ? base + off : nullptr;
-    a.ws_bytes = ws_bytes > off ? ws_bytes - off : 0;
+    a.ws = a.ws_bytes > p.ws_head ? base + p.ws_head : nullptr;
+    a.ws_bytes -= p.ws_head;
     return LA_OK;
-}
-
-// halo kernel where the launch allows it (la_conv_bf16_uses_halo), else the flat kernel (direct or split-K)
-int la_conv_bf16_dispatch(const LaConvArgs& args, int MTsel, dim3 grid, bool split, hipStream_t stream) {
-    LaConvArgs as = args;
-    if (as.precision == LA_PREC_F16X2)      // the fp16 weight scale lives behind the terms of the pack
-        as.acc_scale_w = reinterpret_cast<const float*>(static_cast<const char*>(as.wgt_bf16) + pack_wscale_offset(as.wgt_bf16_term_elems));
-    if (!split && la_conv_bf16_uses_halo(as)) return la_conv_halo_launch(as, MTsel, grid, stream);
-    return la_conv_flat_launch(as, MTsel, grid, split, stream);
 }

@@ -32,15 +32,13 @@ static void set_bwd(LaConvArgs& a, const LaModconv& m, const float* xin, long xi
     if (seam) a.seam = *seam;
 }
 
-// one row tile of the halo kernel = all output channels (tiles of 128, 64 or -- for <= 32 channels -- 32 rows, la_conv_launch)
+// one row tile of the halo kernel = all output channels (tiles of 128, 64 or -- for <= 32 channels -- 32 rows): what la_conv_plan says of
+// the forward launch, with a workspace that holds whatever it asks for
 bool la_modconv3x3_fwd_fuses_rgb(int precision, int B, int cin, int cout, int res) {
     static const bool off = la_dev_env("LA_NO_RGB_FUSE") != nullptr;      // dev knob
-    if (off || precision == LA_PREC_F32 || (cout != 128 && cout != 64 && cout != 32)) return false;
-    LaConvArgs a; la_conv_args_init(a);
-    a.precision = precision;
-    a.B = B; a.C = cin; a.M = cout;
-    la_conv_geom_same(a, res, 3, false);
-    return la_conv_bf16_uses_halo(a);
+    long info[LA_CONV_PLAN_NINFO];
+    return !off && la_conv_plan_query(precision, B, cin, cout, LA_CONV_GEOM_SAME_FWD, res, 0, (size_t)1 << 40, info) == LA_OK &&
+           info[LA_CONV_PLAN_CLS] == LA_PC_CONV_HALO && info[LA_CONV_PLAN_MT] == cout;
 }
 
 int la_modconv3x3_fwd_ex(const float* x, long x_bstride, const LaModconv& m, const LaLayerEpi& epi, float* y, hipStream_t stream,
@@ -239,23 +237,12 @@ extern "C" int la_modconv_ds_tiles(int grid_res) { return la_conv_tiles_per_samp
 // pre-split bf16 copy of the launch input (split-bf16 only) + split-K slice partials (<= 34x34 grids).
 extern "C" size_t la_modconv_workspace_bytes(int B, int cin, int cout, int res, int up) {
     size_t need = 0;
-    const int hin = up ? res / 2 : res;
+    const int hin = up ? res / 2 : res, rb = up ? res + 1 : res;      // input resolution of the forward / of the backward contraction
+    // forward grids: the layer's own, or the phases of the transposed conv -- fp32: one phase per launch, 16-bit: four phases' partials side by side
+    const int gy[4] = {hin + up, hin + 1, hin, hin}, gx[4] = {hin + up, hin, hin + 1, hin};
     for (int prec = 0; prec <= 3; ++prec) {
-        long f, b;
-        size_t qf = 0, qb = 0;
-        if (up) {
-            if (prec == LA_PREC_F32) f = la_conv_splitk_floats(B, cout, cin, hin + 1, hin + 1, prec);   // one phase per launch
-            else {      // four phases' partials side by side
-                const int gy[4] = {hin + 1, hin + 1, hin, hin}, gx[4] = {hin + 1, hin, hin + 1, hin};
-                f = la_conv_splitk_floats_phases(B, cout, cin, 4, gy, gx, prec);
-            }
-            b = la_conv_splitk_floats(B, cin, cout, hin, hin, prec);
-            if (prec) { qf = la_conv_presplit_bytes(B, cin, hin, hin); qb = la_conv_presplit_bytes(B, cout, res + 1, res + 1); }
-        } else {
-            f = la_conv_splitk_floats(B, cout, cin, res, res, prec);
-            b = la_conv_splitk_floats(B, cin, cout, res, res, prec);
-            if (prec) { qf = la_conv_presplit_bytes(B, cin, res, res); qb = la_conv_presplit_bytes(B, cout, res, res); }
-        }
+        const long f = la_conv_splitk_floats_phases(B, cout, cin, up && prec ? 4 : 1, gy, gx, prec), b = la_conv_splitk_floats(B, cin, cout, hin, hin, prec);
+        const size_t qf = prec ? la_conv_presplit_bytes(B, cin, hin, hin) : 0, qb = prec ? la_conv_presplit_bytes(B, cout, rb, rb) : 0;
         const size_t nf = ((qf + 255) & ~(size_t)255) + (size_t)f * 4, nb = ((qb + 255) & ~(size_t)255) + (size_t)b * 4;
         if (nf > need) need = nf;
         if (nb > need) need = nb;

@@ -4,7 +4,8 @@ Each library runs the same calls in a fresh process of its own (`--dump LIB OUT.
 anything loads it, as scripts/bench_with_lib.py does); this process only compares the bytes and prints one line.  In float16, float32 and
 float64: bias_act for the nine activations, with a clamp and without, forward, first order (dx, db) and second order, the bias on axis 1
 of a 4-D tensor and on the last axis, aligned and at a one-element storage offset; upfirdn2d / filter2d / upsample2d / downsample2d
-forward and dx with setup_filter([1,3,3,1]), a dense 3x5 filter at gain 1.7 and a separable 12-tap filter.  Inputs: seeded CPU generator."""
+forward and dx with setup_filter([1,3,3,1]), a dense 3x5 filter at gain 1.7 and a separable 12-tap filter.  In float32: conv2d / conv_transpose2d forward,
+dx and dw on split-K and direct grids, stride 2 and groups.  Inputs: seeded CPU generator."""
 import os
 import subprocess
 import sys
@@ -20,6 +21,11 @@ def dump(lib_path, out_path):
     import torch
     from latentaugment_amd import _lib
     _lib.LIB_PATH = os.path.abspath(lib_path)
+    import ctypes
+    probe = ctypes.CDLL(_lib.LIB_PATH)
+    for k in list(_lib.SIGNATURES):      # (entries the other build lacks are dropped from the binding table, as scripts/bench_with_lib.py does)
+        if not hasattr(probe, k):
+            del _lib.SIGNATURES[k]
     from latentaugment_amd import ops
     dev = torch.device('cuda', 0)
     gen = torch.Generator().manual_seed(0)
@@ -63,6 +69,17 @@ def dump(lib_path, out_path):
                 dx, = torch.autograd.grad(y, [x], draw(list(y.shape), dt))
                 keep(f'{cname}/{dt}/{fname}/y', y)
                 keep(f'{cname}/{dt}/{fname}/dx', dx)
+    # the conv op (float32 only; its contractions go through la_conv_launch): split-K and direct grids, 64- and 128-row tiles, stride 2, groups
+    convs = {'sk_8x8': (ops.conv2d, [2, 40, 8, 8], [12, 40, 3, 3], dict(padding=1)),
+             'direct_40x40': (ops.conv2d, [1, 17, 40, 40], [132, 17, 3, 3], dict(padding=1)),
+             's2_g2': (ops.conv2d, [2, 8, 17, 19], [8, 4, 3, 3], dict(stride=2, padding=(1, 0), groups=2)),
+             't_s2': (ops.conv_transpose2d, [2, 36, 9, 9], [36, 8, 3, 3], dict(stride=2))}
+    for cname, (call, xs, wsh, kw) in convs.items():
+        x, w = draw(xs, torch.float32).requires_grad_(), draw(wsh, torch.float32).requires_grad_()
+        y = call(x, w, **kw)
+        dx, dw = torch.autograd.grad(y, [x, w], draw(list(y.shape), torch.float32))
+        for name, t in zip(('y', 'dx', 'dw'), (y, dx, dw)):
+            keep(f'conv/{cname}/{name}', t)
     torch.cuda.synchronize()
     np.savez(out_path, **res)
 

@@ -239,7 +239,7 @@ def splitk_floats_phases(B, M, C, grids, prec):
 
 
 def presplit_hdr_bytes(B, C):
-    """la_conv_operand.hip presplit_hdr_bytes"""
+    """la_conv_operand.hip la_conv_presplit_hdr_bytes"""
     return r256(PRESPLIT_HDR + B * C * PM_NS * 4)
 
 
@@ -282,14 +282,14 @@ def workspace_bytes(B, cin, cout, res, up):
 
 
 def uses_halo(prec, in_q, dense3x3, Gy, Gx, C, Hin, Win):
-    """la_conv_operand.hip la_conv_bf16_uses_halo (dense3x3: unit strides, no offset, the nine taps within +-1, grid = output)."""
+    """la_conv.hip la_conv_bf16_uses_halo (dense3x3: unit strides, no offset, the nine taps within +-1, grid = output)."""
     return (prec != 0 and not in_q and dense3x3 and Gx % 32 == 0 and Gy % 4 == 0 and Gy * Gx >= SPLITK_MAX_G + 1
             and C * Hin * Win < (1 << 28) and C <= 4096)
 
 
 def conv_launch(prec, B, C, M, grids, Hin, Win, dense3x3, ws_bytes, in_q, counts):
-    """la_conv.hip la_conv_launch (with la_conv_prepare_input and the kernel selection of la_conv_bf16_dispatch, select_halo and
-    launch_flat): the form of ONE contraction launch.  grids: [(Gy, Gx, taps)], more than one = merged phases.  ws_bytes: what the
+    """la_conv.hip la_conv_plan (what la_conv_launch, la_conv_prepare_input, la_conv_flat_launch and la_conv_halo_launch then read from
+    the LaConvPlan): the form of ONE contraction launch.  grids: [(Gy, Gx, taps)], more than one = merged phases.  ws_bytes: what the
     caller hands to the launch.  counts: profiler brackets per class, updated."""
     if M % 4:
         raise Refused('conv: M must be a multiple of 4')
@@ -298,7 +298,7 @@ def conv_launch(prec, B, C, M, grids, Hin, Win, dense3x3, ws_bytes, in_q, counts
     Gy, Gx = grids[0][0], grids[0][1]
     nck = cdiv(C, KCB if bf else KC)
     halo = not merged and uses_halo(prec, in_q, dense3x3, Gy, Gx, C, Hin, Win)
-    mt = 128 if M >= 128 else (32 if (M <= 32 and halo) else 64)      # MTsel
+    mt = 128 if M >= 128 else (32 if (M <= 32 and halo) else 64)      # conv_mt
     mtiles = cdiv(M, mt)
     presplit = bool(in_q)
     if bf and not in_q:      # la_conv_prepare_input
@@ -335,49 +335,55 @@ def conv_launch(prec, B, C, M, grids, Hin, Win, dense3x3, ws_bytes, in_q, counts
         if ks >= 2 and ks * B * M * gsum <= splitk_floats:
             cls = 'conv_splitk' if bf else 'conv_f32'
             counts[cls] += 1
-            mfma = '32x32x2' if not bf else ('16x16x32' if prec == 3 and mt == 128 else '32x32')      # launch_flat: FLAT_MF_16
+            mfma = '32x32x2' if not bf else ('16x16x32' if prec == 3 and mt == 128 else '32x32')      # la_conv_flat.hip: FLAT_MF_16
             return Launch(cls, mt, mfma, ks, presplit, merged)
     if not bf:
         counts['conv_f32'] += 1
         return Launch('conv_f32', mt, '32x32x2', 1, False, False)
-    if halo:      # select_halo
+    if halo:      # la_conv_halo.hip: HALO_MF_F16_16
         counts['conv_halo'] += 1
         return Launch('conv_halo', mt, '16x16x32' if prec == 3 and mt == 128 and C > KCB else '32x32', 1, False, False)
-    counts['conv_flat'] += 1      # launch_flat: FLAT_MF_16_3BUF
+    counts['conv_flat'] += 1      # la_conv_flat.hip: FLAT_MF_16_3BUF
     return Launch('conv_flat', mt, '16x16x32' if prec == 3 and mt == 128 else '32x32', 1, presplit, merged)
 
 
-def _launch_specs(case, prec):
-    """The contraction launches of an entry call as arguments of conv_launch, and the bytes of the workspace that the entry keeps in
-    front of them: la_modconv.hip la_modconv3x3_{fwd,up2_fwd,bwd,up2_bwd}_ex."""
+# geometry of a launch as la_conv_plan_query names it (LA_CONV_GEOM_* of include/latentaug_hip.h)
+GEOM_SAME_FWD, GEOM_SAME_BWD, GEOM_DOWN2, GEOM_UP2_PHASE, GEOM_UP2_MERGED = 0, 1, 2, 3, 7
+
+
+def launch_specs(case, prec):
+    """The contraction launches of an entry call as arguments of conv_launch (geom: what la_conv_plan_query calls that launch), and the
+    bytes of the workspace that the entry keeps in front of them: la_modconv.hip la_modconv3x3_{fwd,up2_fwd,bwd,up2_bwd}_ex."""
     B, cin, cout, res = case['B'], case['cin'], case['cout'], case['res']
     e = case['entry']
     hin = res // 2
     if e == 'fwd':
-        return [dict(C=cin, M=cout, grids=[(res, res, 9)], Hin=res, dense3x3=True)], 0, None
+        return [dict(C=cin, M=cout, grids=[(res, res, 9)], Hin=res, dense3x3=True, geom=GEOM_SAME_FWD)], 0, None
     if e == 'bwd':
-        return [dict(C=cout, M=cin, grids=[(res, res, 9)], Hin=res, dense3x3=True)], 0, None
+        return [dict(C=cout, M=cin, grids=[(res, res, 9)], Hin=res, dense3x3=True, geom=GEOM_SAME_BWD)], 0, None
     if e == 'up2_fwd':
         if prec == 0:      # one launch per phase
-            return [dict(C=cin, M=cout, grids=[g], Hin=hin, dense3x3=False) for g in phase_grids(hin)], 0, None
+            return [dict(C=cin, M=cout, grids=[g], Hin=hin, dense3x3=False, geom=GEOM_UP2_PHASE + k)
+                    for k, g in enumerate(phase_grids(hin))], 0, None
         # the input is split once, up front, for the merged launch
-        return [dict(C=cin, M=cout, grids=phase_grids(hin), Hin=hin, dense3x3=False)], 0, (cin, hin)
+        return [dict(C=cin, M=cout, grids=phase_grids(hin), Hin=hin, dense3x3=False, geom=GEOM_UP2_MERGED)], 0, (cin, hin)
     # up2_bwd, the path of the public entry (no plane maxima handed in): FIR adjoint into the scratch, then the stride-2 gather;
     # fp16 x2 keeps the plane maxima of the scratch at the head of the workspace
     head = r256(B * cout * fir4x4_segments(res + 1, res + 1) * 4) if prec == 3 else 0
-    return [dict(C=cout, M=cin, grids=[(hin, hin, 9)], Hin=res + 1, dense3x3=False)], head, None
+    return [dict(C=cout, M=cin, grids=[(hin, hin, 9)], Hin=res + 1, dense3x3=False, geom=GEOM_DOWN2)], head, None
 
 
-def _run_plan(case, prec, ws_bytes):
-    counts = dict(conv_halo=0, conv_flat=0, conv_splitk=0, conv_f32=0, operand_prep=0)
-    specs, head, up_front = _launch_specs(case, prec)
+def launch_inputs(case, prec, ws_bytes, counts):
+    """The walk of an entry call up to its contraction launches: (specs, the workspace bytes each launch is handed, its input arrives
+    pre-split)."""
+    specs, head, up_front = launch_specs(case, prec)
     B = case['B']
     if case['entry'].startswith('up2') and case['res'] % 2:
         raise Refused('output resolution must be even')
     if head and ws_bytes > head:
         ws_bytes -= head
     in_q = False
-    if up_front:      # la_conv_prepare_input in la_modconv3x3_up2_fwd_ex
+    if up_front:      # la_conv_prepare_input in la_conv_up2_launch
         C, hin = up_front
         counts['operand_prep'] += 1
         qb = presplit_bytes(B, C, hin, hin)
@@ -387,7 +393,17 @@ def _run_plan(case, prec, ws_bytes):
             raise Refused('conv: at most 64 samples')
         ws_bytes = ws_bytes - r256(qb) if ws_bytes > r256(qb) else 0
         in_q = True
-    launches = [conv_launch(prec, B, sp['C'], sp['M'], sp['grids'], sp['Hin'], sp['Hin'], sp['dense3x3'], ws_bytes, in_q, counts)
+    return specs, ws_bytes, in_q
+
+
+def new_counts():
+    return dict(conv_halo=0, conv_flat=0, conv_splitk=0, conv_f32=0, operand_prep=0)
+
+
+def _run_plan(case, prec, ws_bytes):
+    counts = new_counts()
+    specs, ws_bytes, in_q = launch_inputs(case, prec, ws_bytes, counts)
+    launches = [conv_launch(prec, case['B'], sp['C'], sp['M'], sp['grids'], sp['Hin'], sp['Hin'], sp['dense3x3'], ws_bytes, in_q, counts)
                 for sp in specs]
     return launches, counts
 
@@ -399,16 +415,16 @@ def plan(case, precision, with_ws):
     with_ws = True: the workspace of la_modconv_workspace_bytes.  False: the largest workspace that is one float short of the slice
     partials of every launch that would split, so that the direct kernels serve the call (equal to the full one where nothing splits).
 
-    Mirrors (C function -> here): la_conv_launch incl. MTsel, the `small` predicate and the merged-phase rule -> conv_launch;
-    choose_ksplit -> choose_ksplit; la_conv_bf16_uses_halo -> uses_halo; select_halo / launch_flat -> the mfma field of conv_launch;
-    la_conv_prepare_input -> the operand_prep counts and the bytes taken from the workspace; la_modconv_workspace_bytes ->
-    workspace_bytes; the four la_modconv3x3_*_ex -> _launch_specs."""
+    Mirrors (C function -> here): la_conv_plan (la_conv.hip) -> conv_launch, field by field: LaConvPlan::mt (conv_mt), ksplit (the
+    `small` predicate, choose_ksplit -> choose_ksplit), mfma, prep / ws_head (the operand_prep counts and the bytes taken from the
+    workspace), cls; its halo predicate la_conv_bf16_uses_halo -> uses_halo; la_modconv_workspace_bytes -> workspace_bytes; the four
+    la_modconv3x3_*_ex -> launch_specs / launch_inputs.  test_conv_plan_cpu.py compares every field with la_conv_plan_query."""
     full = workspace_bytes(case['B'], case['cin'], case['cout'], case['res'], 1 if case['entry'].startswith('up2') else 0)
     launches, counts = _run_plan(case, precision, full)
     ws = full
     if not with_ws and any(l.ksplit > 1 for l in launches):
         B = case['B']
-        specs, head, up_front = _launch_specs(case, precision)
+        specs, head, up_front = launch_specs(case, precision)
         prefix = head
         if precision:
             if up_front:
@@ -428,7 +444,7 @@ def splits(case, precision):
 
 
 def form_key(precision, l):
-    """What identifies a kernel instantiation: the template arguments that select_halo, launch_flat and la_conv_launch choose."""
+    """What identifies a kernel instantiation: the template arguments that la_conv_halo_launch, la_conv_flat_launch and la_conv_launch read from the LaConvPlan."""
     return (precision, l.cls if l.cls != 'conv_f32' else ('conv_f32_split' if l.ksplit > 1 else 'conv_f32'), l.mt, l.mfma, l.merged)
 
 

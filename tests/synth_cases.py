@@ -266,8 +266,8 @@ SYNTH_REFUSALS = [
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# which form each block takes (la_synth_forward / la_synth_backward, la_torgb_forward, la_modconv3x3_fwd_fuses_rgb with the conditions of
-# la_conv_bf16_uses_halo for a dense 3x3 launch on the whole res x res grid, la_seam_slabs)
+# which form each block takes (la_synth_forward / la_synth_backward, la_torgb_forward, la_modconv3x3_fwd_fuses_rgb = the class la_conv_plan gives
+# a dense 3x3 launch on the whole res x res grid, i.e. the conditions of its halo predicate, la_seam_slabs)
 
 HALO_MIN_GRID = 1157
 TORGB_SMALL_MAX_HW = 4096

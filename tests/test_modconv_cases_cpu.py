@@ -7,8 +7,8 @@ Kernel forms that no call of the four public entries can reach (so the list belo
     wants `(a.Gx & 31) == 0` and the entries are square, so a halo grid is (32 k)^2 and holds 8 k^2 tiles: always a multiple of 8
     (res 64: 32, res 96: 72, res 160: 200).  Only the engine's row / column windows give other counts.  The flat and the exact-fp32
     kernels have the same switch and are run on both sides of it (10, 11 and 18 tiles at res 35, 36 and 48; 32 at the 64x64 grids).
-  * 32-row tiles of the flat kernel: `MTsel` is 32 only under la_conv_bf16_uses_halo (la_conv.hip, la_conv_launch).
-  * a split exact-fp32 launch of merged phases: `small = small && bf` (la_conv_launch); la_modconv3x3_up2_fwd_ex merges for the 16-bit
+  * 32-row tiles of the flat kernel: LaConvPlan::mt is 32 only under la_conv_bf16_uses_halo (la_conv.hip, la_conv_plan).
+  * a split exact-fp32 launch of merged phases: la_conv_plan refuses merged phases at LA_PREC_F32; la_conv_up2_launch merges for the 16-bit
     precisions only.
   * 16 slices from 17 chunks: choose_ksplit skips a slice count k with ceil(nck / ceil(nck / k)) != k, so C = 544 runs 9 slices of two
     chunks (the last of one); 16 slices need 16 chunks (C = 512) or 31 / 32.
@@ -115,7 +115,7 @@ def test_exact_cases_are_float32_numbers(name):
         assert float(v.abs().max()) > 0
 
 
-# every template instantiation that select_halo, launch_flat and la_conv_launch can launch for a call of the public entries:
+# every template instantiation that la_conv_halo_launch, la_conv_flat_launch and la_conv_launch can launch for a call of the public entries:
 # (precision, class, row tile, MFMA form, merged phases)
 EXPECTED_FORMS = (
     # la_conv_igemm_kernel<128 / 64, SPLIT>
