@@ -395,8 +395,61 @@ int la_synth_get_precision(const la_synth* h);
  * without their tile rounding; the launch that writes them rounds them outward to its own 4-row tiles -- and window[2..3] = the tile
  * columns that launch writes for image columns [col_lo, col_hi) (top block's up-sampling layer only).  0, 0 on an axis = all of it. */
 int la_synth_plan_bwd_window(int img_resolution, int row_lo, int row_hi, int col_lo, int col_hi, int conv_index, int* window);
-/* the rows the last la_synth_forward of a handle recorded for its backward pass */
+/* the rows the last la_synth_forward of a handle planned for its backward pass */
 int la_synth_bwd_rows(const la_synth* h, int conv_index, int* row_lo, int* row_hi);
+/* Host only, no launch, no handle, usable without a GPU.  Everything a la_synth_forward of B samples and the la_synth_backward behind it
+ * decide before they launch, for an engine of this shape (channels[k] at resolution 4 << k), this precision and this image window (0, 0 on an
+ * axis = all): the record both passes execute.  info[LA_SYNTH_PLAN_NINFO] holds three kinds of record.
+ *   pass, info[LA_SYNTH_PLAN_*]: blocks, conv layers, B, precision; F16 = the forward contractions take their fp16 operand scales from slot
+ *     rows; XS_HANDOFF = the backward ones too (else plane maxima and a reduction launch); ZT_DENSE = dense transposed-conv scratch rows (else
+ *     column-planar); CONE = the backward launches follow the gradient cone of the image window.
+ *   conv layer ci (engine order), info[LA_SYNTH_PLAN_LAYER(ci) + LA_SYNTH_PLAN_L_*]: FWD = row_lo, row_hi, col_lo, col_hi its forward launch
+ *     computes; CONE = the rows in which the gradient of its output can be non-zero (la_synth_plan_bwd_window); WIN (0 / 1), ROWS_IN, ROWS_OUT =
+ *     the tile-rounded windows (four numbers each, as FWD) its backward launch reads of that gradient and writes of the gradient of its input;
+ *     SEAM = where the backward seam of its output runs: LA_SYNTH_SEAM_KERNEL, a launch of its own (a conv1's with the ToRGB backward), or
+ *     LA_SYNTH_SEAM_FUSED, the epilogue of the backward contraction above it (a conv0's: conv1's of the block; a conv1's: the up-sampling layer's
+ *     one block up); SEAM_PMAX / PMAX_IN = the plane-maxima buffer that seam writes / its backward contraction reads (LA_SYNTH_PMAX_*: none, the
+ *     shared one, the up-sampling layers' fused seams', the conv1 layers' fused seams'); NSEG = segments of its demod-gradient, plane-maxima and
+ *     (conv1) ToRGB weight-gradient partials: seam slabs or contraction tiles; NTILES = tiles of its style-gradient partials.
+ *   block k, info[LA_SYNTH_PLAN_BLOCK(k) + LA_SYNTH_PLAN_B_*]: FUSE_RGB = ToRGB runs in the epilogue of conv1's launch (else the ToRGB kernel,
+ *     which up-samples the skip image itself and is handed the image rows IMG_ROWS lo, hi); SKIP_UP = the skip image is up-sampled by a launch of
+ *     its own before conv1; DOWN_FIR = the backward pass launches the down-FIR of the image gradient at this block; PYRAMID = and one more launch
+ *     for every level below.
+ * Bad arguments are refused with a message. */
+#define LA_SYNTH_PLAN_NBLOCKS 0
+#define LA_SYNTH_PLAN_NCONV 1
+#define LA_SYNTH_PLAN_B 2
+#define LA_SYNTH_PLAN_PRECISION 3
+#define LA_SYNTH_PLAN_F16 4
+#define LA_SYNTH_PLAN_XS_HANDOFF 5
+#define LA_SYNTH_PLAN_ZT_DENSE 6
+#define LA_SYNTH_PLAN_CONE 7
+#define LA_SYNTH_PLAN_PASS_N 8
+#define LA_SYNTH_PLAN_L_FWD 0        /* .. 3 */
+#define LA_SYNTH_PLAN_L_CONE 4       /* .. 5 */
+#define LA_SYNTH_PLAN_L_WIN 6
+#define LA_SYNTH_PLAN_L_ROWS_IN 7    /* .. 10 */
+#define LA_SYNTH_PLAN_L_ROWS_OUT 11  /* .. 14 */
+#define LA_SYNTH_PLAN_L_SEAM 15
+#define LA_SYNTH_PLAN_L_SEAM_PMAX 16
+#define LA_SYNTH_PLAN_L_PMAX_IN 17
+#define LA_SYNTH_PLAN_L_NSEG 18
+#define LA_SYNTH_PLAN_L_NTILES 19
+#define LA_SYNTH_PLAN_LAYER_N 20
+#define LA_SYNTH_PLAN_B_FUSE_RGB 0
+#define LA_SYNTH_PLAN_B_SKIP_UP 1
+#define LA_SYNTH_PLAN_B_IMG_ROWS 2   /* .. 3 */
+#define LA_SYNTH_PLAN_B_DOWN_FIR 4
+#define LA_SYNTH_PLAN_B_PYRAMID 5
+#define LA_SYNTH_PLAN_BLOCK_N 6
+#define LA_SYNTH_PLAN_LAYER(ci) (LA_SYNTH_PLAN_PASS_N + LA_SYNTH_PLAN_LAYER_N * (ci))        /* ci < 24 */
+#define LA_SYNTH_PLAN_BLOCK(k) (LA_SYNTH_PLAN_LAYER(24) + LA_SYNTH_PLAN_BLOCK_N * (k))       /* k < 12 */
+#define LA_SYNTH_PLAN_NINFO LA_SYNTH_PLAN_BLOCK(12)
+#define LA_SYNTH_SEAM_KERNEL 0
+#define LA_SYNTH_SEAM_FUSED 1
+#define LA_SYNTH_PMAX_NONE 0         /* 1, 2, 3: the three buffers in the order above */
+int la_synth_plan_query(int img_resolution, int img_channels, const int* channels, int B, int precision, int row_lo, int row_hi, int col_lo,
+                        int col_hi, long* info);
 /* ws element (b,l,j) = ws[b*ws_bstride + l*ws_lstride + j] (ws_lstride = 0: W space, one w per sample).
  * noise_mode 0 'none', 1 'const', 2 explicit unit-variance tensors noises[layer] [B][res][res] ('random' drawn by the caller).
  * img_out NULL: the image stays in the engine (la_synth_image). */

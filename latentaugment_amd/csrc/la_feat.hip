@@ -346,17 +346,20 @@ static void f_relu_seam(LaConvArgs& a, const la_feat* h, const float* mask_y, fl
     a.seam.xs_out = xs_out; a.seam.xs_mult = 1.f;
 }
 
-extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_out, hipStream_t stream) {
-    LA_CHECK_ARG(h && x && feat_out, "feat_forward: null pointer");
-    LA_CHECK_ARG(N >= 1 && N <= h->maxN, "feat_forward: batch exceeds max_batch");
+// fp16 x2 mode: operand scales as slot rows lowered by the producing kernels; decided once per call (dev knob LA_NO_FEAT_SLOTS: the round-3 passes)
+static bool f_slots(const la_feat* h) { return h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS"); }
+static float* f_rows(const la_feat* h, float* base, int op) { return base + (size_t)op * h->maxN * LA_XS_FAN; }
+
+// The trunk on N rows of x: resets the forward slot rows, walks the op list with the conv, pool and fc launches and hands every tap op, with
+// the activation it taps and its pixel count, to `tap`.  fc_out: where the last fc op of a detector list writes (no other caller has fc ops).
+// fp16 x2 mode: every conv's epilogue lowers the slot rows of the NEXT conv's operand scale (a pool in between only shrinks the maximum;
+// taps do not touch the activation), so only the first conv -- whose input no kernel of this engine produces -- runs the absmax / scale passes
+template <class Tap>
+static int f_trunk(la_feat* h, const float* x, int N, float* fc_out, hipStream_t stream, Tap tap) {
     const float* cur = x;
     int rc;
-    // fp16 x2 mode: every conv's epilogue lowers the slot rows of the NEXT conv's operand scale (a pool in between only shrinks the
-    // maximum; taps do not touch the activation), so only the first conv -- whose input no kernel of this engine produces -- runs the
-    // absmax / scale passes
-    const bool slots = h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS");      // (dev knob: the round-3 passes)
+    const bool slots = f_slots(h);
     if (slots) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_f), (int)LA_XS_INIT, (size_t)h->nops * h->maxN * LA_XS_FAN, stream));
-    auto rows = [&](float* base, int op) { return base + (size_t)op * h->maxN * LA_XS_FAN; };
     bool first_conv = true;
     for (int k = 0; k < h->nops; ++k) {
         FOp& o = h->op[k];
@@ -366,18 +369,16 @@ extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_ou
             for (int q = k + 1; q < h->nops; ++q) if (h->op[q].kind == LA_FEAT_CONV_RELU) { nxt = q; break; }
             LaConvArgs a; f_conv(a, h, o, false, N);
             a.in = cur; a.out = o.y;
-            if (slots && !first_conv) { a.acc_scale_x = rows(h->xs_f, k); a.acc_scale_fan = LA_XS_FAN; }
-            if (slots && nxt >= 0) a.fwd_xs_out = rows(h->xs_f, nxt);
+            if (slots && !first_conv) { a.acc_scale_x = f_rows(h, h->xs_f, k); a.acc_scale_fan = LA_XS_FAN; }
+            if (slots && nxt >= 0) a.fwd_xs_out = f_rows(h, h->xs_f, nxt);
             if ((rc = la_conv_launch(a, stream))) return rc;
             first_conv = false;
             cur = o.y;
         } else if (o.kind == LA_FEAT_TAP) {
-            const int pl = tap_lanes(HWo);
-            hipLaunchKernelGGL(la_tap_fwd_kernel, dim3(la_cdiv(HWo, pl), N), dim3(256), 0, stream, cur, o.lin, feat_out, o.cout, HWo,
-                               (long)h->F, o.feat_off, pl);
+            tap(o, cur, HWo);
         } else if (f_is_fc(o.kind)) {
             // the activation in front is [N][C][res][res] contiguous: torch's flatten is a reinterpretation; the last FC writes the features
-            float* dst = k == h->nops - 1 ? feat_out : o.y;
+            float* dst = k == h->nops - 1 ? fc_out : o.y;
             if ((rc = la_fc_bias_act_f32(cur, o.w, o.bias, dst, N, o.cin, o.cout, o.kind == LA_FEAT_FC_RELU ? LA_ACT_RELU : LA_ACT_LINEAR, h->fcws,
                                          h->fcws_bytes, stream)))
                 return rc;
@@ -390,6 +391,17 @@ extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_ou
         }
     }
     LA_CHECK_LAUNCH();
+    return LA_OK;
+}
+
+extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_out, hipStream_t stream) {
+    LA_CHECK_ARG(h && x && feat_out, "feat_forward: null pointer");
+    LA_CHECK_ARG(N >= 1 && N <= h->maxN, "feat_forward: batch exceeds max_batch");
+    const int rc = f_trunk(h, x, N, feat_out, stream, [&](const FOp& o, const float* cur, int HWo) {
+        const int pl = tap_lanes(HWo);
+        hipLaunchKernelGGL(la_tap_fwd_kernel, dim3(la_cdiv(HWo, pl), N), dim3(256), 0, stream, cur, o.lin, feat_out, o.cout, HWo, (long)h->F, o.feat_off, pl);
+    });
+    if (rc) return rc;
     h->x_in = x; h->lastN = N;
     return LA_OK;
 }
@@ -407,9 +419,9 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
     // last -- the tap behind conv k (la_tap_bwd_kernel, mask fused), or the backward contraction of conv k+1 when it follows directly
     // (its epilogue applies the mask of its xin = y_k, LaConvArgs::seam) -- instead of an activation-backward sweep with plane maxima
     // and a scale-reduction launch per conv.  `masked`: g already carries op k's mask and its slot rows are final.
-    const bool slots = h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS");      // (dev knob: the round-3 passes)
+    const bool slots = f_slots(h);
     if (slots) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_b), (int)LA_XS_INIT, (size_t)h->nops * h->maxN * LA_XS_FAN, stream));
-    auto rows = [&](float* base, int op) { return base + (size_t)op * h->maxN * LA_XS_FAN; };
+    auto rows = [&](float* base, int op) { return f_rows(h, base, op); };
     bool masked = false;
     for (int k = h->nops - 1; k >= 0; --k) {
         FOp& o = h->op[k];
@@ -607,49 +619,25 @@ extern "C" size_t la_feat_pair_workspace_bytes(const la_feat* h, int P) {
     return la_align64(sizeof(double) * (size_t)P * t.n * t.tiles_max);
 }
 
-// dist [P][ntaps] (float64) = per tap, the LPIPS distance of rows p and p + P of xy [2P][in_ch][in_res^2]: the trunk of la_feat_forward
-// once on the 2P rows (its loop, repeated here because that entry stays as it is), the pair kernel where it launches the tap.  No host
-// sync, no allocation.  The activations of an earlier la_feat_forward are overwritten: la_feat_backward refuses until the next forward.
+// dist [P][ntaps] (float64) = per tap, the LPIPS distance of rows p and p + P of xy [2P][in_ch][in_res^2]: the trunk (f_trunk) once on the
+// 2P rows, the pair kernel as its tap step.  No host sync, no allocation.  The activations of an earlier la_feat_forward are overwritten:
+// la_feat_backward refuses until the next forward.
 extern "C" int la_feat_pair_distance(la_feat* h, const float* xy, int P, double* dist, void* ws, size_t ws_bytes, hipStream_t stream) {
     LA_CHECK_ARG(h && xy && dist && ws, "feat_pair_distance: null pointer");
     LA_CHECK_ARG(!h->detector, "feat_pair_distance: a detector list (fc ops) has no taps");
     LA_CHECK_ARG(P >= 1 && 2L * P <= h->maxN, "feat_pair_distance: 2 * pairs exceeds max_batch");
     if (ws_bytes < la_feat_pair_workspace_bytes(h, P)) { la_set_error("feat_pair_distance: workspace too small"); return LA_ERR_WORKSPACE; }
     LaPairTaps t; pair_taps(h, t);
-    const int N = 2 * P;
-    const float* cur = xy;
-    int rc, tap = 0;
+    int tap = 0;
     h->lastN = 0;
-    const bool slots = h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS");
-    if (slots) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_f), (int)LA_XS_INIT, (size_t)h->nops * h->maxN * LA_XS_FAN, stream));
-    auto rows = [&](float* base, int op) { return base + (size_t)op * h->maxN * LA_XS_FAN; };
-    bool first_conv = true;
-    for (int k = 0; k < h->nops; ++k) {
-        FOp& o = h->op[k];
-        const int HWo = o.res_out * o.res_out;
-        if (o.kind == LA_FEAT_CONV_RELU) {
-            int nxt = -1;
-            for (int q = k + 1; q < h->nops; ++q) if (h->op[q].kind == LA_FEAT_CONV_RELU) { nxt = q; break; }
-            LaConvArgs a; f_conv(a, h, o, false, N);
-            a.in = cur; a.out = o.y;
-            if (slots && !first_conv) { a.acc_scale_x = rows(h->xs_f, k); a.acc_scale_fan = LA_XS_FAN; }
-            if (slots && nxt >= 0) a.fwd_xs_out = rows(h->xs_f, nxt);
-            if ((rc = la_conv_launch(a, stream))) return rc;
-            first_conv = false;
-            cur = o.y;
-        } else if (o.kind == LA_FEAT_TAP) {
-            const int pl = tap_lanes(HWo), keep = pair_keep(o.cout, HWo);
-            auto kern = keep == 32 ? la_tap_pair_dist_kernel<32> : keep == 64 ? la_tap_pair_dist_kernel<64> : la_tap_pair_dist_kernel<0>;
-            hipLaunchKernelGGL(kern, dim3(t.tiles[tap], P), dim3(256), 0, stream, cur, o.lin, (double*)ws, o.cout, HWo, P, pl,
-                               (long)t.n * t.tiles_max, (long)tap * t.tiles_max);
-            ++tap;
-        } else {
-            const long planes = (long)N * o.cout;
-            hipLaunchKernelGGL(la_pool2_fwd_kernel, dim3(la_cdiv(planes * HWo, 256)), dim3(256), 0, stream, cur, o.y, o.res_in, planes,
-                               o.kind == LA_FEAT_MAXPOOL2);
-            cur = o.y;
-        }
-    }
+    const int rc = f_trunk(h, xy, 2 * P, nullptr, stream, [&](const FOp& o, const float* cur, int HWo) {
+        const int pl = tap_lanes(HWo), keep = pair_keep(o.cout, HWo);
+        auto kern = keep == 32 ? la_tap_pair_dist_kernel<32> : keep == 64 ? la_tap_pair_dist_kernel<64> : la_tap_pair_dist_kernel<0>;
+        hipLaunchKernelGGL(kern, dim3(t.tiles[tap], P), dim3(256), 0, stream, cur, o.lin, (double*)ws, o.cout, HWo, P, pl,
+                           (long)t.n * t.tiles_max, (long)tap * t.tiles_max);
+        ++tap;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(la_pair_dist_finish_kernel, dim3(t.n, P), dim3(64), 0, stream, (const double*)ws, dist, t);
     LA_CHECK_LAUNCH();
     return LA_OK;

@@ -64,6 +64,8 @@ struct LaTorgbMask { const float* y; int act; float alpha, gain, clamp; };
 int la_torgb_forward(const float* x, const LaRgbFuse& r, int B, int C, int H, int W, hipStream_t, const LaTorgbMask* mask = nullptr, int row_lo = 0,
                      int row_hi = 0, const float* skip_lo = nullptr, const float* fir_host = nullptr);      // skip_lo + fir_host: the block below's image, up-sampled inside the kernel
 // row_lo / row_hi (planes above 64x64; 0 / 0 = all): only these rows of rgb_pre / img are computed and written
+// la_torgb_forward's kernel choice: planes up to 64x64 take the small kernel (whole planes: no row window, no mask), larger ones the large
+static inline bool la_torgb_small(long HW) { return HW <= 4096; }
 int la_seam_slabs(long HW);
 int la_seam_backward(const LaSeamArgs& a, int B, int imgc, hipStream_t);
 // Style-gradient finish of ALL layers of one backward pass in three launches (row sums of every partial buffer, conv layers,

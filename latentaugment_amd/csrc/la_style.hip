@@ -405,13 +405,13 @@ int la_torgb_forward(const float* x, const LaRgbFuse& r, int B, int C, int H, in
     const long p_lo = (long)row_lo * W, p_hi = (long)row_hi * W;
     LaTorgbMask mk{nullptr, 0, 0.f, 0.f, 0.f};
     if (mask) mk = *mask;
-    LA_CHECK_ARG(!mk.y || HW > 4096, "torgb: the fused activation backward exists for planes above 64x64 only");
+    LA_CHECK_ARG(!mk.y || !la_torgb_small(HW), "torgb: the fused activation backward exists for planes above 64x64 only");
     LA_CHECK_ARG(HW % 4 == 0, "torgb: H*W must be a multiple of 4");
     LA_CHECK_ARG(imgc >= 1 && imgc <= 4, "torgb: img_channels must be 1..4");
     // launch profiler: x streamed once (+ the image-sized outputs / skip)
     struct Bracket { int slot; hipStream_t st; ~Bracket() { la_prof_close(slot, st); } }
         br{la_prof_open(LA_PC_TORGB, 2.0 * B * imgc * (double)C * HW, 4.0 * B * ((double)C * HW + (skip ? 3.0 : 2.0) * imgc * (double)HW), stream), stream};
-    if (HW <= 4096) {
+    if (la_torgb_small(HW)) {
         const long nq = HW / 4;
         int px_lanes = 1;
         while (px_lanes < 64 && px_lanes * 2 <= nq) px_lanes *= 2;

@@ -34,6 +34,18 @@ struct RgbLayer {
     float* dwep;            // ToRGB weight-gradient partials [maxB][imgc][cin][slabs]
 };
 
+// What a forward pass and the backward pass that differentiates it decide before they launch anything.  plan_pass builds the record on the
+// host (no handle memory, no stream, no launch), la_synth_forward stores it in the handle, both passes execute it, la_synth_plan_query shows
+// it: every member is an int, in the order of the LA_SYNTH_PLAN_* constants of include/latentaug_hip.h, which describes each of them.
+struct SynthPlan {
+    struct Pass { int nblocks, nconv, B, precision, f16, xs_hand, zt_dense, cone; } pass;      // (B = 0: no pass planned)
+    // per conv layer; rows: what its backward launch reads (in) of the gradient of its output and writes (out) of the gradient of its input
+    struct Layer { LaWindow fwd; int cone_lo, cone_hi, win; LaBwdRows rows; int seam, seam_pmax, pmax_in, nseg, ntiles; } conv[2 * MAX_BLOCKS];
+    struct Block { int fuse_rgb, skip_up, img_lo, img_hi, down_fir, pyramid; } blk[MAX_BLOCKS];
+};
+static_assert(sizeof(SynthPlan::Pass) == LA_SYNTH_PLAN_PASS_N * sizeof(int) && sizeof(SynthPlan::Layer) == LA_SYNTH_PLAN_LAYER_N * sizeof(int) &&
+              sizeof(SynthPlan::Block) == LA_SYNTH_PLAN_BLOCK_N * sizeof(int) && sizeof(SynthPlan) == LA_SYNTH_PLAN_NINFO * sizeof(int), "SynthPlan and its query disagree");
+
 struct la_synth {
     int R, imgc, wdim, nblocks, num_ws, maxB;
     int channels[MAX_BLOCKS];
@@ -58,33 +70,35 @@ struct la_synth {
     float* xs_fwd;           // [nconv][B][LA_XS_FAN] slot rows: fp16 operand scales of the forward contractions (from the clamp bound, one launch per pass)
     float* xs_bwd;           // [nconv][B][LA_XS_FAN] slot rows: running fp16 operand scales of the backward contractions' inputs, lowered by the producing kernels
     float* xs_mult;          // [nconv][B]: max_i |style| of every conv layer = what the producer of its input multiplies its max |x| with
-    int lastB;
     int precision;
     float* final_img;   // where the last forward put the full-resolution image
-    int win_lo, win_hi;  // row window of the image the next forward passes are asked for (la_synth_set_row_window; 0 / 0 = the whole image)
-    int wcol_lo, wcol_hi;      // ... and its column window (la_synth_set_col_window; top block only)
-    int fw_c0, fw_c1;          // column window (32-column tiles) of the top block's conv1 output in the LAST forward pass (0 / 0 = all)
-    int fw_lo[2 * MAX_BLOCKS], fw_hi[2 * MAX_BLOCKS];      // row windows of the conv outputs in the LAST forward pass (0 / 0 = whole plane)
-    int bw_lo[2 * MAX_BLOCKS], bw_hi[2 * MAX_BLOCKS];      // ... and the rows in which the gradient of those outputs can be non-zero (plan_row_windows; 0 / 0 = whole plane)
+    LaWindow win;       // window of the image the next forward passes are asked for (la_synth_set_row_window / _col_window; 0 / 0 on an axis = all)
+    SynthPlan plan;     // of the LAST forward pass: what it ran and what its backward pass runs
+    const float* g_top; // image gradient the running backward pass was handed (top block)
+    float up_mult;      // la_modconv_up2_bwd_xs_mult of the filter
 };
 
-// Row windows of a pass for the image row window [win_lo, win_hi) (la_synth_set_row_window), top block downwards until a window is the whole
-// plane.
-//   wlo / whi  what the FORWARD pass computes of every conv output: conv1 in 4-row tiles around what the image / the block above need, conv0
+enum { SEAM_KERNEL = LA_SYNTH_SEAM_KERNEL, SEAM_FUSED = LA_SYNTH_SEAM_FUSED, PMAX_NONE = LA_SYNTH_PMAX_NONE, PMAX_1, PMAX_2, PMAX_3 };
+
+// Windows of a pass (P.pass.nblocks / nconv set, the rest zero) for the image window `img`, top block downwards until a row window is the
+// whole plane.
+//   fwd rows   what the FORWARD pass computes of every conv output: conv1 in 4-row tiles around what the image / the block above need, conv0
 //              (FIR output) one row more on either side, the block below what conv0's transposed conv reads (la_modconv3x3_up2_fwd_rows)
 //              and what the image up-sampling reads.  Everything a consumer reads must be exact, so the tile rounding of one level is part
 //              of the next level's need.
-//   ilo / ihi  image rows a block has to deliver
-//   blo / bhi  where the GRADIENT of a conv output can be non-zero: the same recursion WITHOUT the tile rounding (a row that was computed
+//   img_lo/hi  image rows a block has to deliver (kept where the large ToRGB kernel runs: la_torgb_small)
+//   cone       where the GRADIENT of a conv output can be non-zero: the same recursion WITHOUT the tile rounding (a row that was computed
 //              only because a tile had to be whole feeds nothing that is read, its gradient is an exact zero) -- need of conv1, conv0 one
-//              row more, the block below what those conv0 rows read united with its image rows.  Inside wlo / whi by construction; set
+//              row more, the block below what those conv0 rows read united with its image rows.  Inside the fwd rows by construction; set
 //              for exactly the layers that have a forward window.  The backward launches round them to their own tiles, once.
-struct SynthRowPlan { int wlo[2 * MAX_BLOCKS], whi[2 * MAX_BLOCKS], ilo[MAX_BLOCKS], ihi[MAX_BLOCKS], blo[2 * MAX_BLOCKS], bhi[2 * MAX_BLOCKS]; };
-static void plan_row_windows(int nblocks, int nconv, int win_lo, int win_hi, SynthRowPlan& p) {
-    memset(&p, 0, sizeof(p));
-    if (win_hi <= 0) return;
-    int img_lo = win_lo, img_hi = win_hi, up_lo = 0, up_hi = 0;      // needs of block k: image rows, rows read by block k + 1
-    int gup_lo = 0, gup_hi = 0;                                       // (gradient cone: rows read by the NEEDED conv0 rows of block k + 1)
+//   fwd cols   top block only, where its conv1 has a row window: conv1 in the 32-column tiles that hold the image columns with a tile column
+//              to spare on both sides (the gradient of conv1's input reaches one column beyond the image window: it must stay inside the
+//              tiles), the FIR in front of it (conv0) one column more on either side.
+static void plan_windows(SynthPlan& P, const LaWindow& img) {
+    const int nblocks = P.pass.nblocks, nconv = P.pass.nconv, R = 4 << (nblocks - 1);
+    if (img.row_hi <= 0) return;
+    int img_lo = img.row_lo, img_hi = img.row_hi, up_lo = 0, up_hi = 0;      // needs of block k: image rows, rows read by block k + 1
+    int gup_lo = 0, gup_hi = 0;                                               // (gradient cone: rows read by the NEEDED conv0 rows of block k + 1)
     for (int k = nblocks - 1, c1 = nconv - 1; k >= 1; --k, c1 -= 2) {
         const int res = 4 << k;
         if (res < 64) break;
@@ -93,37 +107,94 @@ static void plan_row_windows(int nblocks, int nconv, int win_lo, int win_hi, Syn
         if (gup_hi > 0) { glo = gup_lo < glo ? gup_lo : glo; ghi = gup_hi > ghi ? gup_hi : ghi; }
         la_span_tiles(lo, hi, 4, res);
         if (lo <= 0 && hi >= res) break;                      // everything is needed from here down
-        p.wlo[c1] = lo; p.whi[c1] = hi;
-        p.blo[c1] = glo; p.bhi[c1] = ghi;
-        p.ilo[k] = img_lo; p.ihi[k] = img_hi;
-        int l0 = lo, h0 = hi;
-        la_span_grow(l0, h0, 1, 1, res);
-        p.wlo[c1 - 1] = l0; p.whi[c1 - 1] = h0;
-        la_modconv3x3_up2_fwd_rows(res, l0, h0, &up_lo, &up_hi);
+        SynthPlan::Layer &L1 = P.conv[c1], &L0 = P.conv[c1 - 1];
+        L1.fwd.row_lo = lo; L1.fwd.row_hi = hi;
+        L1.cone_lo = glo; L1.cone_hi = ghi;
+        if (!la_torgb_small((long)res * res)) { P.blk[k].img_lo = img_lo; P.blk[k].img_hi = img_hi; }
+        la_span_grow(lo, hi, 1, 1, res);
+        L0.fwd.row_lo = lo; L0.fwd.row_hi = hi;
+        la_modconv3x3_up2_fwd_rows(res, lo, hi, &up_lo, &up_hi);
         la_span_grow(glo, ghi, 1, 1, res);
-        p.blo[c1 - 1] = glo; p.bhi[c1 - 1] = ghi;
+        L0.cone_lo = glo; L0.cone_hi = ghi;
         la_modconv3x3_up2_fwd_rows(res, glo, ghi, &gup_lo, &gup_hi);
         img_lo = (img_lo - 2) >> 1; if (img_lo < 0) img_lo = 0;
         img_hi = (img_hi >> 1) + 1; if (img_hi > res / 2) img_hi = res / 2;
     }
-}
-// Column window (32-column tiles) of the top block's conv1 for the image column window [wcol_lo, wcol_hi): needs a tile column to spare on
-// both sides (the gradient of conv1's input reaches one column beyond the image window: it must stay inside the tiles).  0 / 0: all columns.
-static void plan_col_window(int R, int wcol_lo, int wcol_hi, int& c1lo, int& c1hi) {
-    c1lo = c1hi = 0;
-    if (wcol_hi <= 0 || R < 64) return;
-    int lo = wcol_lo, hi = wcol_hi;
+    LaWindow& c1w = P.conv[nconv - 1].fwd;
+    if (c1w.row_hi <= 0 || img.col_hi <= 0 || R < 64) return;
+    int lo = img.col_lo, hi = img.col_hi;
     la_span_tiles(lo, hi, 32, R);
-    if (wcol_lo - 1 >= lo && wcol_hi + 1 <= hi && (lo > 0 || hi < R)) { c1lo = lo; c1hi = hi; }
+    if (!(img.col_lo - 1 >= lo && img.col_hi + 1 <= hi && (lo > 0 || hi < R))) return;
+    c1w.col_lo = lo; c1w.col_hi = hi;
+    la_span_grow(lo, hi, 1, 1, R);
+    P.conv[nconv - 2].fwd.col_lo = lo; P.conv[nconv - 2].fwd.col_hi = hi;
+}
+
+// The plan of a pass of `nblocks` blocks with the channel table, B samples, the contraction precision and the image window.  The development
+// switches are read here and nowhere else, once per process.
+static void plan_pass(int nblocks, const int* channels, int B, int precision, const LaWindow& img, SynthPlan& P) {
+    static const bool zt_dense = la_dev_env("LA_NO_ZT_PITCH") != nullptr;      // dense interleaved scratch rows + the scalar FIR kernel
+    static const bool no_fuse = la_dev_env("LA_NO_SEAM_FUSE") != nullptr, no_fuse2 = la_dev_env("LA_NO_SEAM2_FUSE") != nullptr;      // A/B of the fused seams on one box
+    static const bool no_xs = la_dev_env("LA_NO_XS_HANDOFF") != nullptr;       // plane maxima + la_xscale_pmax at the consumer
+    memset(&P, 0, sizeof(P));
+    const int top = nblocks - 1;
+    const bool b16 = precision != LA_PREC_F32, f16 = precision == LA_PREC_F16X2, xs_hand = f16 && !no_xs;
+    // 16-bit modes: a conv0 seam runs in the epilogue of conv1's backward contraction (its saved output is that contraction's xin: no pass
+    // of its own over y0 and the gradient), a conv1 seam incl. its ToRGB backward in the epilogue of the up layer's backward one block up
+    const bool fuse0 = b16 && !no_fuse, fuse1 = b16 && !no_fuse2;
+    // the cone needs the default path (fused seams, slot rows) and an image gradient that is zero outside the image window
+    P.pass = {nblocks, 2 * nblocks - 1, B, precision, f16, xs_hand, zt_dense, xs_hand && fuse0 && fuse1};
+    // row / column windows: 16-bit kernels with the column-planar scratch only
+    if (b16 && !zt_dense) plan_windows(P, img);
+    auto seam = [&](SynthPlan::Layer& L, bool fused, int fused_buf, int tiles, int slabs) {
+        L.seam = fused ? SEAM_FUSED : SEAM_KERNEL;
+        L.nseg = fused ? tiles : slabs;      // granularity of the layer's ddn / dweff / plane-maxima partials
+        L.pmax_in = !f16 ? PMAX_NONE : fused ? fused_buf : PMAX_1;
+        L.seam_pmax = (fused || !xs_hand) ? L.pmax_in : PMAX_NONE;      // (a seam kernel lowers the slot row instead where rows are handed on)
+    };
+    auto cone_tiles = [](const SynthPlan::Layer& of, int res, LaWindow& w) {      // the 4-row tiles around the gradient rows of a conv output
+        w.row_lo = of.cone_lo; w.row_hi = of.cone_hi;
+        la_span_tiles(w.row_lo, w.row_hi, 4, res);
+    };
+    bool pyramid_done = false;
+    for (int k = top; k >= 0; --k) {
+        const int res = 4 << k, slabs = la_seam_slabs((long)res * res), tiles1 = la_modconv_ds_tiles(res);
+        SynthPlan::Block& Bk = P.blk[k];
+        SynthPlan::Layer& L1 = P.conv[2 * k];
+        // ToRGB inside the epilogue of the block's conv1 where one row tile of the halo kernel holds all its channels (the top blocks:
+        // <= 128 channels at >= 64^2) -- conv1's output is then not streamed a second time; the skip image has to exist before conv1 runs
+        Bk.fuse_rgb = la_modconv3x3_fwd_fuses_rgb(precision, B, channels[k], channels[k], res);
+        Bk.skip_up = k > 0 && Bk.fuse_rgb;
+        seam(L1, k < top && fuse1, PMAX_3, tiles1, slabs);
+        L1.ntiles = tiles1;
+        if (k == 0) break;
+        SynthPlan::Layer& L0 = P.conv[2 * k - 1];
+        seam(L0, fuse0, PMAX_2, tiles1, slabs);
+        L0.ntiles = la_modconv_ds_tiles(res / 2);
+        // image-gradient levels: a down-FIR per block until one launch makes every level below (la_image_grad_pyramid, from <= 256^2 inputs)
+        Bk.down_fir = !pyramid_done;
+        Bk.pyramid = Bk.down_fir && k >= 2 && res / 2 <= 256;
+        pyramid_done |= Bk.pyramid != 0;
+        // cone: conv1's backward contraction reads the tiles around the gradient rows of conv1's output (what the seam kernel or the block
+        // above wrote into G0) and writes those of conv0's output into G1 -- top block: in the window's tile columns, the FIR adjoint reads
+        // the others as zeros; the up layer's backward reads these and writes the tiles around the gradient rows of the block below's conv1 output
+        if (!(P.pass.cone && L1.cone_hi > 0)) continue;
+        L1.win = L0.win = 1;
+        cone_tiles(L1, res, L1.rows.in);
+        cone_tiles(L0, res, L1.rows.out);
+        if (k == top) { L1.rows.out.col_lo = L1.fwd.col_lo; L1.rows.out.col_hi = L1.fwd.col_hi; }
+        L0.rows.in = L1.rows.out;
+        if (P.conv[2 * k - 2].cone_hi > 0) cone_tiles(P.conv[2 * k - 2], res / 2, L0.rows.out);
+    }
 }
 
 // a layer's epilogue (SynthesisLayer.forward: lrelu, gain sqrt(2), conv_clamp) with the noise the last forward pass used ...
 static LaLayerEpi layer_epi(const la_synth* h, const ConvLayer& L) {
     return LaLayerEpi{h->d_all + L.d_off, h->Dt, L.noise_used, L.noise_bstride, L.noise_strength, L.bias, LA_ACT_LRELU, 0.2f, sqrtf(2.f), h->clamp};
 }
-// ... and its contraction, forward or backward
+// ... and its contraction, forward or backward, in the arithmetic the pass was planned for
 static LaModconv layer_conv(const la_synth* h, const ConvLayer& L, int B, bool backward) {
-    return LaModconv{backward ? L.wb : L.wf, backward ? L.wqb : L.wqf, h->precision, h->s_all + L.s_off, h->S, B, L.cin, L.cout, L.res, h->cws, h->cws_bytes};
+    return LaModconv{backward ? L.wb : L.wf, backward ? L.wqb : L.wqf, h->plan.pass.precision, h->s_all + L.s_off, h->S, B, L.cin, L.cout, L.res, h->cws, h->cws_bytes};
 }
 // the block's ToRGB layer writing its image to `img`
 static LaRgbFuse layer_rgb(const la_synth* h, const RgbLayer& T, const float* skip, float* img) {
@@ -135,8 +206,7 @@ static inline int zt_xhalf(int res) { return (res / 2 + 1 + 3) & ~3; }
 static int layout(la_synth* h, void* workspace, size_t cap, size_t* need) {
     LaCarver c{(char*)workspace, 0, cap};
     const size_t mb = h->maxB;
-    size_t gmax = 0, ztmax = 0, dsp = 0, ddn = 0, dwe = 0;
-    size_t skf = 0;
+    size_t gmax = 0, ztmax = 0, skf = 0;
     for (int k = 0; k < h->nconv; ++k) {
         ConvLayer& L = h->conv[k];
         la_conv_weights_layout(c, L, true);
@@ -154,10 +224,6 @@ static int layout(la_synth* h, void* workspace, size_t cap, size_t* need) {
             L.dsp = c.take(mb * L.cin * (size_t)la_conv_tiles_per_sample(gin, gin));
             L.ddnp = c.take(mb * L.cout * (sl0 > t1 ? sl0 : t1));
         }
-        const size_t t = mb * L.cin * (size_t)la_conv_tiles_per_sample(gin, gin);
-        if (t > dsp) dsp = t;
-        const size_t sl = mb * L.cout * (size_t)la_seam_slabs((long)hw);
-        if (sl > ddn) ddn = sl;
         const size_t sk = la_modconv_workspace_bytes((int)mb, L.cin, L.cout, L.res, L.up);
         if (sk > skf) skf = sk;
     }
@@ -171,8 +237,6 @@ static int layout(la_synth* h, void* workspace, size_t cap, size_t* need) {
             const size_t sl0 = (size_t)la_seam_slabs((long)hw), t1 = (size_t)la_conv_tiles_per_sample(T.res, T.res);
             T.dwep = c.take(mb * h->imgc * T.cin * (sl0 > t1 ? sl0 : t1));
         }
-        const size_t sl = mb * h->imgc * T.cin * (size_t)la_seam_slabs((long)hw);
-        if (sl > dwe) dwe = sl;
     }
     h->s_all = c.take(mb * h->S);
     h->ds_all = c.take(mb * h->S);
@@ -183,31 +247,21 @@ static int layout(la_synth* h, void* workspace, size_t cap, size_t* need) {
     h->aff_part = c.take((size_t)la_affine_bwd_chunks(h->st) * mb * h->wdim);
     h->cws = c.take((skf + 3) / 4);
     h->cws_bytes = skf;
-    {
-        // plane-maxima hand-off buffer: [B][C][segments] of the largest producer (FIR epilogue of an up layer, seam kernel)
-        size_t pmx = 0;
-        for (int k = 0; k < h->nconv; ++k) {
-            const ConvLayer& L = h->conv[k];
-            const size_t a = (size_t)L.cout * (L.up ? la_fir4x4_segments(L.res, L.res) : 1), b2 = (size_t)L.cout * la_seam_slabs((long)L.res * L.res);
-            if (a > pmx) pmx = a;
-            if (b2 > pmx) pmx = b2;
-        }
-        h->pmax = c.take(mb * pmx);
-    }
-    {
-        size_t f2 = 0;
-        for (int k = 0; k < h->nconv; ++k) {
-            const ConvLayer& L = h->conv[k];
-            if (L.up) { const size_t n = mb * L.cout * (size_t)la_conv_tiles_per_sample(L.res, L.res); if (n > f2) f2 = n; }
-        }
-        h->pmax2 = c.take(f2 ? f2 : 16);
-        size_t f3 = 0;
-        for (int k = 0; k < h->nconv; ++k) {
-            const ConvLayer& L = h->conv[k];
-            if (!L.up) { const size_t n = mb * L.cout * (size_t)la_conv_tiles_per_sample(L.res, L.res); if (n > f3) f3 = n; }
-        }
-        h->pmax3 = c.take(f3 ? f3 : 16);
-    }
+    // plane-maxima buffers, each [B][C][segments] of its largest producer: pmax the FIR epilogue of an up layer and the seam kernel, pmax2 /
+    // pmax3 the fused seams of the up layers / of the conv1 layers (contraction tiles)
+    auto largest = [&](auto per_layer) {
+        size_t m = 0;
+        for (int k = 0; k < h->nconv; ++k) { const size_t n = per_layer(h->conv[k]); if (n > m) m = n; }
+        return m;
+    };
+    auto tiles_of = [&](const ConvLayer& L) { return mb * L.cout * (size_t)la_conv_tiles_per_sample(L.res, L.res); };
+    h->pmax = c.take(mb * largest([](const ConvLayer& L) {
+        const size_t a = (size_t)L.cout * (L.up ? la_fir4x4_segments(L.res, L.res) : 1), b2 = (size_t)L.cout * la_seam_slabs((long)L.res * L.res);
+        return a > b2 ? a : b2;
+    }));
+    const size_t f2 = largest([&](const ConvLayer& L) { return L.up ? tiles_of(L) : 0; }), f3 = largest([&](const ConvLayer& L) { return L.up ? 0 : tiles_of(L); });
+    h->pmax2 = c.take(f2 ? f2 : 16);
+    h->pmax3 = c.take(f3 ? f3 : 16);
     h->xs_fwd = c.take((size_t)h->nconv * mb * LA_XS_FAN);
     h->xs_bwd = c.take((size_t)h->nconv * mb * LA_XS_FAN);
     h->xs_mult = c.take((size_t)h->nconv * mb + 16);
@@ -301,11 +355,11 @@ extern "C" int la_synth_create(int img_resolution, int img_channels, int w_dim, 
     layout(h, workspace, workspace_bytes, &need);
     if (need > workspace_bytes) { la_set_error("synth_create: workspace too small"); return LA_ERR_WORKSPACE; }
     h->clamp = conv_clamp;
-    h->win_lo = h->win_hi = 0; h->wcol_lo = h->wcol_hi = 0; h->fw_c0 = h->fw_c1 = 0;
     // every buffer starts as zeros: a forward pass restricted to a row window (la_synth_set_row_window) leaves the other rows of its saved
     // activations as they were, and the backward pass multiplies them with gradients that are exactly zero there -- they must be finite
     if (hipMemsetAsync(workspace, 0, need, stream) != hipSuccess) { la_set_error("synth_create: clearing the workspace failed"); return LA_ERR_HIP; }
     memcpy(h->fir, fir_host, sizeof(float) * 16);
+    h->up_mult = la_modconv_up2_bwd_xs_mult(h->fir);
     int p = 0, ci = 0;
     for (int k = 0; k < h->nblocks; ++k) {
         if (k == 0) h->cst = params[p++];
@@ -324,7 +378,6 @@ extern "C" int la_synth_create(int img_resolution, int img_channels, int w_dim, 
         T.affine_w = params[p++]; T.affine_b = params[p++]; T.weight = params[p++]; T.bias = params[p++];
         h->st.aw[T.style_idx] = T.affine_w; h->st.ab[T.style_idx] = T.affine_b;
     }
-    h->lastB = 0;
     *out = own.release();
     return LA_OK;
 }
@@ -353,7 +406,7 @@ extern "C" int la_synth_set_operand_scale(la_synth* h, int from_data) {
 // backward pass is unchanged: image-gradient rows outside the window must be zero (they are for a criterion that reads the window only).
 extern "C" int la_synth_set_row_window(la_synth* h, int row_lo, int row_hi) {
     LA_CHECK_ARG(h && row_lo >= 0 && (row_hi == 0 ? row_lo == 0 : (row_hi > row_lo && row_hi <= h->R)), "synth_set_row_window: bad window");
-    h->win_lo = row_lo; h->win_hi = row_hi;
+    h->win.row_lo = row_lo; h->win.row_hi = row_hi;
     return LA_OK;
 }
 
@@ -362,7 +415,7 @@ extern "C" int la_synth_set_row_window(la_synth* h, int row_lo, int row_hi) {
 // feeds it and the FIR adjoint behind it (which reads the other columns as zeros); every other kernel computes whole rows.
 extern "C" int la_synth_set_col_window(la_synth* h, int col_lo, int col_hi) {
     LA_CHECK_ARG(h && col_lo >= 0 && (col_hi == 0 ? col_lo == 0 : (col_hi > col_lo && col_hi <= h->R)), "synth_set_col_window: bad window");
-    h->wcol_lo = col_lo; h->wcol_hi = col_hi;
+    h->win.col_lo = col_lo; h->win.col_hi = col_hi;
     return LA_OK;
 }
 
@@ -375,18 +428,34 @@ extern "C" int la_synth_plan_bwd_window(int img_resolution, int row_lo, int row_
     LA_CHECK_ARG(R >= 4 && (R & (R - 1)) == 0 && R <= 4096 && window, "synth_plan_bwd_window: resolution must be a power of two >= 4");
     LA_CHECK_ARG(row_lo >= 0 && (row_hi == 0 ? row_lo == 0 : (row_hi > row_lo && row_hi <= R)), "synth_plan_bwd_window: bad row window");
     LA_CHECK_ARG(col_lo >= 0 && (col_hi == 0 ? col_lo == 0 : (col_hi > col_lo && col_hi <= R)), "synth_plan_bwd_window: bad column window");
-    const int nblocks = la_synth_num_ws(R) / 2, nconv = 2 * nblocks - 1;
-    LA_CHECK_ARG(conv_index >= 0 && conv_index < nconv, "synth_plan_bwd_window: no such conv layer");
-    SynthRowPlan plan;
-    plan_row_windows(nblocks, nconv, row_lo, row_hi, plan);
-    window[0] = plan.blo[conv_index]; window[1] = plan.bhi[conv_index]; window[2] = window[3] = 0;
-    if (conv_index == nconv - 2 && plan.whi[nconv - 1] > 0) plan_col_window(R, col_lo, col_hi, window[2], window[3]);
+    SynthPlan P; memset(&P, 0, sizeof(P));
+    P.pass.nblocks = la_synth_num_ws(R) / 2; P.pass.nconv = 2 * P.pass.nblocks - 1;
+    LA_CHECK_ARG(conv_index >= 0 && conv_index < P.pass.nconv, "synth_plan_bwd_window: no such conv layer");
+    plan_windows(P, LaWindow{row_lo, row_hi, col_lo, col_hi});
+    const LaWindow none = {}, &c1w = conv_index == P.pass.nconv - 2 ? P.conv[conv_index + 1].fwd : none;      // (written by the top conv1's backward)
+    window[0] = P.conv[conv_index].cone_lo; window[1] = P.conv[conv_index].cone_hi; window[2] = c1w.col_lo; window[3] = c1w.col_hi;
     return LA_OK;
 }
-// ... and what the LAST forward pass of a handle recorded for its backward pass (rows only)
+// ... and what the LAST forward pass of a handle planned for its backward pass (rows only)
 extern "C" int la_synth_bwd_rows(const la_synth* h, int conv_index, int* row_lo, int* row_hi) {
     LA_CHECK_ARG(h && row_lo && row_hi && conv_index >= 0 && conv_index < h->nconv, "synth_bwd_rows: no such conv layer");
-    *row_lo = h->bw_lo[conv_index]; *row_hi = h->bw_hi[conv_index];
+    *row_lo = h->plan.conv[conv_index].cone_lo; *row_hi = h->plan.conv[conv_index].cone_hi;
+    return LA_OK;
+}
+// Host only, no launch, no handle: the whole plan of a pass as info[LA_SYNTH_PLAN_NINFO] (include/latentaug_hip.h)
+extern "C" int la_synth_plan_query(int img_resolution, int img_channels, const int* channels, int B, int precision, int row_lo, int row_hi, int col_lo,
+                                   int col_hi, long* info) {
+    const int R = img_resolution;
+    LA_CHECK_ARG(R >= 4 && (R & (R - 1)) == 0 && R <= 4096 && channels && info, "synth_plan_query: resolution must be a power of two >= 4");
+    LA_CHECK_ARG(img_channels >= 1 && img_channels <= 4 && B >= 1 && precision >= 0 && precision <= 3, "synth_plan_query: bad img_channels / batch / precision");
+    LA_CHECK_ARG(row_lo >= 0 && (row_hi == 0 ? row_lo == 0 : (row_hi > row_lo && row_hi <= R)), "synth_plan_query: bad row window");
+    LA_CHECK_ARG(col_lo >= 0 && (col_hi == 0 ? col_lo == 0 : (col_hi > col_lo && col_hi <= R)), "synth_plan_query: bad column window");
+    const int nblocks = la_synth_num_ws(R) / 2;
+    for (int k = 0; k < nblocks; ++k) LA_CHECK_ARG(channels[k] >= 4 && channels[k] % 4 == 0, "synth_plan_query: channel counts must be multiples of 4");
+    SynthPlan P;
+    plan_pass(nblocks, channels, B, precision, LaWindow{row_lo, row_hi, col_lo, col_hi}, P);
+    const int* src = reinterpret_cast<const int*>(&P);      // (ints throughout, in the order of the constants: the static_assert above)
+    for (int i = 0; i < LA_SYNTH_PLAN_NINFO; ++i) info[i] = src[i];
     return LA_OK;
 }
 
@@ -407,239 +476,176 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
     LA_CHECK_ARG(B >= 1 && B <= h->maxB, "synth_forward: batch exceeds the max_batch the workspace was sized for");
     LA_CHECK_ARG(noise_mode >= 0 && noise_mode <= 2, "synth_forward: noise_mode must be 0 (none), 1 (const), 2 (explicit)");
     LA_CHECK_ARG(noise_mode != 2 || noises, "synth_forward: explicit noise requested but no noise tensors given");
+    for (int ci = 0; ci < h->nconv && noise_mode == 2; ++ci) LA_CHECK_ARG(h->conv[ci].noise_strength == 0.f || noises[ci], "synth_forward: missing noise tensor");
+    plan_pass(h->nblocks, h->channels, B, h->precision, h->win, h->plan);
+    const SynthPlan& P = h->plan;
     int rc;
     if ((rc = la_affine_forward(h->st, ws, ws_bstride, ws_lstride, B, h->wdim, h->s_all, stream))) return rc;
     if ((rc = la_demod_forward(h->dt, h->s_all, h->S, B, h->d_all, stream))) return rc;
-    h->lastB = B;
-    const bool f16 = h->precision == LA_PREC_F16X2;
-    // scratch layout of the up layers: column-planar rows (dev knob LA_NO_ZT_PITCH: dense interleaved rows + the scalar FIR kernel)
-    static const bool zt_dense = la_dev_env("LA_NO_ZT_PITCH") != nullptr;
     // fp16 operand scales: the slot rows of every layer start the pass at LA_XS_INIT; the kernel that PRODUCES a layer's input lowers
     // that layer's row (forward: xs_fwd, la_xs_lower with max|style| of the consuming layer; backward: xs_bwd)
-    if (f16 && (rc = la_xscale_from_bounds(h->dt, h->s_all, h->S, h->cst, h->channels[0] * 16, h->xs_fwd, h->xs_mult, B, stream, h->xs_bwd))) return rc;
-    auto fwd_row = [&](int conv_index) { return (f16 && conv_index < h->nconv) ? h->xs_fwd + (long)conv_index * B * LA_XS_FAN : nullptr; };
-    auto fwd_mult = [&](int conv_index) { return (f16 && conv_index < h->nconv) ? h->xs_mult + (long)conv_index * B : nullptr; };
-    // row windows of the pass (plan_row_windows), 16-bit kernels with the column-planar scratch only
-    SynthRowPlan plan;
-    plan_row_windows(h->nblocks, h->nconv, (h->precision != LA_PREC_F32 && !zt_dense) ? h->win_lo : 0, (h->precision != LA_PREC_F32 && !zt_dense) ? h->win_hi : 0, plan);
-    const int *wlo = plan.wlo, *whi = plan.whi, *ilo = plan.ilo, *ihi = plan.ihi;
-    for (int i = 0; i < h->nconv; ++i) { h->fw_lo[i] = wlo[i]; h->fw_hi[i] = whi[i]; h->bw_lo[i] = plan.blo[i]; h->bw_hi[i] = plan.bhi[i]; }
-    // column window: the top block's conv1 in whole 32-column tiles, the FIR in front of it one column more on either side
-    int c1lo = 0, c1hi = 0, c0lo = 0, c0hi = 0;
-    if (whi[h->nconv - 1] > 0) plan_col_window(h->R, h->wcol_lo, h->wcol_hi, c1lo, c1hi);
-    h->fw_c0 = c1lo; h->fw_c1 = c1hi;
-    if (c1hi > 0) { c0lo = c1lo; c0hi = c1hi; la_span_grow(c0lo, c0hi, 1, 1, h->R); }
+    if (P.pass.f16 && (rc = la_xscale_from_bounds(h->dt, h->s_all, h->S, h->cst, h->channels[0] * 16, h->xs_fwd, h->xs_mult, B, stream, h->xs_bwd))) return rc;
+    auto fwd_row = [&](int conv_index) { return (P.pass.f16 && conv_index < h->nconv) ? h->xs_fwd + (long)conv_index * B * LA_XS_FAN : nullptr; };
+    auto fwd_mult = [&](int conv_index) { return (P.pass.f16 && conv_index < h->nconv) ? h->xs_mult + (long)conv_index * B : nullptr; };
     int ci = 0;
     const float* x = h->cst;
     long x_bstride = 0;
     for (int k = 0; k < h->nblocks; ++k) {
         const int res = 4 << k;
-        const int nl = (k == 0) ? 1 : 2;
         RgbLayer& T = h->rgb[k];
         float* const rgb_dst = (k == h->nblocks - 1 && img_out) ? img_out : T.img;
-        // ToRGB inside the epilogue of the block's conv1 where one row tile of the halo kernel holds all its channels (the top blocks:
-        // <= 128 channels at >= 64^2) -- conv1's output is then not streamed a second time
-        const bool fuse_rgb = la_modconv3x3_fwd_fuses_rgb(h->precision, B, h->conv[ci + nl - 1].cin, h->conv[ci + nl - 1].cout, res);
         const float* skip = nullptr;
-        if (k > 0 && fuse_rgb) {      // (the skip image has to exist before conv1 runs)
-            RgbLayer& P = h->rgb[k - 1];
-            if ((rc = la_upfirdn2d_ex(P.img, T.g_img, B, h->imgc, res / 2, res / 2, h->fir, la_fir_up2(), stream)))
-                return rc;
+        if (P.blk[k].skip_up) {
+            if ((rc = la_upfirdn2d_ex(h->rgb[k - 1].img, T.g_img, B, h->imgc, res / 2, res / 2, h->fir, la_fir_up2(), stream))) return rc;
             skip = T.g_img;
         }
-        for (int q = 0; q < nl; ++q, ++ci) {
+        for (int q = k == 0; q < 2; ++q, ++ci) {      // conv0 (up-sampling; none in the first block), conv1
             ConvLayer& L = h->conv[ci];
             L.noise_used = nullptr; L.noise_bstride = 0;
             if (L.noise_strength != 0.f) {
                 if (noise_mode == 1) L.noise_used = L.noise_const;
-                else if (noise_mode == 2) { L.noise_used = noises[ci]; L.noise_bstride = (long)res * res; LA_CHECK_ARG(L.noise_used, "synth_forward: missing noise tensor"); }
+                else if (noise_mode == 2) { L.noise_used = noises[ci]; L.noise_bstride = (long)res * res; }
             }
             const LaRgbFuse rf = layer_rgb(h, T, skip, rgb_dst);
             LaModconvFwdOpts o;
             o.xscale = fwd_row(ci); o.xs_out = fwd_row(ci + 1); o.xs_mult = fwd_mult(ci + 1);
-            o.win.row_lo = wlo[ci]; o.win.row_hi = whi[ci];
+            o.win = P.conv[ci].fwd;
             if (!L.up) {
-                if (fuse_rgb && q == nl - 1) o.rgb = &rf;
-                if (ci == h->nconv - 1) { o.win.col_lo = c1lo; o.win.col_hi = c1hi; }
+                if (P.blk[k].fuse_rgb) o.rgb = &rf;
                 rc = la_modconv3x3_fwd_ex(x, x_bstride, layer_conv(h, L, B, false), layer_epi(h, L), L.y, stream, o);
             } else {
-                if (!zt_dense) { o.scratch_pitch = 2 * zt_xhalf(res); o.scratch_xhalf = zt_xhalf(res); }
-                if (ci == h->nconv - 2) { o.win.col_lo = c0lo; o.win.col_hi = c0hi; }
+                if (!P.pass.zt_dense) { o.scratch_pitch = 2 * zt_xhalf(res); o.scratch_xhalf = zt_xhalf(res); }
                 rc = la_modconv3x3_up2_fwd_ex(x, x_bstride, layer_conv(h, L, B, false), layer_epi(h, L), h->fir, h->zT, L.y, stream, o);
             }
             if (rc) return rc;
             x = L.y; x_bstride = (long)L.cout * res * res;
         }
-        if (!fuse_rgb) {
-            // img = upsample2d(img_prev, f) + torgb(x): up 2, pad (2,1,2,1), gain 4 (upfirdn2d.py:342-348) -- the up-sampled image of the block
-            // below is computed inside the ToRGB kernel (la_up2_quad; round 4: a launch of its own per block, parked in g_img)
-            const float* skip_lo = k > 0 ? h->rgb[k - 1].img : nullptr;
-            const bool iw = ihi[k] > 0 && (long)res * res > 4096;      // (windowed block: only the image rows somebody reads)
-            if ((rc = la_torgb_forward(x, layer_rgb(h, T, nullptr, rgb_dst), B, T.cin, res, res, stream, nullptr, iw ? ilo[k] : 0, iw ? ihi[k] : 0,
-                                       skip_lo, h->fir)))
-                return rc;
-        }
+        // img = upsample2d(img_prev, f) + torgb(x): up 2, pad (2,1,2,1), gain 4 (upfirdn2d.py:342-348) -- the up-sampled image of the block
+        // below is computed inside the ToRGB kernel (la_up2_quad); a windowed block: only the image rows somebody reads
+        if (!P.blk[k].fuse_rgb && (rc = la_torgb_forward(x, layer_rgb(h, T, nullptr, rgb_dst), B, T.cin, res, res, stream, nullptr, P.blk[k].img_lo, P.blk[k].img_hi,
+                                                         k > 0 ? h->rgb[k - 1].img : nullptr, h->fir)))
+            return rc;
         if (k == h->nblocks - 1) h->final_img = rgb_dst;
     }
     return LA_OK;
 }
 
-extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hipStream_t stream) {
-    LA_CHECK_ARG(h && g_img && dws, "synth_backward: null pointer");
-    LA_CHECK_ARG(h->lastB >= 1, "synth_backward: no forward pass to differentiate");
-    const int B = h->lastB;
-    int rc;
-    const float* gi = g_img;   // gradient w.r.t. the image at the current resolution
-    int ci = h->nconv - 1;
-    const float* gx_next = nullptr;   // gradient w.r.t. this block's conv1 output coming from the block above
-    // every layer leaves its style-gradient partials in buffers of its own; ONE finish (3 launches) at the end of the pass turns
-    // them into ds_all (la_style_backward_all), instead of 3 small launches per layer
+// ---- backward pass: the parts of one block, each a function of (handle, plan, block, B, stream); la_synth_backward orders them by the plan.
+// Buffers: G0 holds the gradient of a block's conv1 output, G1 that of its conv0 output; every layer leaves its style-gradient partials in
+// buffers of its own until the finish.  fp16 operand scales: the kernels whose epilogues produce a contraction's input (direct contraction
+// kernels, split-K finish pass, seam kernel) lower the consumer's slot row themselves (la_xs_lower; la_synth_forward reset the rows) where
+// the plan hands rows on; else they leave plane maxima for la_xscale_pmax at the consumer.
+static float* pmax_buf(const la_synth* h, int which) { return which == PMAX_1 ? h->pmax : which == PMAX_2 ? h->pmax2 : which == PMAX_3 ? h->pmax3 : nullptr; }
+static float* bwd_slot(const la_synth* h, int ci) { return h->plan.pass.xs_hand ? h->xs_bwd + (long)ci * h->plan.pass.B * LA_XS_FAN : nullptr; }
+static const float* image_grad(const la_synth* h, int k) { return k == h->nblocks - 1 ? h->g_top : h->rgb[k].g_img; }
+// what the seam of conv layer ci's output needs wherever it runs (LaSeamArgs / LaSeamFuse): the layer's epilogue, its partials, the slot row
+// of the backward contraction that follows (xs_mult: 1, an up layer's la_modconv_up2_bwd_xs_mult)
+template <class S>
+static void seam_common(const la_synth* h, S& s, int ci) {
+    memset(&s, 0, sizeof(s));
+    la_seam_set_epi(s, layer_epi(h, h->conv[ci]));
+    s.ddn_part = h->conv[ci].ddnp;
+    if (h->plan.pass.xs_hand) { s.xs_out = bwd_slot(h, ci); s.xs_mult = h->conv[ci].up ? h->up_mult : 1.f; }
+}
+// a seam kernel's launch: conv layer ci's saved output, gz = (gx_next +) its ToRGB's share, through the activation backward
+static LaSeamArgs seam_kernel(const la_synth* h, int ci, const float* gx_next, float* gz) {
+    const ConvLayer& L = h->conv[ci];
+    LaSeamArgs s; seam_common(h, s, ci);
+    s.y = L.y; s.gx_next = gx_next; s.gz = gz; s.HW = (long)L.res * L.res; s.C = L.cout;
+    s.pmax_out = pmax_buf(h, h->plan.conv[ci].seam_pmax);
+    return s;
+}
+static LaModconvBwdOpts bwd_opts(const la_synth* h, int ci, const LaSeamFuse* seam) {
+    const SynthPlan::Layer& pl = h->plan.conv[ci];
+    LaModconvBwdOpts o;
+    o.in_pmax = pmax_buf(h, pl.pmax_in); o.in_nseg = pl.nseg; o.seam = seam; o.xscale = bwd_slot(h, ci); o.rows = pl.win ? &pl.rows : nullptr;
+    return o;
+}
+
+// conv1 seam as a kernel (top block, or where it was not fused above): ToRGB backward + activation backward at conv1's output
+static int bwd_conv1_seam(la_synth* h, const SynthPlan& P, int k, int B, hipStream_t stream) {
+    const RgbLayer& T = h->rgb[k];
+    const SynthPlan::Layer& pl = P.conv[2 * k];
+    LaSeamArgs s = seam_kernel(h, 2 * k, k == h->nblocks - 1 ? nullptr : h->G0, h->G0);
+    s.g_img = image_grad(h, k); s.rgb_pre = T.rgb_pre; s.rgb_clamp = h->clamp; s.wrgb = T.weight;
+    s.s_rgb = h->s_all + T.s_off; s.s_stride = h->S; s.dweff_part = T.dwep;
+    if (pl.win) { s.p_lo = (long)pl.rows.in.row_lo * T.res; s.p_hi = (long)pl.rows.in.row_hi * T.res; }
+    return la_seam_backward(s, B, h->imgc, stream);
+}
+// conv1 backward-data (+ style-gradient partials); where the plan fuses conv0's seam, this contraction's epilogue applies it (conv0's saved
+// output is its xin): its demod-gradient partials and plane maxima come out per pixel tile
+static int bwd_conv1_data(la_synth* h, const SynthPlan& P, int k, int B, hipStream_t stream) {
+    const ConvLayer& L1 = h->conv[2 * k];
+    LaSeamFuse sf;
+    const bool fused = k > 0 && P.conv[2 * k - 1].seam == SEAM_FUSED;
+    if (fused) { seam_common(h, sf, 2 * k - 1); sf.pmax = pmax_buf(h, P.conv[2 * k - 1].seam_pmax); }
+    return la_modconv3x3_bwd_ex(h->G0, layer_conv(h, L1, B, true), k == 0 ? h->cst : h->conv[2 * k - 1].y, k == 0 ? 0 : (long)L1.cin * L1.res * L1.res, h->G1,
+                                L1.dsp, stream, bwd_opts(h, 2 * k, fused ? &sf : nullptr));
+}
+// conv0 seam as a kernel: activation backward at the up-sampling layer's output, in place in G1
+static int bwd_conv0_seam(la_synth* h, const SynthPlan&, int k, int B, hipStream_t stream) {
+    return la_seam_backward(seam_kernel(h, 2 * k - 1, h->G1, h->G1), B, 0, stream);
+}
+// image gradient one level down: adjoint of upsample2d = FIR (flipped) + decimate 2, pad (1,1,1,1), gain 4; with the pyramid every level
+// below in ONE more launch (the levels depend on the image gradient only)
+static int bwd_image_grad(la_synth* h, const SynthPlan& P, int k, int B, hipStream_t stream) {
+    const int res = 4 << k;
+    int rc = la_upfirdn2d_ex(image_grad(h, k), h->rgb[k - 1].g_img, B, h->imgc, res, res, h->fir, la_fir_down2_adjoint(), stream);
+    if (rc || !P.blk[k].pyramid) return rc;
+    float* outs[MAX_BLOCKS];
+    for (int q = k - 2; q >= 0; --q) outs[k - 2 - q] = h->rgb[q].g_img;
+    return la_image_grad_pyramid(h->rgb[k - 1].g_img, outs, k - 1, B * h->imgc, res / 2, h->fir, stream);
+}
+// up layer's backward-data: FIR adjoint -> stride-2 backward-data; where the plan fuses it, the epilogue applies the conv1 seam of the block
+// BELOW (its saved output is this contraction's xin), incl. its ToRGB backward
+static int bwd_up_data(la_synth* h, const SynthPlan& P, int k, int B, hipStream_t stream) {
+    const ConvLayer &L0 = h->conv[2 * k - 1], &Lb = h->conv[2 * k - 2];
+    const RgbLayer& Tb = h->rgb[k - 1];
+    LaSeamFuse sf;
+    const bool fused = P.conv[2 * k - 2].seam == SEAM_FUSED;
+    if (fused) {
+        seam_common(h, sf, 2 * k - 2);
+        sf.pmax = pmax_buf(h, P.conv[2 * k - 2].seam_pmax);
+        sf.imgc = h->imgc; sf.g_img = Tb.g_img; sf.rgb_pre = Tb.rgb_pre; sf.rgb_clamp = h->clamp;
+        sf.wrgb = Tb.weight; sf.s_rgb = h->s_all + Tb.s_off; sf.s_rgb_stride = h->S; sf.dweff_part = Tb.dwep;
+    }
+    return la_modconv3x3_up2_bwd_ex(h->G1, layer_conv(h, L0, B, true), Lb.y, (long)L0.cin * Lb.res * Lb.res, h->fir, h->zT, h->G0, L0.dsp, stream,
+                                    bwd_opts(h, 2 * k - 1, fused ? &sf : nullptr));
+}
+// the style finish: ONE pass (3 launches) turns the partials of every layer into ds_all, segment counts from the plan
+static int bwd_style_finish(la_synth* h, const SynthPlan& P, int, int B, hipStream_t stream) {
     LaStyleFinish fin; memset(&fin, 0, sizeof(fin));
     fin.imgc = h->imgc; fin.d_stride = h->Dt; fin.s_stride = h->S; fin.ds_stride = h->S;
-    auto fin_conv = [&](const ConvLayer& L, int ntiles, int nslabs) {
-        LaStyleFinish::Conv& c = fin.conv[fin.nconv++];
-        c.ds_part = L.dsp; c.ddn_part = L.ddnp; c.d = h->d_all + L.d_off; c.s = h->s_all + L.s_off; c.wsq = L.wsq;
-        c.ds_out = h->ds_all + L.s_off; c.ntiles = ntiles; c.nslabs = nslabs; c.cin = L.cin; c.cout = L.cout;
-    };
-    static const bool no_fuse = la_dev_env("LA_NO_SEAM_FUSE") != nullptr;      // dev knobs: A/B of the fused seams on one box
-    static const bool no_fuse2 = la_dev_env("LA_NO_SEAM2_FUSE") != nullptr;
-    const bool f16 = h->precision == LA_PREC_F32 ? false : h->precision == LA_PREC_F16X2;
-    // fp16 operand scales of the backward contractions: the kernels whose epilogues produce a contraction's input (direct contraction
-    // kernels, split-K finish pass, seam kernel) lower the consumer's slot row themselves (la_xs_lower; la_synth_forward reset the
-    // rows): no plane maxima, no reduction launch between producer and consumer.  Dev knob LA_NO_XS_HANDOFF: plane maxima +
-    // la_xscale_pmax at the consumer.
-    static const bool no_xs = la_dev_env("LA_NO_XS_HANDOFF") != nullptr;
-    const bool xs_hand = f16 && !no_xs;
-    const float up_mult = la_modconv_up2_bwd_xs_mult(h->fir);
-    auto xs_slot = [&](int conv_index) { return xs_hand ? h->xs_bwd + (long)conv_index * B * LA_XS_FAN : nullptr; };
-    bool seam2_done = false;      // this block's conv1 seam was already applied by the epilogue of the up layer's backward above it
-    bool pyramid_done = false;    // the image-gradient levels below the current block exist already (la_image_grad_pyramid)
-    // Row windows (la_synth_set_row_window): the gradient of a conv output is non-zero only inside the cone of the image window (bw_lo /
-    // bw_hi: the forward windows without their tile rounding, plan_row_windows), so the backward pass of a windowed forward pass reads,
-    // computes and writes those rows only, each launch in its own tiles: a producer writes the tiles around its window, its consumer reads
-    // everything outside them as zeros (LaBwdRows) -- the ping-pong buffers G0 / G1 hold older contents there.  Default path only (fused
-    // seams, slot rows); needs an image gradient that is zero outside the image window.
-    const bool bw = xs_hand && !no_fuse && !no_fuse2 && h->precision != LA_PREC_F32;
-    auto cone_tiles = [&](int conv_index, int res, int& lo, int& hi) {      // the 4-row tiles around the gradient rows of a conv output
-        lo = h->bw_lo[conv_index]; hi = h->bw_hi[conv_index];
-        la_span_tiles(lo, hi, 4, res);
-    };
     for (int k = h->nblocks - 1; k >= 0; --k) {
-        const int res = 4 << k;
-        const long HW = (long)res * res;
-        // rw1: conv1's backward contraction reads the tiles around the gradient rows of conv1's output (what the seam kernel or the block
-        // above wrote into G0) and writes those of conv0's output into G1; rw0: the up-sampling layer's backward reads these and writes
-        // the tiles around the gradient rows of the block below's conv1 output
-        const bool win = bw && k > 0 && h->bw_hi[ci] > 0;
-        LaBwdRows rw1 = {}, rw0 = {};
-        if (win && k == h->nblocks - 1 && h->fw_c1 > 0) {      // top block: conv1's backward contraction writes the window's tile columns, the FIR adjoint reads the others as zeros
-            rw1.out.col_lo = rw0.in.col_lo = h->fw_c0; rw1.out.col_hi = rw0.in.col_hi = h->fw_c1;
+        const RgbLayer& T = h->rgb[k];
+        LaStyleFinish::Rgb& r = fin.rgb[fin.nrgb++];
+        r.dweff_part = T.dwep; r.wrgb = T.weight; r.ds_out = h->ds_all + T.s_off; r.nslabs = P.conv[2 * k].nseg; r.C = T.cin;
+        for (int ci = 2 * k; ci >= 2 * k - 1 && ci >= 0; --ci) {
+            const ConvLayer& L = h->conv[ci];
+            LaStyleFinish::Conv& c = fin.conv[fin.nconv++];
+            c.ds_part = L.dsp; c.ddn_part = L.ddnp; c.d = h->d_all + L.d_off; c.s = h->s_all + L.s_off; c.wsq = L.wsq;
+            c.ds_out = h->ds_all + L.s_off; c.ntiles = P.conv[ci].ntiles; c.nslabs = P.conv[ci].nseg; c.cin = L.cin; c.cout = L.cout;
         }
-        if (win) {
-            cone_tiles(ci, res, rw1.in.row_lo, rw1.in.row_hi);
-            cone_tiles(ci - 1, res, rw1.out.row_lo, rw1.out.row_hi);
-            rw0.in.row_lo = rw1.out.row_lo; rw0.in.row_hi = rw1.out.row_hi;
-            if (ci - 2 >= 0 && h->bw_hi[ci - 2] > 0) cone_tiles(ci - 2, res / 2, rw0.out.row_lo, rw0.out.row_hi);
-        }
-        RgbLayer& T = h->rgb[k];
-        ConvLayer& L1 = h->conv[ci];
-        const int slabs = la_seam_slabs(HW);
-        const int tiles1 = la_modconv_ds_tiles(res);
-        const int nseg1 = seam2_done ? tiles1 : slabs;      // granularity of this block's ddn / dweff / plane-maxima partials
-        // ---- seam at conv1 output: ToRGB backward + act backward (top block, or when it was not fused above)
-        LaSeamArgs s;
-        if (!seam2_done) {
-            memset(&s, 0, sizeof(s));
-            s.y = L1.y; s.gx_next = gx_next; s.gz = h->G0; s.HW = HW; s.C = L1.cout;
-            la_seam_set_epi(s, layer_epi(h, L1));
-            s.ddn_part = L1.ddnp;
-            s.g_img = gi; s.rgb_pre = T.rgb_pre; s.rgb_clamp = h->clamp; s.wrgb = T.weight;
-            s.s_rgb = h->s_all + T.s_off; s.s_stride = h->S; s.dweff_part = T.dwep;
-            if (xs_hand) { s.xs_out = xs_slot(ci); s.xs_mult = 1.f; }      // the seam kernel lowers the slot row of the contraction that follows ...
-            else if (f16) s.pmax_out = h->pmax;                              // ... or leaves the plane maxima of gz for it
-            if (win) { s.p_lo = (long)rw1.in.row_lo * res; s.p_hi = (long)rw1.in.row_hi * res; }
-            if ((rc = la_seam_backward(s, B, h->imgc, stream))) return rc;
-        }
-        {
-            LaStyleFinish::Rgb& r = fin.rgb[fin.nrgb++];
-            r.dweff_part = T.dwep; r.wrgb = T.weight; r.ds_out = h->ds_all + T.s_off; r.nslabs = nseg1; r.C = T.cin;
-        }
-        // ---- conv1 backward-data (+ style-gradient partials).  16-bit modes, blocks above the first: the seam of the up-sampling
-        // layer L0 (whose saved output is this contraction's xin) is applied in the same epilogue -- no separate pass over y0 and
-        // the gradient; its demod-gradient partials and plane maxima come out per pixel tile.
-        const bool fuse_seam = k > 0 && h->precision != LA_PREC_F32 && !no_fuse;
-        {
-            const float* xin = (k == 0) ? h->cst : h->conv[ci - 1].y;
-            const long xin_bs = (k == 0) ? 0 : (long)L1.cin * HW;
-            LaSeamFuse sf; memset(&sf, 0, sizeof(sf));
-            if (fuse_seam) {
-                const ConvLayer& L0f = h->conv[ci - 1];
-                la_seam_set_epi(sf, layer_epi(h, L0f));
-                sf.ddn_part = L0f.ddnp;
-                sf.pmax = f16 ? h->pmax2 : nullptr;
-                if (xs_hand) { sf.xs_out = xs_slot(ci - 1); sf.xs_mult = up_mult; }
-            }
-            LaModconvBwdOpts o;
-            o.in_pmax = f16 ? (seam2_done ? h->pmax3 : h->pmax) : nullptr; o.in_nseg = nseg1;
-            o.seam = fuse_seam ? &sf : nullptr; o.xscale = xs_slot(ci); o.rows = win ? &rw1 : nullptr;
-            if ((rc = la_modconv3x3_bwd_ex(h->G0, layer_conv(h, L1, B, true), xin, xin_bs, h->G1, L1.dsp, stream, o))) return rc;
-            fin_conv(L1, tiles1, nseg1);
-        }
-        --ci;
-        if (k == 0) break;
-        // ---- conv0 (up-sampling layer): act backward (unless fused above) -> FIR adjoint -> stride-2 backward-data
-        ConvLayer& L0 = h->conv[ci];
-        if (!fuse_seam) {
-            memset(&s, 0, sizeof(s));
-            s.y = L0.y; s.gx_next = h->G1; s.gz = h->G1; s.HW = HW; s.C = L0.cout;
-            la_seam_set_epi(s, layer_epi(h, L0));
-            s.ddn_part = L0.ddnp;
-            if (xs_hand) { s.xs_out = xs_slot(ci); s.xs_mult = up_mult; }
-            else if (f16) s.pmax_out = h->pmax;      // plane maxima of gz: bound for the operand scale of the fused FIR-adjoint + split pass
-            if ((rc = la_seam_backward(s, B, 0, stream))) return rc;
-        }
-        // ---- image gradient one level down: adjoint of upsample2d = FIR (flipped) + decimate 2, pad (1,1,1,1), gain 4
-        // (before the up layer's backward contraction: its epilogue may apply the block below's ToRGB backward)
-        RgbLayer& P = h->rgb[k - 1];
-        if (!pyramid_done) {
-            if ((rc = la_upfirdn2d_ex(gi, P.g_img, B, h->imgc, res, res, h->fir, la_fir_down2_adjoint(), stream))) return rc;
-            // every level below in ONE launch (la_image_grad_pyramid: the levels depend on the image gradient only), from <= 256^2 inputs
-            if (k >= 2 && res / 2 <= 256) {
-                float* outs[MAX_BLOCKS];
-                for (int q = k - 2; q >= 0; --q) outs[k - 2 - q] = h->rgb[q].g_img;
-                if ((rc = la_image_grad_pyramid(P.g_img, outs, k - 1, B * h->imgc, res / 2, h->fir, stream))) return rc;
-                pyramid_done = true;
-            }
-        }
-        const bool fuse_seam2 = h->precision != LA_PREC_F32 && !no_fuse2;
-        {
-            const int hin = res / 2;
-            const int tiles = la_modconv_ds_tiles(hin);
-            const int nseg0 = fuse_seam ? tiles1 : slabs;
-            LaSeamFuse sf2; memset(&sf2, 0, sizeof(sf2));
-            if (fuse_seam2) {
-                // the conv1 seam of the block BELOW (its saved output is this contraction's xin), incl. its ToRGB backward
-                const ConvLayer& Lb = h->conv[ci - 1];
-                la_seam_set_epi(sf2, layer_epi(h, Lb));
-                sf2.ddn_part = Lb.ddnp;
-                sf2.pmax = f16 ? h->pmax3 : nullptr;
-                if (xs_hand) { sf2.xs_out = xs_slot(ci - 1); sf2.xs_mult = 1.f; }
-                sf2.imgc = h->imgc; sf2.g_img = P.g_img; sf2.rgb_pre = P.rgb_pre; sf2.rgb_clamp = h->clamp;
-                sf2.wrgb = P.weight; sf2.s_rgb = h->s_all + P.s_off; sf2.s_rgb_stride = h->S; sf2.dweff_part = P.dwep;
-            }
-            LaModconvBwdOpts o;
-            o.in_pmax = f16 ? (fuse_seam ? h->pmax2 : h->pmax) : nullptr; o.in_nseg = nseg0;
-            o.seam = fuse_seam2 ? &sf2 : nullptr; o.xscale = xs_slot(ci); o.rows = win ? &rw0 : nullptr;
-            if ((rc = la_modconv3x3_up2_bwd_ex(h->G1, layer_conv(h, L0, B, true), h->conv[ci - 1].y, (long)L0.cin * hin * hin, h->fir, h->zT, h->G0, L0.dsp,
-                                               stream, o)))
-                return rc;
-            fin_conv(L0, tiles, nseg0);
-        }
-        --ci;
-        gx_next = h->G0;
-        gi = P.g_img;
-        seam2_done = fuse_seam2;
     }
-    if ((rc = la_style_backward_all(fin, B, stream))) return rc;
+    return la_style_backward_all(fin, B, stream);
+}
+
+extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hipStream_t stream) {
+    LA_CHECK_ARG(h && g_img && dws, "synth_backward: null pointer");
+    LA_CHECK_ARG(h->plan.pass.B >= 1, "synth_backward: no forward pass to differentiate");
+    const SynthPlan& P = h->plan;
+    const int B = P.pass.B;
+    h->g_top = g_img;
+    int rc;
+    for (int k = h->nblocks - 1; k >= 0; --k) {
+        if (P.conv[2 * k].seam == SEAM_KERNEL && (rc = bwd_conv1_seam(h, P, k, B, stream))) return rc;
+        if ((rc = bwd_conv1_data(h, P, k, B, stream))) return rc;
+        if (k == 0) break;
+        if (P.conv[2 * k - 1].seam == SEAM_KERNEL && (rc = bwd_conv0_seam(h, P, k, B, stream))) return rc;
+        // (before the up layer's backward contraction: its epilogue may apply the block below's ToRGB backward)
+        if (P.blk[k].down_fir && (rc = bwd_image_grad(h, P, k, B, stream))) return rc;
+        if ((rc = bwd_up_data(h, P, k, B, stream))) return rc;
+    }
+    if ((rc = bwd_style_finish(h, P, 0, B, stream))) return rc;
     return la_affine_backward(h->st, h->ds_all, B, h->wdim, dws, h->num_ws, h->aff_part, stream);
 }

@@ -281,22 +281,42 @@ def seam_slabs(hw):
     return max(1, min(64, hw // 16384))
 
 
+CONV_TILE_PIXELS = 128          # pixels per contraction tile (modconv_cases.NT): la_modconv_ds_tiles(res) = ceil(res^2 / 128)
+PYRAMID_MAX_RES = 256
+
+
+def ds_tiles(res):
+    return -(-res * res // CONV_TILE_PIXELS)
+
+
 def branch_plan(case, mode):
-    """-> dict(nblocks, imgc, clamp, pyramid, blocks=[dict(res, cin, cout, torgb='fused' | 'small' | 'large', up2_skip, seam='kernel' |
-    'fused', slabs)]): per block the ToRGB forward form, whether its skip image is up-sampled inside the ToRGB kernel, where the seam of
-    its conv1 output (with the ToRGB backward) runs, and the slabs of the seam kernel."""
+    """-> dict(nblocks, imgc, clamp, pyramid, pyramid_block, blocks=[dict(res, cin, cout, torgb='fused' | 'small' | 'large', up2_skip,
+    seam='kernel' | 'fused', slabs, ...)]): per block the ToRGB forward form, whether its skip image is up-sampled inside the ToRGB kernel,
+    where the seam of its conv1 output (with the ToRGB backward) runs, and the slabs of the seam kernel.  What la_synth_plan_query has
+    beyond that (test_synth_plan_cpu.py holds the two against each other): skip_launch (the skip image is up-sampled by a launch of its own
+    before conv1), seam0 (where the seam of the block's conv0 output runs: the seam kernel, or fused into conv1's backward; None in the
+    first block), nseg1 / nseg0 (segments of the partials of conv1 / conv0: seam slabs where the seam is a kernel, contraction tiles where
+    it is fused), tiles1 / tiles0 (tiles of the layers' style-gradient partials: the grid of their backward contraction), down_fir (the
+    backward pass launches the image gradient's down-FIR at this block) and pyramid_block (the block whose launch makes every level below)."""
     ch, blocks = case.channels, []
     nb = len(ch)
+    # the image-gradient pyramid: the first block from the top with k >= 2 whose level below is <= 256^2 hands every lower level to one launch
+    pyramid_block = next((k for k in range(nb - 1, 0, -1) if k >= 2 and (4 << k) // 2 <= PYRAMID_MAX_RES), None)
     for k, co in enumerate(ch):
         res = 4 << k
         fused = co in (32, 64, 128) and uses_halo(mode, co, res)
+        seam1 = 'kernel' if (mode == 'f32' or k == nb - 1) else 'fused'
+        seam0 = None if k == 0 else ('kernel' if mode == 'f32' else 'fused')
         blocks.append(dict(res=res, cin=ch[k - 1] if k else 0, cout=co,
                            torgb='fused' if fused else ('small' if res * res <= TORGB_SMALL_MAX_HW else 'large'),
                            up2_skip=k > 0 and not fused,
-                           seam='kernel' if (mode == 'f32' or k == nb - 1) else 'fused', slabs=seam_slabs(res * res)))
-    # the image-gradient pyramid: the first block from the top with k >= 2 whose level below is <= 256^2 hands every lower level to one launch
-    pyramid = any(k >= 2 and (4 << k) // 2 <= 256 for k in range(nb - 1, 0, -1))
-    return dict(nblocks=nb, imgc=case.imgc, clamp=case.clamp, pyramid=pyramid, blocks=blocks)
+                           seam=seam1, slabs=seam_slabs(res * res),
+                           skip_launch=k > 0 and fused, seam0=seam0,
+                           nseg1=ds_tiles(res) if seam1 == 'fused' else seam_slabs(res * res),
+                           nseg0=None if k == 0 else (ds_tiles(res) if seam0 == 'fused' else seam_slabs(res * res)),
+                           tiles1=ds_tiles(res), tiles0=None if k == 0 else ds_tiles(res // 2),
+                           down_fir=k > 0 and (pyramid_block is None or k >= pyramid_block)))
+    return dict(nblocks=nb, imgc=case.imgc, clamp=case.clamp, pyramid=pyramid_block is not None, pyramid_block=pyramid_block, blocks=blocks)
 
 
 # what the sweep claims to reach: name -> predicate over (case, mode, plan)
