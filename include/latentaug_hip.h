@@ -690,6 +690,7 @@ int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const float* con
  *   la_pr_member_f16        precision_recall.py:80-84: member[i] = any_j dist(i, j) <= radius[j].
  *   la_kid_poly3_f32        Kernel Inception Distance of two feature sets (described at its prototype below).
  *   la_dc_count_f16         density and coverage of two feature sets (described at its prototype below).
+ *   la_fd_*                 Frechet distance of two feature sets from their cross-Gram matrix (described at the prototypes below).
  * ws: la_pr_workspace_floats(nr, nc) floats.  The [nr][nc] matrix is not materialised by the last two.
  * ------------------------------------------------------------------------------------------------------------- */
 int la_feature_moments_f64(const float* x, long n, int D, double* raw_mean, double* raw_cov, la_stream_t stream);
@@ -739,6 +740,40 @@ size_t la_dc_workspace_bytes(long ng, long nr);
 int la_dc_col_splits(long ng, long nr);
 int la_dc_count_f16(const void* gen, long ng, const void* real, long nr, int D, const float* radius, int* count, float* nearest,
                     void* ws, size_t ws_bytes, la_stream_t stream);
+
+/* Frechet distance of two feature sets (metrics/frechet_inception_distance.py:41-45) without a covariance matrix or a matrix square
+ * root.  x float32 [nx][D] (generated), y float32 [ny][D] (real), row-major, any D >= 1, 4-byte aligned.  With A, B the two sets minus
+ * their column means and the reference's 1/N covariance (metric_utils.py:136-140):
+ *   FD = |mu_x - mu_y|^2 + |A|_F^2 / nx + |B|_F^2 / ny - 2 nuc(A B^T) / sqrt(nx ny),   nuc = the sum of the singular values
+ * (the non-zero eigenvalues of Sigma_x Sigma_y are the squared singular values of A B^T / sqrt(nx ny)).  It is meant for the
+ * few-samples regime, n = min(nx, ny) <= 8192; nx, ny >= 2.  m = max(nx, ny), n' = n rounded up to even.
+ *   la_fd_gram_f32          column means in float64 (fixed order); C = A B^T in float64 on v_mfma_f64_16x16x4_f64, the float32 operands
+ *                           centred in float64 while they are loaded (no centred copy exists); C is stored at the START of ws as n
+ *                           vectors of m contiguous doubles (C for nx <= ny, C^T otherwise, same bits; no transposing pass), one
+ *                           zero vector appended when n is odd.  terms float64 [4] (device): |mu_x - mu_y|^2, |A|_F^2, |B|_F^2, and a
+ *                           slot for nuc(C) that la_fd_finish_f64 fills.
+ *   la_fd_jacobi_sweep_f64  one sweep of one-sided Jacobi (Hestenes) over v = n' vectors of m doubles (an odd n: the caller's zero
+ *                           vector last), in place: n' - 1 rounds of n'/2 disjoint pairs, la_fd_round_pair's order, one launch per
+ *                           round and one workgroup per pair.  With alpha = |c_p|^2, beta = |c_q|^2, gamma = c_p . c_q the pair is
+ *                           rotated when alpha beta > 0 and |gamma| > sqrt(m) 2^-52 sqrt(alpha beta) (LAPACK dgesvj's criterion):
+ *                           zeta = (beta - alpha) / (2 gamma), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (1 at zeta = 0),
+ *                           c = 1 / sqrt(1 + t^2), s = c t, c_p' = c c_p - s c_q, c_q' = s c_p + c c_q.  rotations int32 [1]
+ *                           (device): zeroed by the entry on `stream`, then the number of rotations of the sweep (integer atomic
+ *                           adds).  The caller repeats the entry until a sweep leaves 0 there.  Up to m = 8192 a pair is held in
+ *                           registers: read once per round, written at most once.
+ *   la_fd_finish_f64        sv float64 [n] (device, may be NULL): the norms of the vectors at the start of ws, in vector order -- the
+ *                           singular values once the sweeps have converged; terms[3] = their sum in index order.
+ *   la_fd_round_pair        pure host: pair k (0 .. n'/2 - 1) of round `round` (0 .. n' - 2) of the circle method for n vectors, *p < *q
+ *                           (index n of an odd n is the zero vector); the kernels use the same arithmetic.  LA_ERR_ARG outside
+ *                           those ranges or n outside 2 .. 8192.
+ * ws: la_fd_workspace_bytes(nx, ny, D) bytes, 8-byte aligned (the n' x m doubles, the means, the reduction partials; 0 for sizes the
+ * entries refuse).  nx < 2, ny < 2, min(nx, ny) > 8192 and null pointers are LA_ERR_ARG, a smaller ws_bytes is LA_ERR_WORKSPACE, all
+ * before anything is launched.  Every float64 sum has a fixed order and there are no float atomics: two runs give the same bits. */
+size_t la_fd_workspace_bytes(long nx, long ny, int D);
+int la_fd_round_pair(int n, int round, int k, int* p, int* q);
+int la_fd_gram_f32(const float* x, long nx, const float* y, long ny, int D, double* terms, void* ws, size_t ws_bytes, la_stream_t stream);
+int la_fd_jacobi_sweep_f64(double* v, long n, long m, int* rotations, la_stream_t stream);
+int la_fd_finish_f64(void* ws, size_t ws_bytes, long nx, long ny, int D, double* sv, double* terms, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Paired image metrics (no reference counterpart): what describes a PAIR of images.  Images are float32 [N][C][H][W]; pair p is

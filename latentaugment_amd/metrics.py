@@ -7,6 +7,8 @@ everything downstream of detector features.
   compute_distances            metrics/precision_recall.py:19-32
   compute_pr_from_features     metrics/precision_recall.py:72-85
   compute_kid_from_features    (not in the reference) Kernel Inception Distance, the community's kid50k_full recipe
+  compute_fd_from_features     the Frechet distance of frechet_inception_distance.py from the features themselves: singular values of
+                               the cross-Gram matrix by Jacobi sweeps on the GPU (la_frechet.hip), exact where N < D
   compute_dc_from_features     (not in the reference) density and coverage, Naeem et al., ICML 2020 (the `prdc` package)
   compute_prdc_from_features   precision, recall, density and coverage in one dict
   compute_feature_stats_for_images        images -> FeatureStats through a `synthesis.DetectorEngine` (metric_utils.py:314-320)
@@ -23,7 +25,8 @@ everything downstream of detector features.
 The detectors (Inception-v3 and VGG16 pickles hosted by NVIDIA, metric_utils.py:46-60) cannot be fetched offline.  The VGG16 one has a
 local counterpart -- the TorchScript `vgg16.pt` the LPIPS criterion already needs -- and `synthesis.DetectorEngine.from_torchscript`
 runs its `return_features=True` branch on the HIP path, so precision / recall, density / coverage and KID start from images.  The
-Inception-v3 pickle has none: FID keeps taking features or moments that the caller supplies.
+Inception-v3 pickle has none: FID keeps taking features (compute_fd_from_features) or moments (compute_fid_from_stats) that the
+caller supplies; from images, the Frechet distance is that of the VGG16 features.
 torch only owns the device memory; the moments, distances, radii, membership tests and kernel sums are HIP kernels (la_metrics.hip).
 """
 import ctypes as C
@@ -272,6 +275,70 @@ def compute_kid_from_features(real_features, gen_features, num_subsets=100, max_
     return kid
 
 
+FD_MAX_SMALL_SIDE = 8192          # la_frechet.hip rotates min(Ng, Nr) vectors; beyond this the moments route is the right one
+
+
+def compute_fd_from_features(real_features, gen_features, device='cuda:0', return_details=False, max_sweeps=30):
+    """Frechet distance of `gen_features` against `real_features` ([N, D] numpy arrays or device tensors of any float dtype, computed
+    from their float32 values) -- the number `compute_fid_from_stats` gives for the moments of the same features, without a covariance
+    matrix or a matrix square root.  With A [Ng][D], B [Nr][D] the two sets minus their column means and the reference's 1/N covariance:
+        FD = |mu_g - mu_r|^2 + |A|_F^2 / Ng + |B|_F^2 / Nr - 2 nuc(A B^T) / sqrt(Ng Nr)
+    nuc = the sum of the singular values of the Ng x Nr cross-Gram matrix, which one-sided Jacobi sweeps (la_fd_jacobi_sweep_f64) find in
+    float64: singular values of a singular matrix are well conditioned where its square root is not, so the result is exact in the
+    few-samples regime (N < D) too.  Sweeps run until one makes no rotation; `max_sweeps` reached raises.  The value is not clamped at 0
+    (the reference's is not either); two calls give the same bits.  Like compute_fid_from_stats it is features-in: the Inception-v3
+    detector of the published FID is not available offline, so the name of the number depends on the detector the features came from.
+    min(Ng, Nr) > 8192 is refused: that regime belongs to FeatureStats moments and compute_fid_from_stats.  There is no CPU fallback.
+    return_details=True: (fd, {'mean_term', 'trace_gen' and 'trace_real' (divided by N), 'nuclear' (divided by sqrt(Ng Nr)), 'sweeps',
+    'singular_values': float64 [min(Ng, Nr)] of A B^T in vector order, 'terms': the four raw float64 sums})."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); got device ' + str(dev))
+    for f in (real_features, gen_features):
+        if torch.is_tensor(f):
+            _lib.require_gpu(f)
+    rshape, gshape = tuple(np.shape(real_features)), tuple(np.shape(gen_features))
+    if len(rshape) != 2 or len(gshape) != 2 or rshape[1] != gshape[1] or rshape[1] < 1:
+        raise _lib.LatentAugHipError(f'features must be two [N, D] arrays of one D >= 1: real {rshape}, generated {gshape}')
+    nr, ng, D = rshape[0], gshape[0], rshape[1]
+    if min(nr, ng) < 2:
+        raise _lib.LatentAugHipError(f'the Frechet distance needs at least 2 samples per side (got {nr} real, {ng} generated)')
+    if min(nr, ng) > FD_MAX_SMALL_SIDE:
+        raise _lib.LatentAugHipError(f'min(Ng, Nr) = {min(nr, ng)} > {FD_MAX_SMALL_SIDE}: the many-samples regime belongs to FeatureStats '
+                                     'moments and compute_fid_from_stats')
+    if not torch.cuda.is_available():
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); none is available')
+    lib = _lib.load()
+    real, gen = _f32_features(real_features, dev), _f32_features(gen_features, dev)
+    n, m = min(ng, nr), max(ng, nr)
+    ws_bytes = lib.la_fd_workspace_bytes(ng, nr, D)
+    ws = torch.empty([ws_bytes // 8], dtype=torch.float64, device=dev)          # the n' vectors of m doubles come first
+    out = torch.empty([4 + n], dtype=torch.float64, device=dev)                # terms [4], singular values [n]
+    rot = torch.empty([1], dtype=torch.int32, device=dev)
+    sweeps = 0
+    with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
+        _lib.check(lib.la_fd_gram_f32(_lib.ptr(gen), ng, _lib.ptr(real), nr, D, _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_ptr()),
+                   'fd_gram')
+        while True:
+            _lib.check(lib.la_fd_jacobi_sweep_f64(_lib.ptr(ws), n, m, _lib.ptr(rot), _lib.stream_ptr()), 'fd_jacobi_sweep')
+            sweeps += 1
+            if int(rot.item()) == 0:          # one integer per sweep: the number of sweeps depends on the data
+                break
+            if sweeps >= max_sweeps:
+                raise _lib.LatentAugHipError(f'Frechet distance: the Jacobi sweeps did not converge in max_sweeps = {max_sweeps} '
+                                             f'({int(rot.item())} rotations in the last one); sets with D < N or many duplicated rows '
+                                             'need the most sweeps: raise max_sweeps, or use compute_fid_from_stats there')
+        _lib.check(lib.la_fd_finish_f64(_lib.ptr(ws), ws_bytes, ng, nr, D, _lib.ptr(out[4:]), _lib.ptr(out), _lib.stream_ptr()), 'fd_finish')
+    out = out.cpu().numpy()
+    mean_term, trace_gen, trace_real = float(out[0]), float(out[1]) / ng, float(out[2]) / nr
+    nuclear = float(out[3]) / float(np.sqrt(float(ng) * float(nr)))
+    fd = mean_term + trace_gen + trace_real - 2.0 * nuclear
+    if return_details:
+        return fd, dict(mean_term=mean_term, trace_gen=trace_gen, trace_real=trace_real, nuclear=nuclear, sweeps=sweeps,
+                        singular_values=out[4:].copy(), terms=out[:4].copy())
+    return fd
+
+
 def compute_dc_from_features(real_features, gen_features, nhood_size=5, device='cuda:0', return_details=False):
     """(density, coverage) of `gen_features` against `real_features` ([N, D] arrays or tensors, rounded to float16 as the precision /
     recall path does): Naeem et al., "Reliable Fidelity and Diversity Metrics for Generative Models", ICML 2020.  Only the balls of the
@@ -380,14 +447,17 @@ def compute_feature_stats_for_aug_dataset(datadir, mode, detector, max_items=Non
 
 
 def compute_metrics_from_images(real_batches, gen_batches, detector, nhood_size=3, mode=None, max_items=None, kid_num_subsets=100,
-                                kid_max_subset_size=1000, kid_seed=0):
+                                kid_max_subset_size=1000, kid_seed=0, frechet=False):
     """{'precision', 'recall', 'density', 'coverage', 'kid'} of generated against real images, through `detector` and the functions
-    above (precision_recall.py:36-85 with nhood_size=3 is the reference's pr50k3)."""
+    above (precision_recall.py:36-85 with nhood_size=3 is the reference's pr50k3).  frechet=True adds 'fd', the Frechet distance of the
+    same detector features (compute_fd_from_features; with the VGG16 detector it is not the published Inception FID)."""
     real = compute_feature_stats_for_images(real_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
     gen = compute_feature_stats_for_images(gen_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
     out = compute_prdc_from_features(real, gen, nhood_size=nhood_size, device=detector.device)
     out['kid'] = compute_kid_from_features(real, gen, num_subsets=kid_num_subsets, max_subset_size=kid_max_subset_size, seed=kid_seed,
                                            device=detector.device)
+    if frechet:
+        out['fd'] = compute_fd_from_features(real, gen, device=detector.device)
     return out
 
 
