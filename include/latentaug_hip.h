@@ -260,6 +260,16 @@ size_t la_modconv_workspace_bytes(int B, int cin, int cout, int res, int up);
  *   2 LA_PREC_BF16X2  2 bf16 terms, 3 bf16 MFMAs (~4e-6 relative error per layer)
  *   3 LA_PREC_F16X2   operands scaled by per-sample / per-layer powers of two and split into 2 fp16 terms, 3 fp16 MFMAs per
  *                     product, fp32 accumulate (fp32-class error: 2 x 11 mantissa bits)
+ * Magnitude range of LA_PREC_F16X2.  Every scale is 2^s with s = 15 - e, e the binary exponent of the largest magnitude max = f * 2^e
+ * (f in [0.5, 1)) of the weight tensor, or of ONE SAMPLE of the (modulated) launch input, so that the scaled maximum lies in
+ * [2^14, 2^15); s is clamped to [-100, 100], and a maximum that is zero, NaN or infinite gives the scale 1.  The fp32-class claim
+ * therefore holds while 2^-86 <= max < 2^115 for the weights and for every sample, and while products and sums stay normal float32
+ * numbers: inside that range multiplying x, gz, xin or W by a power of two (one per sample for the inputs) multiplies y, gx and
+ * ds_part by the same power of two BIT FOR BIT, at every precision (tests/test_hip_operand_range.py).  Below 2^-86 the clamp leaves
+ * the scaled maximum under 2^14 and bits are lost in proportion; from 2^115 on fp16 overflows.  An element far below its sample's
+ * maximum keeps 22 significand bits down to about 2^-16 of that maximum and loses one bit per further halving (fp16 subnormals), as
+ * in any block-scaled format.  A sample (or a weight tensor) that is entirely zero is exact: the products are zero, the scale 1 is
+ * never divided by, and the forward calls return act(noise * noise_strength + bias), the backward calls 0 in gx and ds_part.
  * wq is produced by la_pack_conv_weights_bf16_f32 (transpose = 0 for the forward calls, 1 for the backward calls). */
 #define LA_PREC_F32 0
 #define LA_PREC_BF16X3 1
