@@ -128,8 +128,11 @@ struct LaConvArgs {
     // hold none of them return at once and write nothing (merged phases: the window counts rows of every phase's own grid).  The
     // caller guarantees that nobody reads the rows left out (la_synth.hip: the loop steps of a criterion that sees a crop only).
     int row_lo, row_hi;
-    // ... and a column window on top of it (halo kernel only; 0 / 0 = all columns): the wanted tiles are then the rectangle of 4 x 32 tiles
-    // that holds rows [row_lo, row_hi) x columns [col_lo, col_hi); needs a row window
+    // ... and a column window on top of it (0 / 0 = all columns; needs a row window).  Halo kernel: the wanted tiles are the rectangle of
+    // 4 x 32 tiles that holds rows [row_lo, row_hi) x columns [col_lo, col_hi).  Direct flat kernel: the 128-pixel tiles are flattened over
+    // exactly that rectangle of the grid (merged phases: of every phase's own grid), nothing outside it is computed or read; a backward
+    // launch zero-fills the columns it leaves out in rows [row_lo, row_hi) of `out` (its readers have no column mask) and the partials of
+    // the tile slots past the rectangle's.  The split-K forms compute every column.
     int col_lo, col_hi;
     // Valid rows of the INPUT (16-bit direct kernels; 0 / 0 = all): rows outside [in_row_lo, in_row_hi) read as zeros, as rows outside the
     // image do -- the backward contractions behind a windowed producer, whose other rows hold older contents of a shared buffer while the

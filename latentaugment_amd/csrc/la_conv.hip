@@ -423,6 +423,9 @@ int la_conv_plan(const LaConvArgs& a, LaConvPlan& p) {
         LA_CHECK_ARG(a.tiles_per_sample == la_conv_tiles_per_sample(a.Gy, a.Gx), "conv: tiles_per_sample mismatch");
         LA_CHECK_ARG(a.out_sy == 1 && a.out_sx == 1 && a.out_oy == 0 && a.out_ox == 0, "conv: bwd epilogue needs dense output");
     }
+    LA_CHECK_ARG(a.col_hi == 0 || (a.row_hi > 0 && a.col_lo >= 0 && a.col_hi > a.col_lo), "conv: a column window needs a row window");
+    LA_CHECK_ARG(a.col_hi == 0 || a.epi != LA_EPI_BWD || (a.Gy == a.Hout && a.Gx == a.Wout && a.out_sy == 1 && a.out_sx == 1 && a.out_oy == 0 && a.out_ox == 0),
+                 "conv: a backward launch with a column window needs a dense output (it zero-fills the columns it leaves out)");
     const int nphase = a.nphase, np = nphase > 0 ? nphase : 1;
     LA_CHECK_ARG(nphase >= 0 && nphase <= LA_CONV_MAX_PHASES, "conv: bad phase count");
     if (nphase > 0) LA_CHECK_ARG(a.precision != LA_PREC_F32 && a.epi == LA_EPI_RAW && a.in_q, "conv: merged phases need a pre-split 16-bit launch without epilogue");
@@ -496,7 +499,14 @@ int la_conv_plan(const LaConvArgs& a, LaConvPlan& p) {
             } else {
                 for (int q = 0; q < np; ++q) {
                     grid_of(q, Gy, Gx);
-                    const int t0 = (a.row_lo * Gx) / NT, t1 = la_cdiv((a.row_hi < Gy ? a.row_hi : Gy) * Gx, NT);
+                    const int r1 = a.row_hi < Gy ? a.row_hi : Gy;
+                    if (a.col_hi > 0) {      // the tiles of the rectangle, flattened over its own rows
+                        const int c1 = a.col_hi < Gx ? a.col_hi : Gx;
+                        const int ntq = (r1 > a.row_lo && c1 > a.col_lo) ? la_cdiv((r1 - a.row_lo) * (c1 - a.col_lo), NT) : 0;
+                        if (ntq > nt) nt = ntq;
+                        continue;
+                    }
+                    const int t0 = (a.row_lo * Gx) / NT, t1 = la_cdiv(r1 * Gx, NT);
                     if (t1 - t0 > nt) nt = t1 - t0;
                 }
             }
@@ -518,9 +528,11 @@ static void conv_prof_work(const LaConvArgs& a, const LaConvPlan& p, double& flo
     for (int q = 0; q < a.nphase; ++q) { gt += (double)a.ph[q].Gy * a.ph[q].Gx * a.ph[q].ntaps; gout += (double)a.ph[q].Gy * a.ph[q].Gx; ntw += a.ph[q].ntaps; }
     if (a.row_hi > 0 && a.Gy > 0) {      // row window: only the wanted rows are work (tiles hold 4 rows / 128 flattened pixels: counted as wanted)
         int lo = a.row_lo > 0 ? a.row_lo : 0, hi = a.row_hi < a.Gy ? a.row_hi : a.Gy;
-        lo &= ~3; hi = (hi + 3) & ~3; if (hi > a.Gy) hi = a.Gy;
+        const bool rect = a.col_hi > 0 && a.Gx > 0 && p.form == LA_FORM_FLAT;      // flat kernel: exactly the rectangle
+        if (!rect) { lo &= ~3; hi = (hi + 3) & ~3; if (hi > a.Gy) hi = a.Gy; }
         double f = hi > lo ? (double)(hi - lo) / a.Gy : 0.0;
         if (a.col_hi > 0 && a.Gx > 0 && p.form == LA_FORM_HALO) f *= (double)((((a.col_hi < a.Gx ? a.col_hi : a.Gx) + 31) & ~31) - (a.col_lo & ~31)) / a.Gx;
+        if (rect) f *= (double)((a.col_hi < a.Gx ? a.col_hi : a.Gx) - a.col_lo) / a.Gx;
         gt *= f; gout *= f;
     }
     flops = 2.0 * a.B * gt * a.M * (double)a.C;

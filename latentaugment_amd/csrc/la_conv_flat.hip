@@ -63,13 +63,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
     // run of pixel tiles -- vertically adjacent tiles (which share the +-1 row halos of the 3x3 taps) then hit the same L2.
     int ntile = bx;
     const int m0 = blockIdx.y * MT;
-    const int G = a.Gy * a.Gx;
-    const int Ntot = SPLIT ? a.B * G : G;
+    int G = a.Gy * a.Gx;
+    int goy = 0, gox = 0;      // origin of the part of the grid that the tiles are flattened over (column window: the wanted rectangle)
     if (!SPLIT) {
         // row window (LaConvArgs::row_lo): the tiles that hold a wanted row are a contiguous run [t0, t0 + nt) of the flattened tiles; the
         // first nt workgroups of the launch take them (in the XCD-aware order below, so the run is spread over all XCDs), the rest return
         int t0 = 0, nt = (int)gridDim.x;
-        if (a.row_hi > 0) {
+        if (a.row_hi > 0 && a.col_hi > 0) {
+            // row and column window (LaConvArgs::col_lo): the launch's grid IS the rectangle rows [row_lo, row_hi) x columns [col_lo, col_hi) of
+            // this phase's grid -- its tiles 0 .. nt - 1 are flattened over the rectangle's own rows, so a tile holds wanted pixels only (at
+            // 128 columns every 128-pixel tile of whole rows would touch the wanted columns).  From here on a.Gy / a.Gx / a.out_oy / a.out_ox
+            // describe the rectangle: the epilogue needs nothing else, the loader adds the origin to its input coordinates.
+            const int tall = (G + NT - 1) / NT;
+            const int r1 = a.row_hi < a.Gy ? a.row_hi : a.Gy, c1 = a.col_hi < a.Gx ? a.col_hi : a.Gx;
+            const int nr = r1 > a.row_lo ? r1 - a.row_lo : 0, wc = c1 > a.col_lo ? c1 - a.col_lo : 0;
+            nt = (nr * wc + NT - 1) / NT;
+            // the partials of the tile slots past the rectangle's (the style finish sums every slot of the whole grid) ...
+            for (int j = nt + (int)blockIdx.x; j < tall; j += (int)gridDim.x) la_conv_zero_partials<MT>(a, bz, m0, j);
+            // ... and, backward, the gradient in the columns left out: exact zeros for the contraction that reads these rows next (its loader
+            // masks rows, not columns; the buffer holds another layer's gradient there).  Dense output, grid = output plane.
+            if (a.epi == LA_EPI_BWD && wc < a.Gx) {
+                const int ns = a.Gx - wc, per_m = nr * ns, mrows = a.M - m0 < MT ? a.M - m0 : MT;
+                float* ob = a.out + ((long)bz * a.M + m0) * a.Hout * a.Wout + (long)a.row_lo * a.Wout;
+                for (int e = (int)blockIdx.x * 256 + (int)threadIdx.x; e < mrows * per_m; e += (int)gridDim.x * 256) {
+                    const int m = e / per_m, rem = e - m * per_m, r = rem / ns, c = rem - r * ns;
+                    ob[(long)m * a.Hout * a.Wout + (long)r * a.Wout + (c < a.col_lo ? c : c + wc)] = 0.f;
+                }
+            }
+            const int n8 = (int)gridDim.x;
+            if ((n8 & 7) == 0) ntile = (blockIdx.x & 7) * (n8 >> 3) + (blockIdx.x >> 3);
+            if (ntile >= nt) return;
+            goy = a.row_lo; gox = a.col_lo;
+            a.out_oy += goy * a.out_sy; a.out_ox += gox * a.out_sx;
+            a.Gy = nr; a.Gx = wc; G = nr * wc;
+        } else if (a.row_hi > 0) {
             // (round 5, as the halo kernel: the launch holds the window's tiles only, rounded up to a multiple of eight -- for merged phases
             //  those of the phase with the most -- and its workgroups zero the partials of the tiles outside the window in turn)
             const int tall = (G + NT - 1) / NT;
@@ -84,6 +111,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
         } else if ((nt & 7) == 0) ntile = (blockIdx.x & 7) * (nt >> 3) + (blockIdx.x >> 3);
         ntile += t0;
     }
+    const int Ntot = SPLIT ? a.B * G : G;
     if (!SPLIT && (long)ntile * NT >= G) return;          // merged phases: the launch is sized for the largest phase
     const int l31 = lane & 31, lh = lane >> 5;
 
@@ -96,7 +124,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
     const int g_l = SPLIT ? nidx_l - b_l * G : nidx_l;
     const int gy_l = nvalid ? g_l / a.Gx : 0;
     const int gx_l = nvalid ? g_l - gy_l * a.Gx : 0;
-    const int iy0 = gy_l * a.in_sy, ix0 = gx_l * a.in_sx;
+    const int iy0 = (gy_l + goy) * a.in_sy, ix0 = (gx_l + gox) * a.in_sx;
     const unsigned HWin = (unsigned)(a.Hin * a.Win);
     const int vy0 = a.in_row_hi > 0 ? a.in_row_lo : 0, vy1 = a.in_row_hi > 0 ? a.in_row_hi : a.Hin;      // valid input rows (LaConvArgs::in_row_lo)
     // fp16 pieces: load k of a thread is the 16-byte piece tid & 7 of the 128-byte record of pixel k * 32 + (tid >> 3) -- pieces 0-3 are
@@ -119,7 +147,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV))) void 
             const int bb = SPLIT ? (pv ? nidx / G : 0) : bz;
             const int g = SPLIT ? nidx - bb * G : nidx;
             const int gy = pv ? g / a.Gx : 0, gx = pv ? g - gy * a.Gx : 0;
-            const int py = gy * a.in_sy, px = gx * a.in_sx;
+            const int py = (gy + goy) * a.in_sy, px = (gx + gox) * a.in_sx;
             const unsigned base = (SPLIT ? (unsigned)bb * ((unsigned)((a.C + KCB - 1) / KCB) * KCB * HWin * 4u) : 0u) + (unsigned)(tid & 7) * 16u;
             plin[k] = base + (unsigned)(py * a.Win + px) * (unsigned)(KCB * EB);
             unsigned m = 0u;

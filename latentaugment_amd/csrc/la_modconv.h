@@ -19,7 +19,8 @@ struct LaModconv {
 //   rgb     ToRGB of the block fused into the epilogue (LaConvArgs::rgb; same-resolution call, la_modconv3x3_fwd_fuses_rgb)
 //   xs_out / xs_mult  the operand scale of y for the contraction that consumes it (LaConvArgs::fwd_xs_out / fwd_xs_mult)
 //   win     window of y, a hint: rows (columns) outside it may or may not be written.  Up-sampling call (column-planar scratch only): the FIR
-//           writes exactly these rows and columns, the transposed conv the whole rows of its intermediate that they read
+//           writes exactly these rows and the 4-column groups of these columns, the transposed conv (direct flat kernel) the rectangle of
+//           every phase of its intermediate that they read -- the rest of the scratch is neither written nor read
 //           (la_modconv3x3_up2_fwd_rows: the input rows such a call reads)
 //   y_pmax  (up-sampling call) [B][cout][la_fir4x4_segments(res, res)]: partial max |y| per plane, written by the FIR epilogue
 //   scratch_pitch / scratch_xhalf (up-sampling call; floats; both 0 = dense (res+1)-wide rows, or both set): COLUMN-PLANAR rows of the
@@ -54,7 +55,9 @@ struct LaBwdRows { LaWindow in, out; };
 //   xscale  [B][LA_XS_FAN] slot rows: the fp16 operand scale of gz, already final when this launch starts (left by the producer of gz through
 //           LaSeamFuse::xs_out / LaSeamArgs::xs_out) -- no plane-maxima reduction launch
 //   rows    up-sampling call (fused fp16 path only): in = valid part of gz (res rows), out = window of gx (res/2 rows); the FIR adjoint then
-//           writes the rows of its (res+1)-row result that can be non-zero, [in.row_lo - 2, in.row_hi + 2), and the contraction reads the others as zeros
+//           writes the rows of its (res+1)-row result that can be non-zero, [in.row_lo - 2, in.row_hi + 2), and the contraction reads the others as zeros.
+//           With in.col_* (gz, and the image gradient behind a fused ToRGB seam, are zero outside those columns) the contraction computes only
+//           the columns of gx where the gradient can be non-zero and writes exact zeros into the others of its rows
 struct LaModconvBwdOpts {
     const float* in_pmax = nullptr; int in_nseg = 0;
     const LaSeamFuse* seam = nullptr;

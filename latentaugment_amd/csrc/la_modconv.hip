@@ -81,6 +81,7 @@ int la_modconv3x3_up2_fwd_ex(const float* x, long x_bstride, const LaModconv& m,
     LA_CHECK_ARG(w.row_lo >= 0 && (w.row_hi == 0 || (w.row_hi > w.row_lo && w.row_hi <= res)), "modconv_up2_fwd: bad row window");
     if (scratch_xhalf == 0) w.row_lo = w.row_hi = 0;      // (only the planar FIR kernel honours a window)
     if (w.row_hi == 0) w.col_lo = w.col_hi = 0;
+    LA_CHECK_ARG(w.col_lo >= 0 && (w.col_hi == 0 || (w.col_hi > w.col_lo && w.col_hi <= res)), "modconv_up2_fwd: bad column window");
     LA_CHECK_ARG(scratch_pitch == 0 || scratch_pitch >= res + 1, "modconv_up2_fwd: scratch pitch smaller than a row");
     LA_CHECK_ARG((scratch_xhalf == 0 && scratch_pitch == 0) || (scratch_xhalf >= res / 2 + 1 && scratch_pitch >= scratch_xhalf + res / 2),
                  "modconv_up2_fwd: bad column-planar scratch layout");
@@ -97,6 +98,15 @@ int la_modconv3x3_up2_fwd_ex(const float* x, long x_bstride, const LaModconv& m,
         a.row_lo = zlo >> 1; a.row_hi = ((zhi - 1) >> 1) + 1;
         // the input rows those phase rows read: nothing else is copied into the pre-split operand, and the contraction reads the rest as zeros
         la_modconv3x3_up2_fwd_rows(res, w.row_lo, w.row_hi, &a.in_row_lo, &a.in_row_hi);
+        if (w.col_hi > 0) {
+            // columns likewise; the FIR computes the whole 4-column groups that hold a wanted column (la_fir4x4_s1p_kernel), so the phase
+            // columns are those of the groups: everything the FIR reads is computed, what lies outside is neither written nor read
+            int zc0 = w.col_lo, zc1 = w.col_hi;
+            la_span_tiles(zc0, zc1, 4, res);
+            la_span_grow(zc0, zc1, 1, 2, res + 1);
+            const int q0 = zc0 >> 1, q1 = ((zc1 - 1) >> 1) + 1;
+            if (q0 > 0 || q1 < res / 2 + 1) { a.col_lo = q0; a.col_hi = q1; }
+        }
     }
     // transposed stride-2 conv of the (modulated) input into the scratch
     int rc = la_conv_up2_launch(a, hin, scratch_pitch, scratch_xhalf, stream);
@@ -192,10 +202,28 @@ int la_modconv3x3_up2_bwd_ex(const float* gz, const LaModconv& m, const float* x
             a.in_row_lo = z.row_lo; a.in_row_hi = z.row_hi;
         }
         if (rows) { a.row_lo = rows->out.row_lo; a.row_hi = rows->out.row_hi; }
-        if ((rc = la_fir4x4_adjoint_pack_f16(gz, q, xscale, xs_fan, B, cout, res, res, fir_host, 4.f, stream, 0, in_win, z))) return rc;
         a.in = gz;                       // (not read: the launch takes its operand from in_q)
         a.in_q = q; a.acc_scale_x = xscale; a.acc_scale_fan = xs_fan;
         a.ws = static_cast<char*>(ws) + fused_need; a.ws_bytes = ws_bytes - fused_need;
+        if (a.row_hi > 0 && in_win.row_hi > 0 && in_win.col_hi > 0) {
+            // Column cone, as the rows: gz is non-zero in columns [col_lo, col_hi) only, the adjoint (4 taps, pad 2) two columns further,
+            // and output column X gathers operand columns 2 X .. 2 X + 2 -- outside [x0, x1) the contraction sums zeros.  The fused seam
+            // adds the ToRGB share of the image gradient one level down: the caller keeps that inside the same columns (la_synth.hip: the
+            // window's tile columns hold the image columns with one to spare, which halves to less than the two taken here).  The launch
+            // then computes the rectangle only and zero-fills the other columns of its rows (LaConvArgs::col_lo); the operand is packed in
+            // the 64-column groups it reads.  Only the direct flat kernel follows columns: where the plan runs another form, all stay.
+            int zc0 = in_win.col_lo, zc1 = in_win.col_hi;
+            la_span_grow(zc0, zc1, 2, 2, res + 1);
+            const int x0 = zc0 > 2 ? (zc0 - 1) >> 1 : 0, x1 = ((zc1 - 1) >> 1) + 1 < hin ? ((zc1 - 1) >> 1) + 1 : hin;
+            if (x0 > 0 || x1 < hin) {
+                a.col_lo = x0; a.col_hi = x1;
+                LaConvPlan p;
+                if ((rc = la_conv_plan(a, p))) return rc;
+                if (p.form == LA_FORM_FLAT) { z.col_lo = 2 * x0; z.col_hi = 2 * x1 + 1; }
+                else a.col_lo = a.col_hi = 0;
+            }
+        }
+        if ((rc = la_fir4x4_adjoint_pack_f16(gz, q, xscale, xs_fan, B, cout, res, res, fir_host, 4.f, stream, 0, in_win, z))) return rc;
         return la_conv_launch(a, stream);
     }
     // adjoint of [pad (1,1,1,1) -> FIR] (la_fir_same_pad2, flipped)

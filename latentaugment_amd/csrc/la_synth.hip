@@ -93,7 +93,11 @@ enum { SEAM_KERNEL = LA_SYNTH_SEAM_KERNEL, SEAM_FUSED = LA_SYNTH_SEAM_FUSED, PMA
 //              for exactly the layers that have a forward window.  The backward launches round them to their own tiles, once.
 //   fwd cols   top block only, where its conv1 has a row window: conv1 in the 32-column tiles that hold the image columns with a tile column
 //              to spare on both sides (the gradient of conv1's input reaches one column beyond the image window: it must stay inside the
-//              tiles), the FIR in front of it (conv0) one column more on either side.
+//              tiles), the FIR in front of it (conv0) one column more on either side.  The two flat launches of the top up-sampling layer
+//              derive their columns from these in their builders (la_modconv.hip): the transposed conv the phase columns that FIR reads, the
+//              stride-2 backward the columns where the gradient at res / 2 can be non-zero (it zero-fills the others of its rows).  That
+//              cone must hold the image gradient one level down (ToRGB share of the fused seam): image columns start one inside the tiles
+//              at least, so they reach column lo / 2 .. hi / 2 there, the cone (lo - 3) / 2 .. hi / 2 + 1.
 static void plan_windows(SynthPlan& P, const LaWindow& img) {
     const int nblocks = P.pass.nblocks, nconv = P.pass.nconv, R = 4 << (nblocks - 1);
     if (img.row_hi <= 0) return;
@@ -412,7 +416,9 @@ extern "C" int la_synth_set_row_window(la_synth* h, int row_lo, int row_hi) {
 
 // Column window of the image on top of the row window (0, 0 = all columns).  Only the TOP block follows it -- its conv1 (forward: the 32-column
 // tiles that hold the window; backward: the same tiles, the gradient of its input is non-zero one column further at most), the FIR that
-// feeds it and the FIR adjoint behind it (which reads the other columns as zeros); every other kernel computes whole rows.
+// feeds it, the FIR adjoint behind it (which reads the other columns as zeros) and the two contractions of its up-sampling layer (forward: the
+// phase columns the FIR reads; backward: the columns of the gradient at half the resolution that can be non-zero); every other kernel
+// computes whole rows.
 extern "C" int la_synth_set_col_window(la_synth* h, int col_lo, int col_hi) {
     LA_CHECK_ARG(h && col_lo >= 0 && (col_hi == 0 ? col_lo == 0 : (col_hi > col_lo && col_hi <= h->R)), "synth_set_col_window: bad window");
     h->win.col_lo = col_lo; h->win.col_hi = col_hi;

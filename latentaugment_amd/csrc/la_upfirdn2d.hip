@@ -618,6 +618,7 @@ struct FirPackArgs {
     int in_lo, in_hi;      // valid rows of `in` (0 / 0 = all): the others read as zeros (a windowed producer left older contents there)
     int in_c0, in_c1;      // valid columns of `in` likewise (multiples of 4; 0 / 0 = all)
     int out_lo, out_hi;    // row window of the output (0 / 0 = all): 8-row workgroup tiles without a wanted row write nothing
+    int out_c0, out_c1;    // column window of the output likewise: 64-column workgroup tiles without a wanted column write nothing
 };
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void la_fir4x4_adj_pack_kernel(FirPackArgs a) {
@@ -627,6 +628,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void l
     const int b = blockIdx.z / a.nck, ck = blockIdx.z - b * a.nck;
     const int Xb = blockIdx.x * 64, Yb = blockIdx.y * 8;
     if (a.out_hi > 0 && (Yb + 8 <= a.out_lo || Yb >= a.out_hi)) return;      // row window of the output: nothing wanted in these 8 rows
+    if (a.out_c1 > 0 && (Xb + 64 <= a.out_c0 || Xb >= a.out_c1)) return;     // ... column window: nor in these 64 columns
     const int vin0 = a.in_hi > 0 ? a.in_lo : 0, vin1 = a.in_hi > 0 ? a.in_hi : a.H;
     const int X0 = Xb + xg * 4, Y0 = Yb + rs * 4;
     const float xs = la_xs_get(a.xscale, b, a.xs_fan);
@@ -722,6 +724,8 @@ int la_fir4x4_adjoint_pack_f16(const float* in, unsigned* q, const float* xscale
     FirPackArgs a;
     a.in = in; a.out = q; a.xscale = xscale; a.xs_fan = xs_fan; a.B = B; a.C = C; a.H = H; a.W = W; a.Hz = H + 1; a.Wz = W + 1; a.nck = la_cdiv(C, 32);
     a.in_lo = in_win.row_lo; a.in_hi = in_win.row_hi; a.out_lo = out_lo; a.out_hi = out_hi; a.in_c0 = in_c0; a.in_c1 = in_c1;
+    a.out_c0 = out_win.col_lo; a.out_c1 = out_win.col_hi;
+    LA_CHECK_ARG(a.out_c0 >= 0 && (a.out_c1 == 0 || a.out_c1 > a.out_c0), "fir_adjoint_pack: bad output column window");
     LA_CHECK_ARG(in_c0 % 4 == 0 && in_c1 % 4 == 0, "fir_adjoint_pack: the column mask is in groups of 4");
     a.pad = 2;         // adjoint of pad (1,1,1,1): fw - 1 - pad = 2 per side (upfirdn2d.py:255-266)
     // adjoint = correlation with the flipped filter = flip_filter of the forward op negated; the forward (flip_filter = False)
