@@ -840,6 +840,33 @@ int la_path_points_f32(const float* a, const float* b, const float* t, const dou
                        float* out, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Projector: inversion of images into W / W+ (Karras et al. 2020, Appendix D, without the noise maps).  The reference reads inverted
+ * latents (augments/latent_aug.py:310-324) and has no code that makes them.  The optimisation is an eager sequence of launches over
+ * the synthesis and feature engines (latentaugment_amd/projector.py); these are the kernels that only it needs.  No atomics: two runs
+ * give the same bits.  Bad arguments are LA_ERR_ARG before any launch.
+ *   la_row_dist_f32   a, t [rows][K]: loss[j * loss_stride] = scale * sum_{c < fold} sum_k (a - t)^2 over row c * (rows / fold) + j, for
+ *                     j < rows / fold (fold = 1: one value per row; fold = C: the modality-major rows of la_crop_repeat_f32 folded per
+ *                     sample), and, g not null, g = gscale * (a - t) -- accumulate != 0: added to g.  The difference is formed in
+ *                     float32 and its square summed in float64 in an order fixed by the shape.  ws: la_row_dist_workspace_bytes(rows, K)
+ *                     bytes, 8-byte aligned (LA_ERR_WORKSPACE when short).  rows at most 65535.  Any 4-byte aligned a, t, g.
+ *   la_box_down_f32   x [planes][R][R] -> y [planes][R / k][R / k], the mean of each k x k box; k in 1, 2, 4, 8 and R a multiple of k.
+ *                     Exact on integer-valued planes.  la_box_up_f32: its adjoint, gx [planes][R][R] = gy[..][Y / k][X / k] / k^2 (written).
+ *   la_proj_step_tail_f32   one launch for the end of a step.  p, m, v, ws are [B][L][wdim] with L = 1 (wplus = 0) or num_ws; dws is
+ *                     [B][num_ws][wdim], in W space summed over its num_ws rows in index order.  p, m, v take the Adam step of
+ *                     la_adam_step_f32 (`step` 1-based, lr of this step), then ws = p + sigma * n with n the unit normal of
+ *                     (seed, layer, row0 + b, element l * wdim + j): the stream of la_noise_normal_f32 with rows of L * wdim elements.
+ *                     dws null: no update, ws alone is written (m, v may be null).
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t la_row_dist_workspace_bytes(int rows, long K);
+int la_row_dist_f32(const float* a, const float* t, int rows, long K, int fold, double scale, float gscale, float* g, int accumulate,
+                    double* loss, long loss_stride, void* ws, size_t ws_bytes, la_stream_t stream);
+int la_box_down_f32(const float* x, float* y, long planes, int R, int k, la_stream_t stream);
+int la_box_up_f32(const float* gy, float* gx, long planes, int R, int k, la_stream_t stream);
+int la_proj_step_tail_f32(const float* dws, float* p, float* m, float* v, float* ws, int B, int num_ws, int wdim, int wplus, int step,
+                          float lr, float beta1, float beta2, float eps, float sigma, unsigned long long seed, unsigned layer, long row0,
+                          la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in profiler for the contraction launches (HIP events on the launch stream).  No reference counterpart: the
  * reference's only timing hook is wall-clock stats_time (augments/latent_aug.py:276).
  * la_prof_end: summed device ms, launch count, algorithmic FLOPs (2*MACs) and algorithmic bytes (input + output +

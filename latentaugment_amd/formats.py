@@ -79,6 +79,26 @@ class LatentCodeDataset(_ZipPickles):
             return np.asarray(_restricted_load(f)).astype('float32')
 
 
+def write_latent_zip(path, codes):
+    """The zip LatentCodeDataset reads, from (member name, latent) pairs: each member a pickled float32 ndarray [num_ws, w_dim] under the
+    name of the slice's member of the image zip ("<split>/<patient>/<slice>.pickle"), which is the name `lookup` is called with.  Every
+    code must have the first one's shape, and a name may come once.  Returns the number of members written."""
+    if _ext(path) != '.zip':
+        raise IOError('Path must point to a zip')
+    shape, seen = None, set()
+    with zipfile.ZipFile(path, 'w') as z:
+        for fname, w in codes:
+            w = np.ascontiguousarray(np.asarray(w), dtype=np.float32)
+            shape = w.shape if shape is None else shape
+            if w.ndim != 2 or w.shape != shape:
+                raise ValueError(f'latent of {fname!r} has shape {w.shape}; expected [num_ws, w_dim] = {list(shape)} for every member')
+            if _ext(fname) != '.pickle' or fname in seen:
+                raise ValueError(f'member name {fname!r}: expected a ".pickle" name that has not been written yet')
+            seen.add(fname)
+            z.writestr(fname, pickle.dumps(w))
+    return len(seen)
+
+
 class ImgDataset(_ZipPickles):
     """util_dataset.py:210-279: each member is a pickled dict modality -> 2-D array (raw 0..255); item = CHW float32."""
 
