@@ -89,9 +89,26 @@ template <class H, class F> static inline size_t la_measure_workspace(F measure)
 }
 
 // ---------------------------------------------------------------- device helpers
-__device__ __forceinline__ float la_wave_sum(float v) {
+// Reductions live here (and the noise stream in la_rng.h): a kernel file does not write its own, so that "in a fixed order" has one
+// definition.  The xor butterfly over the W = 64 lanes of a wave, or inside each 32-lane half (W = 32), starting at distance W / 2:
+// every lane ends with the result.  T: float, double or int.
+// (Where a butterfly's result is read only under a following `if (lane == 0)`, the written-out loop and a call compile to different
+// instruction schedules -- the last step is sunk into that block at another moment.  The sites of that shape which were written out
+// when these helpers arrived stay written out -- la_block_max_256 below, la_op_block_sum_256 (la_ops.hip) and pp_block_sum
+// (la_pathpoints.hip) among them; tests/test_host_cpu.py lists them.)
+template <int W = 64, class T> __device__ __forceinline__ T la_wave_sum(T v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+template <int W = 64> __device__ __forceinline__ float la_wave_max(float v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+template <int W = 64> __device__ __forceinline__ float la_wave_min(float v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
     return v;
 }
 
@@ -103,6 +120,19 @@ __device__ __forceinline__ float la_block_sum_256(float v, float* red) {
     if (lane == 0) red[wid] = v;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
+}
+
+// Block-wide float64 sum for blockDim.x == 256 as a halving tree over 256 LDS doubles (`red`); the leading barrier lets calls follow
+// one another on the same `red`.  All threads get the result, which also stays in red[0].
+__device__ __forceinline__ double la_block_tree_sum_256(double v, double* red) {
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    return red[0];
 }
 
 // Block-wide maximum, same shape: wave shuffle, then 4 LDS floats.  Every thread of the workgroup must reach it (lanes with nothing

@@ -347,8 +347,7 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
         else run(std::integral_constant<int, 1>{});
     }
     if (a.epi == LA_EPI_FWD && a.fwd_xs_out) {      // (uniform; PPB == 1: every wave of the plane lowers its own sub-slot)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ymax = fmaxf(ymax, __shfl_xor(ymax, o, 64));
+        ymax = la_wave_max(ymax);
         if (xs_row) la_xs_lower(xs_row, xs_seen, a.fwd_xs_mult ? a.fwd_xs_mult[b] : 1.f, ymax);
     }
     if (a.epi == LA_EPI_BWD && (a.ds_part || seam)) {
@@ -356,8 +355,7 @@ __global__ __launch_bounds__(256) void la_conv_splitk_finish_kernel(LaConvArgs a
         dd = la_wave_sum(dd);
 #pragma unroll
         for (int c = 0; c < 4; ++c) dwe[c] = la_wave_sum(dwe[c]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        mx = la_wave_max(mx);
         if (PPB == 1) {
             __shared__ float wdd[4], wmx[4], wdw[4][4];
             if (lane == 0) {

@@ -286,8 +286,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                         float m = 0.f;
 #pragma unroll
                         for (int k = tid; k < MT; k += 64) m = fmaxf(m, red[12][k]);
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+                        m = la_wave_max(m);
                         if (tid == 0) la_xs_lower(a.seam.xs_out + (long)b * LA_XS_FAN + la_xs_sub(), xs_seen, a.seam.xs_mult, m);
                     }
                 }
@@ -547,8 +546,7 @@ __device__ __forceinline__ void la_conv_epilogue(const LaConvArgs& a, f32x16 (&a
                     float m = 0.f;
                     for (int k = tid; k < MT; k += 64)
                         if (m0 + k < a.M) m = fmaxf(m, red[12][k]);
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+                    m = la_wave_max(m);
                     if (tid == 0) la_xs_lower(a.seam.xs_out + (long)b * LA_XS_FAN + la_xs_sub(), xs_seen, a.seam.xs_mult, m);
                 }
             }

@@ -229,8 +229,7 @@ __global__ __launch_bounds__(256) void la_fromrgb_fwd_kernel(const float* __rest
     }
     }
     if (xs_rows) {      // fp16 operand scale of y for the contractions that read it: every wave lowers a sub-slot of the sample's row (la_common.h)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ymax = fmaxf(ymax, __shfl_xor(ymax, o, 64));
+        ymax = la_wave_max(ymax);
         if ((threadIdx.x & 63) == 0) {
             float* row = xs_rows + (long)b * LA_XS_FAN + la_xs_sub((int)(threadIdx.x >> 6));
             la_xs_lower(row, la_xs_peek(row), 1.f, ymax);

@@ -22,7 +22,7 @@
 //                           m <= 8192; the kernel is instantiated for 1, 2, 4, 8, 16 and 32), so a vector is read once per round and
 //                           written at most once.  Longer vectors take the streaming instantiation, which reads a rotated pair twice.
 //   la_fd_finish_f64        the vector norms (= singular values) and their sum.
-// Every float64 sum is thread-strided and then a fixed tree (fd_block_sum): no float atomics anywhere, two runs give the same bits.
+// Every float64 sum is thread-strided and then a fixed tree (la_block_tree_sum_256): no float atomics anywhere, two runs give the same bits.
 // The only atomic is the integer count of rotations.
 #include "la_common.h"
 
@@ -53,18 +53,6 @@ extern "C" int la_fd_round_pair(int n, int round, int k, int* p, int* q) {
     LA_CHECK_ARG(round >= 0 && round < n2 - 1 && k >= 0 && k < n2 / 2, "fd_round_pair: round in 0 .. n' - 2 and k in 0 .. n'/2 - 1");
     fd_round_pair(n2, round, k, p, q);
     return LA_OK;
-}
-
-// sum over the 256 threads in a fixed tree; every thread gets it.  red: 256 doubles of LDS
-__device__ __forceinline__ double fd_block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 // three sums at once for the Jacobi round (one barrier): xor tree inside each wave, then the four waves in wave order.  Every thread
@@ -122,7 +110,7 @@ __global__ __launch_bounds__(256) void la_fd_rowsq_kernel(const float* __restric
         const double v = (double)row[d] - mu[d];
         acc += v * v;
     }
-    acc = fd_block_sum(acc, red);
+    acc = la_block_tree_sum_256(acc, red);
     if (threadIdx.x == 0) rowsq[b] = acc;
 }
 
@@ -135,13 +123,13 @@ __global__ __launch_bounds__(256) void la_fd_terms_kernel(const double* __restri
         const double v = mux[d] - muy[d];
         acc += v * v;
     }
-    const double t0 = fd_block_sum(acc, red);
+    const double t0 = la_block_tree_sum_256(acc, red);
     acc = 0.0;
     for (long i = threadIdx.x; i < nx; i += 256) acc += rowsq[i];
-    const double t1 = fd_block_sum(acc, red);
+    const double t1 = la_block_tree_sum_256(acc, red);
     acc = 0.0;
     for (long i = threadIdx.x; i < ny; i += 256) acc += rowsq[nx + i];
-    const double t2 = fd_block_sum(acc, red);
+    const double t2 = la_block_tree_sum_256(acc, red);
     if (threadIdx.x == 0) { terms[0] = t0; terms[1] = t1; terms[2] = t2; }
 }
 
@@ -277,7 +265,7 @@ __global__ __launch_bounds__(256) void la_fd_norm_kernel(const double* __restric
     const double* c = v + (long)blockIdx.x * m;
     double acc = 0.0;
     for (long i = threadIdx.x; i < m; i += 256) acc += c[i] * c[i];
-    acc = fd_block_sum(acc, red);
+    acc = la_block_tree_sum_256(acc, red);
     if (threadIdx.x == 0) {
         const double s = sqrt(acc);
         norms[blockIdx.x] = s;
@@ -290,7 +278,7 @@ __global__ __launch_bounds__(256) void la_fd_nuc_kernel(const double* __restrict
     __shared__ double red[256];
     double acc = 0.0;
     for (long i = threadIdx.x; i < n; i += 256) acc += norms[i];
-    acc = fd_block_sum(acc, red);
+    acc = la_block_tree_sum_256(acc, red);
     if (threadIdx.x == 0) nuc[0] = acc;
 }
 

@@ -5,12 +5,13 @@
 // test happens in floating point, before any int exists).  Nothing here uses atomics: every output element is written by one thread
 // from sums taken in a fixed order, so two runs give the same bits.
 //
-//   la_noise_uniform_f32   Philox4x32-10 as la_noise_normal_f32 uses it (la_misc.hip): four words -> four values in (-1, 1)
+//   la_noise_uniform_f32   the noise stream of la_rng.h: four words -> four values in (-1, 1)
 //   la_elastic_field_f32   separable zero-border blur of both noise planes, ONE launch: a workgroup stages its 16 x 64 output tile with a
 //                          halo of (ntaps - 1) / 2 on every side in LDS, filters the rows into a second LDS image, then the columns
 //   la_warp_affine_f32     out[b,c,y,x] = S(in[b,c], Minv[b] (x, y, 1))
 //   la_warp_elastic_f32    out[b,c,y,x] = S(in[b,c], position of the displaced normalised grid)
 #include "la_common.h"
+#include "la_rng.h"
 #include "la_geom_index.h"
 
 #include <limits.h>
@@ -21,19 +22,7 @@
 #define LA_EF_TH 16      // ... 16 rows; LDS at the largest halo (31): (78 x 126 + 78 x 64) floats = 59 280 bytes, two workgroups per CU
 
 // ------------------------------------------------------------------------------------------------------------ uniform noise
-__device__ __forceinline__ void la_geom_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-// counter (e / 4, row, stream_id, high word of e / 4), key (seed low, seed high): word j of the block is element 4 (e / 4) + j.
-// (k + 0.5) * 2^-22 - 1 with k the top 23 bits: (2k + 1 - 2^23) * 2^-23, an odd numerator below 2^23 -- exact in float32, never -1, 0 or 1.
+// word j of the block of counter e / 4 (la_noise_words) is element 4 (e / 4) + j, mapped into (-1, 1) by la_unit_uniform
 __global__ __launch_bounds__(LA_GEOM_BLOCK) void la_noise_uniform_kernel(float* __restrict__ out, long rows, long row_elems, unsigned k0, unsigned k1,
                                                                          unsigned stream_id, long row0) {
     const long q4 = (row_elems + 3) >> 2;
@@ -41,11 +30,11 @@ __global__ __launch_bounds__(LA_GEOM_BLOCK) void la_noise_uniform_kernel(float* 
     if (g >= rows * q4) return;
     const long r = g / q4, q = g - r * q4;
     unsigned x[4];
-    la_geom_philox4x32_10((unsigned)q, (unsigned)(row0 + r), stream_id, (unsigned)((unsigned long long)q >> 32), k0, k1, x);
+    la_noise_words(q, row0 + r, stream_id, k0, k1, x);
     float* o = out + r * row_elems + 4 * q;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-        if (4 * q + k < row_elems) o[k] = ((float)(x[k] >> 9) + 0.5f) * (1.f / 4194304.f) - 1.f;
+        if (4 * q + k < row_elems) o[k] = la_unit_uniform(x[k]);
 }
 
 extern "C" int la_noise_uniform_f32(float* out, long rows, long row_elems, unsigned long long seed, unsigned stream_id, long row0, hipStream_t stream) {

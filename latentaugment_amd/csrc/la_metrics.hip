@@ -117,8 +117,7 @@ __global__ __launch_bounds__(256) void la_pr_tile_kernel(const _Float16* __restr
             float kth = 0.f;
             for (int t = 0; t < kk; ++t) {
                 float m = best[MODE == 0 ? r : 0][0];
-#pragma unroll
-                for (int o = 16; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));      // stays inside each 32-lane half
+                m = la_wave_min<32>(m);      // stays inside each 32-lane half
                 kth = m;
                 // the lowest lane holding m pops its head
                 const unsigned long long has = __ballot(best[MODE == 0 ? r : 0][0] == m);
@@ -246,17 +245,6 @@ struct KidArgs {
     int nxx, nyy, tiles; // tiles per subset: xx upper triangle, yy upper triangle, then tx * ty of xy
     double* part;        // [S][tiles]
 };
-
-// fixed-order sum over the 256 threads of a workgroup; the result is in red[0]
-__device__ __forceinline__ void kid_block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-}
 
 __global__ __launch_bounds__(256) void la_kid_tile_kernel(KidArgs a) {
     __shared__ __attribute__((aligned(16))) float As[2][KID_KC][KID_LD];
@@ -387,7 +375,7 @@ __global__ __launch_bounds__(256) void la_kid_tile_kernel(KidArgs a) {
                 }
             }
         }
-    kid_block_sum(dsum, red);
+    la_block_tree_sum_256(dsum, red);
     if (tid == 0) a.part[blockIdx.x] = (kind != 2 && ti != tj) ? 2.0 * red[0] : red[0];
 }
 
@@ -403,7 +391,7 @@ __global__ __launch_bounds__(256) void la_kid_finish_kernel(const double* __rest
     for (int q = 0; q < 3; ++q) {
         double acc = 0.0;
         for (int t = beg[q] + (int)threadIdx.x; t < beg[q + 1]; t += 256) acc += p[t];
-        kid_block_sum(acc, red);
+        la_block_tree_sum_256(acc, red);
         v[q] = red[0];
     }
     if (threadIdx.x == 0) {
@@ -418,7 +406,7 @@ __global__ __launch_bounds__(256) void la_kid_mean_kernel(const double* __restri
     __shared__ double red[256];
     double acc = 0.0;
     for (long s = threadIdx.x; s < S; s += 256) acc += mmd2[s];
-    kid_block_sum(acc, red);
+    la_block_tree_sum_256(acc, red);
     if (threadIdx.x == 0) kid[0] = red[0] / (double)S;
 }
 

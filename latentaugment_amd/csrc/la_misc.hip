@@ -1,5 +1,6 @@
 // Error reporting + the standalone elementwise ops of the C ABI (the SG2 forms of bias_act, Adam, small vector helpers).
 #include "la_common.h"
+#include "la_rng.h"
 
 #include <string.h>
 
@@ -51,7 +52,6 @@ extern "C" int la_bias_act_f32(const float* x, const float* b, float* y, long n,
     LA_CHECK_ARG(x && y && n > 0, "bias_act: null pointer");
     LA_CHECK_ARG(act_ok(act), "bias_act: only linear(1)/relu(2)/lrelu(3) are implemented on this path");
     LA_CHECK_ARG(!b || (stepb >= 1 && nb >= 1 && n % (stepb * nb) == 0), "bias_act: bias does not tile the tensor");
-    if (n == 0) return LA_OK;
     if (!b) { stepb = 4; nb = 1; }
     long blocks = la_cdiv(la_cdiv(n, 4), 256);
     if (blocks > 8192) blocks = 8192;
@@ -66,7 +66,6 @@ extern "C" int la_bias_act_grad_f32(const float* dy, const float* yref, float* d
     if (n == 0) return LA_OK;
     LA_CHECK_ARG(dy && yref && dx && n > 0, "bias_act_grad: null pointer");
     LA_CHECK_ARG(act_ok(act), "bias_act_grad: only linear(1)/relu(2)/lrelu(3) are implemented on this path");
-    if (n == 0) return LA_OK;
     long blocks = la_cdiv(n, 256);
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(la_bias_act_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dy, yref, dx, n, act, alpha,
@@ -163,22 +162,7 @@ extern "C" int la_adam_step_f32(float* p, const float* g, float* m, float* v, lo
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Counter-based unit normals for the explicit noise tensors of noise_mode='random' (the reference draws torch.randn per layer inside
-// G.synthesis, util_latent_aug.py:308 / SURVEY 3.4 defect g; a draw cannot be bit-equal to another library's stream, it only has to
-// be N(0, 1) and reproducible).  Element e of GLOBAL sample row r of layer l under `seed` is a pure function of (seed, l, r, e):
-// Philox4x32-10 (Salmon et al., SC'11) with counter (e / 4, r, l, 0) and key (seed low, seed high) gives four 32-bit words, two
-// Box-Muller pairs turn them into elements 4 (e / 4) .. 4 (e / 4) + 3.  A rank that holds rows [row0, row0 + rows) of a batch
-// therefore generates exactly its rows -- nothing of the other ranks' -- and the gathered batch does not depend on the sharding.
-__device__ __forceinline__ void la_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
+// The counter-based unit normals of noise_mode='random': one thread per 4-element group of a row (the stream: la_rng.h).
 __global__ __launch_bounds__(256) void la_noise_normal_kernel(float* __restrict__ out, long rows, long row_elems, unsigned k0, unsigned k1,
                                                              unsigned layer, long row0) {
     const long q4 = (row_elems + 3) >> 2;                      // 4-element groups per row
@@ -186,17 +170,9 @@ __global__ __launch_bounds__(256) void la_noise_normal_kernel(float* __restrict_
     if (g >= rows * q4) return;
     const long r = g / q4, q = g - r * q4;
     unsigned x[4];
-    la_philox4x32_10((unsigned)q, (unsigned)(row0 + r), layer, (unsigned)((unsigned long long)q >> 32), k0, k1, x);
+    la_noise_words(q, row0 + r, layer, k0, k1, x);
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)(x[2 * h] >> 8) + 0.5f) * (1.f / 16777216.f);      // (0, 1): 24 bits, exactly representable
-        const float u2 = ((float)(x[2 * h + 1] >> 8) + 0.5f) * (1.f / 16777216.f);
-        const float rad = sqrtf(-2.f * logf(u1));
-        float sn, cs;
-        sincosf(6.283185307179586f * u2, &sn, &cs);
-        z[2 * h] = rad * cs; z[2 * h + 1] = rad * sn;
-    }
+    la_unit_normals4(x, z);
     float* o = out + r * row_elems + 4 * q;
 #pragma unroll
     for (int k = 0; k < 4; ++k)

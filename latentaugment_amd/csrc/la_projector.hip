@@ -5,6 +5,7 @@
 //   la_proj_step_tail_f32   W-space row sum + Adam + the next step's noised latent in one launch
 // No atomics anywhere: two runs give the same bits.
 #include "la_common.h"
+#include "la_rng.h"
 
 #include <math.h>
 
@@ -14,12 +15,6 @@
 // chunk's sum stored as partial[row][chunk].  The finish launch adds the partials of an output's rows in (row, chunk) order: thread i
 // takes partials i, i + 64, ..., then the same shuffle.  Every order is fixed by the shape alone.
 #define LA_RD_CHUNK 8192      // elements per workgroup: 256 threads x 8 float4
-
-__device__ __forceinline__ double la_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void la_row_dist_kernel(const float* __restrict__ a, const float* __restrict__ t, float* __restrict__ g,
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(256) void la_row_dist_kernel(const float* __restric
             if (gr) gr[k] = accumulate ? gr[k] + gscale * d : gscale * d;
         }
     }
-    acc = la_wave_sum_f64(acc);
+    acc = la_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[row * chunks + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
@@ -67,7 +62,7 @@ __global__ __launch_bounds__(64) void la_row_dist_finish_kernel(const double* __
         const double* p = partial + ((long)c * outs + j) * chunks;
         for (int i = threadIdx.x; i < chunks; i += 64) acc += p[i];
     }
-    acc = la_wave_sum_f64(acc);
+    acc = la_wave_sum(acc);
     if (threadIdx.x == 0) loss[(long)j * loss_stride] = scale * acc;
 }
 
@@ -162,20 +157,8 @@ extern "C" int la_box_up_f32(const float* gy, float* gx, long planes, int R, int
 // one sample's row of L * wdim elements, i.e. one Philox counter of the noise stream.  Per element (slot l, column j):
 //   gradient  W: dws[b][0][j] + dws[b][1][j] + ... in slot order (float32);  W+: dws[b][l][j]
 //   Adam      la_adam_update with the bias corrections of the 1-based `step` (the powf / sqrtf of la_adam_step_f32, taken by the host)
-//   ws        p + sigma * n, n the unit normal of (seed, layer, row0 + b, element): the stream of la_noise_normal_f32 (la_misc.hip) --
-//             Philox4x32-10 on counter (q, row, layer, q >> 32), key = the seed's halves, two Box-Muller pairs per counter
+//   ws        p + sigma * n, n the unit normal of (seed, layer, row0 + b, element): the stream of la_noise_normal_f32 (la_rng.h)
 // dws null: no update, only ws is written (the start of a run).
-__device__ __forceinline__ void la_proj_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
 __global__ __launch_bounds__(256) void la_proj_step_tail_kernel(const float* __restrict__ dws, float* __restrict__ p, float* __restrict__ m,
                                                                float* __restrict__ v, float* __restrict__ ws, int B, int num_ws, int wdim, int L,
                                                                float step_size, float bc2_sqrt, float b1, float b2, float eps, float sigma,
@@ -186,17 +169,9 @@ __global__ __launch_bounds__(256) void la_proj_step_tail_kernel(const float* __r
     if (gidx >= (long)B * q4) return;
     const long b = gidx / q4, q = gidx - b * q4;
     unsigned x[4];
-    la_proj_philox4x32_10((unsigned)q, (unsigned)(row0 + b), layer, (unsigned)((unsigned long long)q >> 32), k0, k1, x);
+    la_noise_words(q, row0 + b, layer, k0, k1, x);
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)(x[2 * h] >> 8) + 0.5f) * (1.f / 16777216.f);
-        const float u2 = ((float)(x[2 * h + 1] >> 8) + 0.5f) * (1.f / 16777216.f);
-        const float rad = sqrtf(-2.f * logf(u1));
-        float sn, cs;
-        sincosf(6.283185307179586f * u2, &sn, &cs);
-        z[2 * h] = rad * cs; z[2 * h + 1] = rad * sn;
-    }
+    la_unit_normals4(x, z);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const long e = 4 * q + k;

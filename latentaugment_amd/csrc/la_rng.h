@@ -1,0 +1,46 @@
+// The library's counter-based noise stream (device code; gfx950 / CDNA4 only): the one definition of the generator, of its counter
+// convention and of the two maps from words to values.  A kernel file does not write its own.
+#pragma once
+#include "la_common.h"
+
+// Counter-based unit normals for the explicit noise tensors of noise_mode='random' (the reference draws torch.randn per layer inside
+// G.synthesis, util_latent_aug.py:308 / SURVEY 3.4 defect g; a draw cannot be bit-equal to another library's stream, it only has to
+// be N(0, 1) and reproducible).  Element e of GLOBAL sample row r of stream (layer) l under `seed` is a pure function of (seed, l, r, e):
+// Philox4x32-10 (Salmon et al., SC'11) with counter (e / 4, r, l, high word of e / 4) and key (seed low, seed high) gives four 32-bit
+// words, two Box-Muller pairs turn them into elements 4 (e / 4) .. 4 (e / 4) + 3.  A rank that holds rows [row0, row0 + rows) of a
+// batch therefore generates exactly its rows -- nothing of the other ranks' -- and the gathered batch does not depend on the sharding.
+__device__ __forceinline__ void la_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+// the four words of 4-element group q of global row `row` of stream `stream`: counter (q, row, stream, high word of q), key (k0, k1)
+__device__ __forceinline__ void la_noise_words(long q, long row, unsigned stream, unsigned k0, unsigned k1, unsigned (&x)[4]) {
+    la_philox4x32_10((unsigned)q, (unsigned)row, stream, (unsigned)((unsigned long long)q >> 32), k0, k1, x);
+}
+
+// Four words -> four unit normals: two Box-Muller pairs, u = (k + 0.5) * 2^-24 with k the word's top 24 bits.  In float32 k + 0.5
+// needs 25 bits once k >= 2^23 and rounds to even there: the upper half of the range loses the offset, and u1 can be exactly 1
+// (radius 0, both values of the pair 0).  It can never be 0, so no logarithm is infinite and no value is NaN.
+// oracle/noise_ref.py copies this float32 rounding; the formula is pinned bit for bit and does not change.
+__device__ __forceinline__ void la_unit_normals4(const unsigned (&x)[4], float (&z)[4]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = ((float)(x[2 * h] >> 8) + 0.5f) * (1.f / 16777216.f);
+        const float u2 = ((float)(x[2 * h + 1] >> 8) + 0.5f) * (1.f / 16777216.f);
+        const float rad = sqrtf(-2.f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        z[2 * h] = rad * cs; z[2 * h + 1] = rad * sn;
+    }
+}
+
+// One word -> one value in (-1, 1): (k + 0.5) * 2^-22 - 1 with k the top 23 bits, i.e. (2k + 1 - 2^23) * 2^-23, an odd numerator
+// below 2^23 -- exact in float32, never -1, 0 or 1.
+__device__ __forceinline__ float la_unit_uniform(unsigned word) { return ((float)(word >> 9) + 0.5f) * (1.f / 4194304.f) - 1.f; }

@@ -434,3 +434,25 @@ def test_kernel_class_map_is_the_profilers():
     assert kc.class_of('void la_conv_bf16_kernel<128, false, 16, 3, 2>(LaConvArgs)') == 'conv_flat'
     assert kc.class_of('la_conv_splitk_finish_kernel<4>') == 'conv_splitk' and kc.class_of('la_xscale_bound_kernel') is None
     assert kc.class_of('la_imgrad_pyramid_kernel(PyrArgs)') == 'fir' and kc.class_of('la_step_tail_kernel') is None
+
+
+def test_reductions_and_noise_stream_have_one_home():
+    """The Philox stream is written once (csrc/la_rng.h) and the wave xor butterfly lives in csrc/la_common.h (la_wave_sum / _max / _min):
+    a kernel file calls them and does not write its own.  `kept` counts the written-out butterflies that stay, per file: the ones whose
+    result is read only under a following `if (lane == 0)`, where a call changes the unit's instruction schedule (la_common.h,
+    scripts/device_code_hashes.py).  The list is exact: a new copy fails here, and so does a listed site that has gone."""
+    import glob
+    csrc = os.path.join(ROOT, 'latentaugment_amd', 'csrc')
+    kept = {'la_common.h': 4,            # la_wave_sum, la_wave_max, la_wave_min, la_block_max_256
+            'la_conv_device.h': 5, 'la_conv_operand.hip': 5, 'la_criteria.hip': 2, 'la_frechet.hip': 1, 'la_grid_sample.hip': 1,
+            'la_metrics.hip': 2, 'la_ops.hip': 1, 'la_pairmetrics.hip': 1, 'la_pathpoints.hip': 1, 'la_style.hip': 2}
+    found, philox = {}, []
+    for path in sorted(glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h'))):
+        text, name = open(path).read(), os.path.basename(path)
+        n = len(re.findall(r'for \(int (\w+) = [^;]+; \1 > 0; \1 >>= 1\)[^;]*__shfl_xor', text))      # (a tree loop over LDS has none)
+        if n:
+            found[name] = n
+        if '0xd2511f53' in text.lower():
+            philox.append(name)
+        assert not re.findall(r'\b(?:la_proj_philox4x32_10|la_geom_philox4x32_10|la_wave_sum_f64|fd_block_sum|kid_block_sum)\b', text), name
+    assert philox == ['la_rng.h'] and found == kept
