@@ -11,6 +11,13 @@
  * Conventions
  *   - plain pointers and sizes only; every data pointer is DEVICE memory (fp32, contiguous NCHW) unless its name ends
  *     in `_host`; the caller has selected the device and owns every buffer; nothing here allocates device memory.
+ *   - workspaces (`ws`, `workspace`, `scratch`, the sign buffer `so`, the mapping's `tmp`): a workspace may hold ANY bytes when it is
+ *     handed over -- no entry relies on zeros or on what an earlier call left, except where an entry says that it continues another
+ *     on the same workspace (la_fd_gram_f32 -> la_fd_jacobi_sweep_f64 -> la_fd_finish_f64; the passes of one engine handle) -- and
+ *     nothing outside [base, base + bytes) is written, `bytes` being what the entry's la_*_workspace_bytes / _floats reports (or the
+ *     `workspace_bytes` passed, where that is smaller and still accepted).  Outputs are written in full and nowhere else.
+ *     An engine whose create clears its workspace (la_synth_create) meets the first half that way; the others re-arm what a pass
+ *     accumulates into before the pass does ("Workspace contract"; tests/test_hip_workspace_guard.py).
  *   - all work is enqueued on `stream` (a hipStream_t, passed as void* from foreign code); no host<->device sync.
  *   - return 0 on success, negative on failure (LA_ERR_*); la_last_error() gives the thread's last message.
  *     This replaces the TORCH_CHECKs of the reference bindings (bias_act.cpp:35-51, upfirdn2d.cpp:19-40).
@@ -631,7 +638,7 @@ int la_latent_opt_set_disc(la_latent_opt* h, la_disc* d);
 /* attach the LPIPS criterion used when cfg.w_lpips != 0: feature engine, real-feature banks [C][Mf][F] (register_buffer
  * 'fea_<mode>', util_latent_aug.py:171; modality-major), crop size S (crop_size_aug), input preprocess x*scale+shift.
  * la_latent_opt_set_crop_pos: absolute (x, y) of the S x S window, drawn by the host once per forward
- * (util_dataset.py:284-296 + the centre-crop offset). */
+ * (util_dataset.py:284-296 + the centre-crop offset).  A ws_bytes below la_latent_opt_lpips_workspace_bytes is LA_ERR_WORKSPACE. */
 size_t la_latent_opt_lpips_workspace_bytes(int img_channels, int F, int S, long Mf, int max_batch);
 int la_latent_opt_set_lpips(la_latent_opt* h, la_feat* f, const float* bankF, long Mf, int S, float pre_scale,
                             float pre_shift, void* ws, size_t ws_bytes);

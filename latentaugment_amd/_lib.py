@@ -138,6 +138,16 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def workspace(nbytes, device, dtype=None):
+    """The one place where the package allocates a workspace or scratch buffer that it hands to the library: `nbytes` bytes, seen as
+    `dtype` (uint8 unless given).  Uninitialised on purpose -- the library's contract (include/latentaug_hip.h) is that a workspace may
+    hold any bytes when it is handed over and that nothing outside it is written.  Callers use the module attribute
+    (`_lib.workspace(...)`), so that a test can put a guarded, pre-filled allocator in its place."""
+    import torch
+    dtype = torch.uint8 if dtype is None else dtype
+    return torch.empty([int(nbytes) // torch.empty([], dtype=dtype).element_size()], dtype=dtype, device=device)
+
+
 def stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

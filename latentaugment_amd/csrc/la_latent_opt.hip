@@ -286,7 +286,7 @@ extern "C" int la_latent_opt_set_lpips(la_latent_opt* h, la_feat* f, const float
                                        float pre_shift, void* ws, size_t ws_bytes) {
     LA_CHECK_ARG(h && f && bankF && Mf >= 1 && S >= 1 && ws, "latent_opt_set_lpips: bad arguments");
     const int F = la_feat_num_features(f);
-    LA_CHECK_ARG(ws_bytes >= la_latent_opt_lpips_workspace_bytes(h->imgc, F, S, Mf, h->maxB), "latent_opt_set_lpips: workspace too small");
+    if (ws_bytes < la_latent_opt_lpips_workspace_bytes(h->imgc, F, S, Mf, h->maxB)) { la_set_error("latent_opt_set_lpips: workspace too small"); return LA_ERR_WORKSPACE; }
     h->lp.f = f; h->lp.bankF = bankF; h->lp.Mf = Mf; h->lp.F = F; h->lp.S = S; for (int k = 0; k < 4; ++k) { h->lp.pre_scale[k] = pre_scale; h->lp.pre_shift[k] = pre_shift; }
     carve_lpips(h, (char*)ws);
     h->lp.colsum_valid = 0;

@@ -328,7 +328,7 @@ class LatentAug:
         space = LATENT_SPACES[self.latent_space]
         nbytes = lib.la_latent_opt_workspace_bytes_ex(self.res, self.engine.img_channels, self.w_dim, C.byref(cfg), Mw, Mx,
                                                       max_local, space)
-        self._workspace = torch.empty([max(nbytes, 64)], dtype=torch.uint8, device=self.device)
+        self._workspace = _lib.workspace(max(nbytes, 64), self.device)
         h = C.c_void_p()
         _lib.check(lib.la_latent_opt_create_ex(self.engine.handle, self.res, self.engine.img_channels, self.w_dim,
                                                C.byref(cfg), _lib.ptr(self.W), Mw, _lib.ptr(self.Xc), Mx, max_local, space,
@@ -419,7 +419,7 @@ class LatentAug:
             Mf = self.Fbank.shape[1]
             scale, shift = _preproc3(getattr(opt, 'lpips_preproc', (1.0, 0.0)))
             nb = lib.la_latent_opt_lpips_workspace_bytes(imgc, self.feat.num_features, self.crop_size, Mf, max_local)
-            self._lpips_ws = torch.empty([nb], dtype=torch.uint8, device=self.device)
+            self._lpips_ws = _lib.workspace(nb, self.device)
             _lib.check(lib.la_latent_opt_set_lpips(h, self.feat.handle, _lib.ptr(self.Fbank), Mf, self.crop_size, float(scale[0]),
                                                    float(shift[0]), _lib.ptr(self._lpips_ws), nb), 'la_latent_opt_set_lpips')
             _lib.check(lib.la_latent_opt_set_lpips_preproc(h, (C.c_float * 3)(*scale), (C.c_float * 3)(*shift), 3),

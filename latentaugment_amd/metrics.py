@@ -166,7 +166,7 @@ def compute_distances(row_features, col_features, num_gpus=1, rank=0, col_batch_
     lib = _lib.load()
     r, c = _f16_padded(row_features, dev), _f16_padded(col_features, dev)
     dist = torch.empty([r.shape[0], c.shape[0]], dtype=torch.float32, device=dev)
-    ws = torch.empty([lib.la_pr_workspace_floats(r.shape[0], c.shape[0])], dtype=torch.float32, device=dev)
+    ws = _lib.workspace(4 * lib.la_pr_workspace_floats(r.shape[0], c.shape[0]), dev, torch.float32)
     with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
         _lib.check(lib.la_cdist_f16(_lib.ptr(r), r.shape[0], _lib.ptr(c), c.shape[0], r.shape[1], _lib.ptr(dist), _lib.ptr(ws),
                                     _lib.stream_ptr()), 'cdist')
@@ -184,7 +184,7 @@ def compute_pr_from_features(real_features, gen_features, nhood_size=3, row_batc
     for name, mk, pk in (('precision', 'real', 'gen'), ('recall', 'gen', 'real')):
         manifold, probes = feats[mk], feats[pk]
         nm, npb, D = manifold.shape[0], probes.shape[0], manifold.shape[1]
-        ws = torch.empty([lib.la_pr_workspace_floats(max(nm, npb), nm)], dtype=torch.float32, device=dev)
+        ws = _lib.workspace(4 * lib.la_pr_workspace_floats(max(nm, npb), nm), dev, torch.float32)
         kth = torch.empty([nm], dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(lib.la_pr_kth_f16(_lib.ptr(manifold), nm, _lib.ptr(manifold), nm, D, nhood_size, _lib.ptr(kth), _lib.ptr(ws),
@@ -263,7 +263,7 @@ def compute_kid_from_features(real_features, gen_features, num_subsets=100, max_
     ixd, iyd = torch.from_numpy(ix).to(dev), torch.from_numpy(iy).to(dev)
     out = torch.empty([S * 4 + 1], dtype=torch.float64, device=dev)          # sums [S][3], mmd2 [S], kid [1]
     ws_bytes = lib.la_kid_workspace_bytes(S, mx, my)
-    ws = torch.empty([ws_bytes // 8], dtype=torch.float64, device=dev)
+    ws = _lib.workspace(ws_bytes, dev, torch.float64)
     with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
         _lib.check(lib.la_kid_poly3_f32(_lib.ptr(gen), gen.shape[0], _lib.ptr(real), real.shape[0], gen.shape[1], _lib.ptr(ixd),
                                         _lib.ptr(iyd), S, mx, my, _lib.ptr(out), _lib.ptr(out[S * 3:]), _lib.ptr(out[S * 4:]),
@@ -312,7 +312,7 @@ def compute_fd_from_features(real_features, gen_features, device='cuda:0', retur
     real, gen = _f32_features(real_features, dev), _f32_features(gen_features, dev)
     n, m = min(ng, nr), max(ng, nr)
     ws_bytes = lib.la_fd_workspace_bytes(ng, nr, D)
-    ws = torch.empty([ws_bytes // 8], dtype=torch.float64, device=dev)          # the n' vectors of m doubles come first
+    ws = _lib.workspace(ws_bytes, dev, torch.float64)          # the n' vectors of m doubles come first
     out = torch.empty([4 + n], dtype=torch.float64, device=dev)                # terms [4], singular values [n]
     rot = torch.empty([1], dtype=torch.int32, device=dev)
     sweeps = 0
@@ -371,7 +371,7 @@ def compute_dc_from_features(real_features, gen_features, nhood_size=5, device='
     count = torch.empty([ng], dtype=torch.int32, device=dev)
     nearest = torch.empty([nr], dtype=torch.float32, device=dev)
     ws_bytes = max(lib.la_dc_workspace_bytes(ng, nr), 4 * lib.la_pr_workspace_floats(nr, nr))
-    ws = torch.empty([ws_bytes // 4], dtype=torch.float32, device=dev)
+    ws = _lib.workspace(ws_bytes, dev, torch.float32)
     with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
         _lib.check(lib.la_pr_kth_f16(_lib.ptr(real), nr, _lib.ptr(real), nr, D, k, _lib.ptr(radii), _lib.ptr(ws), _lib.stream_ptr()),
                    'pr_kth')
@@ -609,8 +609,8 @@ def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigm
                          'multiples of 2^(levels-1) and the last level at least win_size x win_size')
     chunk = max(1, min(P, _PAIR_WORKSPACE_BYTES // per_pair))
     ws_bytes = lib.la_pair_metrics_workspace_bytes(chunk, C, H, W, win, levels)
-    ws = torch.empty([ws_bytes // 8], dtype=torch.float64, device=dev)
-    err = torch.empty([P, C, 2], dtype=torch.float64, device=dev)
+    ws = _lib.workspace(ws_bytes, dev, torch.float64)
+    err =torch.empty([P, C, 2], dtype=torch.float64, device=dev)
     ssim = torch.empty([P, C, levels], dtype=torch.float32, device=dev)
     cs = torch.empty([P, C, levels], dtype=torch.float32, device=dev)
     ms = torch.empty([P, C], dtype=torch.float32, device=dev)

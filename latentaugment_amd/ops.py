@@ -321,7 +321,7 @@ class _FilteredLRelu(torch.autograd.Function):
         write = si is None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])      # (filtered_lrelu.py:206)
         if write:
             rows, row_bytes = _flr_sign_shape(h, w, fu_h, fu_w, fd_h, fd_w, up, down, px0, px1, py0, py1)
-            so = torch.empty([n * c * rows * row_bytes], device=x.device, dtype=torch.uint8)
+            so = _lib.workspace(n * c * rows * row_bytes, x.device)
         _lib.check(lib.la_filtered_lrelu_f32(_lib.ptr(x), _lib.ptr(fut), _lib.ptr(fdt), _lib.ptr(b), _lib.ptr(si), _lib.ptr(so), _lib.ptr(y),
                                              n, c, h, w, fu_h, fu_w, fd_h, fd_w, up, down, px0, px1, py0, py1, sx, sy, gain, slope, clamp,
                                              int(flip), int(write), _lib.stream_ptr()), 'filtered_lrelu')
@@ -385,7 +385,7 @@ def l2_loss_vectorized(X, Y, compute_mean=True):
     assert Yf.shape[1] == K
     D = torch.empty([m, n], device=X.device, dtype=torch.float32)
     mean = torch.empty([1], device=X.device, dtype=torch.float32)
-    ws = torch.empty([lib.la_pairwise_l2_workspace_floats(n, m)], device=X.device, dtype=torch.float32)
+    ws = _lib.workspace(4 * lib.la_pairwise_l2_workspace_floats(n, m), X.device, torch.float32)
     _lib.check(lib.la_pairwise_l2_f32(_lib.ptr(Xf), n, _lib.ptr(Yf), m, K, _lib.ptr(D), _lib.ptr(mean), _lib.ptr(ws),
                                       _lib.stream_ptr()), 'pairwise_l2')
     return mean[0] if compute_mean else D
@@ -408,7 +408,7 @@ def _conv_dims(geo):
 def _conv_scratch(op, geo, dev):
     t, s, py, px, groups = geo[:5]
     n = _lib.load().la_conv2d_workspace_bytes(op, *_conv_dims(geo), groups, int(t))
-    return torch.empty([n], device=dev, dtype=torch.uint8)
+    return _lib.workspace(n, dev)
 
 
 def _conv_launch_y(x, w, geo):
@@ -640,7 +640,7 @@ class _GridSampleBackward(torch.autograd.Function):
             lib = _lib.load()
             args = [_lib.ptr(grad_output), _lib.ptr(input), _lib.ptr(grid), _lib.ptr(dx), _lib.ptr(dgrid)]
             if input.dtype == torch.float16:
-                ws = torch.empty([lib.la_grid_sample_grad_workspace_floats(n, c, h, w)], device=input.device, dtype=torch.float32) if mask[0] else None
+                ws = _lib.workspace(4 * lib.la_grid_sample_grad_workspace_floats(n, c, h, w), input.device, torch.float32) if mask[0] else None
                 args.append(_lib.ptr(ws))
             fn = getattr(lib, 'la_grid_sample_grad_' + _DTYPES[input.dtype])
             _lib.check(fn(*args, n, c, h, w, ho, wo, _lib.stream_ptr()), 'grid_sample_grad')

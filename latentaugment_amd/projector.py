@@ -122,7 +122,7 @@ class Projector:
         self._g_small = torch.empty([self.max_batch, Cc, S, S], **f32) if self.k > 1 else None
         self._xc = torch.empty([Cc * self.max_batch, 3, S, S], **f32)
         nbytes = max(self._lib.la_row_dist_workspace_bytes(Cc * self.max_batch, F), self._lib.la_row_dist_workspace_bytes(self.max_batch, Cc * R * R))
-        self._ws = torch.empty([nbytes // 8], device=self.device, dtype=torch.float64)
+        self._ws = _lib.workspace(nbytes, self.device, torch.float64)
 
     # ---- the start
     def w_stats(self, w_avg_samples=10000, seed=123):

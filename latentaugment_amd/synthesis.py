@@ -82,7 +82,7 @@ class SynthesisEngine:
         chan = (C.c_int * len(self.channels))(*self.channels)
         nbytes = lib.la_synth_workspace_bytes(self.img_resolution, self.img_channels, self.w_dim, chan, self.max_batch)
         assert nbytes > 0
-        self._workspace = torch.empty([nbytes], dtype=torch.uint8, device=self.device)
+        self._workspace = _lib.workspace(nbytes, self.device)
         self.workspace_bytes = nbytes
         pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
         ns = (C.c_float * len(strengths))(*strengths)
@@ -289,7 +289,7 @@ class MappingEngine:
         z = z.contiguous().float()
         B = z.shape[0]
         assert z.shape[1] == self.z_dim
-        tmp = torch.empty([2 * B * max(self.z_dim, self.w_dim)], device=self.device, dtype=torch.float32)
+        tmp = _lib.workspace(4 * 2 * B * max(self.z_dim, self.w_dim), self.device, torch.float32)
         ws = torch.empty([B, num_ws, self.w_dim], device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.la_mapping_forward_f32(_lib.ptr(z), B, self.z_dim, self.w_dim, self.num_layers, self._wp,
@@ -343,7 +343,7 @@ class DiscriminatorEngine:
         self.max_batch = int(max_batch)
         nbytes = lib.la_disc_workspace_bytes(R, self.img_channels, chan, self.max_batch)
         assert nbytes > 0
-        self._workspace = torch.empty([nbytes], dtype=torch.uint8, device=self.device)
+        self._workspace = _lib.workspace(nbytes, self.device)
         pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
         h = C.c_void_p()
         clamp = float(-1.0 if conv_clamp is None else conv_clamp)
@@ -442,7 +442,7 @@ class FeatureEngine:
         arr = (_lib.FeatOp * len(desc))(*desc)
         nbytes = lib.la_feat_workspace_bytes(len(desc), arr, in_ch, in_res, self.max_batch)
         assert nbytes > 0, 'invalid feature-net description: ' + (lib.la_last_error() or b'?').decode()
-        self._workspace = torch.empty([nbytes], dtype=torch.uint8, device=self.device)
+        self._workspace = _lib.workspace(nbytes, self.device)
         pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
         h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -543,7 +543,7 @@ class FeatureEngine:
             raise _lib.LatentAugHipError(f'pair_distance: {P} pairs refused (detector list, or 2 * pairs > max_batch = {self.max_batch})')
         ws = getattr(self, '_pair_ws', None)
         if ws is None or ws.numel() * 8 < nbytes:
-            ws = self._pair_ws = torch.empty([nbytes // 8], dtype=torch.float64, device=self.device)
+            ws = self._pair_ws = _lib.workspace(nbytes, self.device, torch.float64)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.la_feat_pair_distance(self._h, _lib.ptr(xy), P, _lib.ptr(dist), _lib.ptr(ws), ws.numel() * 8,
                                                        _lib.stream_ptr()), 'la_feat_pair_distance')
@@ -754,7 +754,7 @@ def fc_bias_act(x, weight, bias, relu=False):
     nbytes = lib.la_fc_workspace_bytes(N, K, O)
     if nbytes == 0:
         raise _lib.LatentAugHipError('la_fc_workspace_bytes refused the shape: ' + (lib.la_last_error() or b'?').decode())
-    ws = torch.empty([nbytes], dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace(nbytes, x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.la_fc_bias_act_f32(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), N, K, O, 2 if relu else 1, _lib.ptr(ws),
                                           nbytes, _lib.stream_ptr()), 'la_fc_bias_act_f32')

@@ -188,6 +188,110 @@ def test_product_never_imports_oracle():
     assert not bad, bad
 
 
+_SIZE_ENTRY = re.compile(r'la_\w*workspace_(?:bytes|floats)\w*$')
+_TORCH_ALLOCATORS = {'empty', 'zeros', 'ones', 'full', 'empty_like', 'zeros_like', 'ones_like', 'full_like', 'empty_strided', 'rand', 'randn',
+                     'tensor', 'arange'}
+
+
+def workspace_allocation_faults(src, name='<src>'):
+    """Where a piece of package source sizes a buffer by a la_*_workspace_bytes / la_*_workspace_floats entry and allocates it with anything
+    but `_lib.workspace`: per function, the names that carry such a size (the call's result, and what is computed from them) may reach
+    `_lib.workspace(...)` and ordinary arithmetic, never a torch allocator.  Also: `workspace` taken out of `_lib` by an import, which a
+    test's monkeypatch of the module attribute would no longer reach."""
+    import ast
+    tree = ast.parse(src)
+    faults = []
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ImportFrom) and (node.module or '').split('.')[-1] == '_lib' and any(a.name in ('workspace', '*') for a in node.names):
+            faults.append(f'{name}:{node.lineno}: workspace imported out of _lib')
+        if isinstance(node, ast.Assign) and isinstance(node.value, ast.Attribute) and node.value.attr == 'workspace' and \
+                isinstance(node.value.value, ast.Name) and node.value.value.id == '_lib':
+            faults.append(f'{name}:{node.lineno}: _lib.workspace bound to another name')
+
+    def is_size_call(n):
+        return isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and _SIZE_ENTRY.match(n.func.attr)
+
+    def is_lib_workspace(n):
+        return isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr == 'workspace' and \
+            isinstance(n.func.value, ast.Name) and n.func.value.id == '_lib'
+
+    def carries(expr, tainted):
+        """A size reaches `expr` other than through a _lib.workspace(...) call inside it."""
+        stack = [expr]
+        while stack:
+            n = stack.pop()
+            if is_lib_workspace(n):
+                continue
+            if is_size_call(n) or (isinstance(n, ast.Name) and n.id in tainted):
+                return True
+            stack.extend(ast.iter_child_nodes(n))
+        return False
+
+    funcs = [n for n in ast.walk(tree) if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef))]
+    for fn in funcs:
+        body = [n for n in ast.walk(fn)]
+        if not any(is_size_call(n) for n in body):
+            continue
+        tainted, grew = set(), True
+        while grew:
+            grew = False
+            for n in body:
+                if isinstance(n, (ast.Assign, ast.AugAssign, ast.AnnAssign)) and n.value is not None and carries(n.value, tainted):
+                    targets = n.targets if isinstance(n, ast.Assign) else [n.target]
+                    for t in targets:
+                        for leaf in ast.walk(t):
+                            if isinstance(leaf, ast.Name) and leaf.id not in tainted:
+                                tainted.add(leaf.id)
+                                grew = True
+        for n in body:
+            if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in _TORCH_ALLOCATORS and \
+                    isinstance(n.func.value, ast.Name) and n.func.value.id in ('torch', 'np', 'numpy') and \
+                    any(carries(a, tainted) for a in list(n.args) + [k.value for k in n.keywords]):
+                faults.append(f'{name}:{n.lineno}: {fn.name} sizes a buffer by a workspace entry and allocates it with {n.func.value.id}.{n.func.attr}')
+            if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in ('new_empty', 'new_zeros', 'new_full', 'new_ones') and \
+                    any(carries(a, tainted) for a in n.args):
+                faults.append(f'{name}:{n.lineno}: {fn.name} sizes a buffer by a workspace entry and allocates it with .{n.func.attr}')
+    return faults
+
+
+def test_every_workspace_is_allocated_by_lib_workspace():
+    """One allocation point (latentaugment_amd/_lib.workspace) for every workspace and scratch buffer the package hands to the library, so
+    that tests/guarded_alloc.py can stand in for it: no package file sizes a buffer by a la_*_workspace_* entry and allocates it otherwise,
+    none takes `workspace` out of the module, and the call sites are these -- a new one is added here, a vanished one fails."""
+    pkg = os.path.join(ROOT, 'latentaugment_amd')
+    sites, faults, entries = {}, [], set()
+    for d, _, files in os.walk(pkg):
+        for f in sorted(files):
+            if f.endswith('.py'):
+                rel = os.path.relpath(os.path.join(d, f), pkg)
+                src = open(os.path.join(d, f)).read()
+                faults += workspace_allocation_faults(src, rel)
+                n = len(re.findall(r'\b_lib\.workspace\(', src))
+                if n and rel != '_lib.py':          # (its own docstring says how it is called)
+                    sites[rel] = n
+                entries |= set(re.findall(r'\b(la_\w*workspace_(?:bytes|floats)\w*)\(', src))
+    assert not faults, faults
+    # synthesis: synth, mapping tmp, disc, feat, LPIPS pair, fc | latent_aug: loop, loop LPIPS | metrics: cdist, PR, KID, FD, DC (+ its PR
+    # part), pair metrics | projector: row distance | ops: filtered_lrelu signs, pairwise L2, conv2d scratch, grid-sample gradient
+    assert sites == {'synthesis.py': 6, 'latent_aug.py': 2, 'metrics.py': 6, 'projector.py': 1, 'ops.py': 4}
+    from latentaugment_amd import _lib
+    declared = {n for n in _lib.SIGNATURES if _SIZE_ENTRY.match(n)}
+    assert len(declared) == 18 and entries <= declared
+    # the entries of the header that the package does not call are those of the layer-level C entries, which only tests and scripts drive
+    assert declared - entries == {'la_latent_opt_workspace_bytes', 'la_modconv_workspace_bytes'}, declared - entries
+    # the scan itself: what it must find, and what it must leave alone
+    bad = ('def f(lib, dev):\n    n = lib.la_kid_workspace_bytes(1, 2, 3)\n    m = max(n, 64) // 8\n'
+           '    return torch.empty([m], dtype=torch.float64, device=dev)\n')
+    assert len(workspace_allocation_faults(bad)) == 1
+    assert len(workspace_allocation_faults('def f(lib):\n    return torch.zeros([lib.la_pr_workspace_floats(3, 4)])\n')) == 1
+    assert len(workspace_allocation_faults('def f(x, lib):\n    n = lib.la_fc_workspace_bytes(1, 2, 3)\n    return x.new_empty([n])\n')) == 1
+    assert len(workspace_allocation_faults('from ._lib import workspace\n')) == 1
+    assert len(workspace_allocation_faults('from . import _lib\nalloc = _lib.workspace\n')) == 1
+    good = ('def f(lib, dev):\n    n = lib.la_kid_workspace_bytes(1, 2, 3)\n    ws = _lib.workspace(max(n, 64), dev, torch.float64)\n'
+            '    out = torch.empty([4], device=dev)\n    return ws, out, ws.numel() * 8\n')
+    assert workspace_allocation_faults(good) == []
+
+
 def test_registry_and_options_match_reference_surface():
     from latentaugment_amd.augments import find_augment_using_name, get_option_setter
     from latentaugment_amd.augments.base_aug import BaseAugment

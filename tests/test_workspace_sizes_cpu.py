@@ -70,7 +70,7 @@ def test_set_lpips_accepts_exactly_the_recorded_size(lib, golden, S, imgc, mb):
         assert F == wc.tap_features(S)
         need = lib.la_latent_opt_lpips_workspace_bytes(imgc, F, S, wc.MF, mb)
         assert need == golden[f'lpips-tap-S{S}-c{imgc}-b{mb}']
-        assert lib.la_latent_opt_set_lpips(h, f, p, wc.MF, S, 1.0, 0.0, p, need - 64) == -1
+        assert lib.la_latent_opt_set_lpips(h, f, p, wc.MF, S, 1.0, 0.0, p, need - 64) == -3          # LA_ERR_WORKSPACE, as every entry that takes one
         assert b'workspace too small' in lib.la_last_error()
         assert lib.la_latent_opt_set_lpips(h, f, p, wc.MF, S, 1.0, 0.0, p, need) == 0
     finally:
