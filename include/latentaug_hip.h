@@ -407,6 +407,9 @@ int la_synth_set_row_window(la_synth* h, int row_lo, int row_hi);
  * whole 32-column tiles; every other kernel computes whole rows. */
 int la_synth_set_col_window(la_synth* h, int col_lo, int col_hi);
 int la_synth_get_precision(const la_synth* h);
+/* per_block 0 (default): the ToRGB layers that are kernels of their own run deferred, two launches for all of them (la_synth_plan_query:
+ * LA_SYNTH_SKIP_CHAIN); 1: one launch behind every block's conv1 and an up-FIR launch per skip image.  Every buffer holds the same bits. */
+int la_synth_set_torgb_schedule(la_synth* h, int per_block);
 /* Host only, no launch.  The backward pass of a windowed forward pass follows the CONE of the image window: window[0..1] = the rows of
  * the gradient of conv output conv_index (engine layer order) that can be non-zero for image rows [row_lo, row_hi) -- the forward windows
  * without their tile rounding; the launch that writes them rounds them outward to its own 4-row tiles -- and window[2..3] = the tile
@@ -429,8 +432,11 @@ int la_synth_bwd_rows(const la_synth* h, int conv_index, int* row_lo, int* row_h
  *     shared one, the up-sampling layers' fused seams', the conv1 layers' fused seams'); NSEG = segments of its demod-gradient, plane-maxima and
  *     (conv1) ToRGB weight-gradient partials: seam slabs or contraction tiles; NTILES = tiles of its style-gradient partials.
  *   block k, info[LA_SYNTH_PLAN_BLOCK(k) + LA_SYNTH_PLAN_B_*]: FUSE_RGB = ToRGB runs in the epilogue of conv1's launch (else the ToRGB kernel,
- *     which up-samples the skip image itself and is handed the image rows IMG_ROWS lo, hi); SKIP_UP = the skip image is up-sampled by a launch of
- *     its own before conv1; DOWN_FIR = the backward pass launches the down-FIR of the image gradient at this block; PYRAMID = and one more launch
+ *     which up-samples the skip image itself and is handed the image rows IMG_ROWS lo, hi); SKIP_UP = where the skip image of a fused ToRGB
+ *     comes from, before conv1: LA_SYNTH_SKIP_LAUNCH, an up-FIR launch of its own, or LA_SYNTH_SKIP_CHAIN, the image-chain launch -- the
+ *     block is then the DEFERRAL POINT of the ToRGB kernels of the blocks below it: none of them launches behind its conv1, one launch in
+ *     front of this block makes rgb_pre of all of them and one their images and this skip image (skip images up to 256^2; a larger one keeps
+ *     its launch behind those two.  No fused block above a ToRGB kernel: its run ends the pass); DOWN_FIR = the backward pass launches the down-FIR of the image gradient at this block; PYRAMID = and one more launch
  *     for every level below.
  * Bad arguments are refused with a message. */
 #define LA_SYNTH_PLAN_NBLOCKS 0
@@ -465,6 +471,8 @@ int la_synth_bwd_rows(const la_synth* h, int conv_index, int* row_lo, int* row_h
 #define LA_SYNTH_SEAM_KERNEL 0
 #define LA_SYNTH_SEAM_FUSED 1
 #define LA_SYNTH_PMAX_NONE 0         /* 1, 2, 3: the three buffers in the order above */
+#define LA_SYNTH_SKIP_LAUNCH 1       /* (0: the block has no skip image of its own) */
+#define LA_SYNTH_SKIP_CHAIN 2
 int la_synth_plan_query(int img_resolution, int img_channels, const int* channels, int B, int precision, int row_lo, int row_hi, int col_lo,
                         int col_hi, long* info);
 /* ws element (b,l,j) = ws[b*ws_bstride + l*ws_lstride + j] (ws_lstride = 0: W space, one w per sample).

@@ -51,12 +51,11 @@ struct LaSeamArgs {
 
 int la_affine_forward(const LaStyleTable& t, const float* ws, long ws_bstride, long ws_lstride, int B, int wdim,
                       float* s_all, hipStream_t);
-// xs[l][b] = power-of-two fp16 operand scale of conv layer l's forward contraction from the bound  bound[l] * max_i |s[b][i]|
-// start of a pass: resets the slot rows xs [nlayers][B][LA_XS_FAN] (layer 0: the scale of the constant input `cst`, cst_n floats) and
-// xs_bwd (optional) and writes xs_mult [nlayers][B] = max_i |style| of every layer (la_style.hip)
-int la_xscale_from_bounds(const LaDemodTable& t, const float* s_all, int s_stride, const float* cst, int cst_n, float* xs, float* xs_mult, int B,
-                          hipStream_t, float* xs_bwd = nullptr);
-int la_demod_forward(const LaDemodTable& t, const float* s_all, int s_stride, int B, float* d_all, hipStream_t);
+// xscale (optional, fp16 x2 mode), in the same launch, the start of a pass for the fp16 operand scales: resets the slot rows xs
+// [nlayers][B][LA_XS_FAN] (layer 0: the scale of the constant input `cst`, cst_n floats) and xs_bwd (optional) and writes xs_mult
+// [nlayers][B] = max_i |style| of every layer (la_style.hip)
+struct LaXscaleBounds { const float* cst; int cst_n; float* xs; float* xs_mult; float* xs_bwd; };
+int la_demod_forward(const LaDemodTable& t, const float* s_all, int s_stride, int B, float* d_all, hipStream_t, const LaXscaleBounds* xscale = nullptr);
 // mask (optional, planes above 64x64): x is a gradient still to be taken through an activation -- x[b][i][p] * act'(mask.y[b][i][p]) is what
 // the 1x1 reads (the discriminator's FromRGB backward: one stream of the gradient and the saved output instead of a sweep + a stream)
 struct LaTorgbMask { const float* y; int act; float alpha, gain, clamp; };
@@ -66,6 +65,28 @@ int la_torgb_forward(const float* x, const LaRgbFuse& r, int B, int C, int H, in
 // row_lo / row_hi (planes above 64x64; 0 / 0 = all): only these rows of rgb_pre / img are computed and written
 // la_torgb_forward's kernel choice: planes up to 64x64 take the small kernel (whole planes: no row window, no mask), larger ones the large
 static inline bool la_torgb_small(long HW) { return HW <= 4096; }
+// The ToRGB layers of several blocks whose images nobody reads before the last of them has run, in two launches instead of one per block
+// (la_synth.hip: the blocks below the first fused ToRGB).  Tables by value, lowest level first.
+//   la_torgb_forward_levels  rgb_pre of every level: per level la_torgb_forward's channel sum (same kernel form per plane size, same order:
+//                            the same bits), rows [row_lo, row_hi) of a plane above 64x64 (0 / 0 = all)
+//   la_image_chain_forward   img_k = clamp(rgb_pre_k) + upsample2d(img_{k-1}) level by level (base: the image below the first level, or null),
+//                            each level's rows [row_lo, row_hi) (they must lie inside what the level below delivers); skip (optional): the
+//                            up-sampled image of the LAST level [B][imgc][2H][2W], whole planes -- what a fused
+//                            ToRGB one block up reads (LaRgbFuse::skip), equal to la_upfirdn2d_ex(.., la_fir_up2()) of that image; it needs
+//                            the levels below the last within 64x64 and the last within 128x128 (the kernel's LDS strips), else refused
+#define LA_TORGB_MAX_LEVELS 12
+struct LaTorgbLevels {
+    int n, imgc, s_stride;
+    struct Level { const float* x; int C, H, W; const float* wrgb; const float* s; const float* bias; float* rgb_pre; int row_lo, row_hi; } lv[LA_TORGB_MAX_LEVELS];
+};
+struct LaImageChain {
+    int n, imgc; float clamp;
+    const float* base;
+    struct Level { const float* rgb_pre; float* img; int H, W, row_lo, row_hi; } lv[LA_TORGB_MAX_LEVELS];
+    float* skip;
+};
+int la_torgb_forward_levels(const LaTorgbLevels& t, int B, hipStream_t);
+int la_image_chain_forward(const LaImageChain& t, int B, const float* fir_host, hipStream_t);
 int la_seam_slabs(long HW);
 int la_seam_backward(const LaSeamArgs& a, int B, int imgc, hipStream_t);
 // Style-gradient finish of ALL layers of one backward pass in three launches (row sums of every partial buffer, conv layers,

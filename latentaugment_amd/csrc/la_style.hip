@@ -96,8 +96,16 @@ int la_affine_forward(const LaStyleTable& t, const float* ws, long ws_bstride, l
 
 // ------------------------------------------------------------------------------------------------------------
 // demod: d[b][doff_l + o] = rsqrt(sum_i s[b][soff_l+i]^2 * wsq_l[o][i] + 1e-8)     one wave per 4 rows (l, o .. o+3), 16-byte loads
+// The workgroups behind the first demod_blocks do the start-of-pass work of the fp16 operand scales (la_xscale_bound_block below: same
+// styles, nothing else in common -- one launch of a pass's chain instead of two).
+__device__ void la_xscale_bound_block(const LaDemodTable& t, const float* __restrict__ s_all, int s_stride, const LaXscaleBounds& x, int B, int l, int b);
 __global__ __launch_bounds__(256) void la_demod_kernel(LaDemodTable t, const float* __restrict__ s_all, int s_stride,
-                                                      int B, float* __restrict__ d_all) {
+                                                      int B, float* __restrict__ d_all, int demod_blocks, LaXscaleBounds xb) {
+    if ((int)blockIdx.x >= demod_blocks) {      // (block-uniform)
+        const int k = blockIdx.x - demod_blocks;
+        la_xscale_bound_block(t, s_all, s_stride, xb, B, k % t.nlayers, k / t.nlayers);
+        return;
+    }
     const int row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
     const int lane = threadIdx.x & 63;
     if (row >= t.total_rows) return;
@@ -138,27 +146,30 @@ __global__ __launch_bounds__(256) void la_demod_kernel(LaDemodTable t, const flo
 }
 
 int la_demod_forward(const LaDemodTable& t, const float* s_all, int s_stride, int B, float* d_all,
-                     hipStream_t stream) {
+                     hipStream_t stream, const LaXscaleBounds* xscale) {
     LA_CHECK_ARG(t.total_rows % 4 == 0 && s_stride % 4 == 0, "demod_forward: channel counts must be multiples of 4");
-    hipLaunchKernelGGL(la_demod_kernel, dim3(la_cdiv(t.total_rows, 16)), dim3(256), 0, stream, t, s_all, s_stride, B,
-                       d_all);
+    LA_CHECK_ARG(!xscale || (xscale->cst && xscale->xs && xscale->xs_mult), "demod_forward: operand scales without their rows");
+    const int demod_blocks = la_cdiv(t.total_rows, 16);
+    hipLaunchKernelGGL(la_demod_kernel, dim3(demod_blocks + (xscale ? t.nlayers * B : 0)), dim3(256), 0, stream, t, s_all, s_stride, B,
+                       d_all, demod_blocks, xscale ? *xscale : LaXscaleBounds{nullptr, 0, nullptr, nullptr, nullptr});
     LA_CHECK_LAUNCH();
     return LA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Start of a pass (fp16 x2 mode), one launch: the slot rows of every conv layer's fp16 operand scales are reset -- forward rows
+// Start of a pass (fp16 x2 mode), in la_demod_kernel's launch: the slot rows of every conv layer's fp16 operand scales are reset -- forward rows
 // xs_fwd [l][b][LA_XS_FAN] and backward rows xs_bwd to LA_XS_INIT -- and what the producers need to lower the forward rows is laid out:
 // xs_mult [l][b] = max_i |s[b][i]| of layer l (the input of layer l is x * s, so |x * s| <= max|x| * max|s|: the producer of x lowers
 // row l to pow2(xs_mult * its max |x|), la_xs_lower).  Layer 0 reads the constant input, which no kernel of the pass produces: its
 // row gets pow2(max|const| * max|s|) here (max|const| reduced from the tensor itself every pass: no stale bound if a caller
 // rewrites the parameter in place).  Every scale is therefore derived from the DATA of this pass -- there is no a-priori bound and
 // no calibration (round 3 kept conv_clamp * max|s| for the forward rows and checked once, on the first batch, that it was tight enough).
-__global__ __launch_bounds__(256) void la_xscale_bound_kernel(LaDemodTable t, const float* __restrict__ s_all, int s_stride,
-                                                             const float* __restrict__ cst, int cst_n, float* __restrict__ xs,
-                                                             float* __restrict__ xs_mult, int B, unsigned* __restrict__ xs_bwd) {
+__device__ void la_xscale_bound_block(const LaDemodTable& t, const float* __restrict__ s_all, int s_stride, const LaXscaleBounds& x, int B, int l, int b) {
     __shared__ float red[4], red2[4];
-    const int l = blockIdx.x, b = blockIdx.y;
+    const float* __restrict__ cst = x.cst;
+    const int cst_n = x.cst_n;
+    float *__restrict__ xs = x.xs, *__restrict__ xs_mult = x.xs_mult;
+    unsigned* __restrict__ xs_bwd = reinterpret_cast<unsigned*>(x.xs_bwd);
     const float* sp = s_all + (long)b * s_stride + t.s_off[l];
     float m = 0.f, mc = 0.f;
     for (int i = threadIdx.x; i < t.cin[l]; i += 256) m = fmaxf(m, fabsf(sp[i]));
@@ -177,14 +188,6 @@ __global__ __launch_bounds__(256) void la_xscale_bound_kernel(LaDemodTable t, co
     }
 }
 
-int la_xscale_from_bounds(const LaDemodTable& t, const float* s_all, int s_stride, const float* cst, int cst_n, float* xs, float* xs_mult, int B,
-                          hipStream_t stream, float* xs_bwd) {
-    hipLaunchKernelGGL(la_xscale_bound_kernel, dim3(t.nlayers, B), dim3(256), 0, stream, t, s_all, s_stride, cst, cst_n, xs, xs_mult, B,
-                       reinterpret_cast<unsigned*>(xs_bwd));
-    LA_CHECK_LAUNCH();
-    return LA_OK;
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // ToRGB forward (+ skip add):  rgb_pre[b][c][p] = sum_i wrgb[c][i] * s[b][i] * x[b][i][p] + bias[c]
 //                              img[b][c][p]     = clamp(rgb_pre) + (skip ? skip[b][c][p] : 0)
@@ -195,7 +198,8 @@ int la_xscale_from_bounds(const LaDemodTable& t, const float* s_all, int s_strid
 // separate up-2 launch + skip read produced; that launch (one 5 us link of a step's serial chain per block) is gone for every block
 // whose ToRGB is its own kernel.
 struct LaSkipUp { const float* lo; int Hl, Wl; float f[16]; };      // lo: [B][imgc][Hl][Wl] (null: none); f: the up-2 taps (gain included)
-__device__ __forceinline__ float4 la_up2_quad(const float* __restrict__ ip, int Hl, int Wl, const float* f, int Y, int x0) {
+// (row0: ip holds the rows of the image from row0 on only -- the caller reads none below it)
+__device__ __forceinline__ float4 la_up2_quad(const float* __restrict__ ip, int Hl, int Wl, const float* f, int Y, int x0, int row0 = 0) {
     const int i = Y >> 1, py = Y & 1, j0 = x0 >> 1;
     float v[2][4];                                               // in[i + py - 1 + ua][j0 - 1 .. j0 + 2], zero outside
 #pragma unroll
@@ -204,7 +208,7 @@ __device__ __forceinline__ float4 la_up2_quad(const float* __restrict__ ip, int 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int ix = j0 - 1 + c;
-            v[ua][c] = (iy >= 0 && iy < Hl && ix >= 0 && ix < Wl) ? ip[(long)iy * Wl + ix] : 0.f;
+            v[ua][c] = (iy >= 0 && iy < Hl && ix >= 0 && ix < Wl) ? ip[(long)(iy - row0) * Wl + ix] : 0.f;
         }
     }
     float o[4];
@@ -221,35 +225,19 @@ __device__ __forceinline__ float4 la_up2_quad(const float* __restrict__ ip, int 
     return make_float4(o[0], o[1], o[2], o[3]);
 }
 
+// The channel sum of the ToRGB kernels: channels [i0, i1) of four consecutive pixels (xb: the pixels in the first channel plane, planes HW
+// apart) onto acc.  Eight channels' 16-byte loads in flight per thread, accumulated in channel order: the kernels are a plain stream of x --
+// with one load per trip of a short unrolled loop the scheduler left most of the latency exposed once the packed-FP32 forms were gone.
+// mb (optional, same layout as xb): x is a gradient still to be taken through the activation whose saved output is there (LaTorgbMask).
 template <int IMGC>
-__global__ __launch_bounds__(256) void la_torgb_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wrgb,
-                                                          const float* __restrict__ s, int s_stride,
-                                                          const float* __restrict__ bias, const float* __restrict__ skip,
-                                                          float* __restrict__ rgb_pre, float* __restrict__ img, int C,
-                                                          long HW, float clamp, LaTorgbMask mk, long p_lo, long p_hi, LaSkipUp su) {
-    extern __shared__ float weff[];   // [IMGC][C]
-    const int b = blockIdx.y;
-    for (int k = threadIdx.x; k < IMGC * C; k += blockDim.x) {
-        const int i = k % C;
-        weff[k] = wrgb[k] * (s ? s[(long)b * s_stride + i] : 1.f);
-    }
-    __syncthreads();
-    const long p4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (p4 >= HW) return;
-    if (p_hi > 0 && (p4 < p_lo || p4 >= p_hi)) return;      // pixel window (rows nobody reads: la_synth.hip)
-    const float* xb = x + (long)b * C * HW + p4;
-    float4 acc[IMGC];
-#pragma unroll
-    for (int c = 0; c < IMGC; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    // (eight channels' 16-byte loads in flight per thread, accumulated in channel order: the kernel is a plain stream of x -- with one
-    //  load per trip of a short unrolled loop the scheduler left most of the latency exposed once the packed-FP32 forms were gone)
-    int i = 0;
-    for (; i + 7 < C; i += 8) {
+__device__ __forceinline__ void la_torgb_channel_sum(const float* __restrict__ xb, const float* __restrict__ mb, const LaTorgbMask& mk,
+                                                     const float* weff, int C, long HW, int i0, int i1, float4 (&acc)[IMGC]) {
+    int i = i0;
+    for (; i + 7 < i1; i += 8) {
         float4 xv[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) xv[u] = *reinterpret_cast<const float4*>(xb + (long)(i + u) * HW);
-        if (mk.y) {      // x is a gradient still to be taken through the activation whose saved output is mk.y (same layout as x)
-            const float* mb = mk.y + (long)b * C * HW + p4;
+        if (mb) {
             float4 mv[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) mv[u] = *reinterpret_cast<const float4*>(mb + (long)(i + u) * HW);
@@ -269,10 +257,10 @@ __global__ __launch_bounds__(256) void la_torgb_fwd_kernel(const float* __restri
                 acc[c].x += wv * xv[u].x; acc[c].y += wv * xv[u].y; acc[c].z += wv * xv[u].z; acc[c].w += wv * xv[u].w;
             }
     }
-    for (; i < C; ++i) {
+    for (; i < i1; ++i) {
         float4 xv = *reinterpret_cast<const float4*>(xb + (long)i * HW);
-        if (mk.y) {
-            const float4 mv = *reinterpret_cast<const float4*>(mk.y + (long)b * C * HW + p4 + (long)i * HW);
+        if (mb) {
+            const float4 mv = *reinterpret_cast<const float4*>(mb + (long)i * HW);
             xv.x *= la_act_bwd_from_y(mv.x, mk.act, mk.alpha, mk.gain, mk.clamp); xv.y *= la_act_bwd_from_y(mv.y, mk.act, mk.alpha, mk.gain, mk.clamp);
             xv.z *= la_act_bwd_from_y(mv.z, mk.act, mk.alpha, mk.gain, mk.clamp); xv.w *= la_act_bwd_from_y(mv.w, mk.act, mk.alpha, mk.gain, mk.clamp);
         }
@@ -282,6 +270,33 @@ __global__ __launch_bounds__(256) void la_torgb_fwd_kernel(const float* __restri
             acc[c].x += wv * xv.x; acc[c].y += wv * xv.y; acc[c].z += wv * xv.z; acc[c].w += wv * xv.w;
         }
     }
+}
+// the effective weights of sample b in LDS: weff[c][i] = wrgb[c][i] * s[b][i]
+__device__ __forceinline__ void la_torgb_fill_weff(float* weff, const float* __restrict__ wrgb, const float* __restrict__ s, int s_stride, int b, int n, int C) {
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {
+        const int i = k % C;
+        weff[k] = wrgb[k] * (s ? s[(long)b * s_stride + i] : 1.f);
+    }
+}
+
+template <int IMGC>
+__global__ __launch_bounds__(256) void la_torgb_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wrgb,
+                                                          const float* __restrict__ s, int s_stride,
+                                                          const float* __restrict__ bias, const float* __restrict__ skip,
+                                                          float* __restrict__ rgb_pre, float* __restrict__ img, int C,
+                                                          long HW, float clamp, LaTorgbMask mk, long p_lo, long p_hi, LaSkipUp su) {
+    extern __shared__ float weff[];   // [IMGC][C]
+    const int b = blockIdx.y;
+    la_torgb_fill_weff(weff, wrgb, s, s_stride, b, IMGC * C, C);
+    __syncthreads();
+    const long p4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (p4 >= HW) return;
+    if (p_hi > 0 && (p4 < p_lo || p4 >= p_hi)) return;      // pixel window (rows nobody reads: la_synth.hip)
+    const float* xb = x + (long)b * C * HW + p4;
+    float4 acc[IMGC];
+#pragma unroll
+    for (int c = 0; c < IMGC; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    la_torgb_channel_sum<IMGC>(xb, mk.y ? mk.y + (long)b * C * HW + p4 : nullptr, mk, weff, C, HW, 0, C, acc);
 #pragma unroll
     for (int c = 0; c < IMGC; ++c) {
         const float bv = bias ? bias[c] : 0.f;
@@ -316,10 +331,7 @@ __global__ __launch_bounds__(256) void la_torgb_fwd_small_kernel(const float* __
     float* weff = sm;
     float4* comb = reinterpret_cast<float4*>(sm + ((IMGC * C + 3) & ~3));
     const int b = blockIdx.y;
-    for (int k = threadIdx.x; k < IMGC * C; k += blockDim.x) {
-        const int i = k % C;
-        weff[k] = wrgb[k] * (s ? s[(long)b * s_stride + i] : 1.f);
-    }
+    la_torgb_fill_weff(weff, wrgb, s, s_stride, b, IMGC * C, C);
     __syncthreads();
     const int parts = 256 / px_lanes;
     const int pl = threadIdx.x % px_lanes, part = threadIdx.x / px_lanes;
@@ -330,29 +342,7 @@ __global__ __launch_bounds__(256) void la_torgb_fwd_small_kernel(const float* __
     float4 acc[IMGC];
 #pragma unroll
     for (int c = 0; c < IMGC; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p4 < HW) {
-        int i = i0;
-        for (; i + 7 < i1; i += 8) {      // (eight loads in flight, summed in channel order)
-            float4 xv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) xv[u] = *reinterpret_cast<const float4*>(xb + (long)(i + u) * HW);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int c = 0; c < IMGC; ++c) {
-                    const float wv = weff[c * C + i + u];
-                    acc[c].x += wv * xv[u].x; acc[c].y += wv * xv[u].y; acc[c].z += wv * xv[u].z; acc[c].w += wv * xv[u].w;
-                }
-        }
-        for (; i < i1; ++i) {
-            const float4 xv = *reinterpret_cast<const float4*>(xb + (long)i * HW);
-#pragma unroll
-            for (int c = 0; c < IMGC; ++c) {
-                const float wv = weff[c * C + i];
-                acc[c].x += wv * xv.x; acc[c].y += wv * xv.y; acc[c].z += wv * xv.z; acc[c].w += wv * xv.w;
-            }
-        }
-    }
+    if (p4 < HW) la_torgb_channel_sum<IMGC>(xb, nullptr, LaTorgbMask{nullptr, 0, 0.f, 0.f, 0.f}, weff, C, HW, i0, i1, acc);
 #pragma unroll
     for (int c = 0; c < IMGC; ++c) comb[(part * px_lanes + pl) * IMGC + c] = acc[c];
     __syncthreads();
@@ -428,6 +418,270 @@ int la_torgb_forward(const float* x, const LaRgbFuse& r, int B, int C, int H, in
 #define LAUNCH(N) hipLaunchKernelGGL(la_torgb_fwd_kernel<N>, grid, dim3(256), lds, stream, x, wrgb, s, s_stride, bias, skip, rgb_pre, img, C, HW, clamp, mk, p_lo, p_hi, su)
     switch (imgc) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
 #undef LAUNCH
+    LA_CHECK_LAUNCH();
+    return LA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The ToRGB layers of several blocks in ONE launch (la_torgb_forward_levels): in the skip architecture nothing between a block's conv1 and
+// the first fused block above reads the block's image, so the per-block launches (each near its latency floor at <= 128^2) need not sit
+// in the chain of a pass.  The grid is the concatenation of the levels' workgroups (blk0: prefix table); a workgroup runs the channel sum
+// of the kernel la_torgb_forward would have chosen for its level -- la_torgb_fwd_small_kernel's parts and their fixed combination order up
+// to 64x64, la_torgb_fwd_kernel's single walk above -- and writes rgb_pre only: clamp, skip image and img are the chain kernel's below.
+struct TorgbLevelDev { const float *x, *wrgb, *s, *bias; float* rgb_pre; long HW, p_lo, p_hi; int C, px_lanes, blk0; };      // px_lanes 0: the large form
+struct TorgbLevelsDev { int n, s_stride; TorgbLevelDev lv[LA_TORGB_MAX_LEVELS]; };
+
+template <int IMGC>
+__global__ __launch_bounds__(256) void la_torgb_fwd_levels_kernel(TorgbLevelsDev t) {
+    extern __shared__ float sm[];     // weff [IMGC][C]  then (small form)  comb [parts][px_lanes][IMGC] float4
+    int l = 0;
+    while (l + 1 < t.n && (int)blockIdx.x >= t.lv[l + 1].blk0) ++l;
+    const TorgbLevelDev& L = t.lv[l];
+    const int b = blockIdx.y, C = L.C, blk = blockIdx.x - L.blk0, px_lanes = L.px_lanes;
+    const long HW = L.HW;
+    float* weff = sm;
+    la_torgb_fill_weff(weff, L.wrgb, L.s, t.s_stride, b, IMGC * C, C);
+    __syncthreads();
+    float4 acc[IMGC];
+#pragma unroll
+    for (int c = 0; c < IMGC; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const LaTorgbMask none{nullptr, 0, 0.f, 0.f, 0.f};
+    if (px_lanes == 0) {      // (block-uniform)
+        const long p4 = ((long)blk * 256 + threadIdx.x) * 4;
+        if (p4 >= HW) return;
+        if (L.p_hi > 0 && (p4 < L.p_lo || p4 >= L.p_hi)) return;
+        la_torgb_channel_sum<IMGC>(L.x + (long)b * C * HW + p4, nullptr, none, weff, C, HW, 0, C, acc);
+#pragma unroll
+        for (int c = 0; c < IMGC; ++c) {
+            const float bv = L.bias ? L.bias[c] : 0.f;
+            *reinterpret_cast<float4*>(L.rgb_pre + ((long)b * IMGC + c) * HW + p4) = make_float4(acc[c].x + bv, acc[c].y + bv, acc[c].z + bv, acc[c].w + bv);
+        }
+        return;
+    }
+    float4* comb = reinterpret_cast<float4*>(sm + ((IMGC * C + 3) & ~3));
+    const int parts = 256 / px_lanes;
+    const int pl = threadIdx.x % px_lanes, part = threadIdx.x / px_lanes;
+    const long p4 = ((long)blk * px_lanes + pl) * 4;
+    const int per = (C + parts - 1) / parts;
+    const int i0 = part * per, i1 = i0 + per < C ? i0 + per : C;
+    if (p4 < HW) la_torgb_channel_sum<IMGC>(L.x + (long)b * C * HW + p4, nullptr, none, weff, C, HW, i0, i1, acc);
+#pragma unroll
+    for (int c = 0; c < IMGC; ++c) comb[(part * px_lanes + pl) * IMGC + c] = acc[c];
+    __syncthreads();
+    if (part != 0 || p4 >= HW) return;
+#pragma unroll
+    for (int c = 0; c < IMGC; ++c) {
+        float4 v = comb[pl * IMGC + c];
+        for (int q = 1; q < parts; ++q) {
+            const float4 u = comb[(q * px_lanes + pl) * IMGC + c];
+            v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+        }
+        const float bv = L.bias ? L.bias[c] : 0.f;
+        *reinterpret_cast<float4*>(L.rgb_pre + ((long)b * IMGC + c) * HW + p4) = make_float4(v.x + bv, v.y + bv, v.z + bv, v.w + bv);
+    }
+}
+
+int la_torgb_forward_levels(const LaTorgbLevels& t, int B, hipStream_t stream) {
+    LA_CHECK_ARG(t.n >= 1 && t.n <= LA_TORGB_MAX_LEVELS && B >= 1, "torgb_levels: 1 .. LA_TORGB_MAX_LEVELS levels");
+    LA_CHECK_ARG(t.imgc >= 1 && t.imgc <= 4, "torgb_levels: img_channels must be 1..4");
+    TorgbLevelsDev d;
+    d.n = t.n; d.s_stride = t.s_stride;
+    long blocks = 0;
+    size_t lds = 0;
+    double flops = 0.0, bytes = 0.0;      // launch profiler: the sum of what la_torgb_forward states for each level
+    for (int k = 0; k < t.n; ++k) {
+        const LaTorgbLevels::Level& s = t.lv[k];
+        TorgbLevelDev& L = d.lv[k];
+        const long HW = (long)s.H * s.W;
+        LA_CHECK_ARG(s.x && s.wrgb && s.rgb_pre && s.C >= 1 && HW >= 4 && HW % 4 == 0, "torgb_levels: null pointer, or H*W no multiple of 4");
+        LA_CHECK_ARG(s.row_lo >= 0 && (s.row_hi == 0 || (s.row_hi > s.row_lo && s.row_hi <= s.H)), "torgb_levels: bad row window");
+        L.x = s.x; L.wrgb = s.wrgb; L.s = s.s; L.bias = s.bias; L.rgb_pre = s.rgb_pre; L.HW = HW; L.C = s.C; L.blk0 = (int)blocks;
+        L.p_lo = (long)s.row_lo * s.W; L.p_hi = (long)s.row_hi * s.W;
+        size_t need = (size_t)t.imgc * s.C * sizeof(float);
+        if (la_torgb_small(HW)) {      // (whole planes, as la_torgb_forward)
+            const long nq = HW / 4;
+            int px_lanes = 1;
+            while (px_lanes < 64 && px_lanes * 2 <= nq) px_lanes *= 2;
+            L.px_lanes = px_lanes; L.p_lo = L.p_hi = 0;
+            blocks += la_cdiv(nq, px_lanes);
+            need = (size_t)((t.imgc * s.C + 3) & ~3) * sizeof(float) + (size_t)256 * t.imgc * sizeof(float4);
+        } else {
+            L.px_lanes = 0;
+            blocks += la_cdiv(HW / 4, 256);
+        }
+        if (need > lds) lds = need;
+        flops += 2.0 * B * t.imgc * (double)s.C * HW;
+        bytes += 4.0 * B * ((double)s.C * HW + 2.0 * t.imgc * (double)HW);
+    }
+    LA_CHECK_ARG(blocks < (1l << 31) && lds <= 64 * 1024, "torgb_levels: too many pixels / channels");
+    const int slot = la_prof_open(LA_PC_TORGB, flops, bytes, stream);
+    dim3 grid((unsigned)blocks, B);
+#define LAUNCH(N) hipLaunchKernelGGL(la_torgb_fwd_levels_kernel<N>, grid, dim3(256), lds, stream, d)
+    switch (t.imgc) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
+#undef LAUNCH
+    la_prof_close(slot, stream);
+    LA_CHECK_LAUNCH();
+    return LA_OK;
+}
+
+// The images of those blocks in ONE more launch, lowest level first:  img_k = clamp(rgb_pre_k) + upsample2d(img_{k-1})  (la_up2_quad on
+// the same operands in the same order as the ToRGB kernels: the same bits), then optionally the up-sampled image of the last level, the
+// skip image that the fused ToRGB of the block above reads (la_fir4x4_up2_kernel's arithmetic, see LaSkipUp).  A level depends on the
+// whole plane below it and on nothing else, so one workgroup per (sample, image channel) walks the levels; planes up to 64x64 are kept in
+// LDS for the level above (two buffers in turn), larger ones are read back from the memory the workgroup itself wrote (L2).  A level
+// with a row window computes those rows only and leaves the others as they were.
+// With a skip image the plane gets `strips` workgroups (the skip image is 4x the last level and a CU's VALUs are the limit: 21 us of a 36 us
+// launch with one workgroup per plane at 128^2 -> 256^2).  Each of them walks the levels below the last on its own, in LDS (they are tiny;
+// strip 0 writes them out), computes the rows of the last level that its strip of the skip image reads into LDS -- rows of its own
+// share are written out, rows outside the level's window are fetched as they are -- and up-samples its strip from there.
+#define CHAIN_THREADS 1024
+#define CHAIN_KEEP 4096
+struct ChainLevelDev { const float* rgb_pre; float* img; int H, W, row_lo, row_hi; };
+struct ChainDev {
+    int n; float clamp;
+    const float* base; int Hb, Wb;      // image below the first level (null: none)
+    ChainLevelDev lv[LA_TORGB_MAX_LEVELS];
+    float* skip; int strips;            // (strips > 1 only with skip)
+    float f[16];
+};
+// the up-sampled image below at four consecutive pixels, from the LDS copy of that image where there is one (two explicit branches: one
+// pointer that may be either is a flat load, which waits on both memory counters)
+__device__ __forceinline__ float4 la_chain_up2(const float* lds_prev, const float* __restrict__ g_prev, int Hp, int Wp, const float* f, int p4, int W) {
+    return lds_prev ? la_up2_quad(lds_prev, Hp, Wp, f, p4 / W, p4 % W) : la_up2_quad(g_prev, Hp, Wp, f, p4 / W, p4 % W);
+}
+__device__ __forceinline__ float4 la_chain_clamp(float4 v, float clamp) {
+    if (clamp >= 0.f) {
+        v.x = fminf(fmaxf(v.x, -clamp), clamp); v.y = fminf(fmaxf(v.y, -clamp), clamp);
+        v.z = fminf(fmaxf(v.z, -clamp), clamp); v.w = fminf(fmaxf(v.w, -clamp), clamp);
+    }
+    return v;
+}
+__global__ __launch_bounds__(CHAIN_THREADS) void la_torgb_fwd_chain_kernel(ChainDev c) {
+    __shared__ float keep[2][CHAIN_KEEP];
+    const long plane = blockIdx.x;      // b * imgc + channel
+    const int strip = blockIdx.y;
+    const float* g_prev = c.base ? c.base + plane * c.Hb * c.Wb : nullptr;      // the image below: in global memory ...
+    int lds_prev = -1;                                                          // ... or in keep[lds_prev]
+    int Hp = c.Hb, Wp = c.Wb;
+    const int nwalk = c.skip ? c.n - 1 : c.n;      // levels every workgroup of the plane walks whole
+    // A level cannot start before the one below is complete: what does not depend on the level below is loaded early.  nxt: this thread's
+    // first quad of rgb_pre of the NEXT level, in flight across the barrier; four quads per trip, all loads of a trip before its stores
+    // (the compiler cannot tell img from rgb_pre).
+    auto first_quad = [&](int k) {
+        const ChainLevelDev& L = c.lv[k];
+        const int q0 = L.row_hi > 0 ? L.row_lo * L.W / 4 : 0, q1 = L.row_hi > 0 ? L.row_hi * L.W / 4 : L.H * L.W / 4, q = q0 + threadIdx.x;
+        return q < q1 ? *reinterpret_cast<const float4*>(L.rgb_pre + plane * ((long)L.H * L.W) + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    float4 nxt = nwalk > 0 ? first_quad(0) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < nwalk; ++k) {
+        const ChainLevelDev& L = c.lv[k];
+        const int W = L.W;
+        const long HW = (long)L.H * W;
+        const float* rp = L.rgb_pre + plane * HW;
+        float* ip = L.img + plane * HW;
+        const int kb = HW <= CHAIN_KEEP ? (k & 1) : -1;
+        const float* lp = lds_prev >= 0 ? keep[lds_prev] : nullptr;
+        const bool below = lp || g_prev;
+        const int q0 = L.row_hi > 0 ? L.row_lo * W / 4 : 0, q1 = L.row_hi > 0 ? L.row_hi * W / 4 : (int)(HW / 4);
+        const float4 cur = nxt;
+        if (k + 1 < nwalk) nxt = first_quad(k + 1);
+        for (int q = q0 + threadIdx.x; q < q1; q += 4 * CHAIN_THREADS) {
+            float4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int p4 = (q + u * CHAIN_THREADS) * 4;
+                if (p4 >= 4 * q1) continue;
+                v[u] = la_chain_clamp((u == 0 && q == q0 + (int)threadIdx.x) ? cur : *reinterpret_cast<const float4*>(rp + p4), c.clamp);
+                if (below) {
+                    const float4 sv = la_chain_up2(lp, g_prev, Hp, Wp, c.f, p4, W);
+                    v[u].x += sv.x; v[u].y += sv.y; v[u].z += sv.z; v[u].w += sv.w;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int p4 = (q + u * CHAIN_THREADS) * 4;
+                if (p4 >= 4 * q1) continue;
+                if (strip == 0) *reinterpret_cast<float4*>(ip + p4) = v[u];
+                if (kb >= 0) *reinterpret_cast<float4*>(keep[kb] + p4) = v[u];
+            }
+        }
+        __syncthreads();      // (the level above reads what every thread of this workgroup wrote, LDS or global)
+        lds_prev = kb; g_prev = ip; Hp = L.H; Wp = W;
+    }
+    if (!c.skip) return;
+    // the last level in the rows [r0, r1) that skip rows [a, b) read, into sbuf (the LDS buffer the level below does not occupy)
+    const ChainLevelDev& L = c.lv[c.n - 1];
+    const int H = L.H, W = L.W, a = strip * (2 * H / c.strips), b = a + 2 * H / c.strips;
+    const int r0 = (a >> 1) - 1 > 0 ? (a >> 1) - 1 : 0, r1 = ((b - 1) >> 1) + 2 < H ? ((b - 1) >> 1) + 2 : H;
+    const int lo = L.row_hi > 0 ? L.row_lo : 0, hi = L.row_hi > 0 ? L.row_hi : H;
+    const float* rp = L.rgb_pre + plane * ((long)H * W);
+    float* ip = L.img + plane * ((long)H * W);
+    const float* lp = lds_prev >= 0 ? keep[lds_prev] : nullptr;
+    float* sbuf = keep[lds_prev == 0 ? 1 : 0];
+    const bool below = lp || g_prev;
+    for (int q = r0 * W / 4 + threadIdx.x; q < r1 * W / 4; q += CHAIN_THREADS) {
+        const int p4 = q * 4, y = p4 / W;
+        float4 v;
+        if (y >= lo && y < hi) {
+            v = la_chain_clamp(*reinterpret_cast<const float4*>(rp + p4), c.clamp);
+            if (below) {
+                const float4 sv = la_chain_up2(lp, g_prev, Hp, Wp, c.f, p4, W);
+                v.x += sv.x; v.y += sv.y; v.z += sv.z; v.w += sv.w;
+            }
+            if (2 * y >= a && 2 * y < b) *reinterpret_cast<float4*>(ip + p4) = v;
+        } else {
+            v = *reinterpret_cast<const float4*>(ip + p4);
+        }
+        *reinterpret_cast<float4*>(sbuf + (p4 - r0 * W)) = v;
+    }
+    __syncthreads();
+    const int W2 = 2 * W;
+    float* sp = c.skip + plane * (long)(2 * H) * W2;
+    for (int q = a * W2 / 4 + threadIdx.x; q < b * W2 / 4; q += 4 * CHAIN_THREADS) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int p4 = (q + u * CHAIN_THREADS) * 4;
+            if (p4 < b * W2) v[u] = la_up2_quad(sbuf, H, W, c.f, p4 / W2, p4 % W2, r0);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int p4 = (q + u * CHAIN_THREADS) * 4;
+            if (p4 < b * W2) *reinterpret_cast<float4*>(sp + p4) = v[u];
+        }
+    }
+}
+
+int la_image_chain_forward(const LaImageChain& t, int B, const float* fir_host, hipStream_t stream) {
+    LA_CHECK_ARG(t.n >= 1 && t.n <= LA_TORGB_MAX_LEVELS && B >= 1 && fir_host, "image_chain: 1 .. LA_TORGB_MAX_LEVELS levels and the filter");
+    LA_CHECK_ARG(t.imgc >= 1 && t.imgc <= 4, "image_chain: img_channels must be 1..4");
+    ChainDev d;
+    d.n = t.n; d.clamp = t.clamp; d.base = t.base; d.Hb = t.lv[0].H / 2; d.Wb = t.lv[0].W / 2;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) d.f[i * 4 + j] = 4.f * fir_host[(3 - i) * 4 + (3 - j)];      // (fir_fill: gain * flipped filter)
+    for (int k = 0; k < t.n; ++k) {
+        const LaImageChain::Level& s = t.lv[k];
+        LA_CHECK_ARG(s.rgb_pre && s.img && s.H >= 1 && s.W % 4 == 0 && (k == 0 || (s.H == 2 * t.lv[k - 1].H && s.W == 2 * t.lv[k - 1].W)),
+                     "image_chain: every level doubles the one below, W % 4 == 0");
+        LA_CHECK_ARG(s.row_lo >= 0 && (s.row_hi == 0 || (s.row_hi > s.row_lo && s.row_hi <= s.H)), "image_chain: bad row window");
+        LA_CHECK_ARG((long)s.H * s.W < (1l << 28), "image_chain: plane too large");
+        LA_CHECK_ARG(!(k == 0 && t.base) || s.H % 2 == 0, "image_chain: the image below the first level has half its size");
+        d.lv[k] = ChainLevelDev{s.rgb_pre, s.img, s.H, s.W, s.row_lo, s.row_hi};
+    }
+    const LaImageChain::Level& top = t.lv[t.n - 1];
+    d.skip = t.skip; d.strips = 1;
+    if (t.skip) {      // (see the kernel: the levels below the last in LDS, the last in strips of H / strips + 2 rows)
+        for (int k = 0; k + 1 < t.n; ++k) LA_CHECK_ARG((long)t.lv[k].H * t.lv[k].W <= CHAIN_KEEP, "image_chain: a skip image needs the levels below the last within 64x64");
+        int S = 8;
+        while (S > 1 && (top.H % S || (top.H / S + 2) * (long)top.W > CHAIN_KEEP)) S >>= 1;
+        LA_CHECK_ARG((top.H / S + 2) * (long)top.W <= CHAIN_KEEP && top.H % 2 == 0, "image_chain: a skip image needs a last level within 128x128");
+        d.strips = S;
+    }
+    // launch profiler: the up-FIR launch of the skip image that this launch takes over (the levels' own traffic is in la_torgb_forward_levels' figures)
+    const double P = (double)B * t.imgc, hw = (double)top.H * top.W;
+    const int slot = la_prof_open(LA_PC_TORGB, t.skip ? 2.0 * 16 * P * 4.0 * hw : 0.0, t.skip ? 4.0 * P * 5.0 * hw : 0.0, stream);
+    hipLaunchKernelGGL(la_torgb_fwd_chain_kernel, dim3((unsigned)(B * t.imgc), d.strips), dim3(CHAIN_THREADS), 0, stream, d);
+    la_prof_close(slot, stream);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }

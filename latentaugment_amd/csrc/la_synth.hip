@@ -76,9 +76,11 @@ struct la_synth {
     SynthPlan plan;     // of the LAST forward pass: what it ran and what its backward pass runs
     const float* g_top; // image gradient the running backward pass was handed (top block)
     float up_mult;      // la_modconv_up2_bwd_xs_mult of the filter
+    int rgb_per_block;  // la_synth_set_torgb_schedule: a ToRGB launch behind every block's conv1 (else deferred, see plan_pass)
 };
 
 enum { SEAM_KERNEL = LA_SYNTH_SEAM_KERNEL, SEAM_FUSED = LA_SYNTH_SEAM_FUSED, PMAX_NONE = LA_SYNTH_PMAX_NONE, PMAX_1, PMAX_2, PMAX_3 };
+enum { SKIP_NONE = 0, SKIP_LAUNCH = LA_SYNTH_SKIP_LAUNCH, SKIP_CHAIN = LA_SYNTH_SKIP_CHAIN };
 
 // Windows of a pass (P.pass.nblocks / nconv set, the rest zero) for the image window `img`, top block downwards until a row window is the
 // whole plane.
@@ -136,7 +138,7 @@ static void plan_windows(SynthPlan& P, const LaWindow& img) {
 
 // The plan of a pass of `nblocks` blocks with the channel table, B samples, the contraction precision and the image window.  The development
 // switches are read here and nowhere else, once per process.
-static void plan_pass(int nblocks, const int* channels, int B, int precision, const LaWindow& img, SynthPlan& P) {
+static void plan_pass(int nblocks, const int* channels, int B, int precision, const LaWindow& img, bool rgb_per_block, SynthPlan& P) {
     static const bool zt_dense = la_dev_env("LA_NO_ZT_PITCH") != nullptr;      // dense interleaved scratch rows + the scalar FIR kernel
     static const bool no_fuse = la_dev_env("LA_NO_SEAM_FUSE") != nullptr, no_fuse2 = la_dev_env("LA_NO_SEAM2_FUSE") != nullptr;      // A/B of the fused seams on one box
     static const bool no_xs = la_dev_env("LA_NO_XS_HANDOFF") != nullptr;       // plane maxima + la_xscale_pmax at the consumer
@@ -168,7 +170,7 @@ static void plan_pass(int nblocks, const int* channels, int B, int precision, co
         // ToRGB inside the epilogue of the block's conv1 where one row tile of the halo kernel holds all its channels (the top blocks:
         // <= 128 channels at >= 64^2) -- conv1's output is then not streamed a second time; the skip image has to exist before conv1 runs
         Bk.fuse_rgb = la_modconv3x3_fwd_fuses_rgb(precision, B, channels[k], channels[k], res);
-        Bk.skip_up = k > 0 && Bk.fuse_rgb;
+        Bk.skip_up = k > 0 && Bk.fuse_rgb ? SKIP_LAUNCH : SKIP_NONE;
         seam(L1, k < top && fuse1, PMAX_3, tiles1, slabs);
         L1.ntiles = tiles1;
         if (k == 0) break;
@@ -190,6 +192,13 @@ static void plan_pass(int nblocks, const int* channels, int B, int precision, co
         L0.rows.in = L1.rows.out;
         if (P.conv[2 * k - 2].cone_hi > 0) cone_tiles(P.conv[2 * k - 2], res / 2, L0.rows.out);
     }
+    // Deferred ToRGBs: nothing reads the image of a block whose ToRGB is a kernel of its own before the next fused ToRGB does (its skip
+    // image), so those blocks run no ToRGB launch of their own.  A run of them ends in front of the first fused block above it
+    // (SKIP_CHAIN: two launches there make rgb_pre and the images of the whole run and that block's skip image, which takes over its
+    // up-FIR launch; la_image_chain_forward makes skip images up to 256^2, a larger one keeps its launch behind the two) or, where no
+    // block above fuses, at the end of the pass.
+    for (int k = 1; k <= top && !rgb_per_block; ++k)
+        if (P.blk[k].skip_up && !P.blk[k - 1].fuse_rgb && (4 << k) <= 256) P.blk[k].skip_up = SKIP_CHAIN;
 }
 
 // a layer's epilogue (SynthesisLayer.forward: lrelu, gain sqrt(2), conv_clamp) with the noise the last forward pass used ...
@@ -397,9 +406,19 @@ extern "C" int la_synth_set_precision(la_synth* h, int precision) {
 extern "C" int la_synth_get_precision(const la_synth* h) { return h ? h->precision : -1; }
 // Kept for ABI compatibility (rounds 1-3 selected between an a-priori bound and data maxima for the fp16 operand scale of the forward
 // contractions): since round 4 every forward scale is derived from the data of the pass by the kernel that produces the tensor
-// (la_xscale_bound_kernel, la_style.hip) -- there is nothing to select, the launch sequence does not depend on this call.
+// (la_xscale_bound_block, la_style.hip) -- there is nothing to select, the launch sequence does not depend on this call.
 extern "C" int la_synth_set_operand_scale(la_synth* h, int from_data) {
     LA_CHECK_ARG(h && (from_data == 0 || from_data == 1), "synth_set_operand_scale: 0 or 1");
+    return LA_OK;
+}
+
+// Where the ToRGB layers that are kernels of their own run in the following forward passes: 0 (default) deferred -- one launch for rgb_pre of
+// all of them and one for their images in front of the first fused ToRGB / at the end of the pass (plan_pass) --, 1 a launch behind
+// every block's conv1 (la_torgb_forward, and an up-FIR launch for every skip image).  Same buffers, same bits: the per-block schedule is
+// what tests/test_hip_image_chain.py holds the deferred one against.
+extern "C" int la_synth_set_torgb_schedule(la_synth* h, int per_block) {
+    LA_CHECK_ARG(h && (per_block == 0 || per_block == 1), "synth_set_torgb_schedule: 0 or 1");
+    h->rgb_per_block = per_block;
     return LA_OK;
 }
 
@@ -459,7 +478,7 @@ extern "C" int la_synth_plan_query(int img_resolution, int img_channels, const i
     const int nblocks = la_synth_num_ws(R) / 2;
     for (int k = 0; k < nblocks; ++k) LA_CHECK_ARG(channels[k] >= 4 && channels[k] % 4 == 0, "synth_plan_query: channel counts must be multiples of 4");
     SynthPlan P;
-    plan_pass(nblocks, channels, B, precision, LaWindow{row_lo, row_hi, col_lo, col_hi}, P);
+    plan_pass(nblocks, channels, B, precision, LaWindow{row_lo, row_hi, col_lo, col_hi}, false, P);
     const int* src = reinterpret_cast<const int*>(&P);      // (ints throughout, in the order of the constants: the static_assert above)
     for (int i = 0; i < LA_SYNTH_PLAN_NINFO; ++i) info[i] = src[i];
     return LA_OK;
@@ -476,6 +495,24 @@ extern "C" const float* la_synth_styles(const la_synth* h) { return h ? h->s_all
 extern "C" const float* la_synth_style_grads(const la_synth* h) { return h ? h->ds_all : nullptr; }
 extern "C" int la_synth_style_rows(const la_synth* h) { return h ? h->S : 0; }
 
+// The deferred ToRGBs of blocks k0 .. k1 (plan_pass) from their saved conv1 outputs, two launches: rgb_pre of every level, then the images
+// level by level (block k1's into top_img where given) and, where a fused block follows, its skip image.  Windowed blocks: the rows the
+// plan asks of them, as the per-block launch computed.
+static int deferred_images(la_synth* h, const SynthPlan& P, int k0, int k1, int B, float* skip, float* top_img, hipStream_t stream) {
+    LaTorgbLevels lv; memset(&lv, 0, sizeof(lv));
+    LaImageChain ch; memset(&ch, 0, sizeof(ch));
+    lv.imgc = ch.imgc = h->imgc; lv.s_stride = h->S; ch.clamp = h->clamp;
+    ch.base = k0 > 0 ? h->rgb[k0 - 1].img : nullptr; ch.skip = skip;
+    for (int k = k0; k <= k1; ++k) {
+        const RgbLayer& T = h->rgb[k];
+        const int lo = P.blk[k].img_lo, hi = P.blk[k].img_hi;
+        lv.lv[lv.n++] = {h->conv[2 * k].y, T.cin, T.res, T.res, T.weight, h->s_all + T.s_off, T.bias, T.rgb_pre, lo, hi};
+        ch.lv[ch.n++] = {T.rgb_pre, (k == k1 && top_img) ? top_img : T.img, T.res, T.res, lo, hi};
+    }
+    int rc = la_torgb_forward_levels(lv, B, stream);
+    return rc ? rc : la_image_chain_forward(ch, B, h->fir, stream);
+}
+
 extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, long ws_lstride, int B, int noise_mode,
                                 const float* const* noises, float* img_out, hipStream_t stream) {
     LA_CHECK_ARG(h && ws, "synth_forward: null pointer");
@@ -483,17 +520,17 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
     LA_CHECK_ARG(noise_mode >= 0 && noise_mode <= 2, "synth_forward: noise_mode must be 0 (none), 1 (const), 2 (explicit)");
     LA_CHECK_ARG(noise_mode != 2 || noises, "synth_forward: explicit noise requested but no noise tensors given");
     for (int ci = 0; ci < h->nconv && noise_mode == 2; ++ci) LA_CHECK_ARG(h->conv[ci].noise_strength == 0.f || noises[ci], "synth_forward: missing noise tensor");
-    plan_pass(h->nblocks, h->channels, B, h->precision, h->win, h->plan);
+    plan_pass(h->nblocks, h->channels, B, h->precision, h->win, h->rgb_per_block != 0, h->plan);
     const SynthPlan& P = h->plan;
     int rc;
     if ((rc = la_affine_forward(h->st, ws, ws_bstride, ws_lstride, B, h->wdim, h->s_all, stream))) return rc;
-    if ((rc = la_demod_forward(h->dt, h->s_all, h->S, B, h->d_all, stream))) return rc;
-    // fp16 operand scales: the slot rows of every layer start the pass at LA_XS_INIT; the kernel that PRODUCES a layer's input lowers
-    // that layer's row (forward: xs_fwd, la_xs_lower with max|style| of the consuming layer; backward: xs_bwd)
-    if (P.pass.f16 && (rc = la_xscale_from_bounds(h->dt, h->s_all, h->S, h->cst, h->channels[0] * 16, h->xs_fwd, h->xs_mult, B, stream, h->xs_bwd))) return rc;
+    // fp16 operand scales: the slot rows of every layer start the pass at LA_XS_INIT (in the demod launch); the kernel that PRODUCES a
+    // layer's input lowers that layer's row (forward: xs_fwd, la_xs_lower with max|style| of the consuming layer; backward: xs_bwd)
+    const LaXscaleBounds xb = {h->cst, h->channels[0] * 16, h->xs_fwd, h->xs_mult, h->xs_bwd};
+    if ((rc = la_demod_forward(h->dt, h->s_all, h->S, B, h->d_all, stream, P.pass.f16 ? &xb : nullptr))) return rc;
     auto fwd_row = [&](int conv_index) { return (P.pass.f16 && conv_index < h->nconv) ? h->xs_fwd + (long)conv_index * B * LA_XS_FAN : nullptr; };
     auto fwd_mult = [&](int conv_index) { return (P.pass.f16 && conv_index < h->nconv) ? h->xs_mult + (long)conv_index * B : nullptr; };
-    int ci = 0;
+    int ci = 0, pending = -1;      // pending: the first block whose deferred ToRGB has not run yet
     const float* x = h->cst;
     long x_bstride = 0;
     for (int k = 0; k < h->nblocks; ++k) {
@@ -501,7 +538,12 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
         RgbLayer& T = h->rgb[k];
         float* const rgb_dst = (k == h->nblocks - 1 && img_out) ? img_out : T.img;
         const float* skip = nullptr;
-        if (P.blk[k].skip_up) {
+        if (P.blk[k].fuse_rgb && pending >= 0) {      // the deferred blocks below: rgb_pre, images and (SKIP_CHAIN) this block's skip image
+            if ((rc = deferred_images(h, P, pending, k - 1, B, P.blk[k].skip_up == SKIP_CHAIN ? T.g_img : nullptr, nullptr, stream))) return rc;
+            pending = -1;
+        }
+        if (P.blk[k].skip_up == SKIP_CHAIN) skip = T.g_img;
+        else if (P.blk[k].skip_up) {
             if ((rc = la_upfirdn2d_ex(h->rgb[k - 1].img, T.g_img, B, h->imgc, res / 2, res / 2, h->fir, la_fir_up2(), stream))) return rc;
             skip = T.g_img;
         }
@@ -527,12 +569,15 @@ extern "C" int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, l
             x = L.y; x_bstride = (long)L.cout * res * res;
         }
         // img = upsample2d(img_prev, f) + torgb(x): up 2, pad (2,1,2,1), gain 4 (upfirdn2d.py:342-348) -- the up-sampled image of the block
-        // below is computed inside the ToRGB kernel (la_up2_quad); a windowed block: only the image rows somebody reads
-        if (!P.blk[k].fuse_rgb && (rc = la_torgb_forward(x, layer_rgb(h, T, nullptr, rgb_dst), B, T.cin, res, res, stream, nullptr, P.blk[k].img_lo, P.blk[k].img_hi,
-                                                         k > 0 ? h->rgb[k - 1].img : nullptr, h->fir)))
+        // below is computed inside the ToRGB kernel (la_up2_quad); a windowed block: only the image rows somebody reads.  Deferred unless the
+        // handle asks for a launch per block: the block joins the run that deferred_images makes in front of the next fused block / at the end
+        if (!P.blk[k].fuse_rgb && !h->rgb_per_block) { if (pending < 0) pending = k; }
+        else if (!P.blk[k].fuse_rgb && (rc = la_torgb_forward(x, layer_rgb(h, T, nullptr, rgb_dst), B, T.cin, res, res, stream, nullptr, P.blk[k].img_lo, P.blk[k].img_hi,
+                                                              k > 0 ? h->rgb[k - 1].img : nullptr, h->fir)))
             return rc;
         if (k == h->nblocks - 1) h->final_img = rgb_dst;
     }
+    if (pending >= 0 && (rc = deferred_images(h, P, pending, h->nblocks - 1, B, nullptr, h->final_img, stream))) return rc;
     return LA_OK;
 }
 

@@ -14,13 +14,14 @@ CLASS_KERNELS = {
     'operand_prep': 'la_presplit_t_kernel / la_plane_absmax_kernel / la_xscale_kernel / la_xscale_pmax_kernel (fp16 operand scale and pre-split copy)',
     'fir': 'la_fir4x4_* / la_upfirdn2d_kernel / la_imgrad_pyramid_kernel (upfirdn2d family, fwd with the layer epilogue, adjoint, image-gradient pyramid)',
     'seam_bwd': 'la_seam_bwd_kernel (bias_act backward + ToRGB backward + demod-gradient reductions)',
-    'torgb_fwd': 'la_torgb_fwd*_kernel (1x1 modulated ToRGB + clamp + skip add)',
+    'torgb_fwd': 'la_torgb_fwd*_kernel (1x1 modulated ToRGB + clamp + skip add; a synthesis pass: la_torgb_fwd_levels_kernel, rgb_pre of every '
+                 'deferred block in one launch, and la_torgb_fwd_chain_kernel, their images and the skip image of the first fused block)',
     'bank': 'la_bank_* (criteria bank scans)',
 }
 
 # (substring of the demangled kernel name, class); first match wins
 _RULES = [
-    ('la_xscale_bound', None),                      # once per pass, with the style tables: outside the brackets
+    ('la_xscale_bound', None),                      # (traces of builds before the demod launch took this work over: outside the brackets)
     ('la_conv_bf16_halo_kernel', 'conv_halo'),
     ('la_conv_splitk_finish', 'conv_splitk'),
     ('la_conv_igemm', 'conv_f32'),

@@ -97,7 +97,7 @@ class SynthesisEngine:
         self.set_precision(precision)
 
     # fp16 operand scales (f16x2 mode): since round 4 every forward contraction's scale is derived from the DATA of the pass by the kernel
-    # that produces its input (la_style.hip: la_xscale_bound_kernel; la_common.h: slot rows) -- no a-priori bound, no calibration, nothing
+    # that produces its input (la_style.hip: la_xscale_bound_block; la_common.h: slot rows) -- no a-priori bound, no calibration, nothing
     # to select.  `operand_scale` is kept as a read-only description for log lines.
     operand_scale = 'data (producer-lowered slot rows)'
 
