@@ -482,6 +482,17 @@ int la_synth_forward(la_synth* h, const float* ws, long ws_bstride, long ws_lstr
                      const float* const* noises, float* img_out, la_stream_t stream);
 /* d(loss)/d(ws) [B][num_ws][w_dim] from d(loss)/d(img) [B][C][R][R]; differentiates the last la_synth_forward. */
 int la_synth_backward(la_synth* h, const float* g_img, float* dws, la_stream_t stream);
+/* The same pass (la_synth_backward is this entry with gnoises NULL: the same launches, the same bits in dws) that also delivers the gradient
+ * with respect to the per-layer noise: gnoises[layer] [B][res][res] in the engine's layer order, the gradient with respect to a unit noise
+ * added to sample b of that layer, whatever noise_mode the forward pass used.  A NULL entry skips its layer; a layer whose
+ * noise_strength is 0 gets zeros.  Per layer one launch of la_noise_grad_f32's kernel behind the seam that wrote the gradient of the
+ * layer's raw output.  Refused (LA_ERR_ARG) while a row or column window is set (windowed passes leave rows of those buffers stale) and
+ * before the first forward pass. */
+int la_synth_backward_noise(la_synth* h, const float* g_img, float* dws, float* const* gnoises, la_stream_t stream);
+/* gn[b][p] = strength * sum_c gz[b][c][p] / d[b * d_stride + c]: gz [B][C][HW] holds the gradient of a modulated layer's raw output times
+ * the demodulation coefficient d > 0 (what the backward seams store).  float32, channels added in an order fixed by the shape (no
+ * atomics: two runs give the same bits); HW a multiple of 4, gz and gn 16-byte aligned. */
+int la_noise_grad_f32(const float* gz, const float* d, long d_stride, int B, int C, long HW, float strength, float* gn, la_stream_t stream);
 const float* la_synth_image(const la_synth* h);
 const float* la_synth_block_image(const la_synth* h, int block);
 const float* la_synth_layer_output(const la_synth* h, int layer);
@@ -855,7 +866,8 @@ int la_path_points_f32(const float* a, const float* b, const float* t, const dou
                        float* out, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * Projector: inversion of images into W / W+ (Karras et al. 2020, Appendix D, without the noise maps).  The reference reads inverted
+ * Projector: inversion of images into W / W+ (Karras et al. 2020, Appendix D; the per-layer noise maps are optimised on request, with the
+ * published regulariser and re-normalisation, and then discarded).  The reference reads inverted
  * latents (augments/latent_aug.py:310-324) and has no code that makes them.  The optimisation is an eager sequence of launches over
  * the synthesis and feature engines (latentaugment_amd/projector.py); these are the kernels that only it needs.  No atomics: two runs
  * give the same bits.  Bad arguments are LA_ERR_ARG before any launch.
@@ -871,6 +883,17 @@ int la_path_points_f32(const float* a, const float* b, const float* t, const dou
  *                     la_adam_step_f32 (`step` 1-based, lr of this step), then ws = p + sigma * n with n the unit normal of
  *                     (seed, layer, row0 + b, element l * wdim + j): the stream of la_noise_normal_f32 with rows of L * wdim elements.
  *                     dws null: no update, ws alone is written (m, v may be null).
+ *   The noise maps: a table of nmaps maps for one batch, map i being [B][res[i]][res[i]] with res[i] = 4 << k (anything else is refused).
+ *   la_noise_reg_f32  the published regulariser of every map and sample -- per pyramid level (the map, then 2 x 2 averages of it while
+ *                     the level above is larger than 8 x 8) the squared means of n * roll(n, 1, x) and n * roll(n, 1, y), shifts cyclic --
+ *                     reg[b * reg_stride] = scale * (sum over maps, levels), and its gradient gn[i] = weight * g (accumulate != 0: added).
+ *                     Levels are float32, every sum float64 in an order fixed by the shapes.  One launch per pyramid level over all maps
+ *                     (it adds up level l and builds level l + 1), one that finishes the sums, one that gathers the gradient.
+ *                     ws: la_noise_reg_scratch_bytes(res, nmaps, B) bytes, 8-byte aligned, any contents (LA_ERR_WORKSPACE when short).
+ *   la_proj_noise_tail_f32   the end of a step for the maps: Adam as above (one optimiser over latent and maps: the same lr, betas,
+ *                     eps, step) on n, m, v from gn, then n -= mean(n); n *= rsqrt(mean(n^2)) per map and sample, moments in float64 in a
+ *                     fixed order (the squares are those of the centred values).  A map whose centred mean square is exactly 0 is left
+ *                     at zeros.  Three launches over all maps.  ws: la_proj_noise_tail_scratch_bytes(res, nmaps, B) bytes.
  * ------------------------------------------------------------------------------------------------------------- */
 size_t la_row_dist_workspace_bytes(int rows, long K);
 int la_row_dist_f32(const float* a, const float* t, int rows, long K, int fold, double scale, float gscale, float* g, int accumulate,
@@ -880,6 +903,12 @@ int la_box_up_f32(const float* gy, float* gx, long planes, int R, int k, la_stre
 int la_proj_step_tail_f32(const float* dws, float* p, float* m, float* v, float* ws, int B, int num_ws, int wdim, int wplus, int step,
                           float lr, float beta1, float beta2, float eps, float sigma, unsigned long long seed, unsigned layer, long row0,
                           la_stream_t stream);
+size_t la_noise_reg_scratch_bytes(const int* res, int nmaps, int B);
+int la_noise_reg_f32(const float* const* maps, const int* res, int nmaps, int B, double scale, float weight, float* const* gn, int accumulate,
+                     double* reg, long reg_stride, void* ws, size_t ws_bytes, la_stream_t stream);
+size_t la_proj_noise_tail_scratch_bytes(const int* res, int nmaps, int B);
+int la_proj_noise_tail_f32(const float* const* gn, float* const* n, float* const* m, float* const* v, const int* res, int nmaps, int B, int step,
+                           float lr, float beta1, float beta2, float eps, void* ws, size_t ws_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Opt-in profiler for the contraction launches (HIP events on the launch stream).  No reference counterpart: the

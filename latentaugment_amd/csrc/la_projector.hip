@@ -1,8 +1,10 @@
-// Projector (inversion of images into W / W+, Karras et al. 2020, Appendix D, without the noise maps): the three kernels that are
-// specific to it.  The optimisation itself is an eager sequence of launches over the synthesis and feature engines (projector.py).
+// Projector (inversion of images into W / W+, Karras et al. 2020, Appendix D): the kernels that are specific to it -- three for the
+// latent, and the regulariser and step tail of the per-layer noise maps, which are optimised on request (second half of the file).  The optimisation itself is an eager sequence of launches over the synthesis and feature engines (projector.py).
 //   la_row_dist_f32     loss[j] = scale * sum_c sum_k (a - t)^2 over rows c * (rows / fold) + j, and g (+)= gscale * (a - t)
 //   la_box_down_f32     [planes][R][R] -> [planes][R / k][R / k], the mean of k x k boxes;  la_box_up_f32: its adjoint
 //   la_proj_step_tail_f32   W-space row sum + Adam + the next step's noised latent in one launch
+//   la_noise_reg_f32    the published noise regulariser over a table of maps, with its gradient as a gather
+//   la_proj_noise_tail_f32  Adam + re-normalisation of every map
 // No atomics anywhere: two runs give the same bits.
 #include "la_common.h"
 #include "la_rng.h"
@@ -210,6 +212,334 @@ extern "C" int la_proj_step_tail_f32(const float* dws, float* p, float* m, float
     const long n = (long)B * (((long)L * wdim + 3) >> 2);
     hipLaunchKernelGGL(la_proj_step_tail_kernel, dim3((unsigned)la_cdiv(n, 256)), dim3(256), 0, stream, dws, p, m, v, ws, B, num_ws, wdim, L, step_size, bc2s,
                        beta1, beta2, eps, sigma, (unsigned)seed, (unsigned)(seed >> 32), layer, row0);
+    LA_CHECK_LAUNCH();
+    return LA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Noise maps.  The published projector optimises the per-layer noise maps beside the latent, keeps them noise-like with a regulariser,
+// re-normalises them after every step and throws them away at the end.  A call takes the maps of ONE batch as a table: map i is
+// [B][res[i]][res[i]], res[i] = 4 << k.  The launches are table-driven: one grid covers every (map, sample, chunk).
+#define LA_NZ_MAXMAPS 32      // (an engine has at most 2 * 12 conv layers)
+#define LA_NZ_MAXLEV 10       // pyramid levels of a 4096^2 map: 4096 .. 8
+
+// A flat grid over (map, sample, chunk): the workgroups of map i are start[i] .. start[i + 1] - 1, sample-major, chunks[i] per sample
+// (0: the map takes no part in the launch).
+struct LaMapGrid { int nmaps, B; int chunks[LA_NZ_MAXMAPS]; int start[LA_NZ_MAXMAPS + 1]; };
+
+static long la_map_grid(LaMapGrid& g, const int* chunks, int nmaps, int B) {
+    g.nmaps = nmaps; g.B = B; g.start[0] = 0;
+    long total = 0;
+    for (int i = 0; i < nmaps; ++i) { g.chunks[i] = chunks[i]; total += (long)B * chunks[i]; g.start[i + 1] = (int)total; }
+    return total;
+}
+
+__device__ __forceinline__ void la_map_locate(const LaMapGrid& g, int blk, int& m, int& b, int& chunk) {
+    m = 0;
+    while (m + 1 < g.nmaps && blk >= g.start[m + 1]) ++m;
+    const int local = blk - g.start[m];
+    b = local / g.chunks[m]; chunk = local - b * g.chunks[m];
+}
+
+// float64 sums over a 256-thread workgroup: lanes by the xor butterfly, then the four waves in order.  `red` is 4 (8) doubles of LDS; the
+// leading barrier lets calls follow one another.  Every thread must reach them; all threads get the result.
+__device__ __forceinline__ double la_block_sum_256_f64(double v, double* red) {
+    v = la_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+static bool la_map_res_ok(int r) { return r >= 4 && r <= 4096 && (r & (r - 1)) == 0; }
+static int la_map_table_check(const int* res, int nmaps, int B, const char* msg) {
+    LA_CHECK_ARG(res && nmaps >= 1 && nmaps <= LA_NZ_MAXMAPS && B >= 1 && B <= 65535, msg);
+    for (int i = 0; i < nmaps; ++i) LA_CHECK_ARG(la_map_res_ok(res[i]), "noise maps: a resolution must be 4 << k (4 .. 4096)");
+    return LA_OK;
+}
+
+// ---- the regulariser.  Per map and sample:  reg = 0; loop: reg += mean(n * roll(n, 1, x))^2 + mean(n * roll(n, 1, y))^2; if r <= 8: break;
+// n = avg_pool2d(n, 2); r /= 2  -- cyclic shifts; a 4 x 4 or 8 x 8 map has one level, a 256 x 256 map six.  With a_l, c_l the two means of
+// level l and N_l = r_l^2 the gradient at a fine pixel is a gather (no scatter, no atomics):
+//   g[y][x] = sum_l 4^-l * (2 a_l / N_l * (n_l[y_l][x_l - 1] + n_l[y_l][x_l + 1]) + 2 c_l / N_l * (n_l[y_l - 1][x_l] + n_l[y_l + 1][x_l])),  (y_l, x_l) = (y >> l, x >> l)
+// Launch l (one per level index, over all maps that have level l): a workgroup takes 256 elements of level l of one (map, sample), adds
+// up their two products in float64 -- the partial [map][level][sample][chunk] -- and, where the map has a level l + 1, writes its 2 x 2
+// averages (float32, 0.25 * (((n00 + n01) + n10) + n11)).  The finish launch adds the partials in chunk order, thread i taking i, i + 64, ...,
+// leaves the two coefficients of every (map, level, sample) and writes reg; the gather launch is one thread per fine pixel.
+struct NregTab {
+    int nmaps, B;
+    const float* n[LA_NZ_MAXMAPS];
+    float* g[LA_NZ_MAXMAPS];
+    int r[LA_NZ_MAXMAPS], nlev[LA_NZ_MAXMAPS];
+    long lev_off[LA_NZ_MAXMAPS], part_off[LA_NZ_MAXMAPS];      // floats into `levels` (levels 1 ..), doubles into `part`
+    float* levels;
+    double *part, *coef;
+};
+
+__host__ __device__ static inline int nreg_levels(int r) { int n = 1; while (r > 8) { r >>= 1; ++n; } return n; }
+__host__ __device__ static inline int nreg_chunks(int r, int l) { const long n = (long)(r >> l) * (r >> l); return (int)((n + 255) / 256); }
+
+__device__ __forceinline__ float* nreg_level(const NregTab& t, int m, int l, int b) {      // (l >= 1)
+    const long r = t.r[m], rl = r >> l;
+    long pre = 0;
+    for (int q = 1; q < l; ++q) pre += (r >> q) * (r >> q);
+    return t.levels + t.lev_off[m] + (long)t.B * pre + (long)b * rl * rl;
+}
+__device__ __forceinline__ const float* nreg_level_in(const NregTab& t, int m, int l, int b) {
+    return l == 0 ? t.n[m] + (long)b * t.r[m] * t.r[m] : nreg_level(t, m, l, b);
+}
+__device__ __forceinline__ long nreg_part(const NregTab& t, int m, int l, int b) {      // first of the (x, y) pairs of (map, level, sample)
+    long pre = 0;
+    for (int q = 0; q < l; ++q) pre += nreg_chunks(t.r[m], q);
+    return t.part_off[m] + 2 * ((long)t.B * pre + (long)b * nreg_chunks(t.r[m], l));
+}
+
+__global__ __launch_bounds__(256) void la_nreg_level_kernel(NregTab t, LaMapGrid g, int l) {
+    __shared__ double red[4];
+    int m, b, chunk;
+    la_map_locate(g, blockIdx.x, m, b, chunk);
+    const int r = t.r[m] >> l;
+    const long N = (long)r * r, e = (long)chunk * 256 + threadIdx.x;
+    const float* src = nreg_level_in(t, m, l, b);
+    double sx = 0.0, sy = 0.0;
+    if (e < N) {
+        const int y = (int)(e / r), x = (int)(e - (long)y * r);
+        const float v = src[e];
+        sx = (double)v * (double)src[(long)y * r + (x == 0 ? r - 1 : x - 1)];
+        sy = (double)v * (double)src[(long)(y == 0 ? r - 1 : y - 1) * r + x];
+        if (l + 1 < t.nlev[m] && !(x & 1) && !(y & 1))
+            nreg_level(t, m, l + 1, b)[(long)(y >> 1) * (r >> 1) + (x >> 1)] = 0.25f * (((v + src[e + 1]) + src[e + r]) + src[e + r + 1]);
+    }
+    sx = la_block_sum_256_f64(sx, red);
+    sy = la_block_sum_256_f64(sy, red);
+    if (threadIdx.x == 0) {
+        double* p = t.part + nreg_part(t, m, l, b) + 2 * chunk;
+        p[0] = sx; p[1] = sy;
+    }
+}
+
+__global__ __launch_bounds__(64) void la_nreg_finish_kernel(NregTab t, double scale, double* __restrict__ reg, long reg_stride) {
+    const int b = blockIdx.x;
+    double total = 0.0;
+    for (int m = 0; m < t.nmaps; ++m)
+        for (int l = 0; l < t.nlev[m]; ++l) {
+            const int chunks = nreg_chunks(t.r[m], l);
+            const double* p = t.part + nreg_part(t, m, l, b);
+            double ax = 0.0, ay = 0.0;
+            for (int i = threadIdx.x; i < chunks; i += 64) { ax += p[2 * i]; ay += p[2 * i + 1]; }
+            ax = la_wave_sum(ax); ay = la_wave_sum(ay);
+            const double N = (double)(t.r[m] >> l) * (double)(t.r[m] >> l);
+            const double a = ax / N, c = ay / N;
+            total += a * a;
+            total += c * c;
+            if (threadIdx.x == 0) {
+                double* cf = t.coef + (((long)m * LA_NZ_MAXLEV + l) * t.B + b) * 2;
+                cf[0] = ldexp(2.0 * a / N, -2 * l); cf[1] = ldexp(2.0 * c / N, -2 * l);
+            }
+        }
+    if (threadIdx.x == 0) reg[(long)b * reg_stride] = scale * total;
+}
+
+__global__ __launch_bounds__(256) void la_nreg_gather_kernel(NregTab t, LaMapGrid g, float weight, int accumulate) {
+    int m, b, chunk;
+    la_map_locate(g, blockIdx.x, m, b, chunk);
+    const int r = t.r[m];
+    const long e = (long)chunk * 256 + threadIdx.x;
+    if (e >= (long)r * r) return;
+    const int y = (int)(e / r), x = (int)(e - (long)y * r);
+    double acc = 0.0;
+    for (int l = 0; l < t.nlev[m]; ++l) {
+        const int rl = r >> l, yl = y >> l, xl = x >> l;
+        const int xm = xl == 0 ? rl - 1 : xl - 1, xp = xl == rl - 1 ? 0 : xl + 1, ym = yl == 0 ? rl - 1 : yl - 1, yp = yl == rl - 1 ? 0 : yl + 1;
+        const float* src = nreg_level_in(t, m, l, b);
+        const double* cf = t.coef + (((long)m * LA_NZ_MAXLEV + l) * t.B + b) * 2;
+        acc += cf[0] * ((double)src[(long)yl * rl + xm] + (double)src[(long)yl * rl + xp]);
+        acc += cf[1] * ((double)src[(long)ym * rl + xl] + (double)src[(long)yp * rl + xl]);
+    }
+    float* out = t.g[m] + (long)b * r * r + e;
+    const float gv = weight * (float)acc;
+    *out = accumulate ? *out + gv : gv;
+}
+
+// workspace: the levels 1 .. of every map [B][r_l][r_l] float32 | the partial pairs [map][level][B][chunks][2] float64 | the coefficient
+// pairs [nmaps][LA_NZ_MAXLEV][B][2] float64
+static size_t nreg_layout(NregTab& t, const int* res, int nmaps, int B, char* base) {
+    LaCarver c; c.base = base;
+    long lev = 0, part = 0;
+    t.nmaps = nmaps; t.B = B;
+    for (int i = 0; i < nmaps; ++i) {
+        t.r[i] = res[i]; t.nlev[i] = nreg_levels(res[i]);
+        t.lev_off[i] = lev; t.part_off[i] = part;
+        for (int l = 0; l < t.nlev[i]; ++l) {
+            if (l >= 1) lev += (long)B * (res[i] >> l) * (res[i] >> l);
+            part += 2l * B * nreg_chunks(res[i], l);
+        }
+    }
+    t.levels = c.take((size_t)lev);
+    t.part = (double*)c.take(2 * (size_t)part);
+    t.coef = (double*)c.take(2 * (size_t)nmaps * LA_NZ_MAXLEV * B * 2);
+    return c.off;
+}
+
+extern "C" size_t la_noise_reg_scratch_bytes(const int* res, int nmaps, int B) {
+    if (la_map_table_check(res, nmaps, B, "noise_reg: nmaps must be 1 .. 32 and B 1 .. 65535")) return 0;
+    NregTab t;
+    return nreg_layout(t, res, nmaps, B, nullptr);
+}
+
+extern "C" int la_noise_reg_f32(const float* const* maps, const int* res, int nmaps, int B, double scale, float weight, float* const* gn, int accumulate,
+                                double* reg, long reg_stride, void* ws, size_t ws_bytes, hipStream_t stream) {
+    LA_CHECK_ARG(maps && reg && ws, "noise_reg: null pointer");
+    int rc = la_map_table_check(res, nmaps, B, "noise_reg: nmaps must be 1 .. 32 and B 1 .. 65535");
+    if (rc) return rc;
+    LA_CHECK_ARG(reg_stride >= 1, "noise_reg: reg_stride must be at least 1");
+    LA_CHECK_ARG((uintptr_t)reg % sizeof(double) == 0 && (uintptr_t)ws % sizeof(double) == 0, "noise_reg: pointer not aligned to its element type");
+    NregTab t;
+    if (ws_bytes < nreg_layout(t, res, nmaps, B, (char*)ws)) {
+        la_set_error("noise_reg: workspace too small (la_noise_reg_scratch_bytes)");
+        return LA_ERR_WORKSPACE;
+    }
+    int maxlev = 0;
+    for (int i = 0; i < nmaps; ++i) {
+        LA_CHECK_ARG(maps[i] && (!gn || gn[i]) && ((uintptr_t)maps[i] | (uintptr_t)(gn ? gn[i] : nullptr)) % sizeof(float) == 0, "noise_reg: null or misaligned map");
+        t.n[i] = maps[i]; t.g[i] = gn ? gn[i] : nullptr;
+        maxlev = t.nlev[i] > maxlev ? t.nlev[i] : maxlev;
+    }
+    LaMapGrid g;
+    int chunks[LA_NZ_MAXMAPS];
+    for (int l = 0; l < maxlev; ++l) {
+        for (int i = 0; i < nmaps; ++i) chunks[i] = l < t.nlev[i] ? nreg_chunks(res[i], l) : 0;
+        const long total = la_map_grid(g, chunks, nmaps, B);
+        LA_CHECK_ARG(total <= 0x7fffffffl, "noise_reg: tables too large");
+        hipLaunchKernelGGL(la_nreg_level_kernel, dim3((unsigned)total), dim3(256), 0, stream, t, g, l);
+        LA_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(la_nreg_finish_kernel, dim3(B), dim3(64), 0, stream, t, scale, reg, reg_stride);
+    LA_CHECK_LAUNCH();
+    if (gn) {
+        for (int i = 0; i < nmaps; ++i) chunks[i] = nreg_chunks(res[i], 0);
+        const long total = la_map_grid(g, chunks, nmaps, B);
+        hipLaunchKernelGGL(la_nreg_gather_kernel, dim3((unsigned)total), dim3(256), 0, stream, t, g, weight, accumulate);
+        LA_CHECK_LAUNCH();
+    }
+    return LA_OK;
+}
+
+// ---- the noise step tail.  Per (map, sample): Adam (la_adam_update, float32, the bias corrections of the 1-based `step` taken by the host
+// as in la_proj_step_tail_f32), then the published re-normalisation n -= mean(n); n *= rsqrt(mean(n^2)).  Maps reach 1024^2 elements, so
+// the moments span workgroups: a workgroup owns 1024 elements (thread t: t, t + 256, ...) of one (map, sample), and there are three launches
+//   1  update, and the chunk's sum                         -> part[workgroup]
+//   2  mean = (partials in chunk order) / N; the chunk's sum of (n - mean)^2   -> part2[workgroup]
+//   3  the same mean, q = (partials of 2) / N, n = (n - mean) / sqrt(q)   (q == 0: zeros)
+// all float64, thread i of a workgroup adding partials i, i + 256, ... before the workgroup sum: fixed by the shape alone.  Summing the
+// CENTRED squares means E[n^2] - mean^2 is never formed; a map of equal values has the exact mean (N is a power of two) and q = 0.
+#define LA_NT_CHUNK 1024
+struct NtailTab {
+    const float* gn[LA_NZ_MAXMAPS];
+    float *n[LA_NZ_MAXMAPS], *m[LA_NZ_MAXMAPS], *v[LA_NZ_MAXMAPS];
+    int r[LA_NZ_MAXMAPS];
+    double *part, *part2;
+};
+
+__device__ __forceinline__ double ntail_total(const double* part, const LaMapGrid& g, int m, int b, double* red) {
+    const double* p = part + g.start[m] + (long)b * g.chunks[m];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < g.chunks[m]; i += 256) s += p[i];
+    return la_block_sum_256_f64(s, red);
+}
+
+__global__ __launch_bounds__(256) void la_ntail_adam_kernel(NtailTab t, LaMapGrid g, float step_size, float bc2_sqrt, float b1, float b2, float eps) {
+    __shared__ double red[4];
+    int m, b, chunk;
+    la_map_locate(g, blockIdx.x, m, b, chunk);
+    const long N = (long)t.r[m] * t.r[m], base = (long)b * N;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < LA_NT_CHUNK / 256; ++k) {
+        const long e = (long)chunk * LA_NT_CHUNK + k * 256 + threadIdx.x;
+        if (e < N) {
+            const long i = base + e;
+            float pv = t.n[m][i], mv = t.m[m][i], vv = t.v[m][i];
+            la_adam_update(pv, mv, vv, t.gn[m][i], step_size, bc2_sqrt, b1, b2, eps);
+            t.n[m][i] = pv; t.m[m][i] = mv; t.v[m][i] = vv;
+            s += (double)pv;
+        }
+    }
+    s = la_block_sum_256_f64(s, red);
+    if (threadIdx.x == 0) t.part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void la_ntail_centre_kernel(NtailTab t, LaMapGrid g) {
+    __shared__ double red[4];
+    int m, b, chunk;
+    la_map_locate(g, blockIdx.x, m, b, chunk);
+    const long N = (long)t.r[m] * t.r[m], base = (long)b * N;
+    const double mean = ntail_total(t.part, g, m, b, red) / (double)N;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < LA_NT_CHUNK / 256; ++k) {
+        const long e = (long)chunk * LA_NT_CHUNK + k * 256 + threadIdx.x;
+        if (e < N) { const double dv = (double)t.n[m][base + e] - mean; s += dv * dv; }
+    }
+    s = la_block_sum_256_f64(s, red);
+    if (threadIdx.x == 0) t.part2[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void la_ntail_scale_kernel(NtailTab t, LaMapGrid g) {
+    __shared__ double red[4];
+    int m, b, chunk;
+    la_map_locate(g, blockIdx.x, m, b, chunk);
+    const long N = (long)t.r[m] * t.r[m], base = (long)b * N;
+    const double mean = ntail_total(t.part, g, m, b, red) / (double)N;
+    const double q = ntail_total(t.part2, g, m, b, red) / (double)N;
+    const double sc = q > 0.0 ? 1.0 / sqrt(q) : 0.0;
+#pragma unroll
+    for (int k = 0; k < LA_NT_CHUNK / 256; ++k) {
+        const long e = (long)chunk * LA_NT_CHUNK + k * 256 + threadIdx.x;
+        if (e < N) t.n[m][base + e] = (float)(((double)t.n[m][base + e] - mean) * sc);
+    }
+}
+
+static long ntail_grid(LaMapGrid& g, const int* res, int nmaps, int B) {
+    int chunks[LA_NZ_MAXMAPS];
+    for (int i = 0; i < nmaps; ++i) chunks[i] = (int)(((long)res[i] * res[i] + LA_NT_CHUNK - 1) / LA_NT_CHUNK);
+    return la_map_grid(g, chunks, nmaps, B);
+}
+
+extern "C" size_t la_proj_noise_tail_scratch_bytes(const int* res, int nmaps, int B) {
+    if (la_map_table_check(res, nmaps, B, "proj_noise_tail: nmaps must be 1 .. 32 and B 1 .. 65535")) return 0;
+    LaMapGrid g;
+    return 2 * la_align64((size_t)ntail_grid(g, res, nmaps, B) * sizeof(double));
+}
+
+extern "C" int la_proj_noise_tail_f32(const float* const* gn, float* const* n, float* const* m, float* const* v, const int* res, int nmaps, int B, int step,
+                                      float lr, float beta1, float beta2, float eps, void* ws, size_t ws_bytes, hipStream_t stream) {
+    LA_CHECK_ARG(gn && n && m && v && ws, "proj_noise_tail: null pointer");
+    int rc = la_map_table_check(res, nmaps, B, "proj_noise_tail: nmaps must be 1 .. 32 and B 1 .. 65535");
+    if (rc) return rc;
+    LA_CHECK_ARG(step >= 1, "proj_noise_tail: the Adam step is 1-based");
+    LA_CHECK_ARG((uintptr_t)ws % sizeof(double) == 0, "proj_noise_tail: workspace not aligned to 8 bytes");
+    LaMapGrid g;
+    const long total = ntail_grid(g, res, nmaps, B);
+    LA_CHECK_ARG(total <= 0x7fffffffl, "proj_noise_tail: tables too large");
+    const size_t half = la_align64((size_t)total * sizeof(double));
+    if (ws_bytes < 2 * half) {
+        la_set_error("proj_noise_tail: workspace too small (la_proj_noise_tail_scratch_bytes)");
+        return LA_ERR_WORKSPACE;
+    }
+    NtailTab t;
+    for (int i = 0; i < nmaps; ++i) {
+        LA_CHECK_ARG(gn[i] && n[i] && m[i] && v[i] && ((uintptr_t)gn[i] | (uintptr_t)n[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) % sizeof(float) == 0,
+                     "proj_noise_tail: null or misaligned map");
+        t.gn[i] = gn[i]; t.n[i] = n[i]; t.m[i] = m[i]; t.v[i] = v[i]; t.r[i] = res[i];
+    }
+    t.part = (double*)ws; t.part2 = (double*)((char*)ws + half);
+    const float step_size = lr / (1.f - powf(beta1, (float)step)), bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(la_ntail_adam_kernel, dim3((unsigned)total), dim3(256), 0, stream, t, g, step_size, bc2s, beta1, beta2, eps);
+    LA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(la_ntail_centre_kernel, dim3((unsigned)total), dim3(256), 0, stream, t, g);
+    LA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(la_ntail_scale_kernel, dim3((unsigned)total), dim3(256), 0, stream, t, g);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }

@@ -681,22 +681,52 @@ static int bwd_style_finish(la_synth* h, const SynthPlan& P, int, int B, hipStre
     return la_style_backward_all(fin, B, stream);
 }
 
-extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hipStream_t stream) {
-    LA_CHECK_ARG(h && g_img && dws, "synth_backward: null pointer");
-    LA_CHECK_ARG(h->plan.pass.B >= 1, "synth_backward: no forward pass to differentiate");
+// noise gradient of conv layer ci from the gz its seam (a kernel, or the epilogue of the contraction above) has just left in `gz`: what is
+// stored there carries the demodulation coefficient, gn[b][p] = strength * sum_c gz[b][c][p] / d[b][c] (la_noise.hip).  A launch of its
+// own between the seam and the layer's backward contraction, which reads the same buffer; a layer without noise gets zeros.
+static int bwd_noise_grad(la_synth* h, int ci, const float* gz, float* const* gnoises, int B, hipStream_t stream) {
+    if (!gnoises || !gnoises[ci]) return LA_OK;
+    const ConvLayer& L = h->conv[ci];
+    const long HW = (long)L.res * L.res;
+    if (L.noise_strength == 0.f) {
+        LA_HIP(hipMemsetAsync(gnoises[ci], 0, (size_t)B * HW * sizeof(float), stream));
+        return LA_OK;
+    }
+    return la_noise_grad_f32(gz, h->d_all + L.d_off, h->Dt, B, L.cout, HW, L.noise_strength, gnoises[ci], stream);
+}
+
+static int synth_backward(la_synth* h, const float* g_img, float* dws, float* const* gnoises, hipStream_t stream) {
     const SynthPlan& P = h->plan;
     const int B = P.pass.B;
     h->g_top = g_img;
     int rc;
     for (int k = h->nblocks - 1; k >= 0; --k) {
         if (P.conv[2 * k].seam == SEAM_KERNEL && (rc = bwd_conv1_seam(h, P, k, B, stream))) return rc;
+        if ((rc = bwd_noise_grad(h, 2 * k, h->G0, gnoises, B, stream))) return rc;
         if ((rc = bwd_conv1_data(h, P, k, B, stream))) return rc;
         if (k == 0) break;
         if (P.conv[2 * k - 1].seam == SEAM_KERNEL && (rc = bwd_conv0_seam(h, P, k, B, stream))) return rc;
+        if ((rc = bwd_noise_grad(h, 2 * k - 1, h->G1, gnoises, B, stream))) return rc;
         // (before the up layer's backward contraction: its epilogue may apply the block below's ToRGB backward)
         if (P.blk[k].down_fir && (rc = bwd_image_grad(h, P, k, B, stream))) return rc;
         if ((rc = bwd_up_data(h, P, k, B, stream))) return rc;
     }
     if ((rc = bwd_style_finish(h, P, 0, B, stream))) return rc;
     return la_affine_backward(h->st, h->ds_all, B, h->wdim, dws, h->num_ws, h->aff_part, stream);
+}
+
+extern "C" int la_synth_backward(la_synth* h, const float* g_img, float* dws, hipStream_t stream) {
+    LA_CHECK_ARG(h && g_img && dws, "synth_backward: null pointer");
+    LA_CHECK_ARG(h->plan.pass.B >= 1, "synth_backward: no forward pass to differentiate");
+    return synth_backward(h, g_img, dws, nullptr, stream);
+}
+
+extern "C" int la_synth_backward_noise(la_synth* h, const float* g_img, float* dws, float* const* gnoises, hipStream_t stream) {
+    LA_CHECK_ARG(h && g_img && dws, "synth_backward_noise: null pointer");
+    LA_CHECK_ARG(h->plan.pass.B >= 1, "synth_backward_noise: no forward pass to differentiate");
+    // a windowed pass leaves rows of the gradient buffers stale: the channel reduction reads whole planes
+    bool windowed = h->win.row_hi > 0 || h->win.col_hi > 0;
+    for (int ci = 0; ci < h->nconv; ++ci) windowed = windowed || h->plan.conv[ci].fwd.row_hi > 0 || h->plan.conv[ci].fwd.col_hi > 0 || h->plan.conv[ci].win;
+    LA_CHECK_ARG(!gnoises || !windowed, "synth_backward_noise: noise gradients need whole planes; clear the row / column window (and run the forward pass again)");
+    return synth_backward(h, g_img, dws, gnoises, stream);
 }

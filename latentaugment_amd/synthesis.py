@@ -204,15 +204,38 @@ class SynthesisEngine:
         self._last_noises = noises   # keep alive until the matching backward
         return img
 
-    def backward(self, g_img):
-        """d(loss)/d(img) [B,C,R,R] -> d(loss)/d(ws) [B,num_ws,w_dim] for the last forward."""
+    def backward(self, g_img, noise_grads=None):
+        """d(loss)/d(img) [B,C,R,R] -> d(loss)/d(ws) [B,num_ws,w_dim] for the last forward.  With `noise_grads` the same pass also
+        delivers d(loss)/d(noise) per layer (la_synth_backward_noise) and the result is (dws, list): `True` allocates a [B,res,res]
+        tensor for every layer with noise_strength != 0 (None elsewhere); a list per layer names the layers wanted -- a tensor is
+        written in place, True is allocated, None / False is skipped (a wanted layer without noise gets zeros)."""
         g_img = g_img.contiguous().float()
         B = g_img.shape[0]
         dws = torch.empty([B, self.num_ws, self.w_dim], device=self.device, dtype=torch.float32)
+        if noise_grads is None:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.la_synth_backward(self._h, _lib.ptr(g_img), _lib.ptr(dws), _lib.stream_ptr()),
+                           'la_synth_backward')
+            return dws
+        if noise_grads is True:
+            noise_grads = [ns != 0.0 for ns in self.noise_strengths]
+        if len(noise_grads) != self.num_layers:
+            raise _lib.LatentAugHipError(f'backward: noise_grads must have one entry per layer ({self.num_layers}); got {len(noise_grads)}')
+        gns = []
+        for t, r in zip(noise_grads, self.layer_resolutions):
+            if t is None or t is False:
+                gns.append(None)
+            elif t is True:
+                gns.append(torch.empty([B, r, r], device=self.device, dtype=torch.float32))
+            else:
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, r, r)):
+                    raise _lib.LatentAugHipError(f'backward: a noise gradient must be a contiguous float32 device tensor [{B}, {r}, {r}]')
+                gns.append(t)
+        arr = (C.c_void_p * len(gns))(*[t.data_ptr() if t is not None else None for t in gns])
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.la_synth_backward(self._h, _lib.ptr(g_img), _lib.ptr(dws), _lib.stream_ptr()),
-                       'la_synth_backward')
-        return dws
+            _lib.check(self._lib.la_synth_backward_noise(self._h, _lib.ptr(g_img), _lib.ptr(dws), arr, _lib.stream_ptr()),
+                       'la_synth_backward_noise')
+        return dws, gns
 
     # debugging / test taps -------------------------------------------------------------------
     def _view(self, p, shape):
@@ -254,8 +277,31 @@ class _SynthesisFn(torch.autograd.Function):
         return dws, None, None, None
 
 
+class _SynthesisNoiseFn(torch.autograd.Function):
+    """The same call with the explicit noise tensors as inputs of the function, so that those which require grad get theirs."""
+    @staticmethod
+    def forward(ctx, ws, engine, noise_mode, *noises):
+        ctx.engine = engine
+        ctx.ws_shape = ws.shape
+        ctx.want = [t is not None and t.requires_grad for t in noises]
+        return engine.forward(ws, noise_mode=noise_mode, noises=[None if t is None else t.detach() for t in noises])
+
+    @staticmethod
+    def backward(ctx, g_img):
+        dws, gns = ctx.engine.backward(g_img, noise_grads=ctx.want)
+        shape = ctx.ws_shape
+        if len(shape) == 2:
+            dws = dws.sum(dim=1)
+        elif shape[1] == 1:
+            dws = dws.sum(dim=1, keepdim=True)
+        return (dws, None, None) + tuple(gns)
+
+
 def synthesis(engine, ws, noise_mode='const', noises=None):
-    """Differentiable (w.r.t. ws) call of the HIP synthesis engine, autograd-compatible."""
+    """Differentiable call of the HIP synthesis engine, autograd-compatible: with respect to ws, and with respect to the entries of
+    `noises` (noise_mode 'random') that require grad."""
+    if noises is not None and any(t is not None and t.requires_grad for t in noises):
+        return _SynthesisNoiseFn.apply(ws, engine, noise_mode, *noises)
     return _SynthesisFn.apply(ws, engine, noise_mode, noises)
 
 

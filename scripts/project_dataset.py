@@ -5,9 +5,12 @@
       --out-zip INTERIM/DS/DSNAME-expinv_00001.zip --modalities MR_nonrigid_CT,MR_MR_T2 \\
       (--vgg16-pt MODELS/vgg16.pt | --lpips-vgg MODELS/vgg16.pth --lpips-lin MODELS/lpips_vgg.pth) \\
       [--split train] [--steps 1000] [--space w|w+] [--w-pix 0.0] [--batch 8] [--lpips-res 256] [--precision f16x2] [--seed 0] [--gpu 0]
+      [--optimize-noise] [--regularize-noise-weight 1e5]
 
 The generator is read from the pickle without running its embedded source (formats.load_network_pkl); the perceptual net is a LOCAL
 copy of NVIDIA's TorchScript vgg16.pt or the two state dicts of the reference's LPIPS('vgg').  One line of progress per batch.
+--optimize-noise optimises the per-layer noise maps beside the latent (regularised, re-normalised every step) and discards them: the
+zip holds the latents alone, as without it.
 """
 import argparse
 import os
@@ -39,6 +42,8 @@ def main():
     ap.add_argument('--precision', default='f16x2')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--optimize-noise', action='store_true', help='optimise the per-layer noise maps beside the latent (then discard them)')
+    ap.add_argument('--regularize-noise-weight', type=float, default=1e5)
     args = ap.parse_args()
     if (args.vgg16_pt is None) == (args.lpips_vgg is None or args.lpips_lin is None):
         ap.error('give either --vgg16-pt, or both --lpips-vgg and --lpips-lin')
@@ -54,7 +59,8 @@ def main():
         net = lpips_reference_net(args.lpips_vgg, args.lpips_lin)
     proj = Projector(G, net, dev, args.batch, precision=args.precision, lpips_res=lpips_res)
     finals = project_dataset(args.img_zip, args.out_zip, args.split, proj, mods, num_steps=args.steps, space=args.space, seed=args.seed,
-                             w_pix=args.w_pix, log=lambda s: print(s, flush=True))
+                             w_pix=args.w_pix, optimize_noise=args.optimize_noise, regularize_noise_weight=args.regularize_noise_weight,
+                             log=lambda s: print(s, flush=True))
     print(f'wrote {len(finals)} codes [{proj.num_ws}, {proj.w_dim}] to {args.out_zip}; final perceptual distance: mean {finals[:, 0].mean():.4g}, '
           f'worst {finals[:, 0].max():.4g}')
 
