@@ -18,6 +18,12 @@
  *     `workspace_bytes` passed, where that is smaller and still accepted).  Outputs are written in full and nowhere else.
  *     An engine whose create clears its workspace (la_synth_create) meets the first half that way; the others re-arm what a pass
  *     accumulates into before the pass does ("Workspace contract"; tests/test_hip_workspace_guard.py).
+ *   - History contract (engine and loop handles: la_synth, la_disc, la_feat, la_latent_opt).  The results of a pass depend on its inputs and
+ *     on the handle's CURRENT settings only, bit for bit: not on the batch sizes, windows, precisions, schedules, traces, captured graphs or
+ *     values of earlier passes on the handle.  A backward pass uses the settings its forward pass ran with (precision, window, ToRGB
+ *     schedule): a setter takes effect at the next forward pass.  A refused call (LA_ERR_ARG before any launch) changes nothing.  A setter
+ *     of an engine attached to a loop handle takes effect at the loop's next run: a captured step of the old settings is never replayed.
+ *     ("Handle history"; tests/test_hip_history.py.)
  *   - all work is enqueued on `stream` (a hipStream_t, passed as void* from foreign code); no host<->device sync.
  *   - return 0 on success, negative on failure (LA_ERR_*); la_last_error() gives the thread's last message.
  *     This replaces the TORCH_CHECKs of the reference bindings (bias_act.cpp:35-51, upfirdn2d.cpp:19-40).
@@ -392,7 +398,9 @@ int la_synth_create(int img_resolution, int img_channels, int w_dim, const int* 
                     const float* fir_host, int fir_h, int fir_w, int max_batch, void* workspace, size_t workspace_bytes,
                     la_stream_t stream, la_synth** out);
 void la_synth_destroy(la_synth* h);
-/* contraction precision of every modulated conv of the engine (LA_PREC_*, default LA_PREC_F32) */
+/* contraction precision of every modulated conv of the engine (LA_PREC_*, default LA_PREC_F32).  History contract: takes effect at the
+ * next la_synth_forward; a backward pass runs in the precision, window and ToRGB schedule of the forward pass it differentiates.  (Noise
+ * gradients are the exception on the safe side: la_synth_backward_noise refuses them while a window is set, whatever the forward ran with.) */
 int la_synth_set_precision(la_synth* h, int precision);
 /* Kept for ABI compatibility, no effect since round 4 (rounds 2-3: 0 = fp16 operand scale of the forward contractions from the a-priori
  * bound conv_clamp * max|style|, 1 = from data maxima).  Every fp16 operand scale is now derived from the data of each pass by the
@@ -531,6 +539,8 @@ int la_disc_create(int img_resolution, int img_channels, const int* channels, fl
                    int nparams, const float* fir_host, int mbstd_group_size, int max_batch, void* workspace,
                    size_t workspace_bytes, la_stream_t stream, la_disc** out);
 void la_disc_destroy(la_disc* h);
+/* History contract: takes effect at the next la_disc_forward; la_disc_backward runs in the precision of the forward pass it differentiates,
+ * so forward(P1), set_precision(P2), backward gives the bits of forward(P1), backward. */
 int la_disc_set_precision(la_disc* h, int precision);
 int la_disc_forward(la_disc* h, const float* img, int B, la_stream_t stream);
 int la_disc_loss(la_disc* h, float w_disc, int norm_batch, float* loss_out, la_stream_t stream);
@@ -575,6 +585,8 @@ int la_feat_create(int nops, const la_feat_op* ops, const float* const* params, 
                    int max_batch, void* workspace, size_t workspace_bytes, la_stream_t stream, la_feat** out);
 void la_feat_destroy(la_feat* h);
 int la_feat_num_features(const la_feat* h);
+/* History contract: takes effect at the next la_feat_forward / la_feat_pair_distance; la_feat_backward runs in the precision of the forward
+ * pass it differentiates. */
 int la_feat_set_precision(la_feat* h, int precision);
 int la_feat_forward(la_feat* h, const float* x, int N, float* feat_out, la_stream_t stream);
 int la_feat_backward(la_feat* h, const float* gfeat, float* gx, la_stream_t stream);
@@ -708,7 +720,9 @@ int la_latent_opt_set_time_trace(la_latent_opt* h, int enable);
 int la_latent_opt_get_times(la_latent_opt* h, float* ms);
 /* The banks handed to la_latent_opt_create / _set_lpips (register_buffer('W'/'X'/'fea_*'), util_latent_aug.py:137-171) must stay
  * IMMUTABLE for the life of the handle: their column sums are reduced once (both criterion modes) and every later gradient uses
- * them.  A caller that does rewrite bank contents in place calls this before the next la_latent_opt_run. */
+ * them.  A caller that does rewrite bank contents in place calls this before the next la_latent_opt_run: all three sets of column sums (W,
+ * the pixel crops, the perceptual features) are reduced again by that run, and the handle then equals, bit for bit, one created on the new
+ * banks (History contract; a captured step reads the sums from the same buffers and stays valid). */
 int la_latent_opt_invalidate_banks(la_latent_opt* h);
 /* w0 [B][w_dim] (W+ handle: [B][num_ws][w_dim]) -> img_out [B][C][R][R], w_aug_out [B][num_ws][w_dim]; losses_out (may be NULL) [steps][4] =
  * weighted {latent, pix, disc, lpips} per step. */

@@ -44,6 +44,11 @@ void la_set_error(const char* msg);
 enum { LA_PC_CONV_HALO = 0, LA_PC_CONV_FLAT, LA_PC_CONV_SPLITK, LA_PC_CONV_F32, LA_PC_PRESPLIT, LA_PC_FIR, LA_PC_SEAM, LA_PC_TORGB,
        LA_PC_BANK, LA_PC_NCLASS };
 bool la_prof_enabled();      // profiler active: callers keep their launches eager
+// Settings generation of an engine handle: raised by every setter that changes what the engine's following passes launch (precision,
+// ToRGB schedule).  The latent loop records the three at capture and drops a captured step whose engines have been set since.
+int la_synth_settings_gen(const la_synth* h);
+int la_disc_settings_gen(const la_disc* h);
+int la_feat_settings_gen(const la_feat* h);
 // Development switches -- kernel-variant selectors for in-process A/B measurements (la_dev_knob_set) and LA_* environment switches --
 // exist in the DEVELOPMENT build only (make dev: -DLA_DEV, liblatentaug_hip_dev.so, used by scripts/).  The product library has
 // neither: every knob reads 0, no LA_* variable is looked at, la_dev_knob_set is not exported.

@@ -48,6 +48,8 @@ struct la_disc {
     float* xs_fwd;          // [maxB] constant fp16 operand scale of every FORWARD contraction input: with a clamp all of them are bounded
                             // (clamped layer outputs, residual sums <= 2 * clamp / sqrt(2), FIR outputs <= their input, |std| <= max|x|)
     int precision, lastB, mbstd_group;
+    int settings_gen;       // la_disc_settings_gen: raised when the precision changes
+    int pass_precision;     // precision of the last forward pass: what its backward pass runs in (a setter takes effect at the next forward)
 };
 
 static inline int dz_xhalf(int res) { return (res / 2 + 1 + 3) & ~3; }      // column-planar rows of a (res+1)-wide intermediate: odd columns start here
@@ -196,9 +198,11 @@ extern "C" int la_disc_create(int img_resolution, int img_channels, const int* c
 extern "C" void la_disc_destroy(la_disc* h) { free(h); }
 extern "C" int la_disc_set_precision(la_disc* h, int precision) {
     LA_CHECK_ARG(h && precision >= 0 && precision <= 3, "disc_set_precision: precision must be 0..3");
+    if (precision != h->precision) ++h->settings_gen;
     h->precision = precision;
     return LA_OK;
 }
+int la_disc_settings_gen(const la_disc* h) { return h->settings_gen; }
 extern "C" const float* la_disc_logits(const la_disc* h) { return h ? h->logits : nullptr; }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -445,9 +449,10 @@ __global__ void la_disc_loss_kernel(const float* __restrict__ logits, float* __r
 static void start_args(LaConvArgs& a, const la_disc* h, const DConv& L, bool backward, int B, const float* xs_rows) {
     la_conv_args_init(a);
     la_conv_weights_select(a, L, backward);
-    a.precision = h->precision; a.ws = h->cws; a.ws_bytes = h->cws_bytes; a.B = B;
+    const int precision = backward ? h->pass_precision : h->precision;
+    a.precision = precision; a.ws = h->cws; a.ws_bytes = h->cws_bytes; a.B = B;
     if (xs_rows) { a.acc_scale_x = xs_rows; a.acc_scale_fan = LA_XS_FAN; }
-    else if (!backward && h->precision == LA_PREC_F16X2 && h->clamp > 0.f && h->maxB <= 256) { a.acc_scale_x = h->xs_fwd; a.acc_scale_fan = LA_XS_FAN; }
+    else if (!backward && precision == LA_PREC_F16X2 && h->clamp > 0.f && h->maxB <= 256) { a.acc_scale_x = h->xs_fwd; a.acc_scale_fan = LA_XS_FAN; }
 }
 // forward epilogue of a Conv2dLayer: bias, activation (lrelu slope 0.2), gain, clamp
 static LaLayerEpi d_epi(const DConv& L, int act, float gain, float clamp) { return LaLayerEpi{nullptr, 0, nullptr, 0, 0.f, L.bias, act, 0.2f, gain, clamp}; }
@@ -523,7 +528,7 @@ extern "C" int la_disc_forward(la_disc* h, const float* img, int B, hipStream_t 
     if ((rc = conv_same(a, h->econv, false, 4, stream))) return rc;
     if ((rc = la_fc_f32(h->yc, h->fc_w, h->fc_b, h->fc, B, h->C4 * 16, h->C4, 1.f, LA_ACT_LRELU, 0.2f, sq2, stream))) return rc;
     if ((rc = la_fc_f32(h->fc, h->out_w, h->out_b, h->logits, B, h->C4, 1, 1.f, LA_ACT_LINEAR, 0.f, 1.f, stream))) return rc;
-    h->lastB = B;
+    h->lastB = B; h->pass_precision = h->precision;
     return LA_OK;
 }
 
@@ -573,11 +578,11 @@ extern "C" int la_disc_backward(la_disc* h, const float* dlogits, float* g_img, 
     // sqrt(1/2) of the skip branch -- inside their pre-split copy (LaConvArgs::in_mask_y / in_gain); the FIR adjoint behind the
     // transposed conv applies act'(y0) and lowers the rows of conv0's backward contraction.  (Round 3: three sweeps of
     // la_act_grad_pmax_kernel + three scale reductions per block.)  The last block's gradient comes from MinibatchStd: sweeps as before.
-    const bool fuse = h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_DISC_FUSE");
+    const bool fuse = h->pass_precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_DISC_FUSE");
     if (fuse) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_b), (int)LA_XS_INIT, (size_t)2 * h->nblocks * h->maxB * LA_XS_FAN, stream));
     auto rows_g = [&](int k) { return h->xs_b + (size_t)(2 * k) * h->maxB * LA_XS_FAN; };
     auto rows_c0 = [&](int k) { return h->xs_b + (size_t)(2 * k + 1) * h->maxB * LA_XS_FAN; };
-    auto zx_of = [&](int res) { return (fuse && h->precision != LA_PREC_F32 && res % 4 == 0) ? dz_xhalf(res) : 0; };
+    auto zx_of = [&](int res) { return (fuse && h->pass_precision != LA_PREC_F32 && res % 4 == 0) ? dz_xhalf(res) : 0; };
     for (int k = h->nblocks - 1; k >= 0; --k) {
         DBlock& b = h->blk[k];
         const int res = b.res, hq = res / 2;

@@ -41,6 +41,8 @@ struct la_feat {
     void* cws; size_t cws_bytes;
     const float* x_in;   // input of the last forward
     int lastN;
+    int settings_gen;    // la_feat_settings_gen: raised when the precision changes
+    int pass_precision;  // precision of the last forward: what its backward runs in (a setter takes effect at the next forward)
     int detector;        // the list ends in an FC op: forward only, F = the last FC's outputs
     void* fcws; size_t fcws_bytes;      // la_fc_bias_act_f32's workspace (detector lists only)
 };
@@ -170,9 +172,11 @@ extern "C" void la_feat_destroy(la_feat* h) { free(h); }
 extern "C" int la_feat_num_features(const la_feat* h) { return h ? h->F : 0; }
 extern "C" int la_feat_set_precision(la_feat* h, int precision) {
     LA_CHECK_ARG(h && precision >= 0 && precision <= 3, "feat_set_precision: precision must be 0..3");
+    if (precision != h->precision) ++h->settings_gen;
     h->precision = precision;
     return LA_OK;
 }
+int la_feat_settings_gen(const la_feat* h) { return h->settings_gen; }
 
 // ------------------------------------------------------------------------------------------------------------
 __global__ void la_pool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int R, long planes, int is_max) {
@@ -333,7 +337,7 @@ static inline int tap_lanes(int HW) { int pl = 1; while (pl * 2 <= HW && pl < 64
 static void f_conv(LaConvArgs& a, const la_feat* h, const FOp& o, bool backward, int N) {
     la_conv_args_init(a);
     la_conv_weights_select(a, o.cw, backward);
-    a.precision = h->precision; a.ws = h->cws; a.ws_bytes = h->cws_bytes; a.B = N;
+    a.precision = backward ? h->pass_precision : h->precision; a.ws = h->cws; a.ws_bytes = h->cws_bytes; a.B = N;
     la_conv_geom_same(a, o.res_in, 3, backward);
     if (backward) a.epi = LA_EPI_BWD;
     else la_conv_set_epi(a, LaLayerEpi{nullptr, 0, nullptr, 0, 0.f, o.bias, LA_ACT_RELU, 0.f, 1.f, -1.f});
@@ -347,7 +351,7 @@ static void f_relu_seam(LaConvArgs& a, const la_feat* h, const float* mask_y, fl
 }
 
 // fp16 x2 mode: operand scales as slot rows lowered by the producing kernels; decided once per call (dev knob LA_NO_FEAT_SLOTS: the round-3 passes)
-static bool f_slots(const la_feat* h) { return h->precision == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS"); }
+static bool f_slots(const la_feat* h, bool backward) { return (backward ? h->pass_precision : h->precision) == LA_PREC_F16X2 && !la_dev_env("LA_NO_FEAT_SLOTS"); }
 static float* f_rows(const la_feat* h, float* base, int op) { return base + (size_t)op * h->maxN * LA_XS_FAN; }
 
 // The trunk on N rows of x: resets the forward slot rows, walks the op list with the conv, pool and fc launches and hands every tap op, with
@@ -358,7 +362,7 @@ template <class Tap>
 static int f_trunk(la_feat* h, const float* x, int N, float* fc_out, hipStream_t stream, Tap tap) {
     const float* cur = x;
     int rc;
-    const bool slots = f_slots(h);
+    const bool slots = f_slots(h, false);
     if (slots) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_f), (int)LA_XS_INIT, (size_t)h->nops * h->maxN * LA_XS_FAN, stream));
     bool first_conv = true;
     for (int k = 0; k < h->nops; ++k) {
@@ -402,7 +406,7 @@ extern "C" int la_feat_forward(la_feat* h, const float* x, int N, float* feat_ou
         hipLaunchKernelGGL(la_tap_fwd_kernel, dim3(la_cdiv(HWo, pl), N), dim3(256), 0, stream, cur, o.lin, feat_out, o.cout, HWo, (long)h->F, o.feat_off, pl);
     });
     if (rc) return rc;
-    h->x_in = x; h->lastN = N;
+    h->x_in = x; h->lastN = N; h->pass_precision = h->precision;
     return LA_OK;
 }
 
@@ -419,7 +423,7 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
     // last -- the tap behind conv k (la_tap_bwd_kernel, mask fused), or the backward contraction of conv k+1 when it follows directly
     // (its epilogue applies the mask of its xin = y_k, LaConvArgs::seam) -- instead of an activation-backward sweep with plane maxima
     // and a scale-reduction launch per conv.  `masked`: g already carries op k's mask and its slot rows are final.
-    const bool slots = f_slots(h);
+    const bool slots = f_slots(h, true);
     if (slots) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->xs_b), (int)LA_XS_INIT, (size_t)h->nops * h->maxN * LA_XS_FAN, stream));
     auto rows = [&](float* base, int op) { return f_rows(h, base, op); };
     bool masked = false;

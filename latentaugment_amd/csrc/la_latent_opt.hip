@@ -57,6 +57,7 @@ struct la_latent_opt {
         LaGraphPart part[4];
         int count;              // 0: none; 1: the whole step, in part[0]; 4: the parts A, P, D, Z (overlap mode 1)
         int B, windowed;        // batch size of the capture, and whether its synthesis passes were windowed
+        int gen[3];             // settings generations of the attached engines (synthesis, discriminator, features) at the capture
         int mode;               // 0 eager, 1 replay a captured step (default; la_latent_opt_set_graph)
         int refused;            // 1: stream capture / instantiation of the step failed once; the handle launches eagerly since
         hipStream_t cap_stream; // capture needs a non-default stream; the replay goes to the caller's stream
@@ -529,21 +530,31 @@ static bool capture(la_latent_opt* h, const LaRun& r, const LaPlan& plan, int k)
     return ok && hipGraphInstantiate(&G.part[k].exec, G.part[k].graph, nullptr, nullptr, 0) == hipSuccess;
 }
 
-// The steps of a run.  A replaying run whose graphs do not fit (none yet, another batch size or window flag) launches step 1 eagerly -- module
+// The steps of a run.  A replaying run whose graphs do not fit (none yet, another batch size or window flag, an attached engine set to
+// another precision or ToRGB schedule since) launches step 1 eagerly -- module
 // loading, per-device attribute opt-ins and every other first-use effect happen outside the capture -- captures the same sequencer and
 // replays it from step 2 on.  If capture is refused the handle falls back to eager launches of the same kernels.
+// the settings generations of the engines a step of this run launches (an engine the run does not use: 0)
+static void engine_gens(const la_latent_opt* h, const LaRun& r, int gen[3]) {
+    gen[0] = la_synth_settings_gen(h->g);
+    gen[1] = r.use_disc ? la_disc_settings_gen(h->d) : 0;
+    gen[2] = r.use_lpips ? la_feat_settings_gen(h->lp.f) : 0;
+}
+
 static int run_steps(la_latent_opt* h, const LaRun& r, const LaPlan& plan, bool want_losses, hipStream_t stream) {
     const la_opt_config& c = h->cfg; const auto& t = h->tr;
     auto& G = h->graphs;
     int first = 1;
-    if (plan.replay && (G.count != plan.parts || G.B != r.B || G.windowed != (int)r.windowed)) {
+    int gen[3]; engine_gens(h, r, gen);
+    const bool engines_set = gen[0] != G.gen[0] || gen[1] != G.gen[1] || gen[2] != G.gen[2];      // a setter of an attached engine since the capture
+    if (plan.replay && (G.count != plan.parts || G.B != r.B || G.windowed != (int)r.windowed || engines_set)) {
         drop_graph(h);
         LA_RC(run_step(h, r, nullptr, plan.side, false, nullptr, nullptr, stream));
         first = 2;
         bool ok = c.steps >= 2;
         if (ok && !G.cap_stream) ok = hipStreamCreateWithFlags(&G.cap_stream, hipStreamNonBlocking) == hipSuccess;
         for (int k = 0; k < plan.parts && ok; ++k) ok = capture(h, r, plan, k);
-        if (ok) { G.count = plan.parts; G.B = r.B; G.windowed = (int)r.windowed; }
+        if (ok) { G.count = plan.parts; G.B = r.B; G.windowed = (int)r.windowed; memcpy(G.gen, gen, sizeof(gen)); }
         else { drop_graph(h); (void)hipGetLastError(); if (c.steps >= 2) { G.mode = 0; G.refused = 1; } }
     }
     const size_t img_floats = (size_t)r.B * h->imgc * h->R * h->R;

@@ -77,6 +77,7 @@ struct la_synth {
     const float* g_top; // image gradient the running backward pass was handed (top block)
     float up_mult;      // la_modconv_up2_bwd_xs_mult of the filter
     int rgb_per_block;  // la_synth_set_torgb_schedule: a ToRGB launch behind every block's conv1 (else deferred, see plan_pass)
+    int settings_gen;   // la_synth_settings_gen: raised when precision or ToRGB schedule change
 };
 
 enum { SEAM_KERNEL = LA_SYNTH_SEAM_KERNEL, SEAM_FUSED = LA_SYNTH_SEAM_FUSED, PMAX_NONE = LA_SYNTH_PMAX_NONE, PMAX_1, PMAX_2, PMAX_3 };
@@ -400,9 +401,11 @@ extern "C" void la_synth_destroy(la_synth* h) { free(h); }
 // contraction arithmetic of every modulated conv of the engine: 0 fp32 MFMA, 1 split-bf16 x3 (fp32-class), 2 split-bf16 x2
 extern "C" int la_synth_set_precision(la_synth* h, int precision) {
     LA_CHECK_ARG(h && precision >= 0 && precision <= 3, "synth_set_precision: precision must be 0..3");
+    if (precision != h->precision) ++h->settings_gen;
     h->precision = precision;
     return LA_OK;
 }
+int la_synth_settings_gen(const la_synth* h) { return h->settings_gen; }
 extern "C" int la_synth_get_precision(const la_synth* h) { return h ? h->precision : -1; }
 // Kept for ABI compatibility (rounds 1-3 selected between an a-priori bound and data maxima for the fp16 operand scale of the forward
 // contractions): since round 4 every forward scale is derived from the data of the pass by the kernel that produces the tensor
@@ -418,6 +421,7 @@ extern "C" int la_synth_set_operand_scale(la_synth* h, int from_data) {
 // what tests/test_hip_image_chain.py holds the deferred one against.
 extern "C" int la_synth_set_torgb_schedule(la_synth* h, int per_block) {
     LA_CHECK_ARG(h && (per_block == 0 || per_block == 1), "synth_set_torgb_schedule: 0 or 1");
+    if (per_block != h->rgb_per_block) ++h->settings_gen;
     h->rgb_per_block = per_block;
     return LA_OK;
 }
