@@ -505,18 +505,35 @@ class FeatureEngine:
     @classmethod
     def from_net(cls, net, device, in_res, max_batch, precision='f32'):
         """Engine for a described net (`lpips_reference_net`, a candidate of `vgg16_from_torchscript`): its op list, with its input
-        affine kept as `engine.pre_scale` / `engine.pre_shift`."""
+        affine kept as `engine.pre_scale` / `engine.pre_shift` (and, of a TorchScript candidate, `engine.lin_is_sqrt`)."""
         eng = cls(net.ops, device, in_res, max_batch, precision=precision)
         eng.pre_scale, eng.pre_shift = tuple(float(v) for v in net.pre_scale), tuple(float(v) for v in net.pre_shift)
+        if getattr(net, 'source', None) is not None:
+            eng.lin_is_sqrt = net.lin_is_sqrt
         return eng
 
     @classmethod
     def from_torchscript(cls, src, device, in_res, max_batch, precision='f32', probe_seed=0, rtol=2e-3):
-        """Engine for a local TorchScript `vgg16.pt` (reference: util_latent_aug.py:35-43, call :394-395).  Every candidate mapping of
-        `vgg16_from_torchscript` is checked ONCE, at load time, against the module's own
+        """Engine for a local TorchScript `vgg16.pt` (reference: util_latent_aug.py:35-43, call :394-395): the verified candidate of
+        `verified_torchscript_net`, with its input affine (`engine.pre_scale`, `engine.pre_shift`) and `engine.lin_is_sqrt`."""
+        c, eng = cls._verify_torchscript(src, device, in_res, max_batch, probe_seed, rtol)
+        if precision != 'f32' or max_batch != eng.max_batch:      # (otherwise the engine the probe ran on is the one asked for)
+            eng = cls(c.ops, device, in_res, max_batch=max_batch, precision=precision)
+        eng.pre_scale, eng.pre_shift, eng.lin_is_sqrt = c.pre_scale, c.pre_shift, c.lin_is_sqrt
+        return eng
+
+    @classmethod
+    def verified_torchscript_net(cls, src, device, in_res, probe_seed=0, rtol=2e-3):
+        """The `ScriptedFeatureNet` of a local TorchScript `vgg16.pt` that reproduces the module's own output (`.ops`, `.pre_scale`,
+        `.pre_shift`, `.lin_is_sqrt`): resolve once, then build as many engines from it as needed (`from_net`)."""
+        return cls._verify_torchscript(src, device, in_res, 2, probe_seed, rtol)[0]
+
+    @classmethod
+    def _verify_torchscript(cls, src, device, in_res, max_batch, probe_seed, rtol):
+        """Every candidate mapping of `vgg16_from_torchscript` is checked ONCE, at load time, against the module's own
         `module(x, resize_images=False, return_lpips=True)` on a small probe batch (the scripted module runs on the host for this
-        check only; the criterion itself never calls it); the first one that agrees is kept together with its input affine
-        (`engine.pre_scale`, `engine.pre_shift`), otherwise loading fails loudly."""
+        check only; the criterion itself never calls it); the first one that agrees is kept -- (candidate, the f32 engine it was
+        probed on) -- otherwise loading fails loudly."""
         cands = vgg16_from_torchscript(src)
         g = torch.Generator().manual_seed(probe_seed)
         probe = torch.rand([2, 1, in_res, in_res], generator=g).repeat(1, 3, 1, 1) * 255.0      # the 0..255 range the script is written for
@@ -537,10 +554,7 @@ class FeatureEngine:
             err = float((got - want).norm() / want.norm().clamp_min(1e-30))
             errs.append(err)
             if err <= rtol:
-                if precision != 'f32' or max_batch != eng.max_batch:
-                    eng = cls(c.ops, device, in_res, max_batch=max_batch, precision=precision)
-                eng.pre_scale, eng.pre_shift, eng.lin_is_sqrt = c.pre_scale, c.pre_shift, c.lin_is_sqrt
-                return eng
+                return c, eng
             del eng
         raise _lib.LatentAugHipError('TorchScript feature net: no mapping of its tensors onto the VGG16-LPIPS op list reproduces the '
                                      f"module's own output (relative errors of the candidates: {errs}); refusing to guess")

@@ -355,14 +355,20 @@ def test_plugin_reference_branch(dev, gl, golden_dir, tmp_path):
                                 w_pix=0.0, w_lpips=w_lpips, w_latent=0.0, w_disc=0.0, crop_size_aug=16, preprocess_aug='center_random_crop',
                                 soft_aug=False, alpha=1.0, verbose_log=False, criterion_mode='gemm', final_noise_mode='const', precision='f32',
                                 lpips_script='lpips', lpips_vgg_path=str(tmp_path / 'vgg16.pth'), lpips_lin_path=str(tmp_path / 'lpips_vgg.pth'))
+    before = dict(vars(opt))
     la = LatentAug('train', opt, str(tmp_path), [0], generator=G, banks={'fea': fea})
+    assert vars(opt) == before      # the net's input affine goes to the loop, never into `opt`
     assert la.feat.num_taps == 3 and la.feat.pre_scale == bank_eng.pre_scale
     w0 = torch.tensor(ll['w0'])[:1]
     img, w_aug, losses = la.run_local(w0.to(dev), want_losses=True, crop_pos=tuple(int(v) for v in gl['plug_pos']))
+    # a second LatentAug from the same `opt`: the same bits
+    again = LatentAug('train', opt, str(tmp_path), [0], generator=G, banks={'fea': fea})
+    img_b, w_aug_b, losses_b = again.run_local(w0.to(dev), want_losses=True, crop_pos=tuple(int(v) for v in gl['plug_pos']))
+    assert vars(opt) == before and torch.equal(img_b, img) and torch.equal(w_aug_b, w_aug) and torch.equal(losses_b, losses)
     got = losses.cpu().numpy()[0, 3]
     lc.check('plugin step-0 lpips loss', np.array([got]), np.array([gl['plug_tr64'].mean() * w_lpips]), np.array([gl['plug_tr32'].mean() * w_lpips]))
     # through <model_dir> instead of the two options
-    opt2 = types.SimpleNamespace(**{k: v for k, v in vars(opt).items() if k not in ('lpips_vgg_path', 'lpips_lin_path', 'lpips_preproc')},
+    opt2 = types.SimpleNamespace(**{k: v for k, v in vars(opt).items() if k not in ('lpips_vgg_path', 'lpips_lin_path')},
                                  model_dir=str(tmp_path))
     la2 = LatentAug('train', opt2, str(tmp_path), [0], generator=G, banks={'fea': fea})
     assert la2.feat.weights_digest == la.feat.weights_digest

@@ -271,9 +271,9 @@ def test_every_workspace_is_allocated_by_lib_workspace():
                     sites[rel] = n
                 entries |= set(re.findall(r'\b(la_\w*workspace_(?:bytes|floats)\w*)\(', src))
     assert not faults, faults
-    # synthesis: synth, mapping tmp, disc, feat, LPIPS pair, fc | latent_aug: loop, loop LPIPS | metrics: cdist, PR, KID, FD, DC (+ its PR
+    # synthesis: synth, mapping tmp, disc, feat, LPIPS pair, fc | loop_handle: loop, loop LPIPS | metrics: cdist, PR, KID, FD, DC (+ its PR
     # part), pair metrics | projector: row distance | ops: filtered_lrelu signs, pairwise L2, conv2d scratch, grid-sample gradient
-    assert sites == {'synthesis.py': 6, 'latent_aug.py': 2, 'metrics.py': 6, 'projector.py': 1, 'ops.py': 4}
+    assert sites == {'synthesis.py': 6, 'loop_handle.py': 2, 'metrics.py': 6, 'projector.py': 1, 'ops.py': 4}
     from latentaugment_amd import _lib
     declared = {n for n in _lib.SIGNATURES if _SIZE_ENTRY.match(n)}
     assert len(declared) == 18 and entries <= declared
