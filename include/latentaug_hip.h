@@ -571,6 +571,31 @@ const float* la_disc_logits(const la_disc* h);
  * bits; no host sync, no allocation.  It overwrites the activations of an earlier la_feat_forward (la_feat_backward then refuses
  * until the next forward).  la_feat_num_taps: taps of the list = columns of dist.  la_crop_repeat_affine_f32: la_crop_repeat_f32
  * with one scale / shift per repeated channel (host arrays of `rep` floats), e.g. the (x - mean_k) / std_k of an input layer.
+ * General ops (the AlexNet and SqueezeNet 1.1 trunks of augments/criteria/lpips/networks.py:52-84): la_feat_op cannot grow, and the
+ * two entries below stay the only ones that take a list, so a general op is its {kind, cin, cout} record FOLLOWED by argument
+ * records {LA_FEAT_OP_ARGS, a, b} that carry the rest:
+ *       LA_FEAT_CONV_RELU_EX  {k, stride}, {pad, 0}        LA_FEAT_MAXPOOL3S2  {ceil_mode, 0}        LA_FEAT_FIRE  {squeeze, expand1}, {expand3, 0}
+ * nops counts records (at most 144, at most 48 ops); a list of the six first kinds is what it was.  The new kinds:
+ *   LA_FEAT_CONV_RELU_EX  y = relu(conv(x, w, stride, pad) + b): square kernel k 1 .. 11, stride 1 | 2 | 4, pad 0 .. 5 and < k, output
+ *                         size floor((res + 2 pad - k) / stride) + 1; cout % 4 == 0; cin % 4 == 0, or cin == 3 as the first op of the
+ *                         list.  params: weight [cout][cin][k][k], bias [cout], used in place.
+ *   LA_FEAT_MAXPOOL3S2    3x3 stride-2 max pool without padding, ceil_mode 0 | 1, output size by torch's rule (in ceil mode the last
+ *                         window must start inside the input; a window that hangs over the edge is clipped).  The gradient goes to
+ *                         the first maximum of a window in row-major scan order, as in torch.  No params.
+ *   LA_FEAT_FIRE          SqueezeNet's Fire module as one op, so that the list stays a chain: s = relu(conv1x1(x, squeeze)), then
+ *                         y[:, :expand1] = relu(conv1x1(s)) and y[:, expand1:] = relu(conv3x3(s), pad 1), written into the two
+ *                         channel slices of one output; cout = expand1 + expand3; cin, squeeze, expand1, expand3 multiples of 4.
+ *                         params: six tensors -- squeeze weight [squeeze][cin][1][1], bias, expand1x1 weight [expand1][squeeze][1][1],
+ *                         bias, expand3x3 weight [expand3][squeeze][3][3], bias.
+ * The resolution is tracked per op and stays square.  A list in which a geometry above is broken, a resolution would fall below 1
+ * or a pool would have no window, or whose argument records are missing, is refused by la_feat_workspace_bytes (0) and la_feat_create
+ * (LA_ERR_ARG) before any launch, and la_last_error names the index of the op (ops counted, not records).  A detector list holds none
+ * of the new conv / fire kinds.  The input of a list with a general op may be one pixel (in_res >= 1; other lists: >= 2).
+ * The new ops compute in exact fp32 (fp32 MFMA products) in EVERY precision mode, as the FC ops do; la_feat_set_precision governs the
+ * LA_FEAT_CONV_RELU ops of a list only.  Where the K = cin * k * k sum of a small layer is split over workgroups the slices are
+ * added in a fixed order: no float atomics, two runs give the same bits; no host sync, no allocation.  Taps, la_feat_forward,
+ * la_feat_backward and la_feat_pair_distance work over them unchanged.  Lists of the six first kinds take the workspace bytes and
+ * give the bits they did before these kinds existed.
  * ------------------------------------------------------------------------------------------------------------- */
 #define LA_FEAT_CONV_RELU 0
 #define LA_FEAT_TAP 1
@@ -578,6 +603,10 @@ const float* la_disc_logits(const la_disc* h);
 #define LA_FEAT_AVGPOOL2 3
 #define LA_FEAT_FC_RELU 4
 #define LA_FEAT_FC 5
+#define LA_FEAT_CONV_RELU_EX 6
+#define LA_FEAT_MAXPOOL3S2 7
+#define LA_FEAT_FIRE 8
+#define LA_FEAT_OP_ARGS 9
 typedef struct la_feat_op { int kind, cin, cout; } la_feat_op;
 typedef struct la_feat la_feat;
 size_t la_feat_workspace_bytes(int nops, const la_feat_op* ops, int in_ch, int in_res, int max_batch);

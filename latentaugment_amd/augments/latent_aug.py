@@ -73,6 +73,10 @@ class LatentAugment(BaseAugment):
         parser.add_argument('--rand_aug', action='store_true', help='no optimisation: images of freshly mapped random z')
         parser.add_argument('--lower_bound_clip', action='store_true', help='clamp output pixels at -1 from below')
         parser.add_argument('--lpips_script', type=str, default='lpips_script', help="perceptual net: 'lpips_script' = the TorchScript vgg16.pt")
+        parser.add_argument('--lpips_net', type=str, default='vgg', choices=['vgg', 'alex', 'squeeze'],
+                            help="trunk of the LPIPS class, read when --lpips_script is not 'lpips_script' (local weights: --lpips_trunk_path / "
+                                 '--lpips_lin_path, else <model_dir>/alexnet.pth + lpips_alex.pth or squeezenet1_1.pth + lpips_squeeze.pth)')
+        parser.add_argument('--lpips_trunk_path', type=str, default=None, help="torchvision state dict of the --lpips_net trunk")
         parser.add_argument('--init_w', type=str, default='random', help="start latent of the optimisation: 'inv' (inverted latent of the slice)")
         parser.add_argument('--preprocess_aug', type=str, default='center_random_crop', help='window policy of the perceptual criterion: center_crop | random_crop | center_random_crop | original')
         parser.add_argument('--soft_aug', type=bool, default=False, help='return a blend of the inverted and the moved latent (see --alpha)')

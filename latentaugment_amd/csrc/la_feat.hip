@@ -7,6 +7,11 @@
 //       f[n][c][p] * rsqrt(sum_c f^2 + 1e-10) * sqrt(lin[c]) / sqrt(H*W)
 // to the output vector, so that squared L2 distance of two vectors is their LPIPS distance.
 // Contractions reuse la_conv*.hip (shared weights); pools / taps are small HBM-bound kernels.
+// General ops (the AlexNet and SqueezeNet 1.1 trunks of augments/criteria/lpips/networks.py:52-84): a convolution + ReLU with any square
+// kernel, stride and padding, a 3x3 stride-2 max pool (floor / ceil mode) and SqueezeNet's Fire module as ONE op -- squeeze, then the
+// two expand branches written into the channel slices of one output -- so that the list stays the chain f_trunk and la_feat_backward
+// walk.  They run on la_feat_conv.hip in exact fp32 in every precision mode and lower no slot rows: a 3x3 op behind one takes its fp16
+// operand scale the way a first conv does.  The resolution is tracked per op (res_in / res_out).
 // Detector lists (the `return_features=True` branch of the same net, metrics/metric_utils.py:264-328) end in fully connected ops
 // instead of taps: forward only, the feature vector is the last FC's output (la_fc_bias_act_f32, la_detector.hip).
 #include "la_feat.h"
@@ -16,14 +21,22 @@
 #include <string.h>
 
 #include "la_conv.h"
+#include "la_feat_conv.h"
 #include "la_modconv.h"
 #include "la_style.h"
 
 #define FEAT_MAX_OPS 48
 
+// One op as the caller describes it: its la_feat_op record with the values of its LA_FEAT_OP_ARGS records (f_parse)
+struct FOpDesc { int kind, cin, cout, k, stride, pad, ceil_mode, squeeze, expand1, expand3; };
+
 struct FOp {
     int kind, cin, cout, res_in, res_out;
-    const float *w, *bias, *lin;      // w: fc ops, used in place [cout][cin]
+    const float *w, *bias, *lin;      // w: fc ops and general convs, used in place ([cout][cin], [cout][cin][k][k])
+    // general conv: k, stride, pad; 3x3 stride-2 pool: ceil_mode; fire: squeeze / expand channels, cout = expand1 + expand3
+    int k, stride, pad, ceil_mode, squeeze, expand1, expand3;
+    const float *sq_w, *sq_b, *e1_w, *e1_b, *e3_w, *e3_b;      // fire: the six tensors, used in place
+    float* sq_y;       // fire: the squeeze activation [maxN][squeeze][res^2]
     LaConvWeights cw;  // conv ops
     float* y;          // output activation [maxN][cout][res_out^2] (conv, pools, fc: res_out = 1); taps have none
     long feat_off;     // taps: offset of the slice inside the feature vector
@@ -45,18 +58,36 @@ struct la_feat {
     int pass_precision;  // precision of the last forward: what its backward runs in (a setter takes effect at the next forward)
     int detector;        // the list ends in an FC op: forward only, F = the last FC's outputs
     void* fcws; size_t fcws_bytes;      // la_fc_bias_act_f32's workspace (detector lists only)
+    // lists with a general conv or a fire op only: the split-K partials of la_featconv_forward, the gradient of a fire's squeeze activation
+    float* fcv_part; size_t fcv_part_floats;
+    float* fire_g;
 };
 
 static inline bool f_is_fc(int kind) { return kind == LA_FEAT_FC_RELU || kind == LA_FEAT_FC; }
+// the three convolutions of a fire op and a general conv as la_feat_conv.hip takes them
+static inline LaFeatConvGeom f_geom(int cin, int cout, int k, int stride, int pad, int R, int Ro) { return LaFeatConvGeom{cin, cout, k, stride, pad, R, Ro}; }
+static inline LaFeatConvGeom f_geom(const FOp& o) { return f_geom(o.cin, o.cout, o.k, o.stride, o.pad, o.res_in, o.res_out); }
+static inline LaFeatConvGeom f_fire_sq(const FOp& o) { return f_geom(o.cin, o.squeeze, 1, 1, 0, o.res_in, o.res_in); }
+static inline LaFeatConvGeom f_fire_e1(const FOp& o) { return f_geom(o.squeeze, o.expand1, 1, 1, 0, o.res_in, o.res_in); }
+static inline LaFeatConvGeom f_fire_e3(const FOp& o) { return f_geom(o.squeeze, o.expand3, 3, 1, 1, o.res_in, o.res_in); }
 
-static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, int in_res, int maxN) {
+// refusal with the index of the op that causes it
+static int f_refuse(int k, const char* why) {
+    static thread_local char msg[160];
+    snprintf(msg, sizeof msg, "feat: op %d: %s", k, why);
+    la_set_error(msg);
+    return LA_ERR_ARG;
+}
+
+// min_res: 2 for a list of the six first kinds (as ever), 1 for a list with a general op (a one-pixel input of a general conv)
+static int f_describe(la_feat* h, int nops, const FOpDesc* ops, int in_ch, int in_res, int maxN, int min_res) {
     LA_CHECK_ARG(nops >= 1 && nops <= FEAT_MAX_OPS && ops, "feat: bad op list");
-    LA_CHECK_ARG(in_ch >= 1 && in_res >= 2 && maxN >= 1, "feat: bad input shape");
+    LA_CHECK_ARG(in_ch >= 1 && in_res >= min_res && maxN >= 1, "feat: bad input shape");
     memset(h, 0, sizeof(*h));
     h->nops = nops; h->in_ch = in_ch; h->in_res = in_res; h->maxN = maxN;
     int c = in_ch, r = in_res;
     long F = 0;
-    int ntap = 0, nfc = 0;
+    int ntap = 0, nfc = 0, nex = 0;
     for (int k = 0; k < nops; ++k) {
         FOp& o = h->op[k];
         o.kind = ops[k].kind; o.cin = c; o.res_in = r;
@@ -73,6 +104,27 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
                 o.cout = c; o.res_out = r / 2; r /= 2; break;
             case LA_FEAT_TAP:
                 o.cout = c; o.res_out = r; o.feat_off = F; F += (long)c * r * r; ++ntap; break;
+            case LA_FEAT_CONV_RELU_EX: {
+                const FOpDesc& d = ops[k];
+                if (d.cin != c) return f_refuse(k, "conv cin does not match the channels in front of it");
+                if (c == 3 && k != 0) return f_refuse(k, "only the first op may have cin = 3");
+                const int ro = la_featconv_out_res(c, d.cout, d.k, d.stride, d.pad, r);
+                if (ro < 1) return f_refuse(k, "conv refused: k 1..11, stride 1|2|4, pad 0..5 and < k, cout % 4 == 0, cin % 4 == 0 (a first op: 3), resolution >= 1");
+                o.cout = d.cout; o.k = d.k; o.stride = d.stride; o.pad = d.pad; o.res_out = ro; c = o.cout; r = ro; ++nex; break;
+            }
+            case LA_FEAT_MAXPOOL3S2: {
+                const int ro = la_pool3s2_out_res(r, ops[k].ceil_mode);
+                if (ro < 1) return f_refuse(k, "3x3 stride-2 pool: the resolution in front of it is too small");
+                o.cout = c; o.ceil_mode = ops[k].ceil_mode ? 1 : 0; o.res_out = ro; r = ro; break;
+            }
+            case LA_FEAT_FIRE: {
+                const FOpDesc& d = ops[k];
+                if (d.cin != c || d.cout != d.expand1 + d.expand3) return f_refuse(k, "fire: cin must match what precedes it and cout = expand1 + expand3");
+                if (la_featconv_out_res(c, d.squeeze, 1, 1, 0, r) != r || la_featconv_out_res(d.squeeze, d.expand1, 1, 1, 0, r) != r ||
+                    la_featconv_out_res(d.squeeze, d.expand3, 3, 1, 1, r) != r || c == 3)
+                    return f_refuse(k, "fire: cin, squeeze, expand1 and expand3 must be positive multiples of 4");
+                o.cout = d.cout; o.squeeze = d.squeeze; o.expand1 = d.expand1; o.expand3 = d.expand3; o.res_out = r; c = o.cout; ++nex; break;
+            }
             case LA_FEAT_FC_RELU: case LA_FEAT_FC:
                 LA_CHECK_ARG(ntap == 0, "feat: taps and fc ops cannot be mixed in one list");
                 LA_CHECK_ARG((long)ops[k].cin == (long)c * r * r, "feat: fc cin must be C*res*res of what precedes it");
@@ -82,6 +134,7 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
                 la_set_error("feat: unknown op kind"); return LA_ERR_ARG;
         }
     }
+    LA_CHECK_ARG(!(nfc && nex), "feat: a detector list (fc ops) holds no general conv or fire op");
     if (nfc) { h->detector = 1; F = c; }
     LA_CHECK_ARG(F > 0 && F < (1L << 31), "feat: no tap op / feature vector too long");
     h->F = (int)F;
@@ -91,7 +144,7 @@ static int f_describe(la_feat* h, int nops, const la_feat_op* ops, int in_ch, in
 static size_t f_layout(la_feat* h, void* ws) {
     LaCarver c{(char*)ws};
     const size_t mn = h->maxN;
-    size_t gmax = mn * h->in_ch * (size_t)h->in_res * h->in_res, cw = 0, pmax = 0;
+    size_t gmax = mn * h->in_ch * (size_t)h->in_res * h->in_res, cw = 0, pmax = 0, part = 0, fire = 0;
     for (int k = 0; k < h->nops; ++k) {
         FOp& o = h->op[k];
         const size_t n_out = mn * o.cout * (size_t)o.res_out * o.res_out;
@@ -106,7 +159,17 @@ static size_t f_layout(la_feat* h, void* ws) {
             if (pmn > pmax) pmax = pmn;
         }
         if (o.kind != LA_FEAT_TAP) { o.y = c.take(n_out); if (n_out > gmax) gmax = n_out; }
+        if (o.kind == LA_FEAT_CONV_RELU_EX) { const size_t f = la_featconv_part_floats((int)mn, f_geom(o)); if (f > part) part = f; }
+        if (o.kind == LA_FEAT_FIRE) {
+            const size_t n_sq = mn * o.squeeze * (size_t)o.res_in * o.res_in;
+            o.sq_y = c.take(n_sq);
+            if (n_sq > fire) fire = n_sq;
+            for (const LaFeatConvGeom& g : {f_fire_sq(o), f_fire_e1(o), f_fire_e3(o)}) { const size_t f = la_featconv_part_floats((int)mn, g); if (f > part) part = f; }
+        }
     }
+    // (carved only for a list that holds one of the new ops: every other list keeps the bytes it had)
+    if (part) { h->fcv_part = c.take(part); h->fcv_part_floats = part; }
+    if (fire) h->fire_g = c.take(fire);
     if (h->detector) {      // forward only: no gradient buffers; the FC kernel's K-slice partials instead
         gmax = 0; pmax = 0;
         size_t fb = 0;
@@ -133,18 +196,19 @@ static size_t f_layout(la_feat* h, void* ws) {
     return c.off;
 }
 
-extern "C" size_t la_feat_workspace_bytes(int nops, const la_feat_op* ops, int in_ch, int in_res, int max_batch) {
-    return la_measure_workspace<la_feat>([&](la_feat* h) { return f_describe(h, nops, ops, in_ch, in_res, max_batch) == LA_OK ? f_layout(h, nullptr) : 0; });
+static size_t f_workspace_bytes(int nops, const FOpDesc* ops, int in_ch, int in_res, int max_batch, int min_res) {
+    return la_measure_workspace<la_feat>([&](la_feat* h) { return f_describe(h, nops, ops, in_ch, in_res, max_batch, min_res) == LA_OK ? f_layout(h, nullptr) : 0; });
 }
 
-// params: for each op in order: conv -> weight [cout][cin][3][3], bias [cout]; tap -> lin [C]; pools -> nothing
-extern "C" int la_feat_create(int nops, const la_feat_op* ops, const float* const* params, int nparams, int in_ch, int in_res,
-                              int max_batch, void* workspace, size_t workspace_bytes, hipStream_t stream, la_feat** out) {
+// params: for each op in order: conv -> weight [cout][cin][k][k], bias [cout]; tap -> lin [C]; pools -> nothing;
+// fire -> squeeze weight, bias, expand1x1 weight, bias, expand3x3 weight, bias
+static int f_create(int nops, const FOpDesc* ops, const float* const* params, int nparams, int in_ch, int in_res,
+                    int max_batch, void* workspace, size_t workspace_bytes, hipStream_t stream, la_feat** out, int min_res) {
     LA_CHECK_ARG(params && workspace && out, "feat_create: null pointer");
     auto own = la_host_handle<la_feat>();
     la_feat* h = own.get();
     LA_CHECK_ARG(h, "feat_create: out of host memory");
-    int rc = f_describe(h, nops, ops, in_ch, in_res, max_batch);
+    int rc = f_describe(h, nops, ops, in_ch, in_res, max_batch, min_res);
     if (rc) return rc;
     if (f_layout(h, workspace) > workspace_bytes) { la_set_error("feat_create: workspace too small"); return LA_ERR_WORKSPACE; }
     int p = 0;
@@ -160,12 +224,65 @@ extern "C" int la_feat_create(int nops, const la_feat_op* ops, const float* cons
         } else if (f_is_fc(o.kind)) {      // used in place: weight [cout][cin], bias [cout]
             if (p + 2 > nparams || !params[p] || !params[p + 1]) { rc = LA_ERR_ARG; la_set_error("feat_create: missing fc tensors"); break; }
             o.w = params[p++]; o.bias = params[p++];
+        } else if (o.kind == LA_FEAT_CONV_RELU_EX) {      // used in place: weight [cout][cin][k][k], bias [cout]
+            if (p + 2 > nparams || !params[p] || !params[p + 1]) { rc = LA_ERR_ARG; la_set_error("feat_create: missing conv tensors"); break; }
+            o.w = params[p++]; o.bias = params[p++];
+        } else if (o.kind == LA_FEAT_FIRE) {
+            bool ok = p + 6 <= nparams;
+            for (int q = 0; ok && q < 6; ++q) ok = params[p + q] != nullptr;
+            if (!ok) { rc = LA_ERR_ARG; la_set_error("feat_create: missing fire tensors"); break; }
+            o.sq_w = params[p]; o.sq_b = params[p + 1]; o.e1_w = params[p + 2]; o.e1_b = params[p + 3]; o.e3_w = params[p + 4]; o.e3_b = params[p + 5];
+            p += 6;
         }
     }
     if (!rc && p != nparams) { rc = LA_ERR_ARG; la_set_error("feat_create: parameter list length mismatch"); }
     if (rc) return rc;
     *out = own.release();
     return LA_OK;
+}
+
+// The caller's records -> ops.  A record of one of the six first kinds is an op; a general op is its record followed by the
+// LA_FEAT_OP_ARGS records that carry what {kind, cin, cout} cannot (include/latentaug_hip.h): conv {k, stride}, {pad, 0}; 3x3 pool
+// {ceil_mode, 0}; fire {squeeze, expand1}, {expand3, 0}.  A list without general ops parses to itself.
+static int f_parse(int nrec, const la_feat_op* rec, FOpDesc* wide, int* nops, int* min_res) {
+    LA_CHECK_ARG(nrec >= 1 && nrec <= 3 * FEAT_MAX_OPS && rec, "feat: bad op list");
+    memset(wide, 0, sizeof(FOpDesc) * FEAT_MAX_OPS);
+    int n = 0;
+    *min_res = 2;      // (a one-pixel input only in front of a general op)
+    for (int r = 0; r < nrec; ++n) {
+        LA_CHECK_ARG(n < FEAT_MAX_OPS, "feat: bad op list");
+        FOpDesc& d = wide[n];
+        d.kind = rec[r].kind; d.cin = rec[r].cin; d.cout = rec[r].cout;
+        ++r;
+        const int nargs = d.kind == LA_FEAT_CONV_RELU_EX || d.kind == LA_FEAT_FIRE ? 2 : d.kind == LA_FEAT_MAXPOOL3S2 ? 1 : 0;
+        if (nargs == 0) {
+            LA_CHECK_ARG(d.kind >= LA_FEAT_CONV_RELU && d.kind <= LA_FEAT_FC, d.kind == LA_FEAT_OP_ARGS ? "feat: argument record without its op" : "feat: unknown op kind");
+            continue;
+        }
+        *min_res = 1;
+        int v[4] = {0, 0, 0, 0};
+        for (int q = 0; q < nargs; ++q, ++r) {
+            if (r >= nrec || rec[r].kind != LA_FEAT_OP_ARGS) return f_refuse(n, "the op's argument records are missing");
+            v[2 * q] = rec[r].cin; v[2 * q + 1] = rec[r].cout;
+        }
+        if (d.kind == LA_FEAT_CONV_RELU_EX) { d.k = v[0]; d.stride = v[1]; d.pad = v[2]; }
+        else if (d.kind == LA_FEAT_MAXPOOL3S2) d.ceil_mode = v[0];
+        else { d.squeeze = v[0]; d.expand1 = v[1]; d.expand3 = v[2]; }
+    }
+    *nops = n;
+    return LA_OK;
+}
+extern "C" size_t la_feat_workspace_bytes(int nops, const la_feat_op* ops, int in_ch, int in_res, int max_batch) {
+    FOpDesc wide[FEAT_MAX_OPS];
+    int n, min_res;
+    return f_parse(nops, ops, wide, &n, &min_res) == LA_OK ? f_workspace_bytes(n, wide, in_ch, in_res, max_batch, min_res) : 0;
+}
+extern "C" int la_feat_create(int nops, const la_feat_op* ops, const float* const* params, int nparams, int in_ch, int in_res,
+                              int max_batch, void* workspace, size_t workspace_bytes, hipStream_t stream, la_feat** out) {
+    FOpDesc wide[FEAT_MAX_OPS];
+    int n, min_res;
+    const int rc = f_parse(nops, ops, wide, &n, &min_res);
+    return rc ? rc : f_create(n, wide, params, nparams, in_ch, in_res, max_batch, workspace, workspace_bytes, stream, out, min_res);
 }
 
 extern "C" void la_feat_destroy(la_feat* h) { free(h); }
@@ -387,6 +504,20 @@ static int f_trunk(la_feat* h, const float* x, int N, float* fc_out, hipStream_t
                                          h->fcws_bytes, stream)))
                 return rc;
             cur = dst;
+        } else if (o.kind == LA_FEAT_CONV_RELU_EX) {
+            if ((rc = la_featconv_forward(cur, o.w, o.bias, o.y, N, f_geom(o), 0, o.cout, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+            cur = o.y;
+            first_conv = true;      // (no slot rows from this producer: a 3x3 op behind it takes its operand scale as a first conv does)
+        } else if (o.kind == LA_FEAT_FIRE) {
+            // squeeze, then the two expand branches into the channel slices [0, expand1) and [expand1, cout) of one output: torch.cat without a copy
+            if ((rc = la_featconv_forward(cur, o.sq_w, o.sq_b, o.sq_y, N, f_fire_sq(o), 0, o.squeeze, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+            if ((rc = la_featconv_forward(o.sq_y, o.e1_w, o.e1_b, o.y, N, f_fire_e1(o), 0, o.cout, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+            if ((rc = la_featconv_forward(o.sq_y, o.e3_w, o.e3_b, o.y, N, f_fire_e3(o), o.expand1, o.cout, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+            cur = o.y;
+            first_conv = true;
+        } else if (o.kind == LA_FEAT_MAXPOOL3S2) {
+            if ((rc = la_pool3s2_forward(cur, o.y, (long)N * o.cout, o.res_in, o.res_out, stream))) return rc;
+            cur = o.y;
         } else {
             const long planes = (long)N * o.cout;
             hipLaunchKernelGGL(la_pool2_fwd_kernel, dim3(la_cdiv(planes * HWo, 256)), dim3(256), 0, stream, cur, o.y, o.res_in, planes,
@@ -467,6 +598,22 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
                                         hipMemcpyDeviceToDevice, stream));
             }
             float* t = g; g = other; other = t;
+        } else if (o.kind == LA_FEAT_CONV_RELU_EX || o.kind == LA_FEAT_FIRE || o.kind == LA_FEAT_MAXPOOL3S2) {
+            LA_CHECK_ARG(have, "feat_backward: the op list must end with a tap");
+            float* dst = k == 0 ? gx : other;      // (a first op writes gx [N][in_ch][in_res^2] itself)
+            if (o.kind == LA_FEAT_CONV_RELU_EX) {
+                // (the ReLU mask of this layer is applied to g on load, from its saved output)
+                if ((rc = la_featconv_backward(g, o.y, o.w, dst, N, f_geom(o), 0, o.cout, 0, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+            } else if (o.kind == LA_FEAT_FIRE) {
+                // expand3x3 gradient, expand1x1 gradient added to it (both masked by their slice of y), then the squeeze mask and gradient
+                if ((rc = la_featconv_backward(g, o.y, o.e3_w, h->fire_g, N, f_fire_e3(o), o.expand1, o.cout, 0, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+                if ((rc = la_featconv_backward(g, o.y, o.e1_w, h->fire_g, N, f_fire_e1(o), 0, o.cout, 1, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+                if ((rc = la_featconv_backward(h->fire_g, o.sq_y, o.sq_w, dst, N, f_fire_sq(o), 0, o.squeeze, 0, h->fcv_part, h->fcv_part_floats, stream))) return rc;
+            } else {
+                if ((rc = la_pool3s2_backward(act_in, g, dst, (long)N * o.cout, o.res_in, o.res_out, stream))) return rc;
+            }
+            float* t = g; g = other; other = t;
+            masked = false;
         } else {
             LA_CHECK_ARG(have, "feat_backward: the op list must end with a tap");
             const long planes = (long)N * o.cout;
@@ -477,8 +624,8 @@ extern "C" int la_feat_backward(la_feat* h, const float* gfeat, float* gx, hipSt
         }
     }
     LA_CHECK_LAUNCH();
-    if (h->op[0].kind != LA_FEAT_CONV_RELU) {
-        // the gradient ended in g (no first conv wrote gx)
+    if (h->op[0].kind == LA_FEAT_TAP || h->op[0].kind == LA_FEAT_MAXPOOL2 || h->op[0].kind == LA_FEAT_AVGPOOL2) {
+        // the gradient ended in g (no first conv, fire or 3x3 pool wrote gx)
         const long n_in = (long)N * h->in_ch * h->in_res * h->in_res;
         LA_HIP(hipMemcpyAsync(gx, g, sizeof(float) * n_in, hipMemcpyDeviceToDevice, stream));
     }

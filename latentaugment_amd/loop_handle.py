@@ -28,7 +28,8 @@ def load_perceptual_net(resolved, device, in_res):
         # reference's d(x, y_m), so sum / (n * M) per modality is its forward_tr (lpips.py:60-68) -- exactly at n = 1, the only
         # batch its broadcast (fx - fy) admits -- through the loop code of the TorchScript branch, unchanged.
         from .synthesis import lpips_reference_net
-        print(f'Loading VGG16 / LPIPS lin weights from: {src}')
+        # (src carries the trunk as a third element for LPIPS('alex') / LPIPS('squeeze'): five / seven taps, the same z-score)
+        print(f'Loading {"VGG16" if len(src) == 2 else src[2]} / LPIPS lin weights from: {src[:2]}')
         return PerceptualNet(kind, lpips_reference_net(*src))
     # the script's own input layer, (x - mean_k) / std_k; the reference hands it the synthesised crop as it is (:394-395)
     print(f'Loading VGG16 from: {src}')

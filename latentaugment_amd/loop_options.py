@@ -16,6 +16,11 @@ LATENT_SPACES = {'w': 0, 'w+': 1}      # opt.latent_space -> latent_space of la_
 CRITERION_MODES = {'gemm': 0, 'collapsed': 1}
 FINAL_NOISE_MODES = {'none': 0, 'const': 1, 'random': 2}
 STREAM_LANES = ('auto', 1, 2)
+# opt.lpips_net: the trunk of the reference's LPIPS class (augments/criteria/lpips/networks.py:12-20) -> the file names looked for under
+# <model_dir> (torchvision's state dict, the LPIPS lin weights) and the smallest crop its stack takes (alex 31 -> conv 7 -> pools 3, 1;
+# squeeze 17 -> conv 8 -> ceil-mode pools 4, 2, 1)
+LPIPS_NET_FILES = {'vgg': ('vgg16.pth', 'lpips_vgg.pth'), 'alex': ('alexnet.pth', 'lpips_alex.pth'), 'squeeze': ('squeezenet1_1.pth', 'lpips_squeeze.pth')}
+LPIPS_NET_MIN_RES = {'alex': 31, 'squeeze': 17}
 
 
 def center_crop_geometry(load_size):
@@ -70,7 +75,9 @@ class LoopOptions:
     soft_aug: bool
     alpha: float
     verbose_log: bool                    # losses / times / snapshots of the FIRST batch
-    lpips_script: str = 'lpips_script'   # 'lpips_script': the TorchScript vgg16.pt; anything else: LPIPS('vgg') from two state dicts
+    # 'lpips_script': the TorchScript vgg16.pt; anything else: the LPIPS class from two state dicts -- LPIPS('vgg'), or with an ':alex' /
+    # ':squeeze' suffix (from_opt appends opt.lpips_net; read back by the `lpips_net` property) LPIPS('alex') / LPIPS('squeeze')
+    lpips_script: str = 'lpips_script'
     model_dir: Optional[str] = None      # read where the generator or the perceptual net comes from disk
     interim_dir: Optional[str] = None    # read where banks come from the interim zips
     dataset_aug: Optional[str] = None
@@ -121,6 +128,16 @@ class LoopOptions:
             raise LatentAugHipError(f'opt.latent_space = {space!r}: expected one of {sorted(LATENT_SPACES)}')
         oc = get('overlap_criteria', True)
         preproc = get('lpips_preproc')
+        # opt.lpips_net ('vgg' | 'alex' | 'squeeze') and opt.lpips_trunk_path are read only on the LPIPS-class branch (lpips_script !=
+        # 'lpips_script').  The record keeps its fields: another trunk than 'vgg' is carried as a ':alex' / ':squeeze' suffix of lpips_script
+        # (`lpips_net` reads it back), the trunk's state dict in lpips_vgg_path (`lpips_trunk_path`), so the 'vgg' default changes nothing.
+        script, trunk_path = get('lpips_script', 'lpips_script'), get('lpips_vgg_path')
+        if script != 'lpips_script':
+            net = _one_of('lpips_net', get('lpips_net', 'vgg') or 'vgg', tuple(LPIPS_NET_FILES))
+            if net != 'vgg':
+                script, trunk_path = f'{script}:{net}', get('lpips_trunk_path')
+            elif get('lpips_trunk_path'):
+                trunk_path = get('lpips_trunk_path')
         return cls(
             img_resolution=opt.img_resolution, batch_size=opt.batch_size,
             modalities=tuple(m for m in str(opt.modalities_aug).split(',') if m),
@@ -128,14 +145,14 @@ class LoopOptions:
             w_pix=opt.w_pix, w_lpips=opt.w_lpips, w_latent=opt.w_latent, w_disc=opt.w_disc,
             crop_size_aug=opt.crop_size_aug, preprocess_aug=opt.preprocess_aug, soft_aug=bool(opt.soft_aug), alpha=opt.alpha,
             verbose_log=bool(opt.verbose_log),
-            lpips_script=get('lpips_script', 'lpips_script'), model_dir=get('model_dir'), interim_dir=get('interim_dir'),
+            lpips_script=script, model_dir=get('model_dir'), interim_dir=get('interim_dir'),
             dataset_aug=get('dataset_aug'), dataset_name_aug=get('dataset_name_aug'), dataset_w_name=str(get('dataset_w_name', '')),
             exp_stylegan=get('exp_stylegan'), network_pkl_stylegan=get('network_pkl_stylegan'),
             step_img=get('step_img'), step_w=get('step_w'),
             criterion_mode=_one_of('criterion_mode', get('criterion_mode', 'gemm'), CRITERION_MODES),
             final_noise_mode=_one_of('final_noise_mode', get('final_noise_mode', 'random'), FINAL_NOISE_MODES),
             precision=get('precision', 'f16x2'), latent_space=latent_space,
-            lpips_script_path=get('lpips_script_path'), lpips_vgg_path=get('lpips_vgg_path'), lpips_lin_path=get('lpips_lin_path'),
+            lpips_script_path=get('lpips_script_path'), lpips_vgg_path=trunk_path, lpips_lin_path=get('lpips_lin_path'),
             lpips_preproc=_preproc3(preproc) if preproc is not None else None,
             lpips_bank_range=get('lpips_bank_range', 'unit'), lpips_cache_compat=bool(get('lpips_cache_compat', False)),
             max_local_batch=int(get('max_local_batch', 0) or 0), norm_batch=int(get('norm_batch', 0) or 0),
@@ -151,6 +168,16 @@ class LoopOptions:
     @property
     def final_noise_code(self):
         return FINAL_NOISE_MODES[self.final_noise_mode]
+
+    @property
+    def lpips_net(self):
+        """Trunk of the LPIPS-class branch: 'vgg' unless from_opt recorded opt.lpips_net = 'alex' | 'squeeze' behind lpips_script."""
+        head, sep, tail = self.lpips_script.rpartition(':')
+        return tail if sep and tail in LPIPS_NET_MIN_RES else 'vgg'
+
+    @property
+    def lpips_trunk_path(self):
+        return self.lpips_vgg_path
 
     @property
     def wplus(self):
@@ -174,7 +201,8 @@ class LoopOptions:
 
 def resolve_perceptual_net(options, feature_net=None):
     """Which perceptual net a configuration asks for, decided before anything touches a device: ('ops', feature_net) |
-    ('script', path) | ('reference', (vgg_path, lin_path)) | None (w_lpips <= 0).  Only os.path.isfile is asked about the files."""
+    ('script', path) | ('reference', (trunk_path, lin_path)) -- with opt.lpips_net = 'alex' | 'squeeze': (trunk_path, lin_path, net) -- |
+    None (w_lpips <= 0).  Only os.path.isfile is asked about the files."""
     if options.w_lpips <= 0:
         return None
     if feature_net is not None:
@@ -192,11 +220,23 @@ def resolve_perceptual_net(options, feature_net=None):
     # util_latent_aug.py:129-131, which downloads torchvision's VGG16 and the LPIPS lin weights): LOCAL state dicts at
     # opt.lpips_vgg_path / opt.lpips_lin_path, or <model_dir>/vgg16.pth and <model_dir>/lpips_vgg.pth
     if not options.lpips_script_path and options.lpips_script != 'lpips_script':
+        net = options.lpips_net
         pair = []
-        for given, name in ((options.lpips_vgg_path, 'vgg16.pth'), (options.lpips_lin_path, 'lpips_vgg.pth')):
+        for given, name in zip((options.lpips_trunk_path, options.lpips_lin_path), LPIPS_NET_FILES[net]):
             pair.append(first_file([given] + ([os.path.join(options.model_dir, name)] if options.model_dir else [])))
         if all(pair):
-            return 'reference', tuple(pair)
+            if net == 'vgg':
+                return 'reference', tuple(pair)
+            if options.crop_size_aug < LPIPS_NET_MIN_RES[net]:
+                raise LatentAugHipError(f'opt.crop_size_aug = {options.crop_size_aug} is too small for opt.lpips_net = {net!r}: its stack '
+                                        f'needs a crop of at least {LPIPS_NET_MIN_RES[net]}')
+            return 'reference', tuple(pair) + (net,)
+        if net != 'vgg' and script is None:
+            raise NotImplementedError(
+                f"w_lpips > 0 with opt.lpips_net = {net!r} needs local state dicts of torchvision's {LPIPS_NET_FILES[net][0][:-4]} at "
+                f'opt.lpips_trunk_path or <model_dir>/{LPIPS_NET_FILES[net][0]}, and of the LPIPS lin layers at opt.lpips_lin_path or '
+                f'<model_dir>/{LPIPS_NET_FILES[net][1]} (the reference downloads both; there is no network here); looked for '
+                f'{[options.lpips_trunk_path, options.lpips_lin_path]} and under model_dir = {options.model_dir!r}')
     if script is not None:
         return 'script', script
     raise NotImplementedError(

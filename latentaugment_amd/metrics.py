@@ -519,7 +519,7 @@ def compute_lpips(x, y, net, pairs=None):
     (`net.pre_scale`, `net.pre_shift`) and sent through `net`, a synthesis.FeatureEngine of three input channels; the distance comes
     from one fused launch per tap (FeatureEngine.pair_distance_rows), no feature vector is written.  x, y: float32 device tensors
     [N, C, R, R] with R == net.in_res (whole frames, not crops), values in the range the net expects ([-1, 1] for
-    lpips_reference_net).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy), gathered chunk by chunk with
+    lpips_reference_net, whose net_type 'alex' gives the LPIPS-Alex number most papers report).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy), gathered chunk by chunk with
     index_select.  Returns float64 CPU tensors: 'lpips' [P] (mean over channels), 'lpips_per_channel' [P, C] (sum over taps),
     'lpips_layers' [P, C, ntaps].  Two calls give the same bits.  There is no CPU fallback."""
     x, y = _device_images(x, 'x'), _device_images(y, 'y')

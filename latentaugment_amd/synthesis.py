@@ -432,6 +432,7 @@ class DiscriminatorEngine:
 
 
 FEAT_CONV, FEAT_TAP, FEAT_MAXPOOL, FEAT_AVGPOOL, FEAT_FC_RELU, FEAT_FC = 0, 1, 2, 3, 4, 5
+FEAT_CONV_EX, FEAT_MAXPOOL3S2, FEAT_FIRE, FEAT_OP_ARGS = 6, 7, 8, 9
 RESIZE_MODES = {'area': 0, 'bilinear': 1}
 
 
@@ -440,7 +441,11 @@ class FeatureEngine:
     util_latent_aug.py:395 and its backward.  `ops` is a list of ('conv', weight, bias) | ('tap', lin) | ('maxpool',) |
     ('avgpool',) in execution order; see `vgg16_lpips_ops` for the VGG16 layout.  ('fc', weight [O, K], bias [O], relu: bool) is a
     fully connected layer on the flattened activation (K = C * res * res in torch's NCHW order); a list that ends in one is a detector
-    list (`DetectorEngine`): forward only, no taps, and its feature vector is the last fc's output."""
+    list (`DetectorEngine`): forward only, no taps, and its feature vector is the last fc's output.
+    General ops (`alexnet_lpips_ops`, `squeezenet_lpips_ops`): ('conv', weight, bias, stride, pad) is a convolution + ReLU with any square
+    kernel up to 11, stride 1 | 2 | 4 and pad 0 .. 5 (the three-tuple form stays "3x3, pad 1, the existing launch"); ('maxpool3', ceil_mode)
+    a 3x3 stride-2 max pool; ('fire', sq_w, sq_b, e1_w, e1_b, e3_w, e3_b) SqueezeNet's Fire module.  They compute in exact fp32 whatever
+    `precision` says; a list the library refuses raises LatentAugHipError with the op's index."""
 
     def __init__(self, ops, device, in_res, max_batch, in_ch=3, precision='f32'):
         lib = _lib.load()
@@ -451,8 +456,27 @@ class FeatureEngine:
         self._keep = []
         desc, params = [], []
         c = in_ch
+
+        def dev(t):
+            return t.detach().to(self.device, torch.float32).contiguous()
         for op in ops:
-            if op[0] == 'conv':
+            if op[0] == 'conv' and len(op) == 5:      # general conv: any square kernel, exact fp32 (la_feat_conv.hip)
+                w, b = dev(op[1]), dev(op[2])
+                assert w.ndim == 4 and w.shape[1] == c and w.shape[2] == w.shape[3] and b.shape == (w.shape[0],)
+                desc += [_lib.FeatOp(FEAT_CONV_EX, c, w.shape[0]), _lib.FeatOp(FEAT_OP_ARGS, w.shape[2], int(op[3])), _lib.FeatOp(FEAT_OP_ARGS, int(op[4]), 0)]
+                c = w.shape[0]
+                params += [w, b]
+            elif op[0] == 'maxpool3':
+                desc += [_lib.FeatOp(FEAT_MAXPOOL3S2, c, c), _lib.FeatOp(FEAT_OP_ARGS, 1 if op[1] else 0, 0)]
+            elif op[0] == 'fire':
+                t = [dev(v) for v in op[1:7]]
+                sq, e1, e3 = t[0].shape[0], t[2].shape[0], t[4].shape[0]
+                assert t[0].shape == (sq, c, 1, 1) and t[2].shape == (e1, sq, 1, 1) and t[4].shape == (e3, sq, 3, 3)
+                assert t[1].shape == (sq,) and t[3].shape == (e1,) and t[5].shape == (e3,)
+                desc += [_lib.FeatOp(FEAT_FIRE, c, e1 + e3), _lib.FeatOp(FEAT_OP_ARGS, sq, e1), _lib.FeatOp(FEAT_OP_ARGS, e3, 0)]
+                c = e1 + e3
+                params += t
+            elif op[0] == 'conv':
                 w = op[1].detach().to(self.device, torch.float32).contiguous()
                 b = op[2].detach().to(self.device, torch.float32).contiguous()
                 assert w.shape[1] == c and w.shape[2:] == (3, 3)
@@ -485,8 +509,12 @@ class FeatureEngine:
                 hsh.update(t.detach().to('cpu', torch.float32).contiguous().numpy().tobytes() if torch.is_tensor(t) else repr(t).encode())
         self.weights_digest = hsh.hexdigest()[:10]
         self.in_ch, self.in_res, self.max_batch = in_ch, in_res, int(max_batch)
+        # (a general op is its record followed by its LA_FEAT_OP_ARGS records: include/latentaug_hip.h)
+        general = any(d.kind == FEAT_OP_ARGS for d in desc)
         arr = (_lib.FeatOp * len(desc))(*desc)
         nbytes = lib.la_feat_workspace_bytes(len(desc), arr, in_ch, in_res, self.max_batch)
+        if nbytes == 0 and general:
+            raise _lib.LatentAugHipError('invalid feature-net description: ' + (lib.la_last_error() or b'?').decode())
         assert nbytes > 0, 'invalid feature-net description: ' + (lib.la_last_error() or b'?').decode()
         self._workspace = _lib.workspace(nbytes, self.device)
         pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
@@ -653,16 +681,55 @@ def vgg16_lpips_ops(state_dict, lins, taps=(0, 1, 2, 3, 4)):
     return ops
 
 
+def alexnet_lpips_ops(state_dict, lins):
+    """Op list of the LPIPS AlexNet from torchvision's names (`features.{0,3,6,8,10}.weight/bias`, networks.py:73-84): conv 11x11
+    stride 4 pad 2, 3x3 stride-2 pool, conv 5x5 pad 2, pool, three 3x3 pad-1 convs; taps after the ReLUs at `features` indices 1, 4, 7,
+    9, 11 with `lins[0..4]`.  The list ends at its last tap (the third pool is never run).  Every conv is a general op: exact fp32."""
+    if len(lins) != 5:
+        raise ValueError(f'5 taps need 5 lin weight vectors (got {len(lins)})')
+    geom = {0: (4, 2), 3: (1, 2), 6: (1, 1), 8: (1, 1), 10: (1, 1)}
+    ops = []
+    for t, i in enumerate((0, 3, 6, 8, 10)):
+        ops.append(('conv', state_dict[f'features.{i}.weight'], state_dict[f'features.{i}.bias'], *geom[i]))
+        ops.append(('tap', lins[t]))
+        if i in (0, 3):
+            ops.append(('maxpool3', False))
+    return ops
+
+
+def squeezenet_lpips_ops(state_dict, lins):
+    """Op list of the LPIPS SqueezeNet 1.1 from torchvision's names (networks.py:60-70): `features.0` a 3x3 stride-2 conv without
+    padding, Fire modules at 3, 4, 6, 7, 9, 10, 11, 12 (`.squeeze` / `.expand1x1` / `.expand3x3`), ceil-mode 3x3 stride-2 pools at 2, 5, 8;
+    seven taps -- after the first ReLU and after the Fire modules 4, 7, 9, 10, 11, 12 -- with `lins[0..6]`.  The list ends at its last tap."""
+    if len(lins) != 7:
+        raise ValueError(f'7 taps need 7 lin weight vectors (got {len(lins)})')
+    tap_after = {1: 0, 4: 1, 7: 2, 9: 3, 10: 4, 11: 5, 12: 6}      # networks.py:70, target_layers [2, 5, 8, 10, 11, 12, 13] (1-based)
+    ops = [('conv', state_dict['features.0.weight'], state_dict['features.0.bias'], 2, 0), ('tap', lins[0])]
+    for i in range(2, 13):
+        if i in (2, 5, 8):
+            ops.append(('maxpool3', True))
+        else:
+            ops.append(('fire',) + tuple(state_dict[f'features.{i}.{part}.{kind}'] for part in ('squeeze', 'expand1x1', 'expand3x3')
+                                         for kind in ('weight', 'bias')))
+        if i in tap_after:
+            ops.append(('tap', lins[tap_after[i]]))
+    return ops
+
+
 LPIPS_ZSCORE_MEAN, LPIPS_ZSCORE_STD = (-.030, -.088, -.188), (.458, .448, .450)      # networks.py:40-43, images in [-1, 1]
 
 
-def lpips_reference_net(vgg_state_dict, lin_state_dict):
-    """The reference's non-TorchScript perceptual net, `augments/criteria/lpips/lpips.py::LPIPS('vgg')`, as a described net for
-    `FeatureEngine.from_net`: VGG16 tapped after relu3_3 / 4_3 / 5_3 (networks.py:94), the z-score (x - mean_k) / std_k as input affine
+def lpips_reference_net(vgg_state_dict, lin_state_dict, net_type='vgg'):
+    """The reference's non-TorchScript perceptual net, `augments/criteria/lpips/lpips.py::LPIPS(net_type)`, as a described net for
+    `FeatureEngine.from_net`.  'vgg': VGG16 tapped after relu3_3 / 4_3 / 5_3 (networks.py:94), the z-score (x - mean_k) / std_k as input affine
     (networks.py:40-50), and the LAST three `lin{k}.model.1.weight` tensors of the LPIPS weight file (what utils.py:32-52 keeps of
-    its five).  Each argument is a state dict or the path of one, read with torch.load(weights_only=True).  A negative lin weight
+    its five).  'alex' / 'squeeze': `alexnet_lpips_ops` / `squeezenet_lpips_ops` on the first argument (torchvision's alexnet /
+    squeezenet1_1 state dict) with all five / seven lin tensors (utils.py:32-37 skips nothing when the counts match) and the same
+    z-score.  Each argument is a state dict or the path of one, read with torch.load(weights_only=True).  A negative lin weight
     is refused: the criterion's tap emits sqrt(lin)."""
     import re
+    if net_type not in ('vgg', 'alex', 'squeeze'):
+        raise ValueError(f"net_type must be 'vgg', 'alex' or 'squeeze' (got {net_type!r})")
 
     def read(src, what):
         if isinstance(src, dict):
@@ -670,14 +737,20 @@ def lpips_reference_net(vgg_state_dict, lin_state_dict):
         if not os.path.isfile(src):
             raise FileNotFoundError(f'{what}: no such file: {src}')
         return torch.load(src, map_location='cpu', weights_only=True)
-    vgg, lin = read(vgg_state_dict, 'VGG16 weights'), read(lin_state_dict, 'LPIPS lin weights')
+    trunk_name = {'vgg': 'VGG16', 'alex': 'AlexNet', 'squeeze': 'SqueezeNet 1.1'}[net_type]
+    vgg, lin = read(vgg_state_dict, f'{trunk_name} weights'), read(lin_state_dict, 'LPIPS lin weights')
     found = sorted((int(m.group(1)), v) for k, v in lin.items() for m in [re.fullmatch(r'lin(\d+)\.model\.1\.weight', k)] if m)
-    if len(found) < 3:
-        raise _lib.LatentAugHipError(f'LPIPS lin weights: found {len(found)} `lin<k>.model.1.weight` tensors, need at least 3')
-    lins = [v.detach().to('cpu', torch.float32).reshape(-1) for _, v in found[-3:]]
+    need = {'vgg': 3, 'alex': 5, 'squeeze': 7}[net_type]
+    if len(found) < need if net_type == 'vgg' else len(found) != need:
+        raise _lib.LatentAugHipError(f'LPIPS lin weights: found {len(found)} `lin<k>.model.1.weight` tensors, need '
+                                     + ('at least 3' if net_type == 'vgg' else f'{need} for {net_type!r}'))
+    lins = [v.detach().to('cpu', torch.float32).reshape(-1) for _, v in found[-need:]]
     if any(float(v.min()) < 0.0 for v in lins):
         raise _lib.LatentAugHipError('LPIPS lin weights: a negative channel weight (the criterion takes its square root); refusing')
-    ops = vgg16_lpips_ops(vgg, lins, taps=(2, 3, 4))
+    if net_type == 'vgg':
+        ops = vgg16_lpips_ops(vgg, lins, taps=(2, 3, 4))
+    else:
+        ops = (alexnet_lpips_ops if net_type == 'alex' else squeezenet_lpips_ops)(vgg, lins)
     return ScriptedFeatureNet(ops, tuple(1.0 / s for s in LPIPS_ZSCORE_STD),
                               tuple(-m / s for m, s in zip(LPIPS_ZSCORE_MEAN, LPIPS_ZSCORE_STD)), False, None)
 

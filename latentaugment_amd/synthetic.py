@@ -129,5 +129,36 @@ def make_vgg16_lpips_ops(seed=7, width=64, in_ch=3):
     return ops
 
 
+def make_lpips_net_state_dicts(net, seed=7):
+    """(trunk state dict in torchvision's names, LPIPS lin state dict) of a full-width AlexNet ('alex') or SqueezeNet 1.1 ('squeeze')
+    with seeded He-initialised weights, biases in [0.3, 0.6] and lin weights in [0.1, 1.1): stand-ins for the published files, which
+    cannot be downloaded offline -- what synthesis.lpips_reference_net(trunk, lin, net) takes."""
+    g = torch.Generator().manual_seed(seed)
+    sd, chans = {}, []
+
+    def conv(name, cout, cin, k):
+        sd[name + '.weight'] = torch.randn([cout, cin, k, k], generator=g) * (2.0 / (cin * k * k)) ** 0.5
+        sd[name + '.bias'] = torch.rand([cout], generator=g) * 0.3 + 0.3
+    if net == 'alex':
+        for i, (cin, cout, k) in zip((0, 3, 6, 8, 10), ((3, 64, 11), (64, 192, 5), (192, 384, 3), (384, 256, 3), (256, 256, 3))):
+            conv(f'features.{i}', cout, cin, k)
+            chans.append(cout)
+    elif net == 'squeeze':
+        conv('features.0', 64, 3, 3)
+        chans.append(64)
+        fires = {3: (64, 16, 64), 4: (128, 16, 64), 6: (128, 32, 128), 7: (256, 32, 128), 9: (256, 48, 192), 10: (384, 48, 192),
+                 11: (384, 64, 256), 12: (512, 64, 256)}
+        for i, (cin, sq, e) in fires.items():
+            conv(f'features.{i}.squeeze', sq, cin, 1)
+            conv(f'features.{i}.expand1x1', e, sq, 1)
+            conv(f'features.{i}.expand3x3', e, sq, 3)
+            if i in (4, 7, 9, 10, 11, 12):
+                chans.append(2 * e)
+    else:
+        raise ValueError(net)
+    lin = {f'lin{k}.model.1.weight': torch.rand([1, c, 1, 1], generator=g) + 0.1 for k, c in enumerate(chans)}
+    return sd, lin
+
+
 def lpips_num_features(crop=64, width=64):
     return sum(m * width * (crop >> i) ** 2 for i, (m, _) in enumerate([(1, 2), (2, 2), (4, 3), (8, 3), (8, 3)]))
