@@ -770,6 +770,7 @@ int la_latent_opt_run(la_latent_opt* h, const float* w0, int B, const float* con
  *   la_kid_poly3_f32        Kernel Inception Distance of two feature sets (described at its prototype below).
  *   la_dc_count_f16         density and coverage of two feature sets (described at its prototype below).
  *   la_fd_*                 Frechet distance of two feature sets from their cross-Gram matrix (described at the prototypes below).
+ *   la_knn_f32, la_realism_f32   nearest bank rows and realism score of single samples (described at the prototypes below).
  * ws: la_pr_workspace_floats(nr, nc) floats.  The [nr][nc] matrix is not materialised by the last two.
  * ------------------------------------------------------------------------------------------------------------- */
 int la_feature_moments_f64(const float* x, long n, int D, double* raw_mean, double* raw_cov, la_stream_t stream);
@@ -853,6 +854,43 @@ int la_fd_round_pair(int n, int round, int k, int* p, int* q);
 int la_fd_gram_f32(const float* x, long nx, const float* y, long ny, int D, double* terms, void* ws, size_t ws_bytes, la_stream_t stream);
 int la_fd_jacobi_sweep_f64(double* v, long n, long m, int* rotations, la_stream_t stream);
 int la_fd_finish_f64(void* ws, size_t ws_bytes, long nx, long ny, int D, double* sv, double* terms, la_stream_t stream);
+
+/* Per-sample neighbour queries (no reference counterpart as entries): the k nearest bank rows of every query row, and the realism
+ * score of the Improved Precision / Recall paper (Kynkaanniemi et al. 2019, whose pr50k3 is metrics/precision_recall.py).  Where the
+ * entries above keep the reference's float16 distances, these two are float64 arithmetic on the float32 features: float16 in
+ * |a|^2 + |b|^2 - 2 a.b form has no digits left at the small distances of a near-copy.
+ * q float32 [nq][D] (queries), x float32 [nx][D] (the bank), row-major, any D >= 1, 4-byte aligned.  One definition of the squared
+ * distance of a pair for both entries:
+ *   d2(q, x) = max(0, (|q|^2 + |x|^2) - 2 q.x)
+ * all three sums in float64 over the inputs widened exactly (a product of two float32 values is exact in float64), the dot products
+ * on v_mfma_f64_16x16x4_f64 in the tile form of la_fd_gram_f32 without centring, the norms of both sides by one kernel as the
+ * diagonal of the same product (the same k order).  The bits of d2(q, x) depend on the two rows and D only: not on the tile, the
+ * column split, the row of the batch or the number of other rows.  Equal rows have equal norms and d2 of two equal rows is exactly
+ * 0: a copy of a bank row is found at distance 0.  For any summation order |d2 - d2_exact| <= (2 D + 4) 2^-53 (|q|^2 + |x|^2): three sums of D exact
+ * products each, then two roundings to combine them.
+ *   la_knn_f32      dist2 float64 [nq][k] ascending, idx int32 [nq][k] (device), 1 <= k <= 32.  The order is (d2, index): of two equal
+ *                   d2 the lower index comes first, so the result does not depend on any merge order.  exclude_self != 0 needs
+ *                   nq == nx and skips bank row i for query i (the queries are the bank).  Slots beyond the number of candidates
+ *                   hold idx = -1 and dist2 = +inf.  A d2 that is not finite (inf or NaN in a row) is never listed.
+ *   la_realism_f32  radius2 float64 [nx] (device): the squared radius of the sphere around bank row i; a negative value drops the
+ *                   sphere.  score2[j] = max over the kept i of radius2[i] / d2(q_j, x_i), the quotient in float64; d2 == 0 on a kept
+ *                   sphere gives +inf; arg int32 [nq] is the maximising i, ties to the lower i.  No kept sphere: score2 = 0, arg = -1.
+ *                   The same tile loop as la_knn_f32 with another selection key, k = 1.
+ * The grid is blocks of 64 query rows x la_knn_col_splits(nq, nx) chunks of bank columns (a host rule that brings the launch to
+ * 512 workgroups or somewhat more, at most 64 chunks; 0 for sizes the launch refuses), so a batch of 8 queries against a bank of thousands
+ * still fills the chip.  A workgroup walks its chunk tile by tile and keeps the sorted k-list of each of its rows in LDS; a finish
+ * launch ranks the candidates of the chunks.  No atomics, no host synchronisation, nothing allocated: the entries can be captured in
+ * a graph and two runs give the same bits.
+ * scratch: la_knn_scratch_bytes(nq, nx, D, k) bytes, 8-byte aligned, any contents (the float64 norms of both sides and the chunks'
+ * lists; non-decreasing in every argument; 0 for sizes the entries refuse); la_realism_f32 needs the size for k = 1.
+ * k outside 1 .. 32, nq or nx < 1, D < 1, null pointers and exclude_self with nq != nx are LA_ERR_ARG, a smaller scratch_bytes is
+ * LA_ERR_WORKSPACE, all before anything is launched. */
+int la_knn_col_splits(long nq, long nx);
+size_t la_knn_scratch_bytes(long nq, long nx, int D, int k);
+int la_knn_f32(const float* q, long nq, const float* x, long nx, int D, int k, int exclude_self, double* dist2, int* idx, void* scratch,
+               size_t scratch_bytes, la_stream_t stream);
+int la_realism_f32(const float* q, long nq, const float* x, long nx, int D, const double* radius2, double* score2, int* arg,
+                   void* scratch, size_t scratch_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Paired image metrics (no reference counterpart): what describes a PAIR of images.  Images are float32 [N][C][H][W]; pair p is

@@ -24,15 +24,10 @@
 //   la_fd_finish_f64        the vector norms (= singular values) and their sum.
 // Every float64 sum is thread-strided and then a fixed tree (la_block_tree_sum_256): no float atomics anywhere, two runs give the same bits.
 // The only atomic is the integer count of rotations.
-#include "la_common.h"
+#include "la_f64_tile.h"      // FD_T, FD_KC and the tile product, shared with la_knn.hip
 
 #include <math.h>
 
-typedef double fd_f64x4 __attribute__((ext_vector_type(4)));
-
-#define FD_T 64              // tile of C per workgroup
-#define FD_KC 32             // k per LDS chunk
-#define FD_LD (FD_KC + 1)    // doubles per LDS row: the 16 rows of a fragment read land on distinct banks
 #define FD_ROWS 64           // rows per column-sum chunk
 #define FD_MAX_N 8192
 
@@ -142,55 +137,23 @@ __global__ __launch_bounds__(256) void la_fd_gram_kernel(const float* __restrict
                                                         double* __restrict__ V, int pad) {
     __shared__ double Ps[FD_T][FD_LD];
     __shared__ double Qs[FD_T][FD_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int l15 = lane & 15, l4 = lane >> 4;
+    const int tid = threadIdx.x;
+    const FdLane t = fd_tile_lane();
     const long i0 = (long)blockIdx.y * FD_T, j0 = (long)blockIdx.x * FD_T;
-    // loader roles: 32 threads per tile row (one k each), tile rows tid / 32 + 8 pass
-    const int lk = tid & 31, lr = tid >> 5;
+    const int lk = tid & 31, lr = tid >> 5;          // loader roles
     fd_f64x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
-    for (int k0 = 0; k0 < D; k0 += FD_KC) {
-        const int k = k0 + lk;
-        const bool in = k < D;
-        const double mp = in ? mup[k] : 0.0, mq = in ? muq[k] : 0.0;
-#pragma unroll
-        for (int pass = 0; pass < FD_T / 8; ++pass) {
-            const int r = lr + 8 * pass;
-            const long gi = i0 + r < np ? i0 + r : np - 1;
-            const long gj = j0 + r < nq ? j0 + r : nq - 1;
-            Ps[r][lk] = in ? (double)p[gi * D + k] - mp : 0.0;
-            Qs[r][lk] = in ? (double)q[gj * D + k] - mq : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < FD_KC / 4; ++ks) {
-            const int kk = ks * 4 + l4;
-            double a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = Ps[wm * 32 + i * 16 + l15][kk];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = Qs[wn * 32 + j * 16 + l15][kk];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    fd_tile_zero(acc);
+    // staging and fragments: la_f64_tile.h
+    fd_tile_loop<true>(Ps, Qs, p, np, mup, i0, q, nq, muq, j0, D, lk, lr,
+                       [&](const double (*P)[FD_LD], const double (*Q)[FD_LD]) { fd_tile_mma(P, Q, acc, t); });
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const long col = j0 + wn * 32 + j * 16 + l15;
+            const long col = j0 + fd_tile_col(t, j);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const long row = i0 + wm * 32 + i * 16 + l4 + 4 * r;
+                const long row = i0 + fd_tile_row(t, i, r);
                 if (row < np && col < nq) V[row * nq + col] = acc[i][j][r];
             }
         }

@@ -11,6 +11,9 @@ everything downstream of detector features.
                                the cross-Gram matrix by Jacobi sweeps on the GPU (la_frechet.hip), exact where N < D
   compute_dc_from_features     (not in the reference) density and coverage, Naeem et al., ICML 2020 (the `prdc` package)
   compute_prdc_from_features   precision, recall, density and coverage in one dict
+  knn_from_features            (not in the reference) the k nearest bank rows of every query row, float64 on float32 features (la_knn_f32)
+  compute_realism_from_features        realism score per generated sample, Kynkaanniemi et al. 2019, section 5 (la_realism_f32)
+  compute_authenticity_from_features   authenticity, Alaa et al. 2022: the share of generated samples that are not near-copies
   compute_feature_stats_for_images        images -> FeatureStats through a `synthesis.DetectorEngine` (metric_utils.py:314-320)
   compute_feature_stats_for_aug_dataset   metrics/metric_utils.py:264-328: the `img_aug/` pickles of the reference's drivers
   compute_metrics_from_images             precision / recall / density / coverage / KID of two image sets
@@ -275,7 +278,12 @@ def compute_kid_from_features(real_features, gen_features, num_subsets=100, max_
     return kid
 
 
-FD_MAX_SMALL_SIDE = 8192          # la_frechet.hip rotates min(Ng, Nr) vectors; beyond this the moments route is the right one
+def _f64_scratch(nbytes, dev):
+    """float64 view of `nbytes` bytes of workspace or scratch for the float64 entries (Frechet distance, neighbour queries)"""
+    return _lib.workspace(nbytes, dev, torch.float64)
+
+
+FD_MAX_SMALL_SIDE = 8192        # la_frechet.hip rotates min(Ng, Nr) vectors; beyond this the moments route is the right one
 
 
 def compute_fd_from_features(real_features, gen_features, device='cuda:0', return_details=False, max_sweeps=30):
@@ -312,7 +320,7 @@ def compute_fd_from_features(real_features, gen_features, device='cuda:0', retur
     real, gen = _f32_features(real_features, dev), _f32_features(gen_features, dev)
     n, m = min(ng, nr), max(ng, nr)
     ws_bytes = lib.la_fd_workspace_bytes(ng, nr, D)
-    ws = _lib.workspace(ws_bytes, dev, torch.float64)          # the n' vectors of m doubles come first
+    ws = _f64_scratch(ws_bytes, dev)          # the n' vectors of m doubles come first
     out = torch.empty([4 + n], dtype=torch.float64, device=dev)                # terms [4], singular values [n]
     rot = torch.empty([1], dtype=torch.int32, device=dev)
     sweeps = 0
@@ -396,6 +404,113 @@ def compute_prdc_from_features(real_features, gen_features, nhood_size=5, device
 
 
 # ------------------------------------------------------------------------------------------------------------
+# questions about a SINGLE sample (la_knn.hip; float64 arithmetic on the float32 features, no CPU fallback)
+KNN_MAX_K = 32
+
+
+def _query_features(device, **named):
+    """The device and the float32 device copies of [N, D] feature arrays that must agree in D, in the order given."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); got device ' + str(dev))
+    shapes = {n: tuple(np.shape(f)) for n, f in named.items()}
+    if any(len(s) != 2 or s[0] < 1 or s[1] < 1 for s in shapes.values()) or len({s[1] for s in shapes.values()}) != 1:
+        raise ValueError(f'features must be non-empty [N, D] arrays of one D: {shapes}')
+    if not torch.cuda.is_available():
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); none is available')
+    return dev, [_f32_features(f, dev) for f in named.values()]
+
+
+def _knn_device(query, bank, k, exclude_self):
+    """la_knn_f32 on float32 device tensors -> (dist2 float64 [nq, k], idx int32 [nq, k]) on the device"""
+    lib = _lib.load()
+    dev, (nq, D), nx = query.device, query.shape, bank.shape[0]
+    dist2 = torch.empty([nq, k], dtype=torch.float64, device=dev)
+    idx = torch.empty([nq, k], dtype=torch.int32, device=dev)
+    nbytes = lib.la_knn_scratch_bytes(nq, nx, D, k)
+    scratch = _f64_scratch(nbytes, dev)
+    with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
+        _lib.check(lib.la_knn_f32(_lib.ptr(query), nq, _lib.ptr(bank), nx, D, k, int(bool(exclude_self)), _lib.ptr(dist2), _lib.ptr(idx),
+                                  _lib.ptr(scratch), nbytes, _lib.stream_ptr()), 'knn')
+    return dist2, idx
+
+
+def knn_from_features(query, bank, k, exclude_self=False, device='cuda:0'):
+    """The `k` nearest rows of `bank` for every row of `query` ([N, D] numpy arrays or tensors of any float dtype, computed from their
+    float32 values): (dist float64 [nq, k] ascending, idx int64 [nq, k]) as numpy arrays -- the Euclidean distance, the square root
+    of la_knn_f32's d2 = max(0, |q|^2 + |x|^2 - 2 q.x) with all three sums in float64 (off the exact value by at most
+    (2 D + 4) 2^-53 (|q|^2 + |x|^2)).  The order is (distance, index): of two equally distant rows the lower index comes first.
+    exclude_self=True (query and bank of one length: the same set) leaves row i out of the neighbours of query i.  Where a query has
+    fewer than k candidates the remaining slots hold idx = -1 and dist = inf.  1 <= k <= 32.  The distance matrix is never built and
+    two calls give the same bits.  (idx, dist) is the `precomputed_knn` form of a UMAP of the latents.  There is no CPU fallback."""
+    if int(k) != k or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f'k must lie in 1 .. {KNN_MAX_K} (got {k})')
+    dev, (q, x) = _query_features(device, query=query, bank=bank)
+    if exclude_self and q.shape[0] != x.shape[0]:
+        raise ValueError(f'exclude_self needs query and bank of one length (got {q.shape[0]} and {x.shape[0]})')
+    dist2, idx = _knn_device(q, x, int(k), exclude_self)
+    return np.sqrt(dist2.cpu().numpy()), idx.cpu().numpy().astype(np.int64)
+
+
+def compute_realism_from_features(real_features, gen_features, nhood_size=3, keep_fraction=0.5, device='cuda:0', return_details=False):
+    """Realism score of every generated sample (Kynkaanniemi et al., "Improved Precision and Recall Metric for Assessing Generative
+    Models", NeurIPS 2019, section 5): float64 [ng],
+        realism[j] = max over the kept real i of radius[i] / dist(gen_j, real_i)
+    radius[i] is the distance of real i to its `nhood_size`-th nearest OTHER real sample (knn of the reals among themselves with
+    exclude_self).  Only the ceil(keep_fraction nr) spheres with the smallest radii are kept, ties by lower index: the paper prunes
+    the large spheres of outliers at its 0.5.  A generated sample that equals a kept real one scores inf.  With keep_fraction=1,
+    realism >= 1 is exactly "inside some real sphere", the membership behind `precision` -- here in float64 arithmetic on the float32
+    features (la_realism_f32: the quotient of squared distances, then one square root), where compute_pr_from_features stays on the
+    reference's float16 distances and float16 radii; near a sphere's surface the two can differ.  1 <= nhood_size <= min(32, nr - 1).
+    Two calls give the same bits.  There is no CPU fallback.
+    return_details=True: (realism, {'radii': float64 [nr], 'kept': bool [nr], 'arg': int64 [ng], the real sample whose sphere gives
+    the score (ties to the lower index)})."""
+    dev, (real, gen) = _query_features(device, real=real_features, gen=gen_features)
+    nr, ng, D = real.shape[0], gen.shape[0], real.shape[1]
+    if int(nhood_size) != nhood_size or not 1 <= nhood_size <= min(KNN_MAX_K, nr - 1):
+        raise ValueError(f'nhood_size must lie in 1 .. min({KNN_MAX_K}, nr - 1) = {min(KNN_MAX_K, nr - 1)} (got {nhood_size} with nr = {nr})')
+    if not 0 < keep_fraction <= 1:
+        raise ValueError(f'keep_fraction must lie in (0, 1] (got {keep_fraction})')
+    lib = _lib.load()
+    radius2 = _knn_device(real, real, int(nhood_size), True)[0][:, int(nhood_size) - 1].cpu().numpy()
+    kept = np.zeros([nr], dtype=bool)
+    kept[np.argsort(radius2, kind='stable')[:int(np.ceil(keep_fraction * nr))]] = True
+    r2 = torch.from_numpy(np.where(kept, radius2, -1.0)).to(dev)          # a negative radius drops the sphere
+    score2 = torch.empty([ng], dtype=torch.float64, device=dev)
+    arg = torch.empty([ng], dtype=torch.int32, device=dev)
+    nbytes = lib.la_knn_scratch_bytes(ng, nr, D, 1)
+    scratch = _f64_scratch(nbytes, dev)
+    with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
+        _lib.check(lib.la_realism_f32(_lib.ptr(gen), ng, _lib.ptr(real), nr, D, _lib.ptr(r2), _lib.ptr(score2), _lib.ptr(arg),
+                                      _lib.ptr(scratch), nbytes, _lib.stream_ptr()), 'realism')
+    realism = np.sqrt(score2.cpu().numpy())
+    if return_details:
+        return realism, dict(radii=np.sqrt(radius2), kept=kept, arg=arg.cpu().numpy().astype(np.int64))
+    return realism
+
+
+def compute_authenticity_from_features(real_features, gen_features, device='cuda:0', return_details=False):
+    """Authenticity (Alaa et al., "How Faithful is your Synthetic Data?", ICML 2022): the share of generated samples that are not
+    near-copies of a real one.  For generated j with nearest real i*: d_gen = dist(gen_j, real_i*), d_real = the distance of real i*
+    to its nearest other real; j is authentic iff d_gen > d_real -- a copy sits closer to its source than any other real sample does.
+    Distances as in knn_from_features (float64 on the float32 features; a float16 distance has no digits left at the distance of a
+    near-copy).  Needs at least 2 real samples.  Two calls give the same bits.  There is no CPU fallback.
+    return_details=True: (authenticity, {'authentic': bool [ng], 'nearest': int64 [ng] (i*), 'd_gen', 'd_real': float64 [ng]})."""
+    dev, (real, gen) = _query_features(device, real=real_features, gen=gen_features)
+    if real.shape[0] < 2:
+        raise ValueError('authenticity needs at least 2 real samples')
+    d2g, ig = _knn_device(gen, real, 1, False)
+    d2r, _ = _knn_device(real, real, 1, True)
+    nearest = ig[:, 0].cpu().numpy().astype(np.int64)
+    d_gen, d_real = np.sqrt(d2g[:, 0].cpu().numpy()), np.sqrt(d2r[:, 0].cpu().numpy())[nearest]
+    authentic = d_gen > d_real
+    authenticity = float(authentic.mean())
+    if return_details:
+        return authenticity, dict(authentic=authentic, nearest=nearest, d_gen=d_gen, d_real=d_real)
+    return authenticity
+
+
+# ------------------------------------------------------------------------------------------------------------
 # images -> detector features -> FeatureStats (synthesis.DetectorEngine; no CPU fallback)
 def _batch_images(batch, mode):
     if isinstance(batch, dict):
@@ -447,10 +562,12 @@ def compute_feature_stats_for_aug_dataset(datadir, mode, detector, max_items=Non
 
 
 def compute_metrics_from_images(real_batches, gen_batches, detector, nhood_size=3, mode=None, max_items=None, kid_num_subsets=100,
-                                kid_max_subset_size=1000, kid_seed=0, frechet=False):
+                                kid_max_subset_size=1000, kid_seed=0, frechet=False, realism=False, authenticity=False):
     """{'precision', 'recall', 'density', 'coverage', 'kid'} of generated against real images, through `detector` and the functions
     above (precision_recall.py:36-85 with nhood_size=3 is the reference's pr50k3).  frechet=True adds 'fd', the Frechet distance of the
-    same detector features (compute_fd_from_features; with the VGG16 detector it is not the published Inception FID)."""
+    same detector features (compute_fd_from_features; with the VGG16 detector it is not the published Inception FID).  realism=True
+    adds 'realism', the mean realism score of the generated images (compute_realism_from_features with this nhood_size), and
+    authenticity=True adds 'authenticity' (compute_authenticity_from_features), both from the same features."""
     real = compute_feature_stats_for_images(real_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
     gen = compute_feature_stats_for_images(gen_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
     out = compute_prdc_from_features(real, gen, nhood_size=nhood_size, device=detector.device)
@@ -458,6 +575,10 @@ def compute_metrics_from_images(real_batches, gen_batches, detector, nhood_size=
                                            device=detector.device)
     if frechet:
         out['fd'] = compute_fd_from_features(real, gen, device=detector.device)
+    if realism:
+        out['realism'] = float(compute_realism_from_features(real, gen, nhood_size=nhood_size, device=detector.device).mean())
+    if authenticity:
+        out['authenticity'] = compute_authenticity_from_features(real, gen, device=detector.device)
     return out
 
 
