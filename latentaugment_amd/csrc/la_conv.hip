@@ -175,7 +175,8 @@ __global__ __launch_bounds__(256) void la_conv_igemm_kernel(LaConvArgs a) {
         stage(0);
     }
     __syncthreads();
-    // double-buffered LDS, one barrier per chunk: loads for chunk i+1 are in flight while chunk i feeds the MFMAs
+    // double-buffered LDS, one barrier per chunk: loads for chunk i+1 are in flight while chunk i feeds the MFMAs.  This is the loop of
+    // la_f32_tile.h (la_tile_pipeline + la_f32_tile_mma) written out: taken from there it costs this kernel registers (see that header)
     for (int ci = ci_beg; ci < ci_end; ++ci) {
         const int buf = (ci - ci_beg) & 1;
         if (ci + 1 < ci_end) prefetch(ci + 1);

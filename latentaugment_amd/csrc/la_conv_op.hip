@@ -13,6 +13,7 @@
 //   generic  kernels up to 7x7, strides up to 8, any groups / channel counts: one thread per output (forward), one workgroup per
 //            dW element with a fixed-order tree reduction (weight gradient); double accumulators.  Correct, not fast.
 #include "la_conv.h"
+#include "la_f32_tile.h"
 #include <string.h>
 
 #define LA_OP_MAX_K 7
@@ -145,15 +146,13 @@ __global__ __launch_bounds__(256) void la_conv_generic_wgrad_kernel(WgArgs a) {
 // chunks of 16 consecutive pixels of ONE grid row (so a chunk's loads are 64-byte runs of P and, at stride 1, of Q, and the row / sample
 // decode is once per chunk, not per element); chunks beyond the row's end, image edges and padding load zeros, ragged Ag / N tails are
 // masked.  The next chunk's global loads are in flight while the current one feeds the MFMAs (register staging, two LDS buffers, one
-// barrier per chunk, as la_conv_igemm_kernel).  LDS rows are [k][128 + 4] floats: the MFMA operand reads (32 consecutive floats per
+// barrier per chunk: la_tile_pipeline of la_f32_tile.h).  LDS rows are [k][128 + 4] floats: the MFMA operand reads (32 consecutive floats per
 // half-wave) and the loader's transposing writes (lane = k, 4-float row step) both spread over all banks.
 // blockIdx = (n tile * mtiles + m tile, group, K slice); the slice's raw tile goes to part[slice][group][Ag][N].
 #define WG_T 128
 #define WG_KC 16
 #define WG_LD (WG_T + 4)
 #define WG_RPT (WG_T / 16)     // rows per thread of each operand tile
-
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256) void la_conv_wgrad_mfma_kernel(WgArgs a) {
     __shared__ __attribute__((aligned(16))) float As[2][WG_KC][WG_LD];
@@ -186,8 +185,8 @@ __global__ __launch_bounds__(256) void la_conv_wgrad_mfma_kernel(WgArgs a) {
         qdy[j] = ky - a.py; qdx[j] = kx - a.px;
     }
 
-    const long c_beg = (long)blockIdx.z * a.per;
-    const long c_end = c_beg + a.per < a.nchunk ? c_beg + a.per : a.nchunk;
+    long c_beg, c_end;
+    la_slice_range<long>(blockIdx.z, a.per, a.nchunk, &c_beg, &c_end);
 
     float areg[WG_RPT], breg[WG_RPT];
     auto prefetch = [&](long ci) {
@@ -222,38 +221,10 @@ __global__ __launch_bounds__(256) void la_conv_wgrad_mfma_kernel(WgArgs a) {
         }
     };
 
-    wg_f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    if (c_beg < c_end) {
-        prefetch(c_beg);
-        stage(0);
-    }
-    __syncthreads();
-    for (long ci = c_beg; ci < c_end; ++ci) {
-        const int buf = (int)(ci - c_beg) & 1;
-        if (ci + 1 < c_end) prefetch(ci + 1);
-#pragma unroll
-        for (int kp = 0; kp < WG_KC / 2; ++kp) {
-            float av[2], bv[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) av[i] = As[buf][2 * kp + lh][wm * 64 + i * 32 + l31];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bv[j] = Bs[buf][2 * kp + lh][wn * 64 + j * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
-        if (ci + 1 < c_end) stage(buf ^ 1);
-        __syncthreads();
-    }
+    la_f32x16 acc[2][2];
+    la_f32_tile_zero(acc);
+    la_tile_pipeline(c_beg, c_end, prefetch, stage,
+                     [&](int buf, long) { la_f32_tile_mma<WG_KC>(As, Bs, buf, wm * 64, wn * 64, l31, lh, acc); });
 
     float* part = a.part + ((long)blockIdx.z * a.groups + grp) * a.Ag * a.N;
 #pragma unroll
@@ -275,8 +246,7 @@ __global__ __launch_bounds__(256) void la_conv_wgrad_finish_kernel(WgArgs a) {
     const long total = (long)a.groups * a.Ag * a.N;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
-    float s = a.part[idx];
-    for (int k = 1; k < a.ks; ++k) s += a.part[(long)k * total + idx];
+    const float s = la_slices_sum(a.part, idx, total, a.ks);
     const int taps = a.kh * a.kw;
     const int n = (int)(idx % a.N);
     const long ch = idx / a.N;                        // grp * Ag + m

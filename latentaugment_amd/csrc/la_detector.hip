@@ -6,6 +6,7 @@
 // The index arithmetic of both is in la_detector_index.h (host and device).
 #include "la_common.h"
 #include "la_detector_index.h"
+#include "la_f32_tile.h"
 
 // ------------------------------------------------------------------------------------------------------------
 struct LaDetAffine { float scale[3], shift[3]; };
@@ -85,12 +86,11 @@ extern "C" int la_detector_prep_f32(const float* img, float* out, int N, int C, 
 // operand (columns = features), so an accumulator register row is a batch row and its 32 lanes are 32 consecutive features (coalesced
 // stores).  K is walked in chunks of LA_FC_KC = 32: loads of the next chunk (16 bytes per lane along K where K % 4 == 0 and the
 // pointers allow, else scalar) are in flight while the current one feeds the MFMAs (register staging, two LDS buffers, one barrier per
-// chunk, as la_conv_wgrad_mfma_kernel).  LDS rows are [k][tile + 4]: the operand reads are 32 consecutive floats per half-wave.
+// chunk: la_tile_pipeline of la_f32_tile.h).  LDS rows are [k][tile + 4]: the operand reads are 32 consecutive floats per half-wave.
 // Parallelism at O = 4096 (32 feature tiles) comes from K slices (la_fc_plan): a slice's raw tile goes to part[slice][N][O] and
 // la_fc_finish_kernel sums the slices in slice order and applies bias and activation -- no float atomics, the same bits on every run.
 // With one slice the kernel applies them itself.  Ragged N, K and O: loads outside load zeros, stores outside are skipped.
 #define FC_WLD (LA_FC_OT + 4)
-typedef float fc_f32x16 __attribute__((ext_vector_type(16)));
 
 struct FcArgs {
     const float *x, *w, *b;
@@ -112,8 +112,8 @@ __global__ __launch_bounds__(256) void la_fc_mfma_kernel(FcArgs a) {
 
     // loader roles: 8 threads x 4 floats cover a row's chunk; 32 rows per pass, 4 passes for W, NB for x
     const int kq = (tid & 7) * 4, r0 = tid >> 3;
-    const long c_beg = (long)blockIdx.y * a.per;
-    const long c_end = c_beg + a.per < a.nchunk ? c_beg + a.per : a.nchunk;
+    long c_beg, c_end;
+    la_slice_range(blockIdx.y, a.per, a.nchunk, &c_beg, &c_end);
 
     float wreg[4][4], xreg[NB][4];
     auto load4 = [&](const float* row, bool ok, long k, float* dst) {
@@ -150,32 +150,10 @@ __global__ __launch_bounds__(256) void la_fc_mfma_kernel(FcArgs a) {
             for (int q = 0; q < 4; ++q) Xs[buf][kq + q][r0 + 32 * j] = xreg[j][q];
     };
 
-    fc_f32x16 acc[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-    if (c_beg < c_end) {
-        prefetch(c_beg);
-        stage(0);
-    }
-    __syncthreads();
-    for (long ci = c_beg; ci < c_end; ++ci) {
-        const int buf = (int)(ci - c_beg) & 1;
-        if (ci + 1 < c_end) prefetch(ci + 1);
-#pragma unroll
-        for (int kp = 0; kp < LA_FC_KC / 2; ++kp) {
-            const float bv = Ws[buf][2 * kp + lh][wid * 32 + l31];
-            float av[NB];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) av[i] = Xs[buf][2 * kp + lh][i * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < NB; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv, acc[i], 0, 0, 0);
-        }
-        if (ci + 1 < c_end) stage(buf ^ 1);
-        __syncthreads();
-    }
+    la_f32x16 acc[NB][1];
+    la_f32_tile_zero(acc);
+    la_tile_pipeline(c_beg, c_end, prefetch, stage,
+                     [&](int buf, long) { la_f32_tile_mma<LA_FC_KC>(Xs, Ws, buf, 0, wid * 32, l31, lh, acc); });
 
     const long o = o0 + wid * 32 + l31;
     if (o >= a.O) return;
@@ -188,7 +166,7 @@ __global__ __launch_bounds__(256) void la_fc_mfma_kernel(FcArgs a) {
         for (int r = 0; r < 16; ++r) {
             const long n = n0 + i * 32 + la_mfma32_row(r, lh);
             if (n >= a.N) continue;
-            float v = acc[i][r];
+            float v = acc[i][0][r];
             if (direct) { v += bias; if (a.act == LA_ACT_RELU) v = v > 0.f ? v : 0.f; }
             dst[n * a.O + o] = v;
         }
@@ -199,9 +177,7 @@ __global__ __launch_bounds__(256) void la_fc_finish_kernel(FcArgs a) {
     const long total = a.N * a.O;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
-    float s = a.part[idx];
-    for (int k = 1; k < a.ks; ++k) s += a.part[(long)k * total + idx];
-    s += a.b[idx % a.O];
+    float s = la_slices_sum(a.part, idx, total, a.ks) + a.b[idx % a.O];
     if (a.act == LA_ACT_RELU) s = s > 0.f ? s : 0.f;
     a.y[idx] = s;
 }

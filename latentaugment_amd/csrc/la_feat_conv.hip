@@ -3,6 +3,7 @@
 // (augments/criteria/lpips/networks.py:52-84).  Exact fp32 in every precision mode of the feature engine, as the FC ops are: these
 // layers are a twentieth of VGG16's multiply-adds and do not need the split-fp16 path.  No float atomics, no host sync, no allocation.
 #include "la_feat_conv.h"
+#include "la_f32_tile.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // Forward: an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 products), D[co][pixel] = sum_K W[co][K] * col[K][pixel],
@@ -11,15 +12,14 @@
 // the A operand and the pixels the B operand, so an accumulator register row is an output channel and its 32 lanes are 32 consecutive
 // pixels (coalesced NCHW stores).  K is walked in chunks of 32: the im2col gather of the next chunk (8 elements per thread, pixel along
 // the lanes, zero outside the image, the batch and K) and its weight rows are in flight in registers while the current chunk feeds the
-// MFMAs from LDS (two buffers, one barrier per chunk, as la_fc_mfma_kernel).  LDS: Ws[co][k + 1] is written along k and read along co,
-// Xs[k][pixel + 4] is written and read along the pixel: both free of bank conflicts.
+// MFMAs from LDS (two buffers, one barrier per chunk: la_tile_pipeline of la_f32_tile.h).  LDS: Ws[co][k + 1] is written along k and
+// read along co, Xs[k][pixel + 4] is written and read along the pixel: both free of bank conflicts.
 // Small M (the loop's 64 x 64 crop leaves 9 .. 225 pixels in the deep layers, with K in the thousands): K is split over gridDim.y
 // workgroups (fcv_plan); a slice's raw tile goes to part[slice][tile][64][64] and la_featconv_finish_kernel sums the slices in slice
 // order, adds the bias and applies the ReLU -- a fixed order, the same bits on every run.  With one slice the kernel applies them itself.
 #define FCV_CT 64
 #define FCV_PT 64
 #define FCV_KC 32
-typedef float fcv_f32x16 __attribute__((ext_vector_type(16)));
 
 // The same kernel is the data gradient of a stride-1 layer (BWD): a convolution of the masked gradient with the flipped kernel and pad
 // k - 1 - pad, rows of the GEMM = input channels, K = cout * k * k.  In GEMM terms, for both directions: the gathered tensor x is
@@ -59,8 +59,8 @@ __global__ __launch_bounds__(256) void la_featconv_gemm_kernel(FcvArgs a) {
     // weight role: K column wk of the chunk, channel rows wc0 + 8 j of the tile
     const int wk = tid & 31, wc0 = tid >> 5;
 
-    const int c_beg = blockIdx.y * a.per;
-    const int c_end = c_beg + a.per < a.nchunk ? c_beg + a.per : a.nchunk;
+    int c_beg, c_end;
+    la_slice_range(blockIdx.y, a.per, a.nchunk, &c_beg, &c_end);
 
     float xreg[8], wreg[8];
     auto prefetch = [&](int ci) {
@@ -104,27 +104,15 @@ __global__ __launch_bounds__(256) void la_featconv_gemm_kernel(FcvArgs a) {
     };
 
     const int ch = wid & 1, ph = wid >> 1;      // this wave's 32 channels / 32 pixels of the tile
-    fcv_f32x16 acc;
+    la_f32x16 tile[1][1];
+    la_f32_tile_zero(tile);
+    la_f32x16& acc = tile[0][0];
+    // (the header's la_f32_tile_mma reads both operands as [k][col]; Ws is [co][k + 1] here, so the inner product stays written out)
+    la_tile_pipeline(c_beg, c_end, prefetch, stage, [&](int buf, int) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    if (c_beg < c_end) {
-        prefetch(c_beg);
-        stage(0);
-    }
-    __syncthreads();
-    for (int ci = c_beg; ci < c_end; ++ci) {
-        const int buf = (ci - c_beg) & 1;
-        if (ci + 1 < c_end) prefetch(ci + 1);
-#pragma unroll
-        for (int kp = 0; kp < FCV_KC / 2; ++kp) {
-            const float av = Ws[buf][ch * 32 + l31][2 * kp + lh];
-            const float bv = Xs[buf][2 * kp + lh][ph * 32 + l31];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
-        if (ci + 1 < c_end) stage(buf ^ 1);
-        __syncthreads();
-    }
+        for (int kp = 0; kp < FCV_KC / 2; ++kp)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[buf][ch * 32 + l31][2 * kp + lh], Xs[buf][2 * kp + lh][ph * 32 + l31], acc, 0, 0, 0);
+    });
 
     const int pl = ph * 32 + l31;
     if (a.ks > 1) {      // raw tile of this slice: every element of the 64 x 64 block, inside the output or not
@@ -162,8 +150,7 @@ __global__ __launch_bounds__(256) void la_featconv_finish_kernel(FcvArgs a) {
     const long tiles = (long)a.ptiles * a.ctiles;
     const long tile = (long)(co / FCV_CT) * a.ptiles + m / FCV_PT;
     const float* src = a.part + tile * (FCV_CT * FCV_PT) + (co % FCV_CT) * FCV_PT + m % FCV_PT;
-    float s = src[0];
-    for (int k = 1; k < a.ks; ++k) s += src[(long)k * tiles * (FCV_CT * FCV_PT)];
+    float s = la_slices_sum(src, 0, tiles * (FCV_CT * FCV_PT), a.ks);
     const int HWo = a.Ro * a.Ro;
     const int n = (int)(m / HWo);
     const int rem = (int)(m - (long)n * HWo);

@@ -14,11 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include "la_common.h"
+#include "la_f32_tile.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define PR_KMAX 8
+
+// The distance of two rows from their squared norms and their dot product: written once, so that la_pr_tile_kernel and
+// la_dc_tile_kernel give a pair the same bits.
+__device__ __forceinline__ float la_pr_dist(float na, float nb, float dot) { return sqrtf(fmaxf(na + nb - 2.f * dot, 1e-30f)); }
 
 // squared norms of fp16 rows, fp32
 __global__ __launch_bounds__(256) void la_rows_sqnorm_f16_kernel(const _Float16* __restrict__ x, long n, int D, float* __restrict__ out) {
@@ -64,7 +68,7 @@ __global__ __launch_bounds__(256) void la_pr_tile_kernel(const _Float16* __restr
             for (int q = 0; q < PR_KMAX; ++q) best[MODE == 0 ? r : 0][q] = __builtin_huge_valf();
     }
     for (long c0 = 0; c0 < nc; c0 += 128) {
-        f32x16 acc[4];
+        la_f32x16 acc[4];
         const _Float16* bp[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(256) void la_pr_tile_kernel(const _Float16* __restr
             const float rad = (MODE == 1) ? radius[cok ? c : nc - 1] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float d = sqrtf(fmaxf(na[r] + nb - 2.f * acc[j][r], 1e-30f));
+                const float d = la_pr_dist(na[r], nb, acc[j][r]);
                 if (MODE == 0) {
                     // sorted insert into the row's k+1 smallest (ascending), columns past the end never enter
                     float v = cok ? d : __builtin_huge_valf();
@@ -223,8 +227,9 @@ extern "C" int la_feature_moments_f64(const float* x, long n, int D, double* raw
 //   sxx = sum_{i != j} k(x_i, x_j),  syy = sum_{i != j} k(y_i, y_j),  sxy = sum_{i, j} k(x_i, y_j),
 // over the rows x_i = X[ix[s][i]] (mx of them) and y_j = Y[iy[s][j]] (my).  The rows are gathered by index while the tiles are loaded;
 // the m x m kernel matrices live in accumulator registers only: one float64 partial per 128 x 128 tile is all that reaches memory.
-// Arithmetic: the exact fp32 MFMA (v_mfma_f32_32x32x2_f32), as la_conv_wgrad_mfma_kernel: 4 waves (2 x 2) of 64 x 64 = 2 x 2 MFMA tiles,
-// K walked in chunks of 16 through two LDS buffers [k][128 + 4] with the next chunk's global loads in flight, one barrier per chunk.
+// Arithmetic: the exact fp32 MFMA (v_mfma_f32_32x32x2_f32) through the tile loop of la_f32_tile.h: 4 waves (2 x 2) of 64 x 64 = 2 x 2
+// MFMA tiles, K walked in chunks of 16 through two LDS buffers [k][128 + 4] with the next chunk's global loads in flight, one barrier
+// per chunk.
 // An MFMA accumulator is one k-ordered fp32 fma chain, whose rounding error grows like sqrt(chain length); with m as small as 2 nothing
 // averages it out, so a chain runs over KID_SEG chunks (128 k) only and is then added into a second fp32 accumulator (two-level
 // summation: ~2.4e-7 relative on a D = 2048 dot product of non-negative features instead of ~9e-7).
@@ -318,34 +323,14 @@ __global__ __launch_bounds__(256) void la_kid_tile_kernel(KidArgs a) {
         }
     };
 
-    f32x16 acc[2][2], tot[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = tot[i][j][r] = 0.f;
+    la_f32x16 acc[2][2], tot[2][2];
+    la_f32_tile_zero(acc);
+    la_f32_tile_zero(tot);
 
     const int nchunk = (D + KID_KC - 1) / KID_KC;
-    prefetch(0);
-    stage(0);
-    __syncthreads();
-    for (int ci = 0; ci < nchunk; ++ci) {
-        const int buf = ci & 1;
-        if (ci + 1 < nchunk) prefetch(ci + 1);
-#pragma unroll
-        for (int kp = 0; kp < KID_KC / 2; ++kp) {
-            float av[2], bv[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) av[i] = As[buf][2 * kp + lh][wm * 64 + i * 32 + l31];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bv[j] = Bs[buf][2 * kp + lh][wn * 64 + j * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
+    __builtin_assume(nchunk > 0);      // D >= 1 (la_kid_poly3_f32 refuses less): without it the compiler keeps a second copy of the loop
+    la_tile_pipeline(0, nchunk, prefetch, stage, [&](int buf, int ci) {
+        la_f32_tile_mma<KID_KC>(As, Bs, buf, wm * 64, wn * 64, l31, lh, acc);
         if ((ci & (KID_SEG - 1)) == KID_SEG - 1 || ci + 1 == nchunk) {      // end of a chain: fold it into the second level
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -354,9 +339,7 @@ __global__ __launch_bounds__(256) void la_kid_tile_kernel(KidArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.f; }
         }
-        if (ci + 1 < nchunk) stage(buf ^ 1);
-        __syncthreads();
-    }
+    });
 
     const bool diag = kind != 2 && ti == tj;
     const float fD = (float)D;
@@ -459,10 +442,11 @@ extern "C" int la_kid_poly3_f32(const float* x, long nx, const float* y, long ny
 // Grid: x = blocks of 128 generated rows (4 waves x 32), y = column chunks of `chunk` (a multiple of 128) real columns; the number
 // of chunks is the host rule dc_col_splits.  A workgroup walks its chunk in steps of 128 columns, and each step's K range in chunks
 // of DC_KC = 64: the 128 x 64 tiles of both operands go through LDS (two buffers each, the next chunk's global loads in flight during
-// the MFMAs, one barrier per chunk, as la_kid_tile_kernel).  Eight lanes load 128 contiguous bytes of a row, so every cache line that
-// is touched is used whole, and the four waves share one copy of the column tile; rows of 64 + 8 halves (144 bytes) keep the 16-byte
+// the MFMAs, one barrier per chunk: la_tile_pipeline of la_f32_tile.h).  Eight lanes load 128 contiguous bytes of a row, so every
+// cache line that is touched is used whole, and the four waves share one copy of the column tile; rows of 64 + 8 halves (144 bytes) keep the 16-byte
 // fragment reads of 16 consecutive rows on distinct banks.  K past D is filled with zeros (an exact no-op in the accumulator).
-// Every accumulator is the same k-ordered chain as in la_pr_tile_kernel, so a distance has the same bits here and in la_pr_kth_f16.
+// Every accumulator is the same k-ordered chain as in la_pr_tile_kernel and both kernels form the distance with la_pr_dist, so a
+// distance has the same bits here and in la_pr_kth_f16.
 // Row side: every lane counts, for its 16 rows, the columns it sees (one per MFMA tile) in 16 integer registers over the whole chunk;
 // the 32 lanes of a half are summed once at the end and one lane adds the row's total into count[] with an integer atomicAdd.
 // Column side: per step of 128 columns a lane takes the minimum over its 16 rows, the two lane halves are combined by a shuffle, the
@@ -542,18 +526,13 @@ __global__ __launch_bounds__(256) void la_dc_tile_kernel(const _Float16* __restr
             const long c = c0 + p * 32 + lrow;
             pb[p] = cols + (c < nr ? c : nr - 1) * D + lk;
         }
-        f32x16 acc[4];
+        la_f32x16 acc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-        // every read of LDS buffer 0 by the previous step was followed by a barrier
-        prefetch(0);
-        stage(0);
-        __syncthreads();
-        for (int kc = 0; kc < nkc; ++kc) {
-            const int b = kc & 1;
-            if (kc + 1 < nkc) prefetch(kc + 1);
+        // the K loop of the step (la_f32_tile.h; LDS is free on its return, so the next step may stage into buffer 0 at once)
+        la_tile_pipeline(0, nkc, prefetch, stage, [&](int b, int) {
 #pragma unroll
             for (int ks = 0; ks < DC_KC / 16; ++ks) {
                 const f16x8 af = *reinterpret_cast<const f16x8*>(&As[b][wid * 32 + l31][ks * 16 + lh * 8]);
@@ -563,9 +542,7 @@ __global__ __launch_bounds__(256) void la_dc_tile_kernel(const _Float16* __restr
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[j], 0, 0, 0);
                 }
             }
-            if (kc + 1 < nkc) stage(b ^ 1);      // last read in iteration kc - 1, before its barrier
-            __syncthreads();
-        }
+        });
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const long c = c0 + j * 32 + l31;
@@ -575,7 +552,7 @@ __global__ __launch_bounds__(256) void la_dc_tile_kernel(const _Float16* __restr
             float cm = __builtin_huge_valf();
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float d = sqrtf(fmaxf(na[r] + nb - 2.f * acc[j][r], 1e-30f));
+                const float d = la_pr_dist(na[r], nb, acc[j][r]);
                 const bool ok = cok && ((rowok >> r) & 1u);
                 if (ok && d <= rad) ++cnt[r];
                 cm = fminf(cm, ok ? d : __builtin_huge_valf());

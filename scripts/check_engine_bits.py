@@ -10,7 +10,13 @@ f32, bf16x3 and f16x2:
                  backward above 64^2; logits and image gradient.  And 16^2, B = 8, MinibatchStd group 4
   feature net    conv, conv, tap, maxpool, conv, tap on a 3-channel 12^2 input, N = 3: the padded first-conv gradient copy, both sources
                  of the ReLU mask; features and input gradient
-  detector       conv, maxpool, conv, fc + ReLU, fc: features
+  detector       conv, maxpool, conv, fc + ReLU, fc: features (its fc layers are 3 x 128 -> 12 and 3 x 12 -> 5: la_fc_mfma_kernel<1, true>,
+                 one slice, 4 chunks and 1)
+  fc             la_fc_bias_act_f32 itself, f32 only: (N, K, O) = (3, 70, 5), one 32-row block, scalar loads, 3 chunks in one slice, ragged
+                 everywhere; (33, 288, 130), two blocks, 16-byte loads, 9 chunks in slices of 5 and 4, two output tiles, the finish pass
+  general convs  f32 only, 13^2 input, N = 2: conv 3 -> 8 k 5 stride 2 pad 2, 3x3 stride-2 pool (ceil), conv 8 -> 32, conv 32 -> 8, tap.  The
+                 last conv's forward and the 8 -> 32 layer's data gradient split K (288 = 9 chunks in 2 slices), the others run in one slice,
+                 the first layer takes the gather backward; features and input gradient
   loop           LatentAug above them (la_latent_opt.hip): every branch of its schedule decision.  The 64^2 generator, a 64^2 discriminator
                  (channel cap 32), the feature net at crop_size_aug 12, banks W [16], X [8], fea [8]; 3 steps, const noise, f16x2; one loop per
                  handle (stream_lanes 1, so that a handle re-captures) except in c.  img and w_aug of every batch of
@@ -87,6 +93,18 @@ def dump(lib_path, out_path):
         keep(f'feat/{mode}/f', f)
         keep(f'feat/{mode}/gx', F.backward(torch.randn(f.shape, generator=torch.Generator().manual_seed(1)).to(dev)))
         keep(f'detector/{mode}/f', synthesis.FeatureEngine(d_ops, dev, in_res=8, max_batch=3, precision=mode).forward(xd))
+    for N, K, O in ((3, 70, 5), (33, 288, 130)):
+        for relu in (False, True):
+            keep(f'fc/{N}x{K}x{O}/relu{int(relu)}', synthesis.fc_bias_act(draw(N, K), draw(O, K) * K ** -0.5, draw(O), relu=relu))
+
+    def convg(cin, cout, k, stride, pad):
+        return ('conv', draw(cout, cin, k, k) * (2.0 / (k * k * cin)) ** 0.5, draw(cout) * 0.1, stride, pad)
+
+    g_ops = [convg(3, 8, 5, 2, 2), ('maxpool3', True), convg(8, 32, 3, 1, 1), convg(32, 8, 3, 1, 1), ('tap', draw(8).abs())]
+    Fg = synthesis.FeatureEngine(g_ops, dev, in_res=13, max_batch=2, precision='f32')
+    f = Fg.forward(draw(2, 3, 13, 13))
+    keep('featconv/f', f)
+    keep('featconv/gx', Fg.backward(torch.randn(f.shape, generator=torch.Generator().manual_seed(2)).to(dev)))
     loop_cases(dev, lib, g_sd, meta, f_ops, draw, keep)
     torch.cuda.synchronize()
     np.savez(out_path, **res)

@@ -5,7 +5,8 @@ anything loads it, as scripts/bench_with_lib.py does); this process only compare
 float64: bias_act for the nine activations, with a clamp and without, forward, first order (dx, db) and second order, the bias on axis 1
 of a 4-D tensor and on the last axis, aligned and at a one-element storage offset; upfirdn2d / filter2d / upsample2d / downsample2d
 forward and dx with setup_filter([1,3,3,1]), a dense 3x5 filter at gain 1.7 and a separable 12-tap filter.  In float32: conv2d / conv_transpose2d forward,
-dx and dw on split-K and direct grids, stride 2 and groups.  Inputs: seeded CPU generator."""
+dx and dw on split-K and direct grids, stride 2 and groups; the KID sums and MMD^2 and the density / coverage outputs (radii, count, nearest) at
+the smallest shapes that reach every form of their tile kernels.  Inputs: seeded CPU generator."""
 import os
 import subprocess
 import sys
@@ -80,6 +81,22 @@ def dump(lib_path, out_path):
         dx, dw = torch.autograd.grad(y, [x, w], draw(list(y.shape), torch.float32))
         for name, t in zip(('y', 'dx', 'dw'), (y, dx, dw)):
             keep(f'conv/{cname}/{name}', t)
+    # (dw of every case above runs la_conv_wgrad_mfma_kernel; sk_8x8 in 2 K slices on a grid 8 wide, direct_40x40 in 15 on one 40 wide:
+    #  more than one slice and a width that is no multiple of the 16-pixel chunk are both there)
+    # the metric entries on the tile loop of la_f32_tile.h.  KID: S = 2, mx = 130 (an off-diagonal and a diagonal xx tile), my = 3 (a
+    # ragged y side); D = 130: scalar loads, 9 chunks (one fold after chunk 7, a ragged last chunk), D = 256: 16-byte loads, two full chains
+    from latentaugment_amd import metrics
+    ix = torch.randint(0, 140, [2, 130], generator=gen).numpy()
+    iy = torch.randint(0, 5, [2, 3], generator=gen).numpy()
+    for D in (130, 256):
+        _, det = metrics.compute_kid_from_features(draw([5, D], torch.float32), draw([140, D], torch.float32), indices=(ix, iy), device=dev,
+                                                   return_details=True)
+        res[f'kid/{D}/sums'], res[f'kid/{D}/mmd2'] = det['sums'].view(np.uint8).ravel(), det['mmd2'].view(np.uint8).ravel()
+    # density and coverage: la_pr_kth_f16 (radii) and la_dc_count_f16 (count, nearest) at 130 x 130 x 80: two row blocks, D past one
+    # 64-wide K chunk with a ragged second one
+    _, _, det = metrics.compute_dc_from_features(draw([130, 80], torch.float32), draw([130, 80], torch.float32), device=dev, return_details=True)
+    for name in ('radii', 'count', 'nearest'):
+        res[f'dc/{name}'] = det[name].view(np.uint8).ravel()
     torch.cuda.synchronize()
     np.savez(out_path, **res)
 

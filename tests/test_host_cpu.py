@@ -560,3 +560,23 @@ def test_reductions_and_noise_stream_have_one_home():
             philox.append(name)
         assert not re.findall(r'\b(?:la_proj_philox4x32_10|la_geom_philox4x32_10|la_wave_sum_f64|fd_block_sum|kid_block_sum)\b', text), name
     assert philox == ['la_rng.h'] and found == kept
+
+
+def test_exact_fp32_tile_loop_has_one_home():
+    """The LDS-staged exact-fp32 MFMA step (v_mfma_f32_32x32x2_f32) is written once, in csrc/la_f32_tile.h (la_f32_tile_mma), beside the
+    pipeline that feeds it.  `kept` counts the written-out steps that stay, per file: la_featconv_gemm_kernel, whose weight tile is
+    [co][k + 1] and not [k][col], and la_conv_igemm_kernel, which the shared form costs 52 VGPRs and global loads turned flat (DESIGN.md,
+    'One home for the exact-fp32 tile loop').  The vector type of the 32 x 32 fp32 accumulator is defined there and, for the 16-bit
+    kernels, in la_conv_device.h.  The list is exact: a new copy fails here, and so does a listed site that has gone."""
+    import glob
+    csrc = os.path.join(ROOT, 'latentaugment_amd', 'csrc')
+    kept = {'la_f32_tile.h': 1, 'la_feat_conv.hip': 1, 'la_conv.hip': 1}
+    found, typedefs = {}, []
+    for path in sorted(glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h'))):
+        text, name = open(path).read(), os.path.basename(path)
+        n = text.count('__builtin_amdgcn_mfma_f32_32x32x2f32')
+        if n:
+            found[name] = n
+        if re.search(r'typedef\s+float\s+\w+\s+__attribute__\(\(ext_vector_type\(16\)\)\)', text):
+            typedefs.append(name)
+    assert found == kept and typedefs == ['la_conv_device.h', 'la_f32_tile.h']
