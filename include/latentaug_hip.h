@@ -893,6 +893,32 @@ int la_realism_f32(const float* q, long nq, const float* x, long nx, int D, cons
                    void* scratch, size_t scratch_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Gram-matrix style distance and content distance of activation pairs: NSTLoss of augments/criteria/nst/nst.py:7-35 on the taps
+ * of VGG19Net (networks.py:60-70).  f float32 [2P][C][HW]; rows p and p + P are a pair.  With G = F F^T / HW for F [C][HW]:
+ *   style[p]   = mean over the C^2 entries of (G1 - G2)^2
+ *   content[p] = mean over the C HW entries of (f1 - f2)^2          (content may be NULL)
+ * computed from D = f1 - f2 and S = f1 + f2, both formed in float32 while loading: E = D S^T + S D^T = 2 HW (G1 - G2),
+ * style = sum E^2 / (4 HW^2 C^2), content = sum D^2 / (C HW).  d(f, f) is exactly 0 and swapping the halves gives the same bits.
+ * E: exact fp32 MFMA products in k-ordered chains over 128 x 128 tiles with I <= J; K = HW is split into la_gram_pair_slices(C, HW)
+ * slices, a function of (C, HW) only, whose partials are added in slice order: a pair gives the same bits alone and at any
+ * position of a batch.  Squares and sums in float64 in a fixed order, one division: no float atomics, two runs give the same bits;
+ * no host sync, no allocation.  scratch: la_gram_pair_scratch_bytes(P, C, HW) bytes, 8-byte aligned, any contents (written before it
+ * is read; non-decreasing in P; 0 for what the entry refuses: P outside 1 .. 65535, C outside 1 .. 8192, HW outside 1 .. 2^26).
+ * Bad shapes and null pointers are LA_ERR_ARG, a smaller scratch_bytes is LA_ERR_WORKSPACE, all before anything is launched.
+ * la_feat_style_distance (tap lists only): the trunk once on xy [2P][in_ch][in_res^2] with the entry above as its tap step, on the
+ * raw activation each LA_FEAT_TAP sees (lin is not read): style, content float64 [P][ntaps].  Same contract as
+ * la_feat_pair_distance: it overwrites the activations of an earlier la_feat_forward (la_feat_backward then refuses until the next
+ * forward); la_feat_style_scratch_bytes is 0 for a detector list or 2P > max_batch, which the entry refuses with LA_ERR_ARG.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t la_gram_pair_scratch_bytes(int P, int C, int HW);
+int la_gram_pair_slices(int C, int HW);
+int la_gram_pair_dist_f32(const float* f, int P, int C, int HW, double* style, double* content, void* scratch, size_t scratch_bytes,
+                          la_stream_t stream);
+size_t la_feat_style_scratch_bytes(const la_feat* h, int P);
+int la_feat_style_distance(la_feat* h, const float* xy, int P, double* style, double* content, void* scratch, size_t scratch_bytes,
+                           la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Paired image metrics (no reference counterpart): what describes a PAIR of images.  Images are float32 [N][C][H][W]; pair p is
  * (x[ix[p]], y[iy[p]]), ix / iy int32 device arrays of length P (NULL: p itself; the caller vouches for the range of the indices).
  *

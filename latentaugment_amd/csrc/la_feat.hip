@@ -22,6 +22,7 @@
 
 #include "la_conv.h"
 #include "la_feat_conv.h"
+#include "la_gram.h"
 #include "la_modconv.h"
 #include "la_style.h"
 
@@ -792,6 +793,43 @@ extern "C" int la_feat_pair_distance(la_feat* h, const float* xy, int P, double*
     hipLaunchKernelGGL(la_pair_dist_finish_kernel, dim3(t.n, P), dim3(64), 0, stream, (const double*)ws, dist, t);
     LA_CHECK_LAUNCH();
     return LA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Gram-matrix style and content distance of image pairs (NSTLoss on the taps of VGG19Net, augments/criteria/nst): the trunk once on the
+// 2P rows, la_gram_pair_launch (la_gram.hip) as its tap step on the raw activation each tap sees; `lin` is not read.  The scratch is
+// the largest tap's, used by one tap after the other on the one stream.
+extern "C" size_t la_feat_style_scratch_bytes(const la_feat* h, int P) {
+    if (!h || h->detector || P < 1 || 2L * P > h->maxN) return 0;
+    size_t need = 0;
+    for (int k = 0; k < h->nops; ++k)
+        if (h->op[k].kind == LA_FEAT_TAP) {
+            const size_t b = la_gram_pair_scratch_bytes(P, h->op[k].cout, h->op[k].res_out * h->op[k].res_out);
+            if (b == 0) return 0;
+            if (b > need) need = b;
+        }
+    return need;
+}
+
+// style, content [P][ntaps] (float64): per tap, the distances of rows p and p + P of xy [2P][in_ch][in_res^2].  No host sync, no
+// allocation.  The activations of an earlier la_feat_forward are overwritten: la_feat_backward refuses until the next forward.
+extern "C" int la_feat_style_distance(la_feat* h, const float* xy, int P, double* style, double* content, void* scratch, size_t scratch_bytes,
+                                      hipStream_t stream) {
+    LA_CHECK_ARG(h && xy && style && content && scratch, "feat_style_distance: null pointer");
+    LA_CHECK_ARG(!h->detector, "feat_style_distance: a detector list (fc ops) has no taps");
+    LA_CHECK_ARG(P >= 1 && 2L * P <= h->maxN, "feat_style_distance: 2 * pairs exceeds max_batch");
+    const size_t need = la_feat_style_scratch_bytes(h, P);
+    LA_CHECK_ARG(need > 0, "feat_style_distance: a tap's shape is refused by la_gram_pair_scratch_bytes");
+    if (scratch_bytes < need) { la_set_error("feat_style_distance: scratch smaller than la_feat_style_scratch_bytes(h, P)"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_ARG(((size_t)scratch & 7) == 0, "feat_style_distance: the scratch must be 8-byte aligned");
+    const int ntaps = la_feat_num_taps(h);
+    int tap = 0, trc = LA_OK;
+    h->lastN = 0;
+    const int rc = f_trunk(h, xy, 2 * P, nullptr, stream, [&](const FOp& o, const float* cur, int HWo) {
+        if (!trc) trc = la_gram_pair_launch(cur, P, o.cout, HWo, style + tap, content + tap, ntaps, scratch, stream);
+        ++tap;
+    });
+    return rc ? rc : trc;
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -634,26 +634,23 @@ def _pair_indices(pairs, nx, ny):
     return ix, iy
 
 
-def compute_lpips(x, y, net, pairs=None):
-    """LPIPS distance per pair of images, modality by modality, the way the perceptual criterion feeds its net
-    (util_latent_aug.py:387-409): every channel of x[p] and of y[p] is repeated to three channels, given the net's input affine
-    (`net.pre_scale`, `net.pre_shift`) and sent through `net`, a synthesis.FeatureEngine of three input channels; the distance comes
-    from one fused launch per tap (FeatureEngine.pair_distance_rows), no feature vector is written.  x, y: float32 device tensors
-    [N, C, R, R] with R == net.in_res (whole frames, not crops), values in the range the net expects ([-1, 1] for
-    lpips_reference_net, whose net_type 'alex' gives the LPIPS-Alex number most papers report).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy), gathered chunk by chunk with
-    index_select.  Returns float64 CPU tensors: 'lpips' [P] (mean over channels), 'lpips_per_channel' [P, C] (sum over taps),
-    'lpips_layers' [P, C, ntaps].  Two calls give the same bits.  There is no CPU fallback."""
+def _pair_row_batches(x, y, net, pairs, name, entry, clamp=None):
+    """The plumbing compute_lpips and compute_style_content share: checks the images against the engine (`entry`: the method of
+    synthesis.FeatureEngine the caller needs), then yields (p0, n, xy) per chunk of `chunk` pairs -- xy [2 C n, 3, R, R] float32, every
+    channel of the n pairs from p0 on repeated to three channels with the net's input affine, rows c * n + b, the x rows then the y
+    rows (la_crop_repeat_affine_f32).  pairs=(ix, iy) are gathered chunk by chunk with index_select; clamp=(lo, hi) clamps the images
+    first.  Returns (P, C, device, chunk, the generator); the generator runs under torch.cuda.device(device)."""
     x, y = _device_images(x, 'x'), _device_images(y, 'y')
     if x.device != y.device or x.shape[1:] != y.shape[1:]:
         raise ValueError(f'x and y must be on one device and agree in [C, H, W]: {tuple(x.shape)} on {x.device}, {tuple(y.shape)} on {y.device}')
-    if not hasattr(net, 'pair_distance_rows'):
-        raise _lib.LatentAugHipError(f'compute_lpips: net must be a synthesis.FeatureEngine; got {type(net).__name__}')
+    if not hasattr(net, entry):
+        raise _lib.LatentAugHipError(f'{name}: net must be a synthesis.FeatureEngine; got {type(net).__name__}')
     per_call = net.pair_rows()          # (refuses a detector engine)
     C_, H, W = (int(s) for s in x.shape[1:])
     if net.in_ch != 3 or H != net.in_res or W != net.in_res:
-        raise ValueError(f'compute_lpips: the net takes [3, {net.in_res}, {net.in_res}] inputs (in_ch {net.in_ch}); the images are [{C_}, {H}, {W}]')
+        raise ValueError(f'{name}: the net takes [3, {net.in_res}, {net.in_res}] inputs (in_ch {net.in_ch}); the images are [{C_}, {H}, {W}]')
     if x.device != net.device:
-        raise ValueError(f'compute_lpips: images on {x.device}, net on {net.device}')
+        raise ValueError(f'{name}: images on {x.device}, net on {net.device}')
     dev, R = x.device, H
     if pairs is None:
         if x.shape[0] != y.shape[0]:
@@ -664,25 +661,79 @@ def compute_lpips(x, y, net, pairs=None):
         P, ixd, iyd = int(ix.size), torch.from_numpy(ix).to(dev).long(), torch.from_numpy(iy).to(dev).long()
     chunk = per_call // C_
     if chunk < 1:
-        raise _lib.LatentAugHipError(f'compute_lpips: one pair of {C_}-channel images is {2 * C_} rows; the net has max_batch = {net.max_batch}')
+        raise _lib.LatentAugHipError(f'{name}: one pair of {C_}-channel images is {2 * C_} rows; the net has max_batch = {net.max_batch}')
     lib = _lib.load()
     sc, sh = (C.c_float * 3)(*net.pre_scale), (C.c_float * 3)(*net.pre_shift)
+
+    def batches():
+        with torch.cuda.device(dev):
+            for p0 in range(0, P, chunk):
+                n = min(chunk, P - p0)
+                xa = x[p0:p0 + n] if pairs is None else x.index_select(0, ixd[p0:p0 + n])
+                ya = y[p0:p0 + n] if pairs is None else y.index_select(0, iyd[p0:p0 + n])
+                if clamp is not None:
+                    xa, ya = xa.clamp(*clamp), ya.clamp(*clamp)
+                xy = torch.empty([2 * C_ * n, 3, R, R], dtype=torch.float32, device=dev)          # rows c * n + b, x then y
+                for half, src in enumerate((xa, ya)):
+                    _lib.check(lib.la_crop_repeat_affine_f32(_lib.ptr(src), _lib.ptr(xy[half * C_ * n:]), n, C_, R, R, 0, 0, 3, sc, sh,
+                                                             _lib.stream_ptr()), 'la_crop_repeat')
+                yield p0, n, xy
+    return P, C_, dev, chunk, batches()
+
+
+def compute_lpips(x, y, net, pairs=None):
+    """LPIPS distance per pair of images, modality by modality, the way the perceptual criterion feeds its net
+    (util_latent_aug.py:387-409): every channel of x[p] and of y[p] is repeated to three channels, given the net's input affine
+    (`net.pre_scale`, `net.pre_shift`) and sent through `net`, a synthesis.FeatureEngine of three input channels; the distance comes
+    from one fused launch per tap (FeatureEngine.pair_distance_rows), no feature vector is written.  x, y: float32 device tensors
+    [N, C, R, R] with R == net.in_res (whole frames, not crops), values in the range the net expects ([-1, 1] for
+    lpips_reference_net, whose net_type 'alex' gives the LPIPS-Alex number most papers report).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy), gathered chunk by chunk with
+    index_select.  Returns float64 CPU tensors: 'lpips' [P] (mean over channels), 'lpips_per_channel' [P, C] (sum over taps),
+    'lpips_layers' [P, C, ntaps].  Two calls give the same bits.  There is no CPU fallback."""
+    P, C_, dev, _, batches = _pair_row_batches(x, y, net, pairs, 'compute_lpips', 'pair_distance_rows')
     out = torch.empty([P, C_, net.num_taps], dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        for p0 in range(0, P, chunk):
-            n = min(chunk, P - p0)
-            xa = x[p0:p0 + n] if pairs is None else x.index_select(0, ixd[p0:p0 + n])
-            ya = y[p0:p0 + n] if pairs is None else y.index_select(0, iyd[p0:p0 + n])
-            xy = torch.empty([2 * C_ * n, 3, R, R], dtype=torch.float32, device=dev)          # rows c * n + b, x then y
-            for half, src in enumerate((xa, ya)):
-                _lib.check(lib.la_crop_repeat_affine_f32(_lib.ptr(src), _lib.ptr(xy[half * C_ * n:]), n, C_, R, R, 0, 0, 3, sc, sh,
-                                                         _lib.stream_ptr()), 'la_crop_repeat')
-            d = torch.empty([C_ * n, net.num_taps], dtype=torch.float64, device=dev)
-            net.pair_distance_rows(xy, C_ * n, d)
-            out[p0:p0 + n] = d.reshape(C_, n, net.num_taps).permute(1, 0, 2)
+    for p0, n, xy in batches:
+        d = torch.empty([C_ * n, net.num_taps], dtype=torch.float64, device=dev)
+        net.pair_distance_rows(xy, C_ * n, d)
+        out[p0:p0 + n] = d.reshape(C_, n, net.num_taps).permute(1, 0, 2)
     layers = out.cpu()
     per_channel = layers.sum(dim=2)
     return {'lpips': per_channel.mean(dim=1), 'lpips_per_channel': per_channel, 'lpips_layers': layers}
+
+
+NST_CONTENT_TAP = 3                                                  # synthesis.NST_CONTENT_TAP (networks.py:11: content_layers ['19'])
+_NST_CLAMP = (-128.0 / 127.5, 127.0 / 127.5)                        # where (x * 127.5 + 128).clamp(0, 255) of networks.py:38 acts, in x
+
+
+def compute_style_content(x, y, net, pairs=None, content_tap=NST_CONTENT_TAP, clamp=True):
+    """Gram-matrix style distance and content distance per pair of images: the reference's `NSTLoss` on the taps of its `VGG19Net`
+    (augments/criteria/nst), which says in WHICH way a sample moved from its source -- texture (feature co-occurrence, the modality's
+    look) or spatial content (the anatomy).  Plumbing of compute_lpips: modality by modality, every channel of x[p] and y[p] repeated
+    to three channels with the net's input affine (`net.pre_scale`, `net.pre_shift`), both images of a pair rows of one batch, chunks
+    of max_batch // 2 rows; `net` is a synthesis.FeatureEngine of a tap list, e.g. of synthesis.nst_reference_net.  clamp=True clamps
+    the images to [-128/127.5, 127/127.5] first: the reference's clamp(0, 255), moved in front of the affine.  Per pair, channel and
+    tap (la_feat_style_distance): style = mean over C^2 of (G1 - G2)^2 with G = F F^T / HW, content = mean over C HW of (f1 - f2)^2.
+    Returns float64 CPU tensors: 'style' [P] (sum over taps, mean over channels), 'content' [P] (tap `content_tap`, mean over
+    channels), 'style_per_channel', 'content_per_channel' [P, C], 'style_layers', 'content_layers' [P, C, ntaps].  d(x, x) is exactly
+    0, d(x, y) = d(y, x) and two calls give the same bits.  There is no CPU fallback."""
+    P, C_, dev, chunk, batches = _pair_row_batches(x, y, net, pairs, 'compute_style_content', 'style_distance_rows',
+                                                   _NST_CLAMP if clamp else None)
+    nt = net.num_taps
+    if not 0 <= int(content_tap) < nt:
+        raise ValueError(f'content_tap must lie in 0 .. {nt - 1} (got {content_tap})')
+    style = torch.empty([P, C_, nt], dtype=torch.float64, device=dev)
+    content = torch.empty([P, C_, nt], dtype=torch.float64, device=dev)
+    scratch = _f64_scratch(net.style_scratch_bytes(C_ * min(chunk, P)), dev)
+    for p0, n, xy in batches:
+        s = torch.empty([C_ * n, nt], dtype=torch.float64, device=dev)
+        c = torch.empty([C_ * n, nt], dtype=torch.float64, device=dev)
+        net.style_distance_rows(xy, C_ * n, s, c, scratch)
+        style[p0:p0 + n] = s.reshape(C_, n, nt).permute(1, 0, 2)
+        content[p0:p0 + n] = c.reshape(C_, n, nt).permute(1, 0, 2)
+    style_layers, content_layers = style.cpu(), content.cpu()
+    style_pc, content_pc = style_layers.sum(dim=2), content_layers[:, :, int(content_tap)].contiguous()
+    return {'style': style_pc.mean(dim=1), 'content': content_pc.mean(dim=1), 'style_per_channel': style_pc, 'content_per_channel': content_pc,
+            'style_layers': style_layers, 'content_layers': content_layers}
 
 
 def compute_lpips_diversity(images, net, num_pairs=1000, seed=0):
@@ -695,7 +746,7 @@ def compute_lpips_diversity(images, net, num_pairs=1000, seed=0):
     return dict(mean=float(d.mean()), lpips=d, ix=ix, iy=iy)
 
 
-def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigma=1.5, levels=5, weights=None, lpips_net=None):
+def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigma=1.5, levels=5, weights=None, lpips_net=None, nst_net=None):
     """Per pair of images: MSE, MAE, PSNR, SSIM and MS-SSIM.  x, y: float32 device tensors [N, C, H, W] in a range of width
     `data_range` (2 for the generator's [-1, 1]).  Pair p is (x[p], y[p]), or (x[ix[p]], y[iy[p]]) with pairs=(ix, iy); the kernel
     gathers, the images are not copied.  A Gaussian window of `win_size` taps (odd, 1 .. 11) and `win_sigma`, 'valid' extent;
@@ -705,7 +756,9 @@ def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigm
     that mean (inf at 0) -- their '*_per_channel' forms [P, C], and 'ssim_levels', 'cs_levels' [P, C, levels].
     Two calls give the same bits (la_pair_metrics_f32).  There is no CPU fallback.
     lpips_net (a synthesis.FeatureEngine, e.g. of lpips_reference_net, with in_res == H == W): adds the keys of compute_lpips for the
-    same pairs; without it the result is what it was."""
+    same pairs; without it the result is what it was.
+    nst_net (a synthesis.FeatureEngine of synthesis.nst_reference_net, in_res == H == W): adds the keys of compute_style_content for
+    the same pairs, likewise."""
     x, y = _device_images(x, 'x'), _device_images(y, 'y')
     if x.device != y.device or x.shape[1:] != y.shape[1:]:
         raise ValueError(f'x and y must be on one device and agree in [C, H, W]: {tuple(x.shape)} on {x.device}, {tuple(y.shape)} on {y.device}')
@@ -755,6 +808,8 @@ def compute_pair_metrics(x, y, pairs=None, data_range=2.0, win_size=11, win_sigm
         out[k] = 10.0 * torch.log10(float(data_range) ** 2 / out[k.replace('psnr', 'mse')])          # x / 0 = inf in float64 tensors
     if lpips_net is not None:
         out.update(compute_lpips(x, y, lpips_net, pairs=pairs))
+    if nst_net is not None:
+        out.update(compute_style_content(x, y, nst_net, pairs=pairs))
     return out
 
 
@@ -772,7 +827,7 @@ def compute_pair_metrics_for_aug_dataset(datadir, device='cuda:0', **kw):
     'A' and 'B' entries ([n, 1, H, W]) become the two channels.  The pickles are read through the allow-list loader of formats.py,
     never a plain unpickle.  Returns the per-sample tensors of compute_pair_metrics over all files, a float '<key>_mean' for each of
     'mse', 'mae', 'psnr', 'ssim', 'ms_ssim', and 'num_items'.  With `lpips_net=` (see compute_pair_metrics) the LPIPS keys and
-    'lpips_mean' are added."""
+    'lpips_mean' are added, with `nst_net=` the style / content keys and 'style_mean', 'content_mean'."""
     from .formats import _restricted_load
     dev = torch.device(device)
     if dev.type != 'cuda':
@@ -791,7 +846,7 @@ def compute_pair_metrics_for_aug_dataset(datadir, device='cuda:0', **kw):
     parts = [compute_pair_metrics(two_channels(src), two_channels(aug), **kw) for src, aug in files]
     out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
     out['num_items'] = int(out['mse'].shape[0])
-    for k in ('mse', 'mae', 'psnr', 'ssim', 'ms_ssim') + (('lpips',) if 'lpips' in out else ()):
+    for k in ('mse', 'mae', 'psnr', 'ssim', 'ms_ssim') + (('lpips',) if 'lpips' in out else ()) + (('style', 'content') if 'style' in out else ()):
         out[k + '_mean'] = float(out[k].mean())
     return out
 

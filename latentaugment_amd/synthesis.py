@@ -636,6 +636,21 @@ class FeatureEngine:
             _lib.check(self._lib.la_feat_pair_distance(self._h, _lib.ptr(xy), P, _lib.ptr(dist), _lib.ptr(ws), ws.numel() * 8,
                                                        _lib.stream_ptr()), 'la_feat_pair_distance')
 
+    def style_scratch_bytes(self, P):
+        """Bytes of scratch la_feat_style_distance needs for P pairs (0: a detector list, or 2 * P > max_batch)."""
+        return int(self._lib.la_feat_style_scratch_bytes(self._h, P))
+
+    def style_distance_rows(self, xy, P, style, content, scratch):
+        """la_feat_style_distance on a prepared batch: xy [2P, in_ch, in_res, in_res] float32 (rows p and p + P are a pair, 2P <=
+        max_batch) -> style, content [P, num_taps] float64: per tap, the Gram-matrix style distance and the content distance of the
+        raw activations (`lin` is not read).  All on the device and contiguous; scratch: a float64 tensor of at least
+        style_scratch_bytes(P) bytes, any contents.  A later backward() needs a new forward() first."""
+        if self.style_scratch_bytes(P) == 0:
+            raise _lib.LatentAugHipError(f'style_distance: {P} pairs refused (detector list, or 2 * pairs > max_batch = {self.max_batch})')
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.la_feat_style_distance(self._h, _lib.ptr(xy), P, _lib.ptr(style), _lib.ptr(content), _lib.ptr(scratch),
+                                                        scratch.numel() * scratch.element_size(), _lib.stream_ptr()), 'la_feat_style_distance')
+
     def pair_distance(self, x, y):
         """LPIPS distance of x[p] and y[p] per tap: float64 [P, num_taps] on the device, dist[p, t] = mean over the tap's pixels of
         sum_c lin_c (fx rx - fy ry)^2 -- what squared L2 of forward(x)[p] - forward(y)[p] gives tap by tap, from one fused launch per tap
@@ -753,6 +768,42 @@ def lpips_reference_net(vgg_state_dict, lin_state_dict, net_type='vgg'):
         ops = (alexnet_lpips_ops if net_type == 'alex' else squeezenet_lpips_ops)(vgg, lins)
     return ScriptedFeatureNet(ops, tuple(1.0 / s for s in LPIPS_ZSCORE_STD),
                               tuple(-m / s for m, s in zip(LPIPS_ZSCORE_MEAN, LPIPS_ZSCORE_STD)), False, None)
+
+
+NST_CONTENT_TAP = 3      # networks.py:11, content_layers ['19']: the fourth of the five style taps
+
+
+def vgg19_nst_ops(state_dict):
+    """Op list of the reference's style / content net, `augments/criteria/nst/networks.py::VGG19Net`, from torchvision's names of
+    vgg19 (`features.{0,2,5,7,10,12,14,16,19,21,23,25,28}.weight/bias`): 13 convs + ReLU, 4 max pools, taps after the convs 0, 5, 10,
+    19 and 28.  networks.py:12 names conv indices, but torchvision's ReLUs are in place, so the tensors its list holds are the
+    post-ReLU activations relu1_1 .. relu5_1: a tap behind the conv + ReLU op.  The list ends at conv 28.  Every tap carries
+    lin = ones (the style distance does not read it), so `forward` and `pair_distance` of such an engine work too."""
+    conv_ids = [0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28]
+    tap_after, pool_after = {0, 5, 10, 19, 28}, {2, 7, 16, 25}
+    ops = []
+    for i in conv_ids:
+        w = state_dict[f'features.{i}.weight']
+        ops.append(('conv', w, state_dict[f'features.{i}.bias']))
+        if i in tap_after:
+            ops.append(('tap', torch.ones([w.shape[0]], dtype=torch.float32)))
+        if i in pool_after:
+            ops.append(('maxpool',))
+    return ops
+
+
+def nst_reference_net(vgg19_state_dict):
+    """The reference's `VGG19Net` (augments/criteria/nst/networks.py) as a described net for `FeatureEngine.from_net`:
+    `vgg19_nst_ops` with the input layer of `prepare_img(synthetic=True, normalize=True)`, (x * 127.5 + 128) / 255 = x * 0.5 + 128 / 255
+    on the three repeated channels (`standardize` is never passed: no ImageNet mean / std); its clamp(0, 255) is the caller's
+    (metrics.compute_style_content clamps the images in front of the affine).  The argument is torchvision's vgg19 state dict or the
+    path of a local file of one, read with torch.load(weights_only=True)."""
+    sd = vgg19_state_dict
+    if not isinstance(sd, dict):
+        if not os.path.isfile(sd):
+            raise FileNotFoundError(f'VGG19 weights: no such file: {sd}')
+        sd = torch.load(sd, map_location='cpu', weights_only=True)
+    return ScriptedFeatureNet(vgg19_nst_ops(sd), (0.5,) * 3, (128.0 / 255.0,) * 3, False, None)
 
 
 # ------------------------------------------------------------------------------------------------------------
