@@ -893,6 +893,59 @@ int la_realism_f32(const float* q, long nq, const float* x, long nx, int D, cons
                    void* scratch, size_t scratch_bytes, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * UMAP embedding (McInnes, Healy, Melville 2018; the reference's analysis/umap_analysis.py calls the umap-learn library): the stages
+ * after the neighbour search, all float64, no float atomics, no host synchronisation, nothing allocated, capturable in a graph; two
+ * runs give the same bits.  Four deliberate differences from umap-learn: (1) an epoch is synchronous -- all forces come from the
+ * positions at the start of the epoch; (2) the randomness is the library's Philox stream (counter convention: csrc/la_rng.h);
+ * (3) the initial layout is random or the caller's, never spectral; (4) the sigma bisection always runs its 64 iterations.
+ * Empty neighbour slots (idx = -1, dist2 = +inf, as la_knn_f32 leaves them) are skipped everywhere.
+ *
+ *   la_umap_smooth_knn_f64   dist2 float64 / idx int32 [n][k] as la_knn_f32 wrote them, 1 <= k <= 32; target = log2(n_neighbors).  Per
+ *       row, d_s = sqrt(dist2_s); rho = the smallest non-zero d_s (0: none); sigma = the root of sum_s exp(-max(0, d_s - rho) / sigma)
+ *       = target by bisection from lo = 0, hi = inf, mid = 1 (mid doubles while hi is infinite, else the bracket's midpoint), 64
+ *       iterations without an early exit; then sigma = max(sigma, 1e-3 * mean of the row's finite d_s); w_s = exp(-max(0, d_s - rho)
+ *       / sigma), 0 in an empty slot.  Out: rho [n], sigma [n], w [n][k].  One wave per row, the sum by the wave butterfly.
+ *   la_umap_graph_f64        the fuzzy union S = A + A^T - A o A^T of the directed weights A[i][idx[i][s]] = w[i][s] as a symmetric
+ *       CSR: row_ptr int32 [n + 1], col int32 ascending within a row, val float64, both of capacity cap >= 2 n k (entries past
+ *       row_ptr[n] are not written); wmax float64 [1] = max(val).  The columns of a row of idx must be distinct (la_knn_f32's are);
+ *       an index outside 0 .. n - 1 counts as an empty slot.  In-degrees by integer atomics, a scan, a fill through integer cursors,
+ *       a rank sort of every row by column: the arrays do not depend on the arrival order.  A row is not bounded by 2 k.
+ *       scratch: la_umap_scratch_bytes(n, k) bytes, 8-byte aligned, any contents (non-decreasing; 0 for refused sizes).
+ *   la_umap_init_f64         y [n][C] = 10 * (the noise stream's exact unit uniform of one Philox word) per coordinate of global
+ *       row row0 + i under `seed`: every value is exact.
+ *   la_umap_transform_init_f64   new rows against a fitted bank: y [n][C] = the w-weighted mean of bank_y [n_bank][C] over the row's
+ *       neighbours (idx, w [n][k]; 0 without a neighbour), and the rows' CSR for the epochs: row_ptr[i] = i k (col = idx and val = w
+ *       are the arrays themselves), wmax = 1 -- the nearest neighbour of every row has weight exactly 1, whatever the batch.
+ *   la_umap_epoch_f64        epoch e of E, alpha = lr (1 - e / E), one wave per head row i.  Entry t of the row (column j, value v,
+ *       skipped if j is outside 0 .. n_tail - 1) is active iff floor((e + 1) p) > floor(e p), p = v / wmax.  An active entry pulls i
+ *       towards tail j with coefficient -2 a b d2^(b-1) / (1 + a d2^b) (0 at d2 = 0), d2 = |y_i - y_j|^2, and draws `rate` (0 .. 32)
+ *       tail rows r = (word n_tail) >> 32, each pushing i with 2 b / ((0.001 + q2) (1 + a q2^b)) (0 at q2 = 0, or at r == i when
+ *       skip_self != 0).  Every component of coefficient (y_i - y_other) is clipped to [-4, 4]; y_out[i] = y_i + alpha (sum of the
+ *       clipped terms), the lanes' sums combined by the wave butterfly; a row without an active entry is copied bit for bit.  Only
+ *       the head moves.  y_in [n][C], y_out [n][C] (not y_in), y_tail [n_tail][C] (a fit: y_in itself), 1 <= C <= 8; col / val hold
+ *       cap entries and row_ptr is clamped to that.  row0: the global index of head row 0 (the Philox counter's; row0 + n < 2^32).
+ *   la_umap_layout_f64       epochs e0 .. e1 - 1 of that launch over the two buffers ya, yb: epoch e0 reads ya.  y_tail NULL: a fit
+ *       (the tails are the buffer being read).  *which (host int) = 0 if ya holds the result, 1 if yb.
+ * Null pointers, n < 1 (graph and fit: n < 2), k outside 1 .. 32, C outside 1 .. 8, e outside 0 .. E - 1, E > 2^28, a, b <= 0 or
+ * not finite, rate outside 0 .. 32, misaligned arrays, cap < what is needed are LA_ERR_ARG, a smaller scratch_bytes is
+ * LA_ERR_WORKSPACE, all before anything is launched.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t la_umap_scratch_bytes(long n, int k);
+int la_umap_smooth_knn_f64(const double* dist2, const int* idx, long n, int k, double target, double* rho, double* sigma, double* w,
+                           la_stream_t stream);
+int la_umap_graph_f64(const int* idx, const double* w, long n, int k, int* row_ptr, int* col, double* val, long cap, double* wmax,
+                      void* scratch, size_t scratch_bytes, la_stream_t stream);
+int la_umap_init_f64(double* y, long n, int C, unsigned long long seed, long row0, la_stream_t stream);
+int la_umap_transform_init_f64(const int* idx, const double* w, long n, int k, const double* bank_y, long n_bank, int C, double* y,
+                               int* row_ptr, double* wmax, la_stream_t stream);
+int la_umap_epoch_f64(const double* y_in, double* y_out, long n, const double* y_tail, long n_tail, int C, const int* row_ptr,
+                      const int* col, const double* val, long cap, const double* wmax, int e, int E, double a, double b, int rate,
+                      double lr, unsigned long long seed, long row0, int skip_self, la_stream_t stream);
+int la_umap_layout_f64(double* ya, double* yb, long n, const double* y_tail, long n_tail, int C, const int* row_ptr, const int* col,
+                       const double* val, long cap, const double* wmax, int e0, int e1, int E, double a, double b, int rate, double lr,
+                       unsigned long long seed, long row0, int skip_self, int* which, la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Gram-matrix style distance and content distance of activation pairs: NSTLoss of augments/criteria/nst/nst.py:7-35 on the taps
  * of VGG19Net (networks.py:60-70).  f float32 [2P][C][HW]; rows p and p + P are a pair.  With G = F F^T / HW for F [C][HW]:
  *   style[p]   = mean over the C^2 entries of (G1 - G2)^2

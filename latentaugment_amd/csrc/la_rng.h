@@ -44,3 +44,20 @@ __device__ __forceinline__ void la_unit_normals4(const unsigned (&x)[4], float (
 // One word -> one value in (-1, 1): (k + 0.5) * 2^-22 - 1 with k the top 23 bits, i.e. (2k + 1 - 2^23) * 2^-23, an odd numerator
 // below 2^23 -- exact in float32, never -1, 0 or 1.
 __device__ __forceinline__ float la_unit_uniform(unsigned word) { return ((float)(word >> 9) + 0.5f) * (1.f / 4194304.f) - 1.f; }
+
+// The UMAP embedding's draws (la_umap.hip) use the same generator under two stream constants that no layer or caller-chosen stream
+// id of the noise entries reaches, and their own counter convention -- again a pure function of GLOBAL indices, so that a row gives
+// the same bits in any batch:
+//   negative samples   counter (position t of the entry in its CSR row, global head row, LA_RNG_STREAM_UMAP_NEG, epoch * 8 + group),
+//                      key (seed low, seed high): word u of group g is draw 4 g + u of that entry in that epoch (at most 32 draws,
+//                      8 groups; epoch < 2^28); the sampled row is (word * n_tail) >> 32
+//   initial layout     counter (c / 4, global row, LA_RNG_STREAM_UMAP_INIT, 0): word c % 4 is coordinate c, 10 * la_unit_uniform(word)
+#define LA_RNG_STREAM_UMAP_NEG 0x554D4150u       // 'UMAP'
+#define LA_RNG_STREAM_UMAP_INIT 0x554D4149u
+#define LA_UMAP_MAX_EPOCHS (1 << 28)
+__device__ __forceinline__ void la_umap_neg_words(int t, long head_row, int epoch, int group, unsigned k0, unsigned k1, unsigned (&x)[4]) {
+    la_philox4x32_10((unsigned)t, (unsigned)head_row, LA_RNG_STREAM_UMAP_NEG, ((unsigned)epoch << 3) | (unsigned)group, k0, k1, x);
+}
+__device__ __forceinline__ void la_umap_init_words(int group, long row, unsigned k0, unsigned k1, unsigned (&x)[4]) {
+    la_philox4x32_10((unsigned)group, (unsigned)row, LA_RNG_STREAM_UMAP_INIT, 0u, k0, k1, x);
+}
