@@ -946,6 +946,70 @@ int la_umap_layout_f64(double* ya, double* yb, long n, const double* y_tail, lon
                        unsigned long long seed, long row0, int skip_self, int* which, la_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Segmented key sort: `ncols` independent columns of float32 keys, ascending, in place.  Column c is keys[c ld .. c ld + M), ld >= M;
+ * elements [M, ld) of a column's stride are neither read nor written.  The order is that of the bit pattern under the sign-flip map
+ * to unsigned (sign set: all bits flipped, else the sign bit flipped): -inf < .. < -0.0 < +0.0 < .. < +inf.  Keys must not be NaN
+ * (not checked; a NaN is placed by its bit pattern, and the pattern 0x7FFFFFFF may change places with the padding).  Keys only, no
+ * payload: the sorted column is a unique bit pattern whatever the algorithm, and two runs agree by construction.
+ * One 256-thread workgroup sorts a tile of la_sort_tile_keys() keys in LDS with a bitonic network, then ceil(log2(tiles)) merge passes
+ * alternate between `keys` and the scratch: a workgroup produces one tile of output, its segment found by a merge-path search, staged
+ * in LDS and merged serially by each thread; grid (tiles, columns).  The first launch starts on the side that makes the last pass end
+ * in `keys`.  No atomics, no host synchronisation, nothing allocated.
+ * scratch: la_sort_columns_scratch_bytes(ncols, M) bytes, 4-byte aligned, any contents (non-decreasing; 0 for refused sizes).
+ * ncols outside 1 .. 65535, M outside 1 .. 2^30, ld < M and null pointers are LA_ERR_ARG, a smaller scratch_bytes is LA_ERR_WORKSPACE,
+ * all before anything is launched.
+ * ------------------------------------------------------------------------------------------------------------- */
+int la_sort_tile_keys(void);
+size_t la_sort_columns_scratch_bytes(long ncols, long M);
+int la_sort_columns_f32(float* keys, long ncols, long M, long ld, void* scratch, size_t scratch_bytes, la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance on a Laplacian pyramid (Karras, Aila, Laine, Lehtinen, ICLR 2018, section 5; the slicing: Rabin, Peyre,
+ * Delon, Bernot 2011).  No reference counterpart and no network: the stages below, each an entry, restated here as their definition.
+ * No float atomics, no host synchronisation, nothing allocated; every float64 sum has a fixed order: two runs give the same bits.
+ *
+ *   la_lap_pyr_down_f32      y [planes][H/2][W/2] = every second row and column (from 0) of x [planes][H][W] under the 5 x 5 binomial
+ *       filter outer([1,4,6,4,1], [1,4,6,4,1]) / 256; borders mirrored without repeating the edge (d c b | a b c d | c b a).
+ *   la_lap_pyr_up_sub_f32    fine [planes][H][W] -= up(coarse [planes][H/2][W/2]) in place: up = the same filter times 4 on the
+ *       zero-stuffed 2x image (samples at even positions), mirrored the same way on the zero-stuffed image.  Polyphase: an even
+ *       position takes [1,6,1] / 8 of its even neighbours, an odd one [4,4] / 8; the zeros are never multiplied.
+ *       Both: H and W even, 2 .. 32768.  A pyramid is G_0 = x, G_{l+1} = down(G_l), L_l = G_l - up(G_{l+1}), the last level G itself.
+ *   la_swd_gather_f32        rows [0, n per_image) of desc [.][D], D = C nhood^2: patch j of GLOBAL image img0 + i is the nhood x nhood
+ *       window of all C channels of img [n][C][H][W] in (channel, y, x) order with corner x0 = (word 0 * (W - nhood + 1)) >> 32,
+ *       y0 = (word 1 * (H - nhood + 1)) >> 32, the words those of the library's Philox stream with counter (j, img0 + i,
+ *       LA_RNG_STREAM_SWD_POS, level) and key seed (csrc/la_rng.h): integers only, and a set gives the same rows in any batches.
+ *   la_swd_channel_stats_f64 mean, std float64 [C] of desc [M][C P] per channel (columns [c P, (c + 1) P) of every row, M P values):
+ *       two passes, the mean first, then sum (x - mean)^2 / (M P) and its root (ddof 0); float64 sums over at most 1024 contiguous
+ *       runs, added in order.  scratch: la_swd_stats_scratch_bytes(M, C, P) bytes, 8-byte aligned, any contents.
+ *   la_swd_normalize_f32     desc = (desc - mean[c]) / std[c] in float64, one rounding to float32.  std[c] == 0 (a constant channel has
+ *       no descriptor; callers refuse it) is not divided by: the channel becomes NaN.
+ *   la_swd_directions_f32    dirs [ndirs][D]: row j is GLOBAL direction dir0 + j: the unit normals of the noise entries' map for row
+ *       dir0 + j of stream LA_RNG_STREAM_SWD_DIR under `seed`, divided by their norm -- sum of squares and quotient in float64, one
+ *       rounding.  Directions can be made in chunks.
+ *   la_swd_f32               w1 float64 [ndirs]: w1[j] = mean over i of |sort(A d_j)_i - sort(B d_j)_i| for descA, descB [M][D] and
+ *       dirs [ndirs][D] (an argument: any vectors will do).  Projections: exact-fp32 MFMA products, each one k-ordered chain,
+ *       written as [direction][M] columns; both sets' columns sorted by la_sort_columns_f32; per column sum |a - b| in float64 in a
+ *       fixed order, divided once by M.  Directions go through in chunks that fit the scratch; a column's bits do not depend on its
+ *       chunk, so any scratch_bytes >= la_swd_scratch_bytes(M, D, ndirs) (chunks of 32 directions; every further 16 M bytes let one
+ *       more direction join a chunk) gives the same bits.  scratch 8-byte aligned, any contents.
+ * Null pointers, odd or out-of-range H / W, nhood > min(H, W), M, n, ndirs or per_image < 1, C outside 1 .. 64 are LA_ERR_ARG, a
+ * smaller scratch_bytes is LA_ERR_WORKSPACE, all before anything is launched; the size queries are non-decreasing and 0 for what the
+ * entries refuse.
+ * ------------------------------------------------------------------------------------------------------------- */
+int la_lap_pyr_down_f32(const float* x, float* y, long planes, int H, int W, la_stream_t stream);
+int la_lap_pyr_up_sub_f32(float* fine, const float* coarse, long planes, int H, int W, la_stream_t stream);
+int la_swd_gather_f32(const float* img, long n, int C, int H, int W, long img0, int level, int nhood, int per_image,
+                      unsigned long long seed, float* desc, la_stream_t stream);
+size_t la_swd_stats_scratch_bytes(long M, int C, int P);
+int la_swd_channel_stats_f64(const float* desc, long M, int C, int P, double* mean, double* std, void* scratch, size_t scratch_bytes,
+                             la_stream_t stream);
+int la_swd_normalize_f32(float* desc, long M, int C, int P, const double* mean, const double* std, la_stream_t stream);
+int la_swd_directions_f32(float* dirs, long ndirs, int D, long dir0, unsigned long long seed, la_stream_t stream);
+size_t la_swd_scratch_bytes(long M, int D, long ndirs);
+int la_swd_f32(const float* descA, const float* descB, long M, int D, const float* dirs, long ndirs, double* w1, void* scratch,
+               size_t scratch_bytes, la_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Gram-matrix style distance and content distance of activation pairs: NSTLoss of augments/criteria/nst/nst.py:7-35 on the taps
  * of VGG19Net (networks.py:60-70).  f float32 [2P][C][HW]; rows p and p + P are a pair.  With G = F F^T / HW for F [C][HW]:
  *   style[p]   = mean over the C^2 entries of (G1 - G2)^2

@@ -61,3 +61,11 @@ __device__ __forceinline__ void la_umap_neg_words(int t, long head_row, int epoc
 __device__ __forceinline__ void la_umap_init_words(int group, long row, unsigned k0, unsigned k1, unsigned (&x)[4]) {
     la_philox4x32_10((unsigned)group, (unsigned)row, LA_RNG_STREAM_UMAP_INIT, 0u, k0, k1, x);
 }
+
+// The sliced Wasserstein distance's draws (la_swd.hip), under two more constants that nothing else reaches:
+//   patch positions    counter (patch j of the image, global image, LA_RNG_STREAM_SWD_POS, pyramid level), key (seed low, seed high):
+//                      the corner is x0 = (word 0 * (W - nhood + 1)) >> 32, y0 = (word 1 * (H - nhood + 1)) >> 32 -- integers only
+//   directions         la_noise_words(q, global direction, LA_RNG_STREAM_SWD_DIR) -> la_unit_normals4: elements 4 q .. 4 q + 3 of the
+//                      direction before it is divided by its norm, i.e. the noise entries' map with the direction as the row
+#define LA_RNG_STREAM_SWD_POS 0x53574450u        // 'SWDP'
+#define LA_RNG_STREAM_SWD_DIR 0x53574444u        // 'SWDD'

@@ -20,6 +20,9 @@ everything downstream of detector features.
   compute_pair_metrics                    (not in the reference) MSE / MAE / PSNR / SSIM / MS-SSIM of image PAIRS (la_pair_metrics_f32)
   compute_pair_metrics_for_aug_dataset    the same for `img/img_{i}` against `img_aug/img_aug_{i}` of a run directory of the drivers
   compute_msssim_diversity                MS-SSIM over random pairs of one image set (the usual collapse check)
+  laplacian_pyramid, compute_swd_from_images, compute_swd_from_features, compute_swd_for_aug_dataset
+                                          (not in the reference) sliced Wasserstein distance of two image sets per Laplacian pyramid
+                                          level, Karras et al. 2018, and of two feature sets: no detector (la_swd.hip, la_sort.hip)
   compute_modality_mi, compute_pair_mi    mutual information of two planes from their joint histogram (la_joint_hist_f32)
   compute_ppl, ppl_from_distances         (not in the reference) perceptual path length of the generator, Karras et al. 2019 / 2020
   compute_path_length                     perceptual length of the straight segment between two latents (la_path_points_f32)
@@ -562,12 +565,16 @@ def compute_feature_stats_for_aug_dataset(datadir, mode, detector, max_items=Non
 
 
 def compute_metrics_from_images(real_batches, gen_batches, detector, nhood_size=3, mode=None, max_items=None, kid_num_subsets=100,
-                                kid_max_subset_size=1000, kid_seed=0, frechet=False, realism=False, authenticity=False):
+                                kid_max_subset_size=1000, kid_seed=0, frechet=False, realism=False, authenticity=False, swd=False, **swd_kwargs):
     """{'precision', 'recall', 'density', 'coverage', 'kid'} of generated against real images, through `detector` and the functions
     above (precision_recall.py:36-85 with nhood_size=3 is the reference's pr50k3).  frechet=True adds 'fd', the Frechet distance of the
     same detector features (compute_fd_from_features; with the VGG16 detector it is not the published Inception FID).  realism=True
     adds 'realism', the mean realism score of the generated images (compute_realism_from_features with this nhood_size), and
-    authenticity=True adds 'authenticity' (compute_authenticity_from_features), both from the same features."""
+    authenticity=True adds 'authenticity' (compute_authenticity_from_features), both from the same features.  swd=True adds the
+    'swd_<res>' and 'swd_avg' keys of compute_swd_from_images (to which `swd_kwargs` go) from the same batches, which are then held as
+    lists; it needs no detector features.  With swd=False nothing of it is launched."""
+    if swd:
+        real_batches, gen_batches = list(real_batches), list(gen_batches)
     real = compute_feature_stats_for_images(real_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
     gen = compute_feature_stats_for_images(gen_batches, detector, mode=mode, max_items=max_items, capture_all=True).get_all()
     out = compute_prdc_from_features(real, gen, nhood_size=nhood_size, device=detector.device)
@@ -579,6 +586,10 @@ def compute_metrics_from_images(real_batches, gen_batches, detector, nhood_size=
         out['realism'] = float(compute_realism_from_features(real, gen, nhood_size=nhood_size, device=detector.device).mean())
     if authenticity:
         out['authenticity'] = compute_authenticity_from_features(real, gen, device=detector.device)
+    if swd:
+        held = min(sum(int(_batch_images(b, mode).shape[0]) for b in side) for side in (real_batches, gen_batches))
+        out.update(compute_swd_from_images(real_batches, gen_batches, mode=mode, num_items=held if max_items is None else min(held, max_items),
+                                           device=detector.device, **swd_kwargs))
     return out
 
 
@@ -821,6 +832,28 @@ def _aug_pair_files(datadir):
     return files
 
 
+def _aug_two_channels(fname, dev):
+    """the 'A' and 'B' batches ([n, 1, H, W]) of one pickled dict of a run directory as the two channels of a float32 device tensor"""
+    from .formats import _restricted_load
+    with open(fname, 'rb') as f:
+        d = _restricted_load(f)
+    planes = [torch.as_tensor(d[m]).to(torch.float32) for m in ('A', 'B')]
+    if any(p.ndim != 4 or p.shape[1] != 1 for p in planes):
+        raise ValueError(f"{fname}: 'A' and 'B' must be [n, 1, H, W] batches")
+    return torch.cat(planes, dim=1).to(dev)
+
+
+def _aug_pair_run(datadir, device):
+    """(device, [(img/img_{i}, img_aug/img_aug_{i})]) of a run directory; raises without a ROCm device or without a first pair"""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); got device ' + str(dev))
+    files = _aug_pair_files(datadir)
+    if not files:
+        raise FileNotFoundError(f"no img/img_0 with img_aug/img_aug_0 under {datadir}")
+    return dev, files
+
+
 def compute_pair_metrics_for_aug_dataset(datadir, device='cuda:0', **kw):
     """compute_pair_metrics of every source image against its augmented version in a run directory of the reference's drivers
     (backbone_latentaug.py:112-118): `img/img_{i}` and `img_aug/img_aug_{i}`, i = 0, 1, .., each a pickled dict of image batches whose
@@ -828,27 +861,194 @@ def compute_pair_metrics_for_aug_dataset(datadir, device='cuda:0', **kw):
     never a plain unpickle.  Returns the per-sample tensors of compute_pair_metrics over all files, a float '<key>_mean' for each of
     'mse', 'mae', 'psnr', 'ssim', 'ms_ssim', and 'num_items'.  With `lpips_net=` (see compute_pair_metrics) the LPIPS keys and
     'lpips_mean' are added, with `nst_net=` the style / content keys and 'style_mean', 'content_mean'."""
-    from .formats import _restricted_load
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.LatentAugHipError('latentaugment_amd needs a ROCm device (no CPU fallback); got device ' + str(dev))
-    files = _aug_pair_files(datadir)
-    if not files:
-        raise FileNotFoundError(f"no img/img_0 with img_aug/img_aug_0 under {datadir}")
-
-    def two_channels(fname):
-        with open(fname, 'rb') as f:
-            d = _restricted_load(f)
-        planes = [torch.as_tensor(d[m]).to(torch.float32) for m in ('A', 'B')]
-        if any(p.ndim != 4 or p.shape[1] != 1 for p in planes):
-            raise ValueError(f"{fname}: 'A' and 'B' must be [n, 1, H, W] batches")
-        return torch.cat(planes, dim=1).to(dev)
-    parts = [compute_pair_metrics(two_channels(src), two_channels(aug), **kw) for src, aug in files]
+    dev, files = _aug_pair_run(datadir, device)
+    parts = [compute_pair_metrics(_aug_two_channels(src, dev), _aug_two_channels(aug, dev), **kw) for src, aug in files]
     out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
     out['num_items'] = int(out['mse'].shape[0])
     for k in ('mse', 'mae', 'psnr', 'ssim', 'ms_ssim') + (('lpips',) if 'lpips' in out else ()) + (('style', 'content') if 'style' in out else ()):
         out[k + '_mean'] = float(out[k].mean())
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# sliced Wasserstein distance (la_swd.hip, la_sort.hip; no reference counterpart, no detector, no CPU fallback)
+SWD_LEVEL_DIR_STRIDE = 1 << 20          # global direction index of direction j of pyramid level l: l * 2^20 + j
+
+
+def _pyramid_levels(H, W, min_resolution):
+    n, r = 1, min(H, W)
+    while H % 2 == 0 and W % 2 == 0 and r // 2 >= min_resolution:
+        n, r, H, W = n + 1, r // 2, H // 2, W // 2
+    return n
+
+
+def laplacian_pyramid(images, min_resolution=16):
+    """The Laplacian pyramid of `images` [N, C, H, W] (a float32 device tensor): the list of level tensors at resolutions H, H/2, ..
+    down to the last one whose smaller side is still >= `min_resolution` (halving stops earlier at an odd side).  G_0 = x,
+    G_{l+1} = down(G_l) with the 5 x 5 binomial filter, mirrored borders, every second sample; level l is G_l - up(G_{l+1}), the
+    last level is G itself (la_lap_pyr_down_f32, la_lap_pyr_up_sub_f32), so level 0 + up(level 1 + up(..)) gives the images back."""
+    x = _device_images(images, 'images')
+    lib = _lib.load()
+    N, C, H, W = x.shape
+    g = [x.clone()]
+    with torch.cuda.device(x.device):
+        for _ in range(_pyramid_levels(H, W, min_resolution) - 1):
+            h, w = g[-1].shape[2:]
+            y = torch.empty([N, C, h // 2, w // 2], dtype=torch.float32, device=x.device)
+            _lib.check(lib.la_lap_pyr_down_f32(_lib.ptr(g[-1]), _lib.ptr(y), N * C, h, w, _lib.stream_ptr()), 'lap_pyr_down')
+            g.append(y)
+        for l in range(len(g) - 1):
+            h, w = g[l].shape[2:]
+            _lib.check(lib.la_lap_pyr_up_sub_f32(_lib.ptr(g[l]), _lib.ptr(g[l + 1]), N * C, h, w, _lib.stream_ptr()), 'lap_pyr_up_sub')
+    return g
+
+
+def _swd_directions(ndirs, D, dir0, seed, dev):
+    lib = _lib.load()
+    dirs = torch.empty([ndirs, D], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.la_swd_directions_f32(_lib.ptr(dirs), ndirs, D, dir0, seed, _lib.stream_ptr()), 'swd_directions')
+    return dirs
+
+
+def _swd_w1(a, b, dirs):
+    """la_swd_f32 on float32 device tensors a, b [M, D] and dirs [ndirs, D] -> w1 float64 [ndirs] (numpy)"""
+    lib = _lib.load()
+    dev, (M, D), ndirs = a.device, a.shape, dirs.shape[0]
+    w1 = torch.empty([ndirs], dtype=torch.float64, device=dev)
+    floor_bytes = lib.la_swd_scratch_bytes(M, D, ndirs)
+    # the documented minimum holds chunks of 32 directions; give every direction room (up to 1 GiB): the bits do not depend on it
+    nbytes = max(floor_bytes, min(floor_bytes * -(-ndirs // 32), 1 << 30))
+    scratch = _f64_scratch(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.la_swd_f32(_lib.ptr(a), _lib.ptr(b), M, D, _lib.ptr(dirs), ndirs, _lib.ptr(w1), _lib.ptr(scratch), nbytes,
+                                  _lib.stream_ptr()), 'swd')
+    return w1.cpu().numpy()
+
+
+def compute_swd_from_features(a, b, num_dirs=512, seed=0, device='cuda:0', return_details=False):
+    """Sliced Wasserstein distance of two sets of rows ([N, D] numpy arrays or tensors of any float dtype, computed from their float32
+    values; equal N): the mean over `num_dirs` random unit directions d_j of W1_j = mean_i |sort(a d_j)_i - sort(b d_j)_i|, the
+    1-Wasserstein distance of the two projected samples (Rabin et al. 2011).  The rows are taken as they are -- scale them yourself if
+    the columns should weigh alike -- and the result is not multiplied by 1e3.  Directions are those of la_swd_directions_f32 for
+    global indices 0 .. num_dirs - 1 under `seed`.  A translation by t gives W1_j = |t . d_j|; two calls give the same bits.
+    There is no CPU fallback.  return_details=True: (swd, {'w1': float64 [num_dirs], 'dirs': float32 [num_dirs, D]})."""
+    dev, (fa, fb) = _query_features(device, a=a, b=b)
+    if fa.shape[0] != fb.shape[0]:
+        raise ValueError(f'the sliced Wasserstein distance needs sets of one size (got {fa.shape[0]} and {fb.shape[0]} rows)')
+    if int(num_dirs) != num_dirs or num_dirs < 1:
+        raise ValueError(f'num_dirs must be a positive integer (got {num_dirs})')
+    dirs = _swd_directions(int(num_dirs), fa.shape[1], 0, int(seed), dev)
+    w1 = _swd_w1(fa, fb, dirs)
+    swd = float(w1.mean())
+    if return_details:
+        return swd, dict(w1=w1, dirs=dirs.cpu().numpy())
+    return swd
+
+
+def _swd_descriptor_banks(batches, mode, num_items, nhood_size, nhoods_per_image, min_resolution, seed, device):
+    """Per pyramid level the descriptor rows of the first `num_items` images of `batches` (all of them: None), batch by batch:
+    ([level][rows, D] float32 device tensors, number of images, (C, H, W)).  The images themselves are never resident as a set."""
+    lib = _lib.load()
+    banks, count, shape = None, 0, None
+    for batch in batches:
+        x = _batch_images(batch, mode)
+        x = _device_images(x if device is None else x.to(device, torch.float32), 'images')
+        if num_items is not None:
+            x = x[:num_items - count]
+        if x.shape[0] == 0:
+            break
+        if shape is None:
+            shape = tuple(x.shape[1:])
+            if min(shape[1:]) < nhood_size:
+                raise ValueError(f'images of {shape[1]} x {shape[2]} hold no {nhood_size} x {nhood_size} neighbourhood')
+            banks = [[] for _ in range(_pyramid_levels(shape[1], shape[2], max(min_resolution, nhood_size)))]
+        elif tuple(x.shape[1:]) != shape:
+            raise ValueError(f'every batch must hold [N, {shape[0]}, {shape[1]}, {shape[2]}] images (got {tuple(x.shape)})')
+        n, C = x.shape[:2]
+        levels = laplacian_pyramid(x, max(min_resolution, nhood_size))
+        with torch.cuda.device(x.device):
+            for l, lv in enumerate(levels):
+                desc = torch.empty([n * nhoods_per_image, C * nhood_size ** 2], dtype=torch.float32, device=x.device)
+                _lib.check(lib.la_swd_gather_f32(_lib.ptr(lv), n, C, lv.shape[2], lv.shape[3], count, l, nhood_size, nhoods_per_image, seed,
+                                                 _lib.ptr(desc), _lib.stream_ptr()), 'swd_gather')
+                banks[l].append(desc)
+        count += n
+        if num_items is not None and count >= num_items:
+            break
+    if banks is None:
+        raise ValueError('no images')
+    return [torch.cat(b, dim=0) for b in banks], count, shape
+
+
+def _swd_normalize(desc, C, what):
+    """desc [M, C P] in place -> (mean, std) float64 [C] numpy; a constant channel is an error"""
+    lib = _lib.load()
+    M, P, dev = desc.shape[0], desc.shape[1] // C, desc.device
+    stats = torch.empty([2, C], dtype=torch.float64, device=dev)
+    nbytes = lib.la_swd_stats_scratch_bytes(M, C, P)
+    scratch = _f64_scratch(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.la_swd_channel_stats_f64(_lib.ptr(desc), M, C, P, _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(scratch), nbytes,
+                                                _lib.stream_ptr()), 'swd_channel_stats')
+        mean, std = stats.cpu().numpy()
+        if not (std > 0).all():
+            raise ValueError(f'{what}: channel(s) {np.flatnonzero(~(std > 0)).tolist()} are constant over all neighbourhoods (standard deviation '
+                             '0): a constant channel has no descriptor')
+        _lib.check(lib.la_swd_normalize_f32(_lib.ptr(desc), M, C, P, _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.stream_ptr()), 'swd_normalize')
+    return mean, std
+
+
+def compute_swd_from_images(real_batches, gen_batches, mode=None, num_items=None, nhood_size=7, nhoods_per_image=128, dir_repeats=4,
+                            dirs_per_repeat=128, min_resolution=16, seed=0, return_details=False, device=None):
+    """Sliced Wasserstein distance of two image sets on a Laplacian pyramid (Karras, Aila, Laine, Lehtinen, ICLR 2018, section 5): the
+    one established GAN metric that needs no network and no weight file.  `real_batches`, `gen_batches`: iterables of [N, C, H, W]
+    float32 device tensors in [-1, 1] (C = 1, 2 or 3: any C the descriptors can hold), or of the augmentation plugins' output dicts
+    with `mode`, as for compute_feature_stats_for_images; with `device=` every batch is first moved there as float32.  Both sides use their first `num_items` images (default: the smaller count; an
+    explicit num_items that a side cannot fill is an error).  Per pyramid level (laplacian_pyramid): `nhoods_per_image` patches of
+    nhood_size^2 pixels over all channels at positions drawn from the library's Philox stream (keyed by patch, global image index,
+    level and `seed`: a set gives the same descriptors in whatever batches it arrives), each channel normalised to mean 0 and
+    standard deviation 1 over the set, then the mean over dir_repeats * dirs_per_repeat random unit directions -- shared by both
+    sets, keyed by level and seed only -- of the 1-Wasserstein distance of the projections.  Returns {'swd_<res>': .., 'swd_avg': ..}
+    times 1e3 as published, <res> the height of the level: coarse levels say whether the anatomy moved, fine ones whether the texture
+    did.  The descriptor banks are filled batch by batch.  Two calls give the same bits; a set against itself gives exactly 0.
+    There is no CPU fallback.  return_details=True: (dict, {'levels': [{'res', 'w1': float64 [dirs], 'mean', 'std': float64 [2, C]
+    (real, gen)}], 'num_items'})."""
+    if num_items is not None and (int(num_items) != num_items or num_items < 1):
+        raise ValueError(f'num_items must be a positive integer (got {num_items})')
+    if min(nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat) < 1 or dir_repeats * dirs_per_repeat > SWD_LEVEL_DIR_STRIDE:
+        raise ValueError('nhood_size, nhoods_per_image, dir_repeats, dirs_per_repeat must be positive and at most 2^20 directions asked for')
+    seed, ndirs = int(seed), int(dir_repeats) * int(dirs_per_repeat)
+    sides = [_swd_descriptor_banks(b, mode, num_items, int(nhood_size), int(nhoods_per_image), int(min_resolution), seed, device)
+             for b in (real_batches, gen_batches)]
+    (rb, rn, rshape), (gb, gn, gshape) = sides
+    if rshape != gshape:
+        raise ValueError(f'real and generated images differ in shape: {rshape} and {gshape}')
+    n = min(rn, gn) if num_items is None else int(num_items)
+    if min(rn, gn) < n:
+        raise ValueError(f'num_items = {n}, but the sets hold {rn} real and {gn} generated images')
+    C, rows = rshape[0], n * int(nhoods_per_image)
+    out, levels = {}, []
+    for l, (a, b) in enumerate(zip(rb, gb)):
+        a, b = a[:rows], b[:rows]
+        res = rshape[1] >> l
+        stats = [_swd_normalize(d, C, f'swd_{res}, {who} images') for d, who in ((a, 'real'), (b, 'generated'))]
+        dirs = _swd_directions(ndirs, a.shape[1], l * SWD_LEVEL_DIR_STRIDE, seed, a.device)
+        w1 = _swd_w1(a, b, dirs)
+        out[f'swd_{res}'] = float(w1.mean()) * 1e3
+        levels.append(dict(res=res, w1=w1, mean=np.stack([s[0] for s in stats]), std=np.stack([s[1] for s in stats])))
+    out['swd_avg'] = float(np.mean([out[k] for k in out]))
+    if return_details:
+        return out, dict(levels=levels, num_items=n)
+    return out
+
+
+def compute_swd_for_aug_dataset(datadir, device='cuda:0', **kw):
+    """compute_swd_from_images of the source images against their augmented versions in a run directory of the reference's drivers:
+    `img/img_{i}` and `img_aug/img_aug_{i}`, i = 0, 1, .., read like compute_pair_metrics_for_aug_dataset reads them -- the allow-list
+    loader of formats.py, 'A' and 'B' as the two channels -- one file a batch."""
+    dev, files = _aug_pair_run(datadir, device)
+    return compute_swd_from_images((_aug_two_channels(src, dev) for src, _ in files), (_aug_two_channels(aug, dev) for _, aug in files), **kw)
 
 
 def msssim_diversity_pairs(num_images, num_pairs=1000, seed=0):
