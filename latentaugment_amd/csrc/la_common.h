@@ -22,6 +22,15 @@ void la_set_error(const char* msg);
         }                                  \
     } while (0)
 
+// the one refusal of a caller-owned workspace or scratch that is smaller than its size entry reports
+#define LA_CHECK_WORKSPACE(have, need, msg) \
+    do {                                   \
+        if ((have) < (need)) {             \
+            la_set_error(msg);             \
+            return LA_ERR_WORKSPACE;       \
+        }                                  \
+    } while (0)
+
 #define LA_CHECK_LAUNCH()                              \
     do {                                               \
         hipError_t e__ = hipGetLastError();            \
@@ -70,18 +79,23 @@ void la_prof_close(int slot, hipStream_t stream);
 static inline int la_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Workspace carving: every buffer of a caller-supplied region starts on a 64-byte boundary.  A layout function is written once
-// and run twice -- with a null base to measure (take returns null, `off` ends as the bytes needed), then over the region.
+// and run twice -- with a null base to measure (take returns null, `off` ends as the bytes needed), then over the region.  A size
+// is counted in elements of the buffer's own type (take<double>(n), take<int>(n)): a count converted by hand to another unit is
+// where a layout goes wrong by a factor.
 static inline size_t la_align64(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
 struct LaCarver {
     char* base = nullptr;
     size_t off = 0;
     size_t cap = 0;      // bytes behind `base` where the caller knows them (0: not given)
-    float* take(size_t nfloats) {
-        float* p = base ? (float*)(base + off) : nullptr;
-        off += la_align64(nfloats * sizeof(float));
+    template <class T> T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += la_align64(count * sizeof(T));
         return p;
     }
+    float* take(size_t nfloats) { return take<float>(nfloats); }
 };
+// every pointer on a multiple of N bytes (a null pointer counts as aligned: optional arguments are tested with the rest)
+template <size_t N, class... P> static inline bool la_aligned(const P*... p) { return (((uintptr_t)p | ... | (uintptr_t)0) & (N - 1)) == 0; }
 
 // A host handle (plain data, malloc'ed: the destroy entries free() it), owned by its create entry until that releases it into *out
 struct LaFree { void operator()(void* p) const { free(p); } };

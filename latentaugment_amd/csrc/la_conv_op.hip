@@ -415,7 +415,7 @@ extern "C" int la_conv2d_f32(const float* x, const float* w, float* y, void* ws,
     if (rc) return rc;
     if (engine_ok(LA_OP_FWD, Cout, kh, kw, stride, groups)) {
         LA_CHECK_ARG(ws && ((size_t)ws & 15) == 0, "conv2d: the engine path needs a 16-byte aligned workspace (la_conv2d_workspace_bytes)");
-        if (ws_bytes < workspace_bytes(LA_OP_FWD, g)) { la_set_error("conv2d: workspace too small (la_conv2d_workspace_bytes)"); return LA_ERR_WORKSPACE; }
+        LA_CHECK_WORKSPACE(ws_bytes, workspace_bytes(LA_OP_FWD, g), "conv2d: workspace too small (la_conv2d_workspace_bytes)");
         return engine_forward(g, x, w, y, ws, ws_bytes, stream);
     }
     const long total = (long)B * Cout * Hout * Wout;
@@ -440,7 +440,7 @@ extern "C" int la_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, v
     const long nel = (long)a.A * a.N;
     if (engine_ok(LA_OP_WGRAD, Cout, kh, kw, stride, groups)) {
         LA_CHECK_ARG(ws && ((size_t)ws & 15) == 0, "conv2d_wgrad: the MFMA path needs a 16-byte aligned workspace (la_conv2d_workspace_bytes)");
-        if (ws_bytes < workspace_bytes(LA_OP_WGRAD, g)) { la_set_error("conv2d_wgrad: workspace too small (la_conv2d_workspace_bytes)"); return LA_ERR_WORKSPACE; }
+        LA_CHECK_WORKSPACE(ws_bytes, workspace_bytes(LA_OP_WGRAD, g), "conv2d_wgrad: workspace too small (la_conv2d_workspace_bytes)");
         a.part = static_cast<float*>(ws);
         hipLaunchKernelGGL(la_conv_wgrad_mfma_kernel, dim3(a.mtiles * a.ntiles, a.groups, a.ks), dim3(256), 0, stream, a);
         LA_CHECK_LAUNCH();

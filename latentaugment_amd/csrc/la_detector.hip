@@ -201,7 +201,7 @@ extern "C" int la_fc_bias_act_f32(const float* x, const float* w, const float* b
     int rc = fc_check_shape(N, K, O);
     if (rc) return rc;
     LA_CHECK_ARG(act == LA_ACT_LINEAR || act == LA_ACT_RELU, "fc: act must be linear or relu");
-    if (workspace_bytes < la_fc_workspace_bytes(N, K, O)) { la_set_error("fc: workspace too small"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_WORKSPACE(workspace_bytes, la_fc_workspace_bytes(N, K, O), "fc: workspace too small");
     const LaFcPlan p = la_fc_plan(N, K, O);
     LA_CHECK_ARG((long)p.ntiles * p.otiles < (1L << 31) - 1, "fc: too many tiles for one launch");
     FcArgs a;

@@ -155,7 +155,7 @@ extern "C" int la_disc_create(int img_resolution, int img_channels, const int* c
     if (rc) return rc;
     LA_CHECK_ARG(nparams == la_disc_num_params(img_resolution), "disc_create: parameter list length mismatch");
     for (int i = 0; i < nparams; ++i) LA_CHECK_ARG(params[i], "disc_create: null parameter tensor");
-    if (d_layout(h, workspace) > workspace_bytes) { la_set_error("disc_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_WORKSPACE(workspace_bytes, d_layout(h, workspace), "disc_create: workspace too small");
     h->clamp = conv_clamp; h->mbstd_group = mbstd_group_size > 0 ? mbstd_group_size : 4;
     memcpy(h->fir, fir_host, sizeof(float) * 16);
     int p = 0;

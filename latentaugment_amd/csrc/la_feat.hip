@@ -211,7 +211,7 @@ static int f_create(int nops, const FOpDesc* ops, const float* const* params, in
     LA_CHECK_ARG(h, "feat_create: out of host memory");
     int rc = f_describe(h, nops, ops, in_ch, in_res, max_batch, min_res);
     if (rc) return rc;
-    if (f_layout(h, workspace) > workspace_bytes) { la_set_error("feat_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_WORKSPACE(workspace_bytes, f_layout(h, workspace), "feat_create: workspace too small");
     int p = 0;
     for (int k = 0; k < nops && !rc; ++k) {
         FOp& o = h->op[k];
@@ -778,7 +778,7 @@ extern "C" int la_feat_pair_distance(la_feat* h, const float* xy, int P, double*
     LA_CHECK_ARG(h && xy && dist && ws, "feat_pair_distance: null pointer");
     LA_CHECK_ARG(!h->detector, "feat_pair_distance: a detector list (fc ops) has no taps");
     LA_CHECK_ARG(P >= 1 && 2L * P <= h->maxN, "feat_pair_distance: 2 * pairs exceeds max_batch");
-    if (ws_bytes < la_feat_pair_workspace_bytes(h, P)) { la_set_error("feat_pair_distance: workspace too small"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_WORKSPACE(ws_bytes, la_feat_pair_workspace_bytes(h, P), "feat_pair_distance: workspace too small");
     LaPairTaps t; pair_taps(h, t);
     int tap = 0;
     h->lastN = 0;
@@ -820,8 +820,8 @@ extern "C" int la_feat_style_distance(la_feat* h, const float* xy, int P, double
     LA_CHECK_ARG(P >= 1 && 2L * P <= h->maxN, "feat_style_distance: 2 * pairs exceeds max_batch");
     const size_t need = la_feat_style_scratch_bytes(h, P);
     LA_CHECK_ARG(need > 0, "feat_style_distance: a tap's shape is refused by la_gram_pair_scratch_bytes");
-    if (scratch_bytes < need) { la_set_error("feat_style_distance: scratch smaller than la_feat_style_scratch_bytes(h, P)"); return LA_ERR_WORKSPACE; }
-    LA_CHECK_ARG(((size_t)scratch & 7) == 0, "feat_style_distance: the scratch must be 8-byte aligned");
+    LA_CHECK_WORKSPACE(scratch_bytes, need, "feat_style_distance: scratch smaller than la_feat_style_scratch_bytes(h, P)");
+    LA_CHECK_ARG(la_aligned<8>(scratch), "feat_style_distance: the scratch must be 8-byte aligned");
     const int ntaps = la_feat_num_taps(h);
     int tap = 0, trc = LA_OK;
     h->lastN = 0;

@@ -223,10 +223,7 @@ int la_featconv_forward(const float* x, const float* w, const float* b, float* y
     a.mask = nullptr; a.in_coff = 0; a.in_ctotal = g.cin; a.wcin = g.cin; a.accumulate = 0;
     const FcvPlan p = fcv_plan(a.M, g.cout, a.K);
     a.ptiles = p.ptiles; a.ctiles = p.ctiles; a.ks = p.ks; a.per = p.per; a.nchunk = p.nchunk;
-    if (p.ks > 1 && (!part || part_floats < (size_t)p.ks * p.ptiles * p.ctiles * (FCV_CT * FCV_PT))) {
-        la_set_error("featconv: split-K workspace too small");
-        return LA_ERR_WORKSPACE;
-    }
+    if (p.ks > 1) LA_CHECK_WORKSPACE(part ? part_floats : 0, (size_t)p.ks * p.ptiles * p.ctiles * (FCV_CT * FCV_PT), "featconv: split-K workspace too small");
     hipLaunchKernelGGL(la_featconv_gemm_kernel<false>, dim3((unsigned)(p.ptiles * p.ctiles), (unsigned)p.ks), dim3(256), 0, stream, a);
     if (p.ks > 1) hipLaunchKernelGGL(la_featconv_finish_kernel<false>, dim3(la_cdiv(a.M * g.cout, 256)), dim3(256), 0, stream, a);
     LA_CHECK_LAUNCH();
@@ -292,10 +289,7 @@ int la_featconv_backward(const float* gy, const float* y, const float* w, float*
         a.K = g.cout * g.k * g.k; a.M = (long)N * g.R * g.R;
         const FcvPlan p = fcv_plan(a.M, a.cout, a.K);
         a.ptiles = p.ptiles; a.ctiles = p.ctiles; a.ks = p.ks; a.per = p.per; a.nchunk = p.nchunk;
-        if (p.ks > 1 && (!part || part_floats < (size_t)p.ks * p.ptiles * p.ctiles * (FCV_CT * FCV_PT))) {
-            la_set_error("featconv_backward: split-K workspace too small");
-            return LA_ERR_WORKSPACE;
-        }
+        if (p.ks > 1) LA_CHECK_WORKSPACE(part ? part_floats : 0, (size_t)p.ks * p.ptiles * p.ctiles * (FCV_CT * FCV_PT), "featconv_backward: split-K workspace too small");
         hipLaunchKernelGGL(la_featconv_gemm_kernel<true>, dim3((unsigned)(p.ptiles * p.ctiles), (unsigned)p.ks), dim3(256), 0, stream, a);
         if (p.ks > 1) hipLaunchKernelGGL(la_featconv_finish_kernel<true>, dim3(la_cdiv(a.M * a.cout, 256)), dim3(256), 0, stream, a);
         LA_CHECK_LAUNCH();

@@ -246,11 +246,13 @@ __global__ __launch_bounds__(256) void la_fd_nuc_kernel(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-// The workspace, in doubles: the n' vectors of m, then what the Gram and finish entries need beside them.
+// The workspace: the n' vectors of m (first: la_fd_jacobi_sweep_f64 is handed the start of the workspace as its vectors), then what
+// the Gram and finish entries need beside them.
 struct FdLayout {
     long n, n2, m;
     int chunksx, chunksy;
-    size_t vec, mux, muy, partx, party, rowsq, norms, total;      // offsets in doubles
+    double *vec, *mux, *muy, *partx, *party, *rowsq, *norms;
+    size_t bytes;
 };
 
 static inline bool fd_sizes_ok(long nx, long ny, int D) {
@@ -258,30 +260,29 @@ static inline bool fd_sizes_ok(long nx, long ny, int D) {
     return nx >= 2 && ny >= 2 && D >= 1 && n <= FD_MAX_N && m <= 65535L * FD_ROWS;      // (the row chunks are a grid's y axis)
 }
 
-static inline FdLayout fd_layout(long nx, long ny, int D) {
+static inline FdLayout fd_layout(long nx, long ny, int D, void* base) {
     FdLayout L;
     L.n = nx < ny ? nx : ny;
     L.m = nx < ny ? ny : nx;
     L.n2 = (L.n + 1) & ~1L;
     L.chunksx = la_cdiv(nx, FD_ROWS);
     L.chunksy = la_cdiv(ny, FD_ROWS);
-    size_t off = 0;
-    auto take = [&](size_t doubles) { const size_t o = off; off += (doubles + 7) & ~(size_t)7; return o; };
-    L.vec = take((size_t)L.n2 * (size_t)L.m);
-    L.mux = take((size_t)D);
-    L.muy = take((size_t)D);
-    L.partx = take((size_t)L.chunksx * (size_t)D);
-    L.party = take((size_t)L.chunksy * (size_t)D);
-    L.rowsq = take((size_t)nx + (size_t)ny);
-    L.norms = take((size_t)L.n2);
-    L.total = off;
+    LaCarver c{(char*)base};
+    L.vec = c.take<double>((size_t)L.n2 * (size_t)L.m);
+    L.mux = c.take<double>((size_t)D);
+    L.muy = c.take<double>((size_t)D);
+    L.partx = c.take<double>((size_t)L.chunksx * (size_t)D);
+    L.party = c.take<double>((size_t)L.chunksy * (size_t)D);
+    L.rowsq = c.take<double>((size_t)nx + (size_t)ny);
+    L.norms = c.take<double>((size_t)L.n2);
+    L.bytes = c.off;
     return L;
 }
 
 // bytes of the workspace of one problem (0 for sizes the entries refuse)
 extern "C" size_t la_fd_workspace_bytes(long nx, long ny, int D) {
     if (!fd_sizes_ok(nx, ny, D)) return 0;
-    return fd_layout(nx, ny, D).total * sizeof(double);
+    return fd_layout(nx, ny, D, nullptr).bytes;
 }
 
 static int fd_check_sizes(long nx, long ny, int D) {
@@ -297,31 +298,27 @@ extern "C" int la_fd_gram_f32(const float* x, long nx, const float* y, long ny, 
                               hipStream_t stream) {
     LA_CHECK_ARG(x && y && terms && ws, "fd_gram: null pointer");
     if (const int rc = fd_check_sizes(nx, ny, D)) return rc;
-    if (ws_bytes < la_fd_workspace_bytes(nx, ny, D)) {
-        la_set_error("fd_gram: workspace smaller than la_fd_workspace_bytes(nx, ny, D)");
-        return LA_ERR_WORKSPACE;
-    }
-    LA_CHECK_ARG((((size_t)x | (size_t)y) & 3) == 0 && (((size_t)ws | (size_t)terms) & 7) == 0,
+    LA_CHECK_WORKSPACE(ws_bytes, la_fd_workspace_bytes(nx, ny, D), "fd_gram: workspace smaller than la_fd_workspace_bytes(nx, ny, D)");
+    LA_CHECK_ARG(la_aligned<4>(x, y) && la_aligned<8>(ws, terms),
                  "fd_gram: features must be 4-byte aligned, terms and the workspace 8-byte aligned");
-    const FdLayout L = fd_layout(nx, ny, D);
-    double* w = (double*)ws;
+    const FdLayout L = fd_layout(nx, ny, D, ws);
     const unsigned dblocks = (unsigned)la_cdiv(D, 256);
-    hipLaunchKernelGGL(la_fd_colsum_kernel, dim3(dblocks, (unsigned)L.chunksx), dim3(256), 0, stream, x, nx, D, w + L.partx);
-    hipLaunchKernelGGL(la_fd_colsum_kernel, dim3(dblocks, (unsigned)L.chunksy), dim3(256), 0, stream, y, ny, D, w + L.party);
-    hipLaunchKernelGGL(la_fd_mean_kernel, dim3(dblocks, 2), dim3(256), 0, stream, (const double*)(w + L.partx), L.chunksx, nx, w + L.mux,
-                       (const double*)(w + L.party), L.chunksy, ny, w + L.muy, D);
-    hipLaunchKernelGGL(la_fd_rowsq_kernel, dim3((unsigned)(nx + ny)), dim3(256), 0, stream, x, nx, (const double*)(w + L.mux), y,
-                       (const double*)(w + L.muy), D, w + L.rowsq);
-    hipLaunchKernelGGL(la_fd_terms_kernel, dim3(1), dim3(256), 0, stream, (const double*)(w + L.mux), (const double*)(w + L.muy), D,
-                       (const double*)(w + L.rowsq), nx, ny, terms);
+    hipLaunchKernelGGL(la_fd_colsum_kernel, dim3(dblocks, (unsigned)L.chunksx), dim3(256), 0, stream, x, nx, D, L.partx);
+    hipLaunchKernelGGL(la_fd_colsum_kernel, dim3(dblocks, (unsigned)L.chunksy), dim3(256), 0, stream, y, ny, D, L.party);
+    hipLaunchKernelGGL(la_fd_mean_kernel, dim3(dblocks, 2), dim3(256), 0, stream, (const double*)L.partx, L.chunksx, nx, L.mux,
+                       (const double*)L.party, L.chunksy, ny, L.muy, D);
+    hipLaunchKernelGGL(la_fd_rowsq_kernel, dim3((unsigned)(nx + ny)), dim3(256), 0, stream, x, nx, (const double*)L.mux, y,
+                       (const double*)L.muy, D, L.rowsq);
+    hipLaunchKernelGGL(la_fd_terms_kernel, dim3(1), dim3(256), 0, stream, (const double*)L.mux, (const double*)L.muy, D,
+                       (const double*)L.rowsq, nx, ny, terms);
     // the side with fewer rows supplies the vectors: C for nx <= ny, C^T otherwise, by exchanging the operands
     const bool xs = nx <= ny;
     const float* p = xs ? x : y;
     const float* q = xs ? y : x;
-    const double* mup = w + (xs ? L.mux : L.muy);
-    const double* muq = w + (xs ? L.muy : L.mux);
+    const double* mup = xs ? L.mux : L.muy;
+    const double* muq = xs ? L.muy : L.mux;
     hipLaunchKernelGGL(la_fd_gram_kernel, dim3((unsigned)la_cdiv(L.m, FD_T), (unsigned)la_cdiv(L.n, FD_T)), dim3(256), 0, stream, p, L.n, mup,
-                       q, L.m, muq, D, w + L.vec, (int)(L.n2 != L.n));
+                       q, L.m, muq, D, L.vec, (int)(L.n2 != L.n));
     LA_CHECK_LAUNCH();
     return LA_OK;
 }
@@ -330,7 +327,7 @@ extern "C" int la_fd_jacobi_sweep_f64(double* v, long n, long m, int* rotations,
     LA_CHECK_ARG(v && rotations, "fd_jacobi_sweep: null pointer");
     LA_CHECK_ARG(n >= 2 && n <= FD_MAX_N, "fd_jacobi_sweep: the number of vectors must lie in 2 .. 8192");
     LA_CHECK_ARG(m >= 1 && m <= 0x7fffffffL, "fd_jacobi_sweep: the vector length must lie in 1 .. 2^31 - 1");
-    LA_CHECK_ARG(((size_t)v & 7) == 0 && ((size_t)rotations & 3) == 0, "fd_jacobi_sweep: v must be 8-byte and rotations 4-byte aligned");
+    LA_CHECK_ARG(la_aligned<8>(v) && la_aligned<4>(rotations), "fd_jacobi_sweep: v must be 8-byte and rotations 4-byte aligned");
     const int n2 = (int)((n + 1) & ~1L);
     const double tol = ldexp(sqrt((double)m), -52);      // LAPACK dgesvj's criterion: sqrt(m) eps
     LA_HIP(hipMemsetAsync(rotations, 0, sizeof(int), stream));
@@ -347,15 +344,11 @@ extern "C" int la_fd_jacobi_sweep_f64(double* v, long n, long m, int* rotations,
 extern "C" int la_fd_finish_f64(void* ws, size_t ws_bytes, long nx, long ny, int D, double* sv, double* terms, hipStream_t stream) {
     LA_CHECK_ARG(ws && terms, "fd_finish: null pointer");
     if (const int rc = fd_check_sizes(nx, ny, D)) return rc;
-    if (ws_bytes < la_fd_workspace_bytes(nx, ny, D)) {
-        la_set_error("fd_finish: workspace smaller than la_fd_workspace_bytes(nx, ny, D)");
-        return LA_ERR_WORKSPACE;
-    }
-    LA_CHECK_ARG((((size_t)ws | (size_t)terms | (size_t)sv) & 7) == 0, "fd_finish: the workspace, terms and sv must be 8-byte aligned");
-    const FdLayout L = fd_layout(nx, ny, D);
-    double* w = (double*)ws;
-    hipLaunchKernelGGL(la_fd_norm_kernel, dim3((unsigned)L.n), dim3(256), 0, stream, (const double*)(w + L.vec), L.m, w + L.norms, sv);
-    hipLaunchKernelGGL(la_fd_nuc_kernel, dim3(1), dim3(256), 0, stream, (const double*)(w + L.norms), L.n, terms + 3);
+    LA_CHECK_WORKSPACE(ws_bytes, la_fd_workspace_bytes(nx, ny, D), "fd_finish: workspace smaller than la_fd_workspace_bytes(nx, ny, D)");
+    LA_CHECK_ARG(la_aligned<8>(ws, terms, sv), "fd_finish: the workspace, terms and sv must be 8-byte aligned");
+    const FdLayout L = fd_layout(nx, ny, D, ws);
+    hipLaunchKernelGGL(la_fd_norm_kernel, dim3((unsigned)L.n), dim3(256), 0, stream, (const double*)L.vec, L.m, L.norms, sv);
+    hipLaunchKernelGGL(la_fd_nuc_kernel, dim3(1), dim3(256), 0, stream, (const double*)L.norms, L.n, terms + 3);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }

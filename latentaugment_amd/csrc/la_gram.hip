@@ -238,9 +238,9 @@ struct GramScratch { float* part; double *tsum, *csum; size_t bytes; };
 static GramScratch gram_scratch(void* base, int P, const GramPlan& g) {
     LaCarver c{(char*)base};
     GramScratch s;
-    s.part = c.take((size_t)P * g.ks * g.ntile * g.tw * g.tw);
-    s.tsum = (double*)c.take(2 * (size_t)P * g.ntile * g.nseg);
-    s.csum = (double*)c.take(2 * (size_t)P * g.cblk);
+    s.part = c.take<float>((size_t)P * g.ks * g.ntile * g.tw * g.tw);
+    s.tsum = c.take<double>((size_t)P * g.ntile * g.nseg);
+    s.csum = c.take<double>((size_t)P * g.cblk);
     s.bytes = c.off;
     return s;
 }
@@ -277,7 +277,7 @@ extern "C" int la_gram_pair_dist_f32(const float* f, int P, int C, int HW, doubl
     LA_CHECK_ARG(f && style && scratch, "gram_pair_dist: null pointer");
     const size_t need = la_gram_pair_scratch_bytes(P, C, HW);
     LA_CHECK_ARG(need > 0, "gram_pair_dist: P must lie in 1 .. 65535, C in 1 .. 8192, HW in 1 .. 2^26");
-    if (scratch_bytes < need) { la_set_error("gram_pair_dist: scratch smaller than la_gram_pair_scratch_bytes(P, C, HW)"); return LA_ERR_WORKSPACE; }
-    LA_CHECK_ARG(((size_t)scratch & 7) == 0, "gram_pair_dist: the scratch must be 8-byte aligned");
+    LA_CHECK_WORKSPACE(scratch_bytes, need, "gram_pair_dist: scratch smaller than la_gram_pair_scratch_bytes(P, C, HW)");
+    LA_CHECK_ARG(la_aligned<8>(scratch), "gram_pair_dist: the scratch must be 8-byte aligned");
     return la_gram_pair_launch(f, P, C, HW, style, content, 1, scratch, stream);
 }

@@ -210,62 +210,55 @@ extern "C" int la_knn_col_splits(long nq, long nx) {
     return (int)((ct + tiles - 1) / tiles);
 }
 
-// The scratch, in doubles: the squared norms of both sides, then the split lists' keys, then (as ints) their indices.  The lists are
-// sized by a bound on row blocks x splits that grows with nq and with nx (the product itself does not: more row blocks take fewer
-// splits): min(2 (KNN_TARGET_WG + row blocks), row blocks x min(column tiles, KNN_MAX_SPLITS)).
+// The scratch: the squared norms of both sides, then the split lists' keys, then their indices.  The lists are sized by a bound on
+// row blocks x splits that grows with nq and with nx (the product itself does not: more row blocks take fewer splits):
+// min(2 (KNN_TARGET_WG + row blocks), row blocks x min(column tiles, KNN_MAX_SPLITS)).
 struct KnnLayout {
-    size_t rowsq, keys, idx, total;      // offsets in doubles
+    double *rowsq, *keys;
+    int* idx;
+    size_t bytes;
 };
 
-static inline KnnLayout knn_layout(long nq, long nx, int k) {
+static inline KnnLayout knn_layout(long nq, long nx, int k, void* base) {
     const size_t rb = (size_t)((nq + FD_T - 1) / FD_T), ct = (size_t)((nx + FD_T - 1) / FD_T);
-    const size_t a = 2 * (KNN_TARGET_WG + rb), b =rb * (ct < KNN_MAX_SPLITS ? ct : KNN_MAX_SPLITS);
+    const size_t a = 2 * (KNN_TARGET_WG + rb), b = rb * (ct < KNN_MAX_SPLITS ? ct : KNN_MAX_SPLITS);
     const size_t lists = (a < b ? a : b) * (size_t)k * FD_T;
     KnnLayout L;
-    size_t off = 0;
-    auto take = [&](size_t doubles) { const size_t o = off; off += (doubles + 7) & ~(size_t)7; return o; };
-    L.rowsq = take((size_t)nq + (size_t)nx);
-    L.keys = take(lists);
-    L.idx = take((lists + 1) / 2);
-    L.total = off;
+    LaCarver c{(char*)base};
+    L.rowsq = c.take<double>((size_t)nq + (size_t)nx);
+    L.keys = c.take<double>(lists);
+    L.idx = c.take<int>(lists);
+    L.bytes = c.off;
     return L;
 }
 
 extern "C" size_t la_knn_scratch_bytes(long nq, long nx, int D, int k) {
     if (!knn_sizes_ok(nq, nx) || D < 1 || k < 1 || k > KNN_MAX_K) return 0;
-    return knn_layout(nq, nx, k).total * sizeof(double);
+    return knn_layout(nq, nx, k, nullptr).bytes;
 }
 
 template <bool REALISM>
 static int knn_launch(const char* who, const float* q, long nq, const float* x, long nx, int D, int k, int exclude_self,
                       const double* radius2, double* out_key, int* out_idx, void* scratch, size_t scratch_bytes, hipStream_t stream) {
     char msg[160];
-    auto fail = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); la_set_error(msg); };
-    if (!q || !x || !out_key || !out_idx || !scratch || (REALISM && !radius2)) { fail("null pointer"); return LA_ERR_ARG; }
-    if (nq < 1 || nx < 1) { fail("queries and bank need at least one row each"); return LA_ERR_ARG; }
-    if (D < 1) { fail("the feature dimension must be positive"); return LA_ERR_ARG; }
-    if (k < 1 || k > KNN_MAX_K) { fail("k must lie in 1 .. 32"); return LA_ERR_ARG; }
-    if (exclude_self && nq != nx) { fail("exclude_self needs nq == nx (the queries are the bank)"); return LA_ERR_ARG; }
-    if (!knn_sizes_ok(nq, nx)) { fail("sizes exceed the grid"); return LA_ERR_ARG; }
-    if (scratch_bytes < la_knn_scratch_bytes(nq, nx, D, k)) {
-        fail("scratch smaller than la_knn_scratch_bytes(nq, nx, D, k)");
-        return LA_ERR_WORKSPACE;
-    }
-    if ((((size_t)q | (size_t)x | (size_t)out_idx) & 3) != 0 || (((size_t)out_key | (size_t)scratch | (size_t)radius2) & 7) != 0) {
-        fail("features and indices must be 4-byte aligned, float64 arrays and the scratch 8-byte aligned");
-        return LA_ERR_ARG;
-    }
+    auto says = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return (const char*)msg; };
+    LA_CHECK_ARG(q && x && out_key && out_idx && scratch && (!REALISM || radius2), says("null pointer"));
+    LA_CHECK_ARG(nq >= 1 && nx >= 1, says("queries and bank need at least one row each"));
+    LA_CHECK_ARG(D >= 1, says("the feature dimension must be positive"));
+    LA_CHECK_ARG(k >= 1 && k <= KNN_MAX_K, says("k must lie in 1 .. 32"));
+    LA_CHECK_ARG(!exclude_self || nq == nx, says("exclude_self needs nq == nx (the queries are the bank)"));
+    LA_CHECK_ARG(knn_sizes_ok(nq, nx), says("sizes exceed the grid"));
+    LA_CHECK_WORKSPACE(scratch_bytes, la_knn_scratch_bytes(nq, nx, D, k), says("scratch smaller than la_knn_scratch_bytes(nq, nx, D, k)"));
+    LA_CHECK_ARG(la_aligned<4>(q, x, out_idx) && la_aligned<8>(out_key, scratch, radius2),
+                 says("features and indices must be 4-byte aligned, float64 arrays and the scratch 8-byte aligned"));
     const long tiles = knn_chunk_tiles(nq, nx);
     const int splits = la_knn_col_splits(nq, nx);
     const long rb = (nq + FD_T - 1) / FD_T;
-    const KnnLayout L = knn_layout(nq, nx, k);
-    double* w = (double*)scratch;
-    double* pkey = w + L.keys;
-    int* pidx = (int*)(w + L.idx);
-    hipLaunchKernelGGL(la_knn_rowsq_kernel, dim3((unsigned)(rb + (nx + FD_T - 1) / FD_T)), dim3(256), 0, stream, q, nq, x, nx, D, w + L.rowsq);
+    const KnnLayout L = knn_layout(nq, nx, k, scratch);
+    hipLaunchKernelGGL(la_knn_rowsq_kernel, dim3((unsigned)(rb + (nx + FD_T - 1) / FD_T)), dim3(256), 0, stream, q, nq, x, nx, D, L.rowsq);
     hipLaunchKernelGGL(la_knn_tile_kernel<REALISM>, dim3((unsigned)rb, (unsigned)splits), dim3(256), knn_list_bytes(k), stream, q, nq, x, nx, D,
-                       (const double*)(w + L.rowsq), tiles * FD_T, k, exclude_self, radius2, pkey, pidx);
-    hipLaunchKernelGGL(la_knn_finish_kernel<REALISM>, dim3((unsigned)nq), dim3(256), 0, stream, (const double*)pkey, (const int*)pidx, splits,
+                       (const double*)L.rowsq, tiles * FD_T, k, exclude_self, radius2, L.keys, L.idx);
+    hipLaunchKernelGGL(la_knn_finish_kernel<REALISM>, dim3((unsigned)nq), dim3(256), 0, stream, (const double*)L.keys, (const int*)L.idx, splits,
                        k, out_key, out_idx);
     LA_CHECK_LAUNCH();
     return LA_OK;

@@ -78,7 +78,7 @@ static size_t carve(la_latent_opt* h, char* base) {
     h->xc = c.take(B * h->imgc * cc2);
     h->losses = c.take((size_t)(h->cfg.steps > 0 ? h->cfg.steps : 1) * 4);
     h->adam_tab = c.take((size_t)(h->cfg.steps > 0 ? h->cfg.steps : 1) * 2);
-    h->step_ctr = reinterpret_cast<int*>(c.take(16));
+    h->step_ctr = c.take<int>(16);
     h->crop_dev = h->step_ctr + 4;
     return c.off;
 }
@@ -137,7 +137,7 @@ extern "C" int la_latent_opt_create_ex(la_synth* g, int img_resolution, int img_
     h->num_ws = la_synth_num_ws(img_resolution); h->maxB = max_batch; h->wplus = latent_space;
     h->bankW = bankW; h->Mw = cfg->w_latent != 0.f ? Mw : 0; h->bankX = bankXc; h->Mx = cfg->w_pix != 0.f ? Mx : 0;
     const size_t need = carve(h, (char*)workspace);
-    if (need > workspace_bytes) { la_set_error("latent_opt_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_WORKSPACE(workspace_bytes, need, "latent_opt_create: workspace too small");
     h->adam_tab_host = (float*)malloc(sizeof(float) * 2 * (size_t)(cfg->steps > 0 ? cfg->steps : 1));
     LA_CHECK_ARG(h->adam_tab_host, "latent_opt_create: out of host memory");
     la_adam_fill_table(h->adam_tab_host, cfg->steps, cfg->beta1, cfg->beta2);
@@ -287,7 +287,7 @@ extern "C" int la_latent_opt_set_lpips(la_latent_opt* h, la_feat* f, const float
                                        float pre_shift, void* ws, size_t ws_bytes) {
     LA_CHECK_ARG(h && f && bankF && Mf >= 1 && S >= 1 && ws, "latent_opt_set_lpips: bad arguments");
     const int F = la_feat_num_features(f);
-    if (ws_bytes < la_latent_opt_lpips_workspace_bytes(h->imgc, F, S, Mf, h->maxB)) { la_set_error("latent_opt_set_lpips: workspace too small"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_WORKSPACE(ws_bytes, la_latent_opt_lpips_workspace_bytes(h->imgc, F, S, Mf, h->maxB), "latent_opt_set_lpips: workspace too small");
     h->lp.f = f; h->lp.bankF = bankF; h->lp.Mf = Mf; h->lp.F = F; h->lp.S = S; for (int k = 0; k < 4; ++k) { h->lp.pre_scale[k] = pre_scale; h->lp.pre_shift[k] = pre_shift; }
     carve_lpips(h, (char*)ws);
     h->lp.colsum_valid = 0;

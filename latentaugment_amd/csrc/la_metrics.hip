@@ -412,11 +412,8 @@ extern "C" int la_kid_poly3_f32(const float* x, long nx, const float* y, long ny
     LA_CHECK_ARG(mx <= 0x7fffffffL && my <= 0x7fffffffL && nx <= 0x7fffffffL && ny <= 0x7fffffffL, "kid: sizes beyond int32 indices");
     const long tiles = kid_tiles(mx, my);
     LA_CHECK_ARG(tiles <= 0x7fffffffL / S, "kid: num_subsets x tiles exceeds the grid");
-    if (ws_bytes < la_kid_workspace_bytes(S, mx, my)) {
-        la_set_error("kid: workspace smaller than la_kid_workspace_bytes(S, mx, my)");
-        return LA_ERR_WORKSPACE;
-    }
-    LA_CHECK_ARG(((size_t)ws & 7) == 0, "kid: the workspace must be 8-byte aligned");
+    LA_CHECK_WORKSPACE(ws_bytes, la_kid_workspace_bytes(S, mx, my), "kid: workspace smaller than la_kid_workspace_bytes(S, mx, my)");
+    LA_CHECK_ARG(la_aligned<8>(ws), "kid: the workspace must be 8-byte aligned");
     KidArgs a;
     a.x = x; a.y = y; a.ix = ix; a.iy = iy;
     a.nx = nx; a.ny = ny; a.mx = mx; a.my = my;
@@ -606,14 +603,11 @@ extern "C" int la_dc_count_f16(const void* gen, long ng, const void* real, long 
     LA_CHECK_ARG(ng >= 1 && nr >= 1, "dc: both feature sets need at least one row");
     LA_CHECK_ARG(D >= 16 && D % 16 == 0, "dc: the feature dimension must be a multiple of 16 (pad with zeros)");
     LA_CHECK_ARG((((size_t)gen | (size_t)real) & 15) == 0, "dc: feature matrices must be 16-byte aligned");
-    LA_CHECK_ARG((((size_t)radius | (size_t)count | (size_t)nearest | (size_t)ws) & 3) == 0, "dc: radius, count, nearest and ws must be 4-byte aligned");
+    LA_CHECK_ARG(la_aligned<4>(radius, count, nearest, ws), "dc: radius, count, nearest and ws must be 4-byte aligned");
     const long chunk = dc_chunk_cols(ng, nr);
     const long rb = (ng + 127) / 128, splits = (nr + chunk - 1) / chunk;
     LA_CHECK_ARG(rb <= 0x7fffffffL && splits <= 65535, "dc: sizes exceed the grid");
-    if (ws_bytes < la_dc_workspace_bytes(ng, nr)) {
-        la_set_error("dc: workspace smaller than la_dc_workspace_bytes(ng, nr)");
-        return LA_ERR_WORKSPACE;
-    }
+    LA_CHECK_WORKSPACE(ws_bytes, la_dc_workspace_bytes(ng, nr), "dc: workspace smaller than la_dc_workspace_bytes(ng, nr)");
     float* gn = (float*)ws;
     float* rn = gn + ng;
     const long nmax = ng > nr ? ng : nr;

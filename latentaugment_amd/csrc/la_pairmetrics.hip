@@ -232,14 +232,14 @@ static bool pm_plan(PmPlan* pp, long P, int C, int H, int W, int win, int levels
         pp->h[l] = H >> l; pp->w[l] = W >> l;
         pp->ntx[l] = la_cdiv(pp->w[l], PM_T);
         pp->tiles[l] = pp->ntx[l] * la_cdiv(pp->h[l], PM_T);
-        pp->part[l] = (double*)cv.take((size_t)pp->planes * pp->tiles[l] * 4);          // 2 doubles per tile
+        pp->part[l] = cv.take<double>((size_t)pp->planes * pp->tiles[l] * 2);          // 2 doubles per tile
     }
-    pp->epart = (double*)cv.take((size_t)pp->planes * pp->tiles[0] * 4);
-    pp->means = (double*)cv.take((size_t)pp->planes * levels * 4);
+    pp->epart = cv.take<double>((size_t)pp->planes * pp->tiles[0] * 2);
+    pp->means = cv.take<double>((size_t)pp->planes * levels * 2);
     pp->px[0] = pp->py[0] = nullptr;
     for (int l = 1; l < levels; ++l) {
-        pp->px[l] = cv.take((size_t)pp->planes * pp->h[l] * pp->w[l]);
-        pp->py[l] = cv.take((size_t)pp->planes * pp->h[l] * pp->w[l]);
+        pp->px[l] = cv.take<float>((size_t)pp->planes * pp->h[l] * pp->w[l]);
+        pp->py[l] = cv.take<float>((size_t)pp->planes * pp->h[l] * pp->w[l]);
     }
     *bytes = cv.off;
     return true;
@@ -270,12 +270,9 @@ extern "C" int la_pair_metrics_f32(const float* x, const float* y, const int* ix
     PmPlan pp;
     size_t need = 0;
     LA_CHECK_ARG(pm_plan(&pp, P, C, H, W, win, levels, nullptr, &need), "pair_metrics: sizes beyond the launch limits");
-    if (workspace_bytes < need) {
-        la_set_error("pair_metrics: workspace smaller than la_pair_metrics_workspace_bytes(P, C, H, W, win, levels)");
-        return LA_ERR_WORKSPACE;
-    }
-    LA_CHECK_ARG(((size_t)workspace & 7) == 0, "pair_metrics: the workspace must be 8-byte aligned");
-    LA_CHECK_ARG(((((size_t)x | (size_t)y) & 3) == 0), "pair_metrics: image pointers must be 4-byte aligned");
+    LA_CHECK_WORKSPACE(workspace_bytes, need, "pair_metrics: workspace smaller than la_pair_metrics_workspace_bytes(P, C, H, W, win, levels)");
+    LA_CHECK_ARG(la_aligned<8>(workspace), "pair_metrics: the workspace must be 8-byte aligned");
+    LA_CHECK_ARG(la_aligned<4>(x, y), "pair_metrics: image pointers must be 4-byte aligned");
     for (int l = 0; l < levels; ++l) LA_CHECK_ARG(weights_host[l] >= 0.f, "pair_metrics: weights must be non-negative");
     pm_plan(&pp, P, C, H, W, win, levels, (char*)workspace, &need);
 
@@ -394,7 +391,7 @@ extern "C" int la_joint_hist_f32(const float* a, long a_plane_stride, const floa
     LA_CHECK_ARG(planes <= 0x7fffffffL, "joint_hist: too many planes");
     LA_CHECK_ARG(a_plane_stride >= 0 && b_plane_stride >= 0, "joint_hist: negative plane stride");
     LA_CHECK_ARG(scale > 0.f && scale == scale && lo == lo, "joint_hist: scale must be positive and lo a number");
-    LA_CHECK_ARG(((((size_t)a | (size_t)b | (size_t)hist) & 3) == 0), "joint_hist: pointers must be 4-byte aligned");
+    LA_CHECK_ARG(la_aligned<4>(a, b, hist), "joint_hist: pointers must be 4-byte aligned");
     LA_HIP(hipMemsetAsync(hist, 0, (size_t)planes * bins * bins * sizeof(unsigned), stream));
     const int vec = ((((size_t)a | (size_t)b) & 15) == 0 && a_plane_stride % 4 == 0 && b_plane_stride % 4 == 0) ? 1 : 0;
     const long chunks = (npix + JH_CHUNK - 1) / JH_CHUNK;

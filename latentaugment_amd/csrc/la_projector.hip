@@ -81,14 +81,10 @@ extern "C" int la_row_dist_f32(const float* a, const float* t, int rows, long K,
     LA_CHECK_ARG(rows >= 1 && rows <= 65535 && K >= 1, "row_dist: rows must be 1 .. 65535 and K at least 1");
     LA_CHECK_ARG(fold >= 1 && rows % fold == 0, "row_dist: fold must divide rows");
     LA_CHECK_ARG(loss_stride >= 1, "row_dist: loss_stride must be at least 1");
-    LA_CHECK_ARG(((uintptr_t)a | (uintptr_t)t | (uintptr_t)g) % sizeof(float) == 0 && (uintptr_t)loss % sizeof(double) == 0 &&
-                 (uintptr_t)ws % sizeof(double) == 0, "row_dist: pointer not aligned to its element type");
+    LA_CHECK_ARG(la_aligned<4>(a, t, g) && la_aligned<8>(loss, ws), "row_dist: pointer not aligned to its element type");
     const long chunks = la_row_dist_chunks(K);
     LA_CHECK_ARG(chunks <= 0x7fffffffl, "row_dist: K too large");
-    if (ws_bytes < la_row_dist_workspace_bytes(rows, K)) {
-        la_set_error("row_dist: workspace too small (la_row_dist_workspace_bytes)");
-        return LA_ERR_WORKSPACE;
-    }
+    LA_CHECK_WORKSPACE(ws_bytes, la_row_dist_workspace_bytes(rows, K), "row_dist: workspace too small (la_row_dist_workspace_bytes)");
     const bool vec = K % 4 == 0 && ((uintptr_t)a | (uintptr_t)t | (uintptr_t)g) % 16 == 0;
     double* partial = (double*)ws;
     if (vec)
@@ -375,9 +371,9 @@ static size_t nreg_layout(NregTab& t, const int* res, int nmaps, int B, char* ba
             part += 2l * B * nreg_chunks(res[i], l);
         }
     }
-    t.levels = c.take((size_t)lev);
-    t.part = (double*)c.take(2 * (size_t)part);
-    t.coef = (double*)c.take(2 * (size_t)nmaps * LA_NZ_MAXLEV * B * 2);
+    t.levels = c.take<float>((size_t)lev);
+    t.part = c.take<double>((size_t)part);
+    t.coef = c.take<double>((size_t)nmaps * LA_NZ_MAXLEV * B * 2);
     return c.off;
 }
 
@@ -393,15 +389,12 @@ extern "C" int la_noise_reg_f32(const float* const* maps, const int* res, int nm
     int rc = la_map_table_check(res, nmaps, B, "noise_reg: nmaps must be 1 .. 32 and B 1 .. 65535");
     if (rc) return rc;
     LA_CHECK_ARG(reg_stride >= 1, "noise_reg: reg_stride must be at least 1");
-    LA_CHECK_ARG((uintptr_t)reg % sizeof(double) == 0 && (uintptr_t)ws % sizeof(double) == 0, "noise_reg: pointer not aligned to its element type");
+    LA_CHECK_ARG(la_aligned<8>(reg, ws), "noise_reg: pointer not aligned to its element type");
     NregTab t;
-    if (ws_bytes < nreg_layout(t, res, nmaps, B, (char*)ws)) {
-        la_set_error("noise_reg: workspace too small (la_noise_reg_scratch_bytes)");
-        return LA_ERR_WORKSPACE;
-    }
+    LA_CHECK_WORKSPACE(ws_bytes, nreg_layout(t, res, nmaps, B, (char*)ws), "noise_reg: workspace too small (la_noise_reg_scratch_bytes)");
     int maxlev = 0;
     for (int i = 0; i < nmaps; ++i) {
-        LA_CHECK_ARG(maps[i] && (!gn || gn[i]) && ((uintptr_t)maps[i] | (uintptr_t)(gn ? gn[i] : nullptr)) % sizeof(float) == 0, "noise_reg: null or misaligned map");
+        LA_CHECK_ARG(maps[i] && (!gn || gn[i]) && la_aligned<4>(maps[i], gn ? gn[i] : (float*)nullptr), "noise_reg: null or misaligned map");
         t.n[i] = maps[i]; t.g[i] = gn ? gn[i] : nullptr;
         maxlev = t.nlev[i] > maxlev ? t.nlev[i] : maxlev;
     }
@@ -500,6 +493,14 @@ __global__ __launch_bounds__(256) void la_ntail_scale_kernel(NtailTab t, LaMapGr
     }
 }
 
+// scratch: the launch-1 partials [workgroups] float64, then the launch-2 partials
+static size_t ntail_layout(NtailTab& t, long total, void* base) {
+    LaCarver c{(char*)base};
+    t.part = c.take<double>((size_t)total);
+    t.part2 = c.take<double>((size_t)total);
+    return c.off;
+}
+
 static long ntail_grid(LaMapGrid& g, const int* res, int nmaps, int B) {
     int chunks[LA_NZ_MAXMAPS];
     for (int i = 0; i < nmaps; ++i) chunks[i] = (int)(((long)res[i] * res[i] + LA_NT_CHUNK - 1) / LA_NT_CHUNK);
@@ -509,7 +510,8 @@ static long ntail_grid(LaMapGrid& g, const int* res, int nmaps, int B) {
 extern "C" size_t la_proj_noise_tail_scratch_bytes(const int* res, int nmaps, int B) {
     if (la_map_table_check(res, nmaps, B, "proj_noise_tail: nmaps must be 1 .. 32 and B 1 .. 65535")) return 0;
     LaMapGrid g;
-    return 2 * la_align64((size_t)ntail_grid(g, res, nmaps, B) * sizeof(double));
+    NtailTab t;
+    return ntail_layout(t, ntail_grid(g, res, nmaps, B), nullptr);
 }
 
 extern "C" int la_proj_noise_tail_f32(const float* const* gn, float* const* n, float* const* m, float* const* v, const int* res, int nmaps, int B, int step,
@@ -518,22 +520,17 @@ extern "C" int la_proj_noise_tail_f32(const float* const* gn, float* const* n, f
     int rc = la_map_table_check(res, nmaps, B, "proj_noise_tail: nmaps must be 1 .. 32 and B 1 .. 65535");
     if (rc) return rc;
     LA_CHECK_ARG(step >= 1, "proj_noise_tail: the Adam step is 1-based");
-    LA_CHECK_ARG((uintptr_t)ws % sizeof(double) == 0, "proj_noise_tail: workspace not aligned to 8 bytes");
+    LA_CHECK_ARG(la_aligned<8>(ws), "proj_noise_tail: workspace not aligned to 8 bytes");
     LaMapGrid g;
     const long total = ntail_grid(g, res, nmaps, B);
     LA_CHECK_ARG(total <= 0x7fffffffl, "proj_noise_tail: tables too large");
-    const size_t half = la_align64((size_t)total * sizeof(double));
-    if (ws_bytes < 2 * half) {
-        la_set_error("proj_noise_tail: workspace too small (la_proj_noise_tail_scratch_bytes)");
-        return LA_ERR_WORKSPACE;
-    }
     NtailTab t;
+    LA_CHECK_WORKSPACE(ws_bytes, ntail_layout(t, total, ws), "proj_noise_tail: workspace too small (la_proj_noise_tail_scratch_bytes)");
     for (int i = 0; i < nmaps; ++i) {
-        LA_CHECK_ARG(gn[i] && n[i] && m[i] && v[i] && ((uintptr_t)gn[i] | (uintptr_t)n[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) % sizeof(float) == 0,
+        LA_CHECK_ARG(gn[i] && n[i] && m[i] && v[i] && la_aligned<4>(gn[i], n[i], m[i], v[i]),
                      "proj_noise_tail: null or misaligned map");
         t.gn[i] = gn[i]; t.n[i] = n[i]; t.m[i] = m[i]; t.v[i] = v[i]; t.r[i] = res[i];
     }
-    t.part = (double*)ws; t.part2 = (double*)((char*)ws + half);
     const float step_size = lr / (1.f - powf(beta1, (float)step)), bc2s = sqrtf(1.f - powf(beta2, (float)step));
     hipLaunchKernelGGL(la_ntail_adam_kernel, dim3((unsigned)total), dim3(256), 0, stream, t, g, step_size, bc2s, beta1, beta2, eps);
     LA_CHECK_LAUNCH();

@@ -113,11 +113,8 @@ extern "C" int la_sort_columns_f32(float* keys, long ncols, long M, long ld, voi
     LA_CHECK_ARG(keys && scratch, "sort_columns: null pointer");
     LA_CHECK_ARG(sort_sizes_ok(ncols, M), "sort_columns: ncols must lie in 1 .. 65535 and M in 1 .. 2^30");
     LA_CHECK_ARG(ld >= M, "sort_columns: the column stride ld must be at least M");
-    LA_CHECK_ARG(((size_t)keys & 3) == 0 && ((size_t)scratch & 3) == 0, "sort_columns: keys and scratch must be 4-byte aligned");
-    if (scratch_bytes < la_sort_columns_scratch_bytes(ncols, M)) {
-        la_set_error("sort_columns: scratch smaller than la_sort_columns_scratch_bytes(ncols, M)");
-        return LA_ERR_WORKSPACE;
-    }
+    LA_CHECK_ARG(la_aligned<4>(keys, scratch), "sort_columns: keys and scratch must be 4-byte aligned");
+    LA_CHECK_WORKSPACE(scratch_bytes, la_sort_columns_scratch_bytes(ncols, M), "sort_columns: scratch smaller than la_sort_columns_scratch_bytes(ncols, M)");
     const long tiles = (M + SORT_TILE - 1) / SORT_TILE;
     int passes = 0;
     for (long runs = tiles; runs > 1; runs = (runs + 1) / 2) ++passes;

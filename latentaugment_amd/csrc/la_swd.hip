@@ -231,12 +231,10 @@ __global__ __launch_bounds__(256) void la_swd_w1_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-static inline bool swd_al8(const void* p) { return ((size_t)p & 7) == 0; }
-static inline bool swd_al4(const void* p) { return ((size_t)p & 3) == 0; }
 #define SWD_MAX_ELEMS 0x7fffffffffffL          // (far beyond any memory: keeps the 64-bit products of the checks from overflowing)
 
 extern "C" int la_lap_pyr_down_f32(const float* x, float* y, long planes, int H, int W, hipStream_t stream) {
-    LA_CHECK_ARG(x && y && swd_al4(x) && swd_al4(y), "lap_pyr_down: null or misaligned pointer");
+    LA_CHECK_ARG(x && y && la_aligned<4>(x, y), "lap_pyr_down: null or misaligned pointer");
     LA_CHECK_ARG(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && H <= 32768 && W <= 32768, "lap_pyr_down: H and W must be even and lie in 2 .. 32768");
     LA_CHECK_ARG(planes >= 1 && planes <= 0x7fffffffL && planes * (long)H * W <= 0x3fffffffffL, "lap_pyr_down: planes out of range");
     LA_CHECK_ARG(x != y, "lap_pyr_down: y must not be x");
@@ -246,7 +244,7 @@ extern "C" int la_lap_pyr_down_f32(const float* x, float* y, long planes, int H,
 }
 
 extern "C" int la_lap_pyr_up_sub_f32(float* fine, const float* coarse, long planes, int H, int W, hipStream_t stream) {
-    LA_CHECK_ARG(fine && coarse && swd_al4(fine) && swd_al4(coarse), "lap_pyr_up_sub: null or misaligned pointer");
+    LA_CHECK_ARG(fine && coarse && la_aligned<4>(fine, coarse), "lap_pyr_up_sub: null or misaligned pointer");
     LA_CHECK_ARG(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && H <= 32768 && W <= 32768, "lap_pyr_up_sub: H and W must be even and lie in 2 .. 32768");
     LA_CHECK_ARG(planes >= 1 && planes <= 0x7fffffffL && planes * (long)H * W <= 0x3fffffffffL, "lap_pyr_up_sub: planes out of range");
     LA_CHECK_ARG(fine != coarse, "lap_pyr_up_sub: coarse must not be fine");
@@ -257,7 +255,7 @@ extern "C" int la_lap_pyr_up_sub_f32(float* fine, const float* coarse, long plan
 
 extern "C" int la_swd_gather_f32(const float* img, long n, int C, int H, int W, long img0, int level, int nhood, int per_image,
                                  unsigned long long seed, float* desc, hipStream_t stream) {
-    LA_CHECK_ARG(img && desc && swd_al4(img) && swd_al4(desc), "swd_gather: null or misaligned pointer");
+    LA_CHECK_ARG(img && desc && la_aligned<4>(img, desc), "swd_gather: null or misaligned pointer");
     LA_CHECK_ARG(C >= 1 && C <= 64 && H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "swd_gather: C must lie in 1 .. 64, H and W in 1 .. 32768");
     LA_CHECK_ARG(nhood >= 1 && nhood <= 64 && nhood <= H && nhood <= W, "swd_gather: nhood must lie in 1 .. min(64, H, W)");
     LA_CHECK_ARG(per_image >= 1 && per_image <= 65536 && level >= 0, "swd_gather: per_image must lie in 1 .. 65536 and level be non-negative");
@@ -283,11 +281,8 @@ extern "C" int la_swd_channel_stats_f64(const float* desc, long M, int C, int P,
                                         hipStream_t stream) {
     LA_CHECK_ARG(desc && mean && std && scratch, "swd_channel_stats: null pointer");
     LA_CHECK_ARG(swd_stats_sizes_ok(M, C, P), "swd_channel_stats: M must be at least 1, C in 1 .. 64, P in 1 .. 4096");
-    LA_CHECK_ARG(swd_al4(desc) && swd_al8(mean) && swd_al8(std) && swd_al8(scratch), "swd_channel_stats: float64 arrays and the scratch must be 8-byte aligned");
-    if (scratch_bytes < la_swd_stats_scratch_bytes(M, C, P)) {
-        la_set_error("swd_channel_stats: scratch smaller than la_swd_stats_scratch_bytes(M, C, P)");
-        return LA_ERR_WORKSPACE;
-    }
+    LA_CHECK_ARG(la_aligned<4>(desc) && la_aligned<8>(mean, std, scratch), "swd_channel_stats: float64 arrays and the scratch must be 8-byte aligned");
+    LA_CHECK_WORKSPACE(scratch_bytes, la_swd_stats_scratch_bytes(M, C, P), "swd_channel_stats: scratch smaller than la_swd_stats_scratch_bytes(M, C, P)");
     const int nb = swd_stats_blocks(M, P);
     double* part = (double*)scratch;
     const double count = (double)M * (double)P;
@@ -302,14 +297,14 @@ extern "C" int la_swd_channel_stats_f64(const float* desc, long M, int C, int P,
 extern "C" int la_swd_normalize_f32(float* desc, long M, int C, int P, const double* mean, const double* std, hipStream_t stream) {
     LA_CHECK_ARG(desc && mean && std, "swd_normalize: null pointer");
     LA_CHECK_ARG(swd_stats_sizes_ok(M, C, P), "swd_normalize: M must be at least 1, C in 1 .. 64, P in 1 .. 4096");
-    LA_CHECK_ARG(swd_al4(desc) && swd_al8(mean) && swd_al8(std), "swd_normalize: float64 arrays must be 8-byte aligned");
+    LA_CHECK_ARG(la_aligned<4>(desc) && la_aligned<8>(mean, std), "swd_normalize: float64 arrays must be 8-byte aligned");
     hipLaunchKernelGGL(la_swd_normalize_kernel, dim3((unsigned)((M * C * P + 255) / 256)), dim3(256), 0, stream, desc, M, C, P, mean, std);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }
 
 extern "C" int la_swd_directions_f32(float* dirs, long ndirs, int D, long dir0, unsigned long long seed, hipStream_t stream) {
-    LA_CHECK_ARG(dirs && swd_al4(dirs), "swd_directions: null or misaligned pointer");
+    LA_CHECK_ARG(dirs && la_aligned<4>(dirs), "swd_directions: null or misaligned pointer");
     LA_CHECK_ARG(ndirs >= 1 && ndirs <= 0x3fffffffL && D >= 1 && D <= (1 << 24), "swd_directions: ndirs must lie in 1 .. 2^30 - 1 and D in 1 .. 2^24");
     LA_CHECK_ARG(dir0 >= 0 && dir0 + ndirs <= 0xffffffffL, "swd_directions: direction index exceeds 32 bits");
     hipLaunchKernelGGL(la_swd_directions_kernel, dim3((unsigned)((ndirs + 3) / 4)), dim3(256), 0, stream, dirs, ndirs, D, dir0, (unsigned)seed,
@@ -324,40 +319,44 @@ extern "C" int la_swd_directions_f32(float* dirs, long ndirs, int D, long dir0, 
 static inline bool swd_sizes_ok(long M, int D, long ndirs) {
     return M >= 1 && M <= 0x40000000L && D >= 1 && D <= (1 << 20) && ndirs >= 1 && ndirs <= 0x7fffffffL && M * (long)D <= 0x3fffffffffL;
 }
-static inline size_t swd_chunk_bytes(long M, long c) { return la_align64((size_t)2 * c * M * sizeof(float)) + la_sort_columns_scratch_bytes(2 * c, M); }
+struct SwdScratch { float* proj; char* sort; size_t sort_bytes, bytes; };
+static inline SwdScratch swd_scratch(long M, long c, void* base) {
+    LaCarver cv{(char*)base};
+    SwdScratch s;
+    s.proj = cv.take<float>((size_t)2 * c * M);
+    s.sort_bytes = la_sort_columns_scratch_bytes(2 * c, M);
+    s.sort = cv.take<char>(s.sort_bytes);
+    s.bytes = cv.off;
+    return s;
+}
 
 extern "C" size_t la_swd_scratch_bytes(long M, int D, long ndirs) {
     if (!swd_sizes_ok(M, D, ndirs)) return 0;
-    return swd_chunk_bytes(M, ndirs < SWD_MIN_CHUNK ? ndirs : SWD_MIN_CHUNK);
+    return swd_scratch(M, ndirs < SWD_MIN_CHUNK ? ndirs : SWD_MIN_CHUNK, nullptr).bytes;
 }
 
 extern "C" int la_swd_f32(const float* descA, const float* descB, long M, int D, const float* dirs, long ndirs, double* w1, void* scratch,
                           size_t scratch_bytes, hipStream_t stream) {
     LA_CHECK_ARG(descA && descB && dirs && w1 && scratch, "swd: null pointer");
     LA_CHECK_ARG(swd_sizes_ok(M, D, ndirs), "swd: M must lie in 1 .. 2^30, D in 1 .. 2^20, ndirs be at least 1");
-    LA_CHECK_ARG(swd_al4(descA) && swd_al4(descB) && swd_al4(dirs) && swd_al8(w1) && swd_al8(scratch),
+    LA_CHECK_ARG(la_aligned<4>(descA, descB, dirs) && la_aligned<8>(w1, scratch),
                  "swd: w1 and the scratch must be 8-byte aligned, float arrays 4-byte aligned");
-    if (scratch_bytes < la_swd_scratch_bytes(M, D, ndirs)) {
-        la_set_error("swd: scratch smaller than la_swd_scratch_bytes(M, D, ndirs)");
-        return LA_ERR_WORKSPACE;
-    }
+    LA_CHECK_WORKSPACE(scratch_bytes, la_swd_scratch_bytes(M, D, ndirs), "swd: scratch smaller than la_swd_scratch_bytes(M, D, ndirs)");
     // the largest chunk that fits (at least the documented minimum's): a column's bits do not depend on its chunk
     long chunk = (long)(scratch_bytes / ((size_t)16 * M));
     chunk = chunk > ndirs ? ndirs : chunk;
     chunk = chunk > SWD_MAX_CHUNK ? SWD_MAX_CHUNK : chunk;
     const long floor_chunk = ndirs < SWD_MIN_CHUNK ? ndirs : SWD_MIN_CHUNK;
     chunk = chunk < floor_chunk ? floor_chunk : chunk;
-    while (chunk > floor_chunk && swd_chunk_bytes(M, chunk) > scratch_bytes) --chunk;
-    float* proj = (float*)scratch;
-    void* sort_scratch = (char*)scratch + la_align64((size_t)2 * chunk * M * sizeof(float));
-    const size_t sort_bytes = la_sort_columns_scratch_bytes(2 * chunk, M);
+    while (chunk > floor_chunk && swd_scratch(M, chunk, nullptr).bytes > scratch_bytes) --chunk;
+    const SwdScratch s = swd_scratch(M, chunk, scratch);
     for (long j0 = 0; j0 < ndirs; j0 += chunk) {
         const int nd = (int)(ndirs - j0 < chunk ? ndirs - j0 : chunk);
         hipLaunchKernelGGL(la_swd_project_kernel, dim3((unsigned)((M + SWD_T - 1) / SWD_T), (unsigned)((nd + SWD_T - 1) / SWD_T), 2), dim3(256), 0,
-                           stream, descA, descB, M, D, dirs + j0 * D, nd, proj);
-        const int rc = la_sort_columns_f32(proj, 2 * nd, M, M, sort_scratch, sort_bytes, stream);
+                           stream, descA, descB, M, D, dirs + j0 * D, nd, s.proj);
+        const int rc = la_sort_columns_f32(s.proj, 2 * nd, M, M, s.sort, s.sort_bytes, stream);
         if (rc != LA_OK) return rc;
-        hipLaunchKernelGGL(la_swd_w1_kernel, dim3((unsigned)nd), dim3(256), 0, stream, (const float*)proj, M, nd, w1 + j0);
+        hipLaunchKernelGGL(la_swd_w1_kernel, dim3((unsigned)nd), dim3(256), 0, stream, (const float*)s.proj, M, nd, w1 + j0);
     }
     LA_CHECK_LAUNCH();
     return LA_OK;

@@ -367,7 +367,7 @@ extern "C" int la_synth_create(int img_resolution, int img_channels, int w_dim, 
     for (int i = 0; i < nparams; ++i) LA_CHECK_ARG(params[i], "synth_create: null parameter tensor");
     size_t need = 0;
     layout(h, workspace, workspace_bytes, &need);
-    if (need > workspace_bytes) { la_set_error("synth_create: workspace too small"); return LA_ERR_WORKSPACE; }
+    LA_CHECK_WORKSPACE(workspace_bytes, need, "synth_create: workspace too small");
     h->clamp = conv_clamp;
     // every buffer starts as zeros: a forward pass restricted to a row window (la_synth_set_row_window) leaves the other rows of its saved
     // activations as they were, and the backward pass multiplies them with gradients that are exactly zero there -- they must be finite

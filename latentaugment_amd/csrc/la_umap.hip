@@ -69,27 +69,28 @@ __global__ __launch_bounds__(256) void la_umap_smooth_knn_kernel(const double* _
 // scratch of the graph build: three int arrays [n] (one-sided in-degree, fill cursor, out-degree), then the unsorted columns and
 // values (2 n k each)
 struct UmapLayout {
-    size_t cnt, cur, outdeg, ucol, uval, total;      // byte offsets
+    int *cnt, *cur, *outdeg, *ucol;
+    double* uval;
+    size_t bytes;
 };
 
 static inline bool umap_sizes_ok(long n, int k) { return n >= 2 && n <= 0x3fffffffL && k >= 1 && k <= UMAP_MAX_K && 2 * n * (long)k <= 0x7fffffffL; }
 
-static inline UmapLayout umap_layout(long n, int k) {
+static inline UmapLayout umap_layout(long n, int k, void* base) {
     UmapLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += la_align64(bytes); return o; };
-    L.cnt = take((size_t)n * sizeof(int));
-    L.cur = take((size_t)n * sizeof(int));
-    L.outdeg = take((size_t)n * sizeof(int));
-    L.ucol = take(2 * (size_t)n * k * sizeof(int));
-    L.uval = take(2 * (size_t)n * k * sizeof(double));
-    L.total = off;
+    LaCarver c{(char*)base};
+    L.cnt = c.take<int>((size_t)n);
+    L.cur = c.take<int>((size_t)n);
+    L.outdeg = c.take<int>((size_t)n);
+    L.ucol = c.take<int>(2 * (size_t)n * k);
+    L.uval = c.take<double>(2 * (size_t)n * k);
+    L.bytes = c.off;
     return L;
 }
 
 extern "C" size_t la_umap_scratch_bytes(long n, int k) {
     if (!umap_sizes_ok(n, k)) return 0;
-    return umap_layout(n, k).total;
+    return umap_layout(n, k, nullptr).bytes;
 }
 
 __device__ __forceinline__ bool umap_slot_ok(int j, long n) { return j >= 0 && (long)j < n; }
@@ -304,8 +305,6 @@ __global__ __launch_bounds__(256) void la_umap_epoch_kernel(const UmapEpochArgs 
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-static inline bool umap_al8(const void* p) { return ((size_t)p & 7) == 0; }
-static inline bool umap_al4(const void* p) { return ((size_t)p & 3) == 0; }
 static inline unsigned umap_row_blocks(long n) { return (unsigned)((n + UMAP_ROWS_PER_WG - 1) / UMAP_ROWS_PER_WG); }
 
 extern "C" int la_umap_smooth_knn_f64(const double* dist2, const int* idx, long n, int k, double target, double* rho, double* sigma, double* w,
@@ -314,7 +313,7 @@ extern "C" int la_umap_smooth_knn_f64(const double* dist2, const int* idx, long 
     LA_CHECK_ARG(n >= 1 && n <= 0x3fffffffL, "umap_smooth_knn: n must lie in 1 .. 2^30 - 1");
     LA_CHECK_ARG(k >= 1 && k <= UMAP_MAX_K, "umap_smooth_knn: k must lie in 1 .. 32");
     LA_CHECK_ARG(target > 0.0 && target < INFINITY, "umap_smooth_knn: the target must be positive and finite");
-    LA_CHECK_ARG(umap_al8(dist2) && umap_al8(rho) && umap_al8(sigma) && umap_al8(w) && umap_al4(idx),
+    LA_CHECK_ARG(la_aligned<8>(dist2, rho, sigma, w) && la_aligned<4>(idx),
                  "umap_smooth_knn: float64 arrays must be 8-byte aligned, indices 4-byte aligned");
     hipLaunchKernelGGL(la_umap_smooth_knn_kernel, dim3(umap_row_blocks(n)), dim3(256), 0, stream, dist2, idx, n, k, target, rho, sigma, w);
     LA_CHECK_LAUNCH();
@@ -327,34 +326,25 @@ extern "C" int la_umap_graph_f64(const int* idx, const double* w, long n, int k,
     LA_CHECK_ARG(k >= 1 && k <= UMAP_MAX_K, "umap_graph: k must lie in 1 .. 32");
     LA_CHECK_ARG(umap_sizes_ok(n, k), "umap_graph: n must be at least 2 and 2 n k below 2^31");
     LA_CHECK_ARG(cap >= 2 * n * (long)k, "umap_graph: col and val need a capacity of 2 n k entries");
-    LA_CHECK_ARG(umap_al8(w) && umap_al8(val) && umap_al8(wmax) && umap_al8(scratch) && umap_al4(idx) && umap_al4(row_ptr) && umap_al4(col),
+    LA_CHECK_ARG(la_aligned<8>(w, val, wmax, scratch) && la_aligned<4>(idx, row_ptr, col),
                  "umap_graph: float64 arrays and the scratch must be 8-byte aligned, int arrays 4-byte aligned");
-    if (scratch_bytes < la_umap_scratch_bytes(n, k)) {
-        la_set_error("umap_graph: scratch smaller than la_umap_scratch_bytes(n, k)");
-        return LA_ERR_WORKSPACE;
-    }
-    const UmapLayout L = umap_layout(n, k);
-    char* base = (char*)scratch;
-    int* cnt = (int*)(base + L.cnt);
-    int* cur = (int*)(base + L.cur);
-    int* outdeg = (int*)(base + L.outdeg);
-    int* ucol = (int*)(base + L.ucol);
-    double* uval = (double*)(base + L.uval);
+    LA_CHECK_WORKSPACE(scratch_bytes, la_umap_scratch_bytes(n, k), "umap_graph: scratch smaller than la_umap_scratch_bytes(n, k)");
+    const UmapLayout L = umap_layout(n, k, scratch);
     const unsigned slots = (unsigned)la_cdiv(n * k, 256);
-    hipLaunchKernelGGL(la_umap_degree_kernel, dim3((unsigned)la_cdiv(n, 256)), dim3(256), 0, stream, idx, n, k, cnt, cur, outdeg);
-    hipLaunchKernelGGL(la_umap_count_kernel, dim3(slots), dim3(256), 0, stream, idx, n, k, cnt);
-    hipLaunchKernelGGL(la_umap_scan_kernel, dim3(1), dim3(256), 0, stream, (const int*)outdeg, (const int*)cnt, n, row_ptr);
-    hipLaunchKernelGGL(la_umap_fill_kernel, dim3(slots), dim3(256), 0, stream, idx, w, n, k, (const int*)row_ptr, (const int*)outdeg, cur, ucol,
-                       uval);
-    hipLaunchKernelGGL(la_umap_sort_kernel, dim3(umap_row_blocks(n)), dim3(256), 0, stream, (const int*)row_ptr, n, (const int*)ucol,
-                       (const double*)uval, col, val);
+    hipLaunchKernelGGL(la_umap_degree_kernel, dim3((unsigned)la_cdiv(n, 256)), dim3(256), 0, stream, idx, n, k, L.cnt, L.cur, L.outdeg);
+    hipLaunchKernelGGL(la_umap_count_kernel, dim3(slots), dim3(256), 0, stream, idx, n, k, L.cnt);
+    hipLaunchKernelGGL(la_umap_scan_kernel, dim3(1), dim3(256), 0, stream, (const int*)L.outdeg, (const int*)L.cnt, n, row_ptr);
+    hipLaunchKernelGGL(la_umap_fill_kernel, dim3(slots), dim3(256), 0, stream, idx, w, n, k, (const int*)row_ptr, (const int*)L.outdeg, L.cur, L.ucol,
+                       L.uval);
+    hipLaunchKernelGGL(la_umap_sort_kernel, dim3(umap_row_blocks(n)), dim3(256), 0, stream, (const int*)row_ptr, n, (const int*)L.ucol,
+                       (const double*)L.uval, col, val);
     hipLaunchKernelGGL(la_umap_wmax_kernel, dim3(1), dim3(256), 0, stream, (const int*)row_ptr, n, (const double*)val, wmax);
     LA_CHECK_LAUNCH();
     return LA_OK;
 }
 
 extern "C" int la_umap_init_f64(double* y, long n, int C, unsigned long long seed, long row0, hipStream_t stream) {
-    LA_CHECK_ARG(y && umap_al8(y), "umap_init: null or misaligned pointer");
+    LA_CHECK_ARG(y && la_aligned<8>(y), "umap_init: null or misaligned pointer");
     LA_CHECK_ARG(n >= 1 && n <= 0x3fffffffL, "umap_init: n must lie in 1 .. 2^30 - 1");
     LA_CHECK_ARG(C >= 1 && C <= UMAP_MAX_C, "umap_init: C must lie in 1 .. 8");
     LA_CHECK_ARG(row0 >= 0 && row0 + n <= 0xffffffffL, "umap_init: row index exceeds 32 bits");
@@ -370,7 +360,7 @@ extern "C" int la_umap_transform_init_f64(const int* idx, const double* w, long 
     LA_CHECK_ARG(k >= 1 && k <= UMAP_MAX_K, "umap_transform_init: k must lie in 1 .. 32");
     LA_CHECK_ARG(n >= 1 && n * (long)k <= 0x7fffffffL && n_bank >= 1 && n_bank <= 0x7fffffffL, "umap_transform_init: sizes out of range");
     LA_CHECK_ARG(C >= 1 && C <= UMAP_MAX_C, "umap_transform_init: C must lie in 1 .. 8");
-    LA_CHECK_ARG(umap_al8(w) && umap_al8(bank_y) && umap_al8(y) && umap_al8(wmax) && umap_al4(idx) && umap_al4(row_ptr),
+    LA_CHECK_ARG(la_aligned<8>(w, bank_y, y, wmax) && la_aligned<4>(idx, row_ptr),
                  "umap_transform_init: float64 arrays must be 8-byte aligned, int arrays 4-byte aligned");
     hipLaunchKernelGGL(la_umap_transform_init_kernel, dim3((unsigned)la_cdiv(n * C, 256)), dim3(256), 0, stream, idx, w, n, k, bank_y, n_bank, C,
                        y, row_ptr, wmax);
@@ -402,7 +392,7 @@ static int umap_epoch_check(const char* who, const UmapEpochCall& c) {
     if (!(c.lr == c.lr) || c.lr == INFINITY || c.lr == -INFINITY) return fail("the learning rate must be finite");
     if (c.cap < 0 || c.cap > 0x7fffffffL) return fail("cap out of range");
     if (c.row0 < 0 || c.row0 + c.n > 0xffffffffL) return fail("row index exceeds 32 bits");
-    if (!umap_al8(c.val) || !umap_al8(c.wmax) || !umap_al4(c.row_ptr) || !umap_al4(c.col))
+    if (!la_aligned<8>(c.val, c.wmax) || !la_aligned<4>(c.row_ptr, c.col))
         return fail("float64 arrays must be 8-byte aligned, int arrays 4-byte aligned");
     return LA_OK;
 }
@@ -434,7 +424,7 @@ extern "C" int la_umap_epoch_f64(const double* y_in, double* y_out, long n, cons
     const UmapEpochCall c = {n, n_tail, cap, row0, C, E, rate, skip_self, a, b, lr, seed, row_ptr, col, val, wmax};
     const int rc = umap_epoch_check("umap_epoch", c);
     if (rc != LA_OK) return rc;
-    LA_CHECK_ARG(y_in && y_out && y_tail && umap_al8(y_in) && umap_al8(y_out) && umap_al8(y_tail), "umap_epoch: null or misaligned positions");
+    LA_CHECK_ARG(y_in && y_out && y_tail && la_aligned<8>(y_in, y_out, y_tail), "umap_epoch: null or misaligned positions");
     LA_CHECK_ARG(y_in != y_out && y_tail != y_out, "umap_epoch: an epoch is synchronous: y_out must not be y_in or y_tail");
     LA_CHECK_ARG(e >= 0 && e < E, "umap_epoch: e must lie in 0 .. E - 1");
     umap_epoch_enqueue(c, y_in, y_out, y_tail, e, stream);
@@ -448,7 +438,7 @@ extern "C" int la_umap_layout_f64(double* ya, double* yb, long n, const double* 
     const UmapEpochCall c = {n, n_tail, cap, row0, C, E, rate, skip_self, a, b, lr, seed, row_ptr, col, val, wmax};
     const int rc = umap_epoch_check("umap_layout", c);
     if (rc != LA_OK) return rc;
-    LA_CHECK_ARG(ya && yb && which && umap_al8(ya) && umap_al8(yb) && umap_al8(y_tail), "umap_layout: null or misaligned positions");
+    LA_CHECK_ARG(ya && yb && which && la_aligned<8>(ya, yb, y_tail), "umap_layout: null or misaligned positions");
     LA_CHECK_ARG(ya != yb && y_tail != ya && y_tail != yb, "umap_layout: ya, yb and y_tail must be three buffers");
     LA_CHECK_ARG(e0 >= 0 && e0 <= e1 && e1 <= E, "umap_layout: the epochs must satisfy 0 <= e0 <= e1 <= E");
     LA_CHECK_ARG(y_tail || n_tail == n, "umap_layout: a fit (y_tail NULL) has n_tail == n");

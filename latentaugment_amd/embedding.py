@@ -143,7 +143,7 @@ class LatentUMAP:
         wmax = torch.empty([1], dtype=torch.float64, device=dev)
         ya = torch.empty([n, Cc], dtype=torch.float64, device=dev)
         yb = torch.empty([n, Cc], dtype=torch.float64, device=dev)
-        scratch = metrics._f64_scratch(nbytes, dev)
+        scratch = _lib.workspace(nbytes, dev, torch.float64)
         with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
             _, _, w = self._smooth_knn(dist2, idx)
             _lib.check(lib.la_umap_graph_f64(p(idx), p(w), n, k, p(row_ptr), p(col), p(val), cap, p(wmax), p(scratch), nbytes, _lib.stream_ptr()),

@@ -281,11 +281,6 @@ def compute_kid_from_features(real_features, gen_features, num_subsets=100, max_
     return kid
 
 
-def _f64_scratch(nbytes, dev):
-    """float64 view of `nbytes` bytes of workspace or scratch for the float64 entries (Frechet distance, neighbour queries)"""
-    return _lib.workspace(nbytes, dev, torch.float64)
-
-
 FD_MAX_SMALL_SIDE = 8192        # la_frechet.hip rotates min(Ng, Nr) vectors; beyond this the moments route is the right one
 
 
@@ -323,7 +318,7 @@ def compute_fd_from_features(real_features, gen_features, device='cuda:0', retur
     real, gen = _f32_features(real_features, dev), _f32_features(gen_features, dev)
     n, m = min(ng, nr), max(ng, nr)
     ws_bytes = lib.la_fd_workspace_bytes(ng, nr, D)
-    ws = _f64_scratch(ws_bytes, dev)          # the n' vectors of m doubles come first
+    ws = _lib.workspace(ws_bytes, dev, torch.float64)          # the n' vectors of m doubles come first
     out = torch.empty([4 + n], dtype=torch.float64, device=dev)                # terms [4], singular values [n]
     rot = torch.empty([1], dtype=torch.int32, device=dev)
     sweeps = 0
@@ -431,7 +426,7 @@ def _knn_device(query, bank, k, exclude_self):
     dist2 = torch.empty([nq, k], dtype=torch.float64, device=dev)
     idx = torch.empty([nq, k], dtype=torch.int32, device=dev)
     nbytes = lib.la_knn_scratch_bytes(nq, nx, D, k)
-    scratch = _f64_scratch(nbytes, dev)
+    scratch = _lib.workspace(nbytes, dev, torch.float64)
     with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
         _lib.check(lib.la_knn_f32(_lib.ptr(query), nq, _lib.ptr(bank), nx, D, k, int(bool(exclude_self)), _lib.ptr(dist2), _lib.ptr(idx),
                                   _lib.ptr(scratch), nbytes, _lib.stream_ptr()), 'knn')
@@ -482,7 +477,7 @@ def compute_realism_from_features(real_features, gen_features, nhood_size=3, kee
     score2 = torch.empty([ng], dtype=torch.float64, device=dev)
     arg = torch.empty([ng], dtype=torch.int32, device=dev)
     nbytes = lib.la_knn_scratch_bytes(ng, nr, D, 1)
-    scratch = _f64_scratch(nbytes, dev)
+    scratch = _lib.workspace(nbytes, dev, torch.float64)
     with torch.cuda.device(dev):          # the stream must be `dev`'s, not the current device's
         _lib.check(lib.la_realism_f32(_lib.ptr(gen), ng, _lib.ptr(real), nr, D, _lib.ptr(r2), _lib.ptr(score2), _lib.ptr(arg),
                                       _lib.ptr(scratch), nbytes, _lib.stream_ptr()), 'realism')
@@ -734,7 +729,7 @@ def compute_style_content(x, y, net, pairs=None, content_tap=NST_CONTENT_TAP, cl
         raise ValueError(f'content_tap must lie in 0 .. {nt - 1} (got {content_tap})')
     style = torch.empty([P, C_, nt], dtype=torch.float64, device=dev)
     content = torch.empty([P, C_, nt], dtype=torch.float64, device=dev)
-    scratch = _f64_scratch(net.style_scratch_bytes(C_ * min(chunk, P)), dev)
+    scratch = _lib.workspace(net.style_scratch_bytes(C_ * min(chunk, P)), dev, torch.float64)
     for p0, n, xy in batches:
         s = torch.empty([C_ * n, nt], dtype=torch.float64, device=dev)
         c = torch.empty([C_ * n, nt], dtype=torch.float64, device=dev)
@@ -919,7 +914,7 @@ def _swd_w1(a, b, dirs):
     floor_bytes = lib.la_swd_scratch_bytes(M, D, ndirs)
     # the documented minimum holds chunks of 32 directions; give every direction room (up to 1 GiB): the bits do not depend on it
     nbytes = max(floor_bytes, min(floor_bytes * -(-ndirs // 32), 1 << 30))
-    scratch = _f64_scratch(nbytes, dev)
+    scratch = _lib.workspace(nbytes, dev, torch.float64)
     with torch.cuda.device(dev):
         _lib.check(lib.la_swd_f32(_lib.ptr(a), _lib.ptr(b), M, D, _lib.ptr(dirs), ndirs, _lib.ptr(w1), _lib.ptr(scratch), nbytes,
                                   _lib.stream_ptr()), 'swd')
@@ -987,7 +982,7 @@ def _swd_normalize(desc, C, what):
     M, P, dev = desc.shape[0], desc.shape[1] // C, desc.device
     stats = torch.empty([2, C], dtype=torch.float64, device=dev)
     nbytes = lib.la_swd_stats_scratch_bytes(M, C, P)
-    scratch = _f64_scratch(nbytes, dev)
+    scratch = _lib.workspace(nbytes, dev, torch.float64)
     with torch.cuda.device(dev):
         _lib.check(lib.la_swd_channel_stats_f64(_lib.ptr(desc), M, C, P, _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(scratch), nbytes,
                                                 _lib.stream_ptr()), 'swd_channel_stats')

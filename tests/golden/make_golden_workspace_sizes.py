@@ -3,9 +3,10 @@
 
 Run from the repo root:   python tests/golden/make_golden_workspace_sizes.py [path/to/liblatentaug_hip.so]
 
-The committed record was taken from the library built at the commit BEFORE the engines' private workspace carvers were folded into
-LaCarver (la_common.h): the test that reads it checks that the fold moved no byte.  Re-record only when a layout changes on purpose,
-and from a build that is trusted.  Needs no GPU: every call only computes a size.
+The committed record was taken from the library built at commit 1e856d4, the last one BEFORE the metric entries' private layouts became
+typed takes of LaCarver (la_common.h); its engine sizes are those recorded before the engines' own carvers were folded in, unchanged
+since.  The test that reads it checks that neither fold moved a byte.  Re-record only when a layout changes on purpose, and from a
+build that is trusted.  Needs no GPU: every call only computes a size.
 """
 import json
 import os

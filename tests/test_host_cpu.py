@@ -188,13 +188,13 @@ def test_product_never_imports_oracle():
     assert not bad, bad
 
 
-_SIZE_ENTRY = re.compile(r'la_\w*workspace_(?:bytes|floats)\w*$')
+_SIZE_ENTRY = re.compile(r'la_\w*(?:workspace|scratch)_(?:bytes|floats)\w*$')
 _TORCH_ALLOCATORS = {'empty', 'zeros', 'ones', 'full', 'empty_like', 'zeros_like', 'ones_like', 'full_like', 'empty_strided', 'rand', 'randn',
                      'tensor', 'arange'}
 
 
 def workspace_allocation_faults(src, name='<src>'):
-    """Where a piece of package source sizes a buffer by a la_*_workspace_bytes / la_*_workspace_floats entry and allocates it with anything
+    """Where a piece of package source sizes a buffer by a la_*_(workspace|scratch)_(bytes|floats) entry and allocates it with anything
     but `_lib.workspace`: per function, the names that carry such a size (the call's result, and what is computed from them) may reach
     `_lib.workspace(...)` and ordinary arithmetic, never a torch allocator.  Also: `workspace` taken out of `_lib` by an import, which a
     test's monkeypatch of the module attribute would no longer reach."""
@@ -222,7 +222,7 @@ def workspace_allocation_faults(src, name='<src>'):
             n = stack.pop()
             if is_lib_workspace(n):
                 continue
-            if is_size_call(n) or (isinstance(n, ast.Name) and n.id in tainted):
+            if is_size_call(n) or (isinstance(n, (ast.Name, ast.Attribute)) and ast.unparse(n) in tainted):
                 return True
             stack.extend(ast.iter_child_nodes(n))
         return False
@@ -237,12 +237,16 @@ def workspace_allocation_faults(src, name='<src>'):
             grew = False
             for n in body:
                 if isinstance(n, (ast.Assign, ast.AugAssign, ast.AnnAssign)) and n.value is not None and carries(n.value, tainted):
-                    targets = n.targets if isinstance(n, ast.Assign) else [n.target]
-                    for t in targets:
-                        for leaf in ast.walk(t):
-                            if isinstance(leaf, ast.Name) and leaf.id not in tainted:
-                                tainted.add(leaf.id)
-                                grew = True
+                    targets = list(n.targets) if isinstance(n, ast.Assign) else [n.target]
+                    while targets:          # a name, an attribute as its dotted path (`self.n`, not all of `self`), the container of an item
+                        t = targets.pop()
+                        if isinstance(t, (ast.Tuple, ast.List)):
+                            targets += t.elts
+                        elif isinstance(t, (ast.Subscript, ast.Starred)):
+                            targets.append(t.value)
+                        elif ast.unparse(t) not in tainted:
+                            tainted.add(ast.unparse(t))
+                            grew = True
         for n in body:
             if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in _TORCH_ALLOCATORS and \
                     isinstance(n.func.value, ast.Name) and n.func.value.id in ('torch', 'np', 'numpy') and \
@@ -269,22 +273,30 @@ def test_every_workspace_is_allocated_by_lib_workspace():
                 n = len(re.findall(r'\b_lib\.workspace\(', src))
                 if n and rel != '_lib.py':          # (its own docstring says how it is called)
                     sites[rel] = n
-                entries |= set(re.findall(r'\b(la_\w*workspace_(?:bytes|floats)\w*)\(', src))
+                entries |= set(re.findall(r'\b(la_\w*(?:workspace|scratch)_(?:bytes|floats)\w*)\(', src))
     assert not faults, faults
     # synthesis: synth, mapping tmp, disc, feat, LPIPS pair, fc | loop_handle: loop, loop LPIPS | metrics: cdist, PR, KID, FD, DC (+ its PR
-    # part), pair metrics | projector: row distance | ops: filtered_lrelu signs, pairwise L2, conv2d scratch, grid-sample gradient
-    assert sites == {'synthesis.py': 6, 'loop_handle.py': 2, 'metrics.py': 6, 'projector.py': 1, 'ops.py': 4}
+    # part), kNN, realism, style distance, pair metrics, SWD, SWD channel statistics | embedding: UMAP graph | projector: row distance
+    # with the noise regulariser and tail | ops: filtered_lrelu signs, pairwise L2, conv2d scratch, grid-sample gradient
+    assert sites == {'synthesis.py': 6, 'loop_handle.py': 2, 'metrics.py': 11, 'embedding.py': 1, 'projector.py': 1, 'ops.py': 4}
     from latentaugment_amd import _lib
     declared = {n for n in _lib.SIGNATURES if _SIZE_ENTRY.match(n)}
-    assert len(declared) == 18 and entries <= declared
-    # the entries of the header that the package does not call are those of the layer-level C entries, which only tests and scripts drive
-    assert declared - entries == {'la_latent_opt_workspace_bytes', 'la_modconv_workspace_bytes'}, declared - entries
+    assert len(declared) == 27 and entries <= declared
+    # the entries of the header that the package does not call are those of the layer-level C entries, which only tests and scripts drive,
+    # and the two that the library itself calls for the package (the Gram scratch inside la_feat_style_scratch_bytes, the sort's inside
+    # la_swd_scratch_bytes)
+    assert declared - entries == {'la_latent_opt_workspace_bytes', 'la_modconv_workspace_bytes', 'la_gram_pair_scratch_bytes',
+                                  'la_sort_columns_scratch_bytes'}, declared - entries
     # the scan itself: what it must find, and what it must leave alone
     bad = ('def f(lib, dev):\n    n = lib.la_kid_workspace_bytes(1, 2, 3)\n    m = max(n, 64) // 8\n'
            '    return torch.empty([m], dtype=torch.float64, device=dev)\n')
     assert len(workspace_allocation_faults(bad)) == 1
     assert len(workspace_allocation_faults('def f(lib):\n    return torch.zeros([lib.la_pr_workspace_floats(3, 4)])\n')) == 1
     assert len(workspace_allocation_faults('def f(x, lib):\n    n = lib.la_fc_workspace_bytes(1, 2, 3)\n    return x.new_empty([n])\n')) == 1
+    assert len(workspace_allocation_faults('def f(lib, dev):\n    nbytes = lib.la_knn_scratch_bytes(5, 7, 4, 3)\n'
+                                           '    return torch.empty([nbytes // 8], dtype=torch.float64, device=dev)\n')) == 1
+    assert len(workspace_allocation_faults('def f(self, lib):\n    self.n = lib.la_umap_scratch_bytes(9, 3)\n    self.ws = torch.empty([self.n])\n'
+                                           '    self.out = torch.empty([4], device=self.device)\n')) == 1
     assert len(workspace_allocation_faults('from ._lib import workspace\n')) == 1
     assert len(workspace_allocation_faults('from . import _lib\nalloc = _lib.workspace\n')) == 1
     good = ('def f(lib, dev):\n    n = lib.la_kid_workspace_bytes(1, 2, 3)\n    ws = _lib.workspace(max(n, 64), dev, torch.float64)\n'
@@ -560,6 +572,33 @@ def test_reductions_and_noise_stream_have_one_home():
             philox.append(name)
         assert not re.findall(r'\b(?:la_proj_philox4x32_10|la_geom_philox4x32_10|la_wave_sum_f64|fd_block_sum|kid_block_sum)\b', text), name
     assert philox == ['la_rng.h'] and found == kept
+
+
+def test_workspace_contract_has_one_home():
+    """A caller-owned workspace is laid out by LaCarver (csrc/la_common.h) in elements of each buffer's own type, refused by
+    LA_CHECK_WORKSPACE when it is short and by la_aligned<N> when it is misaligned: no file carves with a lambda of its own, none casts
+    what a take returns (a float-counted take seen as doubles is where a factor of two goes missing), none keeps private alignment
+    helpers, and LA_ERR_WORKSPACE is returned by the macro alone -- and by the launch profiler's two overflow reports, which are no
+    workspace refusals.  The lists are exact: a new copy fails here, and so does a listed site that has gone."""
+    import glob
+    csrc = os.path.join(ROOT, 'latentaugment_amd', 'csrc')
+    returns, lambdas, casts, helpers = {}, [], [], []
+    for path in sorted(glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h'))):
+        text, name = open(path).read(), os.path.basename(path)
+        n = len(re.findall(r'\breturn\b[^;]*\bLA_ERR_WORKSPACE\b', text))
+        if n:
+            returns[name] = n
+        if re.search(r'auto\s+take\s*=', text):
+            lambdas.append(name)
+        if re.search(r'(?:\*\s*\)|_cast\s*<[^;()]*>\s*\()\s*\w+(?:\.|->)take\b', text):
+            casts.append(name)
+        if re.search(r'\w_al(?:4|8)\b', text):
+            helpers.append(name)
+    assert returns == {'la_common.h': 1, 'la_prof.hip': 2}
+    assert lambdas == [] and casts == [] and helpers == []
+    # the scan itself: the forms it replaced
+    assert re.search(r'(?:\*\s*\)|_cast\s*<[^;()]*>\s*\()\s*\w+(?:\.|->)take\b', 's.tsum = (double*)c.take(2 * (size_t)P * g.ntile * g.nseg);')
+    assert re.search(r'\w_al(?:4|8)\b', 'LA_CHECK_ARG(swd_al4(desc) && umap_al8(mean), "...");')
 
 
 def test_exact_fp32_tile_loop_has_one_home():

@@ -1,7 +1,9 @@
-"""Workspace byte counts of the engines and the loop, pinned to tests/golden/workspace_sizes.json (recorded by
-tests/golden/make_golden_workspace_sizes.py from the build before the engines' private carvers became LaCarver): the shared carver
-lays every buffer out where the private ones did.  No GPU needed: the library loads without one and every call here returns before
-any launch."""
+"""Workspace byte counts of the engines, the loop and every stand-alone size entry of the metric side, pinned to
+tests/golden/workspace_sizes.json (recorded by tests/golden/make_golden_workspace_sizes.py from the build of commit 1e856d4, the last
+one before the metric entries' private layouts -- counted in doubles, in bytes, or as casts of float counts -- became typed takes of
+LaCarver; the engines' sizes in it are those of the build before their own carvers were folded in, which that commit still gives):
+the shared carver lays every buffer out where the private ones did.  No GPU needed: the library loads without one and every call here
+returns before any launch."""
 import ctypes as C
 import json
 import os
@@ -37,7 +39,11 @@ def test_table_covers_what_it_claims(golden):
         for mb in wc.MAX_BATCH:
             assert {f'feat-vgg16-res{in_res}-b{mb}', f'feat-detector-res{in_res}-b{mb}'} <= names
             assert {f'lpips-{net}-S{in_res}-c{imgc}-b{mb}' for net in ('vgg16', 'tap') for imgc in wc.IMG_CHANNELS} <= names
-    assert all(isinstance(v, int) and v > 0 and v % 64 == 0 for v in golden.values())
+    assert {name for name, _, _ in wc.metric_cases()} <= names
+    assert {name.split('-')[0] for name, _, _ in wc.metric_cases()} == {
+        'fd', 'knn', 'umap', 'sort', 'swd', 'swd_stats', 'gram', 'pair_metrics', 'kid', 'dc', 'pr', 'row_dist', 'noise_reg', 'noise_tail', 'fc'}
+    assert all(isinstance(v, int) and v > 0 for v in golden.values())
+    assert [k for k, v in golden.items() if v % 64 and k.split('-')[0] not in wc.UNROUNDED] == []
 
 
 def test_workspace_sizes_are_the_recorded_ones(lib, golden):

@@ -90,4 +90,68 @@ def measure(lib):
             for imgc in IMG_CHANNELS:
                 for net, F in feats.items():
                     out[f'lpips-{net}-S{in_res}-c{imgc}-b{mb}'] = lib.la_latent_opt_lpips_workspace_bytes(imgc, F, in_res, MF, mb)
+    out.update(measure_metrics(lib))
+    return out
+
+
+# Entries whose workspace is one buffer of exactly what it holds: their sizes are not rounded to 64 (and 'pr' counts floats).  The
+# other single-buffer entries (sort, swd_stats, row_dist, fc) do round.
+UNROUNDED = ('kid', 'dc', 'pr')
+# Row counts around the places where a layout rounds: the byte count of an array of them is 0, 4, 8, 60 or 64 (mod 64) for 4- and
+# 8-byte elements.
+EDGE_ROWS = (1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65)
+
+
+def metric_cases():
+    """[(name, size entry, argument tuple)] of the stand-alone size entries of the metric side: a handful of shapes each, chosen where
+    the layout rounds or takes another branch.  Integer arguments only, but the two `res` tables (tuples, passed as int arrays)."""
+    cases = []
+    add = lambda kind, entry, *args: cases.append((f'{kind}-' + '-'.join(                                   # noqa: E731
+        'x'.join(map(str, a)) if isinstance(a, tuple) else str(a) for a in args), entry, args))
+    for nx, ny in [(2, 2), (2, 3), (3, 2), (7, 9), (8, 8), (63, 65), (64, 64), (65, 200), (129, 64), (1000, 1001)]:
+        for D in (1, 8, 9, 2048):                      # odd and even min(nx, ny); D on both sides of 8 doubles
+            add('fd', 'la_fd_workspace_bytes', nx, ny, D)
+    for k in (1, 5, 32):
+        for nq, nx in [(1, 1), (1, 63), (63, 1), (63, 64), (64, 63), (64, 65), (65, 65), (7, 4097), (65, 4161), (1089, 4161), (40000, 129)]:
+            add('knn', 'la_knn_scratch_bytes', nq, nx, 16, k)      # 4097 .. columns: past KNN_MAX_SPLITS tiles; 1089, 40000: the other bound
+    for n in (2, 3, 15, 16, 17, 63, 64, 65, 1001):
+        for k in (1, 3, 15, 32):                       # odd n k among them
+            add('umap', 'la_umap_scratch_bytes', n, k)
+    for ncols in (1, 2, 3, 64):
+        for M in (1, 15, 16, 17, 4096, 4097):
+            add('sort', 'la_sort_columns_scratch_bytes', ncols, M)
+    for M in (1, 7, 8, 9, 4097):
+        for ndirs in (1, 3, 31, 32, 33, 128):
+            add('swd', 'la_swd_scratch_bytes', M, 48, ndirs)
+    for M, Cc, P in [(1, 1, 1), (7, 3, 9), (100, 8, 49), (4097, 9, 49), (100000, 64, 4096)]:
+        add('swd_stats', 'la_swd_stats_scratch_bytes', M, Cc, P)
+    for P in (1, 3, 8):
+        for Cc, HW in [(1, 1), (3, 7), (64, 256), (65, 256), (128, 1024), (129, 100), (512, 16), (512, 4096)]:
+            add('gram', 'la_gram_pair_scratch_bytes', P, Cc, HW)
+    for P, Cc in [(1, 1), (3, 1), (2, 3)]:
+        for H, W, win, levels in [(11, 11, 11, 1), (16, 16, 1, 1), (33, 47, 7, 1), (32, 48, 3, 2), (176, 176, 11, 5), (192, 208, 7, 5)]:
+            add('pair_metrics', 'la_pair_metrics_workspace_bytes', P, Cc, H, W, win, levels)
+    for S, mx, my in [(1, 2, 2), (1, 3, 2), (3, 63, 65), (7, 64, 129), (100, 1000, 1000)]:
+        add('kid', 'la_kid_workspace_bytes', S, mx, my)
+    for ng in EDGE_ROWS:
+        add('dc', 'la_dc_workspace_bytes', ng, 1)
+        add('dc', 'la_dc_workspace_bytes', 5, ng)
+        add('pr', 'la_pr_workspace_floats', ng, 3)
+        add('pr', 'la_pr_workspace_floats', 129, ng + 1000)
+    for rows in (1, 2, 7, 8, 9):
+        for K in (1, 8192, 8193, 100000):
+            add('row_dist', 'la_row_dist_workspace_bytes', rows, K)
+    for res in [(4,), (8,), (16,), (4, 8, 8, 16, 16), (4, 8, 8, 16, 16, 32, 32, 64, 64, 128, 128), (1024,)]:
+        for B in (1, 3, 8):
+            add('noise_reg', 'la_noise_reg_scratch_bytes', res, len(res), B)
+            add('noise_tail', 'la_proj_noise_tail_scratch_bytes', res, len(res), B)
+    for N, K, O in [(1, 1, 1), (3, 7, 5), (8, 4096, 1000), (17, 25088, 4096), (64, 64, 10)]:
+        add('fc', 'la_fc_workspace_bytes', N, K, O)
+    return cases
+
+
+def measure_metrics(lib):
+    out = {}
+    for name, entry, args in metric_cases():
+        out[name] = getattr(lib, entry)(*[(C.c_int * len(a))(*a) if isinstance(a, tuple) else a for a in args])
     return out
