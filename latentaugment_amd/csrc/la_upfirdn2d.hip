@@ -13,7 +13,7 @@ struct FirArgs {
     int upx, upy, dnx, dny, padx0, pady0;
     int fw, fh;
     float f[LA_FIR_MAX * LA_FIR_MAX];  // effective correlation kernel (already flipped as needed, gain folded in)
-    int epi;                     // 0 plain, 1 modconv epilogue, 2 activation backward: out = fir(in) * act'(yref) (4x4 stride-1 scalar kernel)
+    int epi;                     // 0 plain, 1 modconv epilogue, 2 activation backward: out = fir(in) * act'(yref) (4x4 stride-1 planar vector kernel)
     const float* yref;           // epi 2: saved output of the activation, same shape as `out`
     const float* demod; int demod_stride;   // [B][stride]
     const float* noise; long noise_bstride; float noise_strength;
@@ -94,8 +94,6 @@ __device__ __forceinline__ float la_fir4x4_plane(const FirArgs& a, const float (
             v = v * dm + bv;
             if (a.noise) v += a.noise[(long)(p / a.C) * a.noise_bstride + pos] * a.noise_strength;
             v = la_act_fwd(v, a.act, a.alpha, a.gain, a.clamp);
-        } else if (EPI == 2) {
-            v *= la_act_bwd_from_y(a.yref[(long)p * HWout + pos], a.act, a.alpha, a.gain, a.clamp);
         } else if (a.addend) {
             v += a.addend[(long)p * HWout + pos];
         }
@@ -517,9 +515,11 @@ static int fir_launch_inner(const FirArgs& a, hipStream_t stream) {
         LA_CHECK_ARG(items < (1l << 38), "upfirdn2d: too many planes");
         dim3 g((unsigned)((items + 255) / 256));
         const float4 vx = make_float4(fx[0], fx[1], fx[2], fx[3]), vy = make_float4(fy[0], fy[1], fy[2], fy[3]);
+        // a column-planar intermediate has two producers, and each brings its epilogue: the up-sampling layer's forward (modconv epilogue, 1)
+        // and the discriminator's fused backward tail (activation backward, 2); there is no plain planar form
+        LA_CHECK_ARG(a.epi == 1 || a.epi == 2, "upfirdn2d: column-planar input comes with the modconv epilogue or the activation backward");
         if (a.epi == 1) { if (rows == 4) hipLaunchKernelGGL((la_fir4x4_s1p_kernel<1, 4>), g, dim3(256), 0, stream, a, vx, vy); else hipLaunchKernelGGL((la_fir4x4_s1p_kernel<1, 16>), g, dim3(256), 0, stream, a, vx, vy); }
-        else if (a.epi == 2) { if (rows == 4) hipLaunchKernelGGL((la_fir4x4_s1p_kernel<2, 4>), g, dim3(256), 0, stream, a, vx, vy); else hipLaunchKernelGGL((la_fir4x4_s1p_kernel<2, 16>), g, dim3(256), 0, stream, a, vx, vy); }
-        else { if (rows == 4) hipLaunchKernelGGL((la_fir4x4_s1p_kernel<0, 4>), g, dim3(256), 0, stream, a, vx, vy); else hipLaunchKernelGGL((la_fir4x4_s1p_kernel<0, 16>), g, dim3(256), 0, stream, a, vx, vy); }
+        else { if (rows == 4) hipLaunchKernelGGL((la_fir4x4_s1p_kernel<2, 4>), g, dim3(256), 0, stream, a, vx, vy); else hipLaunchKernelGGL((la_fir4x4_s1p_kernel<2, 16>), g, dim3(256), 0, stream, a, vx, vy); }
         LA_CHECK_LAUNCH();
         return LA_OK;
     }
@@ -527,8 +527,9 @@ static int fir_launch_inner(const FirArgs& a, hipStream_t stream) {
     if (a.upx == 1 && a.upy == 1 && a.dnx == 1 && a.dny == 1 && a.fw == 4 && a.fh == 4) {
         dim3 g(la_cdiv(a.Wout, 64), la_cdiv(a.Hout, 4 * FIR_ROWS), a.P < 4096 ? a.P : 4096);
         LA_CHECK_ARG(g.y <= 65535, "upfirdn2d: output too tall");
+        // (the activation backward reads a column-planar intermediate: its only caller, the discriminator's fused tail, always has one)
+        LA_CHECK_ARG(a.epi != 2, "upfirdn2d: the fused activation backward needs the column-planar input layout");
         if (a.epi == 1) hipLaunchKernelGGL(la_fir4x4_s1_kernel<1>, g, dim3(256), 0, stream, a);
-        else if (a.epi == 2) hipLaunchKernelGGL(la_fir4x4_s1_kernel<2>, g, dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(la_fir4x4_s1_kernel<0>, g, dim3(256), 0, stream, a);
         LA_CHECK_LAUNCH();
         return LA_OK;

@@ -400,6 +400,10 @@ CLAMP = 0.5
 DISC_CASES = [
     DiscCase('R8', 8, T8, 4, seed=0),
     DiscCase('R128', 128, {4: 16, 8: 16, 16: 16, 32: 8, 64: 8, 128: 4}, 2, seed=0, kind='bulk'),
+    # img_channels 1 / 3 / 4 above 64 x 64: the FromRGB backward runs la_torgb_fwd_kernel<imgc> there (la_torgb_fwd_small_kernel below)
+    DiscCase('R128-imgc1', 128, {4: 16, 8: 16, 16: 16, 32: 8, 64: 8, 128: 4}, 1, imgc=1, seed=0, kind='bulk'),
+    DiscCase('R128-imgc3', 128, {4: 16, 8: 16, 16: 16, 32: 8, 64: 8, 128: 4}, 1, imgc=3, seed=0, kind='bulk'),
+    DiscCase('R128-imgc4', 128, {4: 16, 8: 16, 16: 16, 32: 8, 64: 8, 128: 4}, 1, imgc=4, seed=0, kind='bulk'),
     DiscCase('imgc1', 16, {4: 16, 8: 16, 16: 8}, 4, imgc=1, seed=2),
     DiscCase('imgc3', 16, {4: 16, 8: 16, 16: 8}, 4, imgc=3, seed=2),
     DiscCase('imgc4', 16, {4: 16, 8: 16, 16: 8}, 4, imgc=4, seed=5),

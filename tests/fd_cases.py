@@ -157,4 +157,14 @@ def jacobi_cases():
     out['7 x 5'] = rs.randn(7, 5)
     out['2 x 2'] = rs.randn(2, 2)
     out['300 x 9'] = rs.randn(300, 9)
+    # vector lengths on both sides of the seams at which la_fd_jacobi_sweep_f64 changes its round kernel (m <= 2048, <= 4096, <= 8192
+    # elements in registers; streaming above), a few vectors each
+    out['2048 x 4'] = rs.randn(2048, 4)
+    out['2049 x 3'] = rs.randn(2049, 3)
+    out['8192 x 5'] = rs.randn(8192, 5)
+    out['8193 x 6'] = rs.randn(8193, 6)
     return out
+
+
+# the matrices of the one-sweep test at the C ABI (test_hip_fd.test_sweeps_follow_the_restatement)
+SWEEP_CASES = ('7 x 5', '2 x 2', '300 x 9', '2048 x 4', '2049 x 3', '8192 x 5', '8193 x 6')

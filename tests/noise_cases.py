@@ -211,7 +211,8 @@ def simulate(case, tgt, steps, optimize_noise, dtype=torch.float64, reg_weight=R
 
 
 # ---- case tables of the kernel tests
-GRAD_SHAPES = [(HW, C, B) for HW in (16, 64, 1024) for C in (4, 16, 132, 512) for B in (1, 3)] + [(256, 16, 3), (65536, 4, 1)]
+GRAD_SHAPES = [(HW, C, B) for HW in (16, 64, 1024) for C in (4, 16, 132, 512) for B in (1, 3)] + [(256, 16, 3), (65536, 4, 1)] + \
+    [(1048576, 5, 1), (1048572, 5, 1)]      # B HW / 4 = 256 x 1024 float4 groups, where la_noise_grad_f32 stops slicing the channels (<1>), and one group fewer (<4>)
 REG_SHAPES = [(r, B) for r in (4, 8, 16, 32, 64, 256) for B in (1, 3)]
 TAIL_SHAPES = [(r, B) for r in (4, 8, 32, 256) for B in (1, 3)]
 STEP_CASES = [('w', 0.0, 1, False), ('w+', 0.1, 1, False), ('w', 0.1, 2, True)]      # (space, w_pix, k, affine): both spaces, w_pix 0 and > 0, k 1 and 2

@@ -180,10 +180,17 @@ def integer_images(P, C, H, W, seed=0):
 SINGLE = [(11, 11, 11, 1, 1, 'texture'), (11, 75, 11, 1, 1, 'smooth'), (42, 42, 11, 1, 1, 'texture'), (43, 42, 11, 2, 1, 'background'),
           (42, 43, 11, 1, 3, 'smooth'), (74, 75, 11, 3, 1, 'texture'), (64, 96, 11, 2, 3, 'background'),
           (8, 8, 1, 1, 1, 'texture'), (8, 8, 3, 2, 1, 'smooth'), (8, 8, 7, 1, 3, 'texture'),
-          (33, 34, 1, 3, 1, 'smooth'), (33, 34, 3, 1, 1, 'background'), (33, 34, 7, 2, 3, 'texture')]
+          (33, 34, 1, 3, 1, 'smooth'), (33, 34, 3, 1, 1, 'background'), (33, 34, 7, 2, 3, 'texture'),
+          # windows 5 and 9 (no other case selects la_pm_level_kernel<5, .> / <9, .> at the C ABI): the smallest legal plane, H = W = win,
+          # and one size above
+          (5, 5, 5, 1, 1, 'texture'), (6, 6, 5, 2, 1, 'texture'), (9, 9, 9, 1, 1, 'texture'), (10, 10, 9, 1, 2, 'smooth')]
 # (H, W, levels, win, C, P, kind)
 MULTI = [(192, 176, 5, 11, 2, 1, 'background'), (176, 352, 5, 11, 1, 2, 'smooth'), (32, 32, 2, 11, 3, 1, 'texture'),
-         (48, 80, 3, 3, 1, 3, 'texture')]
+         (48, 80, 3, 3, 1, 3, 'texture'),
+         # two levels at windows 1, 5, 7 and 9 (the deeper-level kernel form of each window): the smallest legal plane, H = W = 2 win, and
+         # the next legal size above it (H and W are multiples of 2^(levels-1))
+         (2, 2, 2, 1, 1, 1, 'texture'), (4, 4, 2, 1, 2, 1, 'smooth'), (10, 10, 2, 5, 1, 1, 'texture'), (12, 12, 2, 5, 2, 1, 'smooth'),
+         (14, 14, 2, 7, 1, 1, 'texture'), (16, 16, 2, 7, 1, 2, 'texture'), (18, 18, 2, 9, 1, 1, 'texture'), (20, 20, 2, 9, 1, 2, 'smooth')]
 # special inputs, all at 64 x 96, 3 levels, win 11, C 2, P 2
 SPECIAL = [(64, 96, 3, 11, 2, 2, k) for k in ('identical', 'constant', 'background', 'negated')]
 

@@ -79,7 +79,7 @@ def test_first_sweeps_of_the_sweep_cases_are_decisive():
     """test_hip_fd compares the rotation COUNT of the kernel's sweep with jacobi_sweep's.  A count can only be compared where no
     pair's |gamma| lies near the threshold (the two sides add in different orders); this pins that the sweeps compared there are
     such sweeps, so that test cannot become vacuous."""
-    for name in ('7 x 5', '2 x 2', '300 x 9'):
+    for name in fc.SWEEP_CASES:
         V = fc.vectors_of(fc.jacobi_cases()[name])
         margin = []
         rot = fc.jacobi_sweep(V, fc.jacobi_tol(V.shape[1]), margin)

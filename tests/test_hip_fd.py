@@ -110,9 +110,10 @@ def test_gram_is_centred_in_float64(lib, dev):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # one sweep at the C ABI
 
-@pytest.mark.parametrize('name', ['7 x 5', '2 x 2', '300 x 9'])
+@pytest.mark.parametrize('name', fc.SWEEP_CASES)
 def test_sweeps_follow_the_restatement(lib, dev, name):
-    """7 x 5: odd n, the padding vector takes part in every round; 300 x 9: m above one workgroup's width.  After every sweep the Gram
+    """7 x 5: odd n, the padding vector takes part in every round; 300 x 9: m above one workgroup's width; 2048 .. 8193: the last and the
+    first m of the round kernel's forms with 8, 16 and 32 elements a thread in registers and of the streaming one.  After every sweep the Gram
     matrix of the vectors equals the restatement's.  The rotation counts are compared in the sweeps whose decisions are all clear of
     the threshold by a factor 8 in the restatement (the first always is: tests/test_fd_cases_cpu.py); next to the threshold the two
     summation orders may decide differently, by a rotation of an angle near eps."""

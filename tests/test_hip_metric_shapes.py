@@ -12,9 +12,9 @@ rounding of the largest term, carried through the root); moments with 16 x 2^-53
 tiles of 16 plus the final add, with slack; products of two float32 values are exact in float64, only the order differs).
 Every float case prints its err / budget ratio.
 
-Largest measured ratio on an MI355X: moments 0.105 (D15 n50).  cdist, the radii and the membership bits: NOT MEASURED -- this file's
-precision / recall tests have not had a valid GPU run yet, so whether sqrtf is correctly rounded (and the 1-ulp rule could become
-equality) is not known either.
+Largest measured ratio on an MI355X: moments 0.105 (D15 n50); cdist 0.194 (D48-r32-c32: err 7.856e-07 against a budget of 3.773e-06 ..
+4.278e-06).  On the exact inputs every distance and every k-th radius came out as the correctly rounded root: 0 values differed in each
+of the 196 printed one-ulp checks (the rule stays at 1 ulp, which is what sqrtf promises), and every membership bit was equal.
 """
 import os
 import sys

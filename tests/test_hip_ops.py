@@ -46,6 +46,53 @@ def test_library_loaded_is_in_tree():
     assert mapped == {os.path.realpath(_lib.LIB_PATH)}, mapped
 
 
+# (n, stepb, nb, bias): the float4 body with a bias row per 4 k elements, the scalar body (stepb % 4 != 0) with a ragged tail, no bias with a
+# ragged tail, one element, and more float4 groups than the 8192 x 256 threads of the largest grid (the grid-stride loop)
+BIAS_ACT_F32_SHAPES = [(2 * 3 * 64, 64, 3, True), (5 * 7 * 9, 9, 7, True), (1027, 0, 0, False), (1, 1, 1, True), (12 * 5 * 139811, 12, 5, True)]          # (the last: 8 388 660 elements, 13 float4 groups past the grid)
+
+
+@pytest.mark.parametrize('act,alpha,gain,clamp', [(1, 0.0, 1.0, -1.0), (2, 0.0, 2.0 ** 0.5, 0.75), (3, 0.2, 2.0 ** 0.5, -1.0), (3, 0.2, 2.0 ** 0.5, 0.5)])
+@pytest.mark.parametrize('n,stepb,nb,bias', BIAS_ACT_F32_SHAPES, ids=lambda v: str(v))
+def test_bias_act_f32_c_abi(dev, n, stepb, nb, bias, act, alpha, gain, clamp):
+    """la_bias_act_f32 (la_bias_act_fwd_kernel, the SG2 path's linear / relu / lrelu form) against float64: y = clamp(act(x + b) gain).
+    The kernel rounds three times in float32 (the sum, the slope, the gain; the clamp is exact and shrinks an error), each by at most
+    2^-24 relative, so |y - y64| <= 3.01 x 2^-24 x |act(x + b) gain| in float64; and op by op in float32 numpy gives the same bits."""
+    from latentaugment_amd import _lib
+    lib = _lib.load()
+    rs = np.random.RandomState(n % 9973 + 17 * act)
+    x = rs.standard_normal(n).astype(np.float32)
+    b = (0.5 * rs.standard_normal(nb)).astype(np.float32) if bias else None
+    al, ga, cl = np.float32(alpha), np.float32(gain), np.float32(clamp)
+    idx = (np.arange(n) // stepb) % nb if bias else None
+
+    def restate(dt):
+        v = x.astype(dt) + (b.astype(dt)[idx] if bias else dt(0))
+        if act == 3:
+            v = np.where(v > 0, v, v * dt(al))
+        elif act == 2:
+            v = np.where(v > 0, v, dt(0))
+        v = v * dt(ga)
+        return v, (np.clip(v, -dt(cl), dt(cl)) if cl >= 0 else v)
+    free64, want64 = restate(np.float64)
+    _, want32 = restate(np.float32)
+    assert want32.dtype == np.float32
+    xd = torch.from_numpy(x).to(dev)
+    bd = torch.from_numpy(b).to(dev) if bias else None
+    yd = torch.full([n], float('nan'), device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.la_bias_act_f32(_lib.ptr(xd), _lib.ptr(bd), _lib.ptr(yd), n, stepb, nb, act, float(al), float(ga), float(cl), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0, lib.la_last_error()
+    y = yd.cpu().numpy()
+    err, bud = np.abs(y.astype(np.float64) - want64), 3.01 * 2.0 ** -24 * np.abs(free64)
+    worst = float((err / np.maximum(bud, 1e-300)).max()) if n else 0.0
+    print(f'bias_act_f32 n {n} stepb {stepb} nb {nb} act {act} clamp {clamp}: worst err / budget {worst:.3f}')
+    assert np.isfinite(y).all() and (err <= bud).all()
+    assert y.tobytes() == want32.tobytes()
+    if cl >= 0 and n > 100:
+        assert float(np.abs(y).max()) <= float(cl) and (np.abs(free64) > cl).any()          # (the clamp binds somewhere)
+
+
 def test_bias_act_golden(dev, g):
     from latentaugment_amd import ops
     for k in range(int(g['G2_count'])):

@@ -129,19 +129,15 @@ def test_no_packed_fp32_arithmetic_in_any_kernel(lib, tmp_path):
     therefore built without them: every gfx950 code object embedded in the product .so is disassembled here and must contain none."""
     import subprocess
     from latentaugment_amd import _lib
-    bundler, objdump = '/opt/rocm/lib/llvm/bin/clang-offload-bundler', '/opt/rocm/lib/llvm/bin/llvm-objdump'
-    if not (os.path.isfile(bundler) and os.path.isfile(objdump)):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import kernel_symbols
+    objdump = '/opt/rocm/lib/llvm/bin/llvm-objdump'
+    if not (os.path.isfile(kernel_symbols.BUNDLER) and os.path.isfile(objdump)):
         pytest.skip('LLVM tools of the ROCm image not found')
-    blob = open(_lib.LIB_PATH, 'rb').read()
-    starts = [m.start() for m in re.finditer(b'__CLANG_OFFLOAD_BUNDLE__', blob)]
-    assert len(starts) >= 8
+    objs = kernel_symbols.code_objects(_lib.LIB_PATH, tmp_path)          # (asserts that every bundle unbundles to a non-empty object)
+    assert len(objs) >= 8
     kernels = mfma = 0
-    for i, p in enumerate(starts):
-        src, obj = tmp_path / f'b{i}.bin', tmp_path / f'c{i}.o'
-        src.write_bytes(blob[p:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-        r = subprocess.run([bundler, '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', f'--input={src}', f'--output={obj}', '--unbundle'],
-                           capture_output=True)
-        assert r.returncode == 0 and obj.stat().st_size > 0, r.stderr.decode()[-500:]
+    for i, obj in enumerate(objs):
         dis = subprocess.run([objdump, '-d', str(obj)], capture_output=True).stdout.decode(errors='replace')
         bad = re.findall(r'v_pk_(?:fma|mul|add)_f32', dis)
         assert not bad, f'code object {i}: {len(bad)} packed-FP32 instructions'

@@ -48,7 +48,7 @@ def test_window_and_weights():
     assert float(pc.weights_for(3).astype(np.float64).sum()) == pytest.approx(1.0, abs=1e-7)
     assert pc.weights_for(1).tolist() == [1.0]
     from latentaugment_amd import metrics
-    for win in (1, 3, 7, 11):
+    for win in (1, 3, 5, 7, 9, 11):
         assert (metrics.gaussian_window(win, 1.5) == pc.window(win)).all()
     for lv in range(1, 6):
         assert (metrics.msssim_weights(lv) == pc.weights_for(lv)).all()
